@@ -7,24 +7,29 @@ input: `vpf_convert_batch` over a ring of RING distinct device-resident 4K NV12 
 RGB frames (RING*37.3 MB >> the 256 MiB Infinity Cache, so the traffic is really HBM).  Inputs are resident
 in HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: build the ring, pre-heat and warm up, time exactly K steps
+in one block, and print one JSON line (ms_per_step = milliseconds per timed step).  --dump-outputs DIR
+then also writes what the last timed step computed (a fixed sample of the ring's outputs) as DIR/<name>.npy.
+--full adds what the headline does not need: the timed block repeated (--repeats, default 5 there; median reported),
+the CPU baseline (cpu_baseline, unless --no-cpu) and the other BASELINE configs (other_configs).
 
 Multi-GPU: frames are independent, so the ring is replicated per rank (weak scaling), no data-path
 collective; ranks only meet at the timing barriers.  value = pixels converted by all ranks / max-over-ranks time.
 
 Extra flags (not used by the driver): --variant V (kernel variant), --mode single (one dispatch per frame,
 what the unmodified per-Execute() API does), --workload {nv12_rgb_4k, nv12_planar_1080p, resize_4k_720p,
-fused_4k_720p}, --sweep (table of variants on stderr), --no-cpu.
+fused_4k_720p}, --sweep (table of variants on stderr), --no-cpu, --extra (other_configs alone).
 """
 from __future__ import annotations
-
-import os
 
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -73,7 +78,7 @@ class Workload:
             self.w, self.h = (3840, 2160) if name == "nv12_rgb_4k" else (1920, 1080)
             self.dst_fmt = capi.RGB if name == "nv12_rgb_4k" else capi.RGB_PLANAR
             w, h = self.w, self.h
-            frames = []
+            frames, dsts = [], []
             for _ in range(ring):
                 src, sp = _pitched(h * 3 // 2, w, dev, gen)  # NV12: one W x 1.5H plane, shared pitch (reference layout)
                 if self.dst_fmt == capi.RGB:
@@ -83,7 +88,9 @@ class Workload:
                     dst, dp = _pitched(3 * h, w, dev)  # one W x 3H allocation, plane i at base + i*H*pitch
                     dd = [(dst.data_ptr() + i * h * dp, dp) for i in range(3)]
                 self.keep += [src, dst]
+                dsts.append(dst)
                 frames.append(([(src.data_ptr(), sp), (src.data_ptr() + h * sp, sp)], dd))
+            self.outputs = [("rgb", dsts, h, 3 * w) if self.dst_fmt == capi.RGB else ("rgb_planar", dsts, 3 * h, w)]  # --dump-outputs
             self.frames = [(capi.planes(s_), capi.planes(d_)) for s_, d_ in frames]  # descriptors built once, like a C caller
             self.batch = capi.make_batch(frames)
             self.px_per_step = ring * w * h
@@ -101,6 +108,7 @@ class Workload:
                 dst, dp = _pitched(self.dh, 3 * self.dw, dev)
                 self.keep += [src, mid, dst]
                 self.items.append((capi.planes([(src.data_ptr(), sp), (src.data_ptr() + h * sp, sp)]), capi.planes([(mid.data_ptr(), mp)]), capi.planes([(dst.data_ptr(), dp)])))
+            self.outputs = [("rgb_720p", self.keep[2::3], self.dh, 3 * self.dw)]  # --dump-outputs: the 720p frames (the 4K intermediate is not returned by the fused path)
             self.px_per_step = ring * w * h
             luma_rows = _rows_touched(h, self.dh)  # algorithmic bytes at row granularity: only the rows the taps touch
             chroma_rows = {r >> 1 for r in luma_rows}
@@ -122,6 +130,7 @@ class Workload:
                 dst, dp = _pitched(self.dh, 3 * self.dw, dev)
                 self.keep += [src, dst]
                 frames.append(([(src.data_ptr(), sp)], [(dst.data_ptr(), dp)]))
+            self.outputs = [("rgb_720p", self.keep[1::2], self.dh, 3 * self.dw)]  # --dump-outputs
             self.batch = capi.make_batch(frames)
             self.px_per_step = ring * self.w * self.h
             self.bytes_per_step = ring * 3 * (self.w * self.h + self.dw * self.dh)  # algorithmic: source read once, destination written once
@@ -349,12 +358,36 @@ def decode_leg():
             else "no clip given (VPF_BENCH_CLIP)") + "; this is the conversion half only (the reference itself has no CPU converter)"
 
 
+DUMP_VALUES = 12 << 20  # float32 values written by --dump-outputs in all: 48 MiB, under the 64 MB cap
+
+
+def dump_outputs(wl: Workload, out_dir: str):
+    """--dump-outputs: what the last timed step left in the ring's destination frames, as float32 `<name>.npy` of shape (ring, rows, row bytes).
+    Every frame in full when the ring fits DUMP_VALUES, else the same rows of every frame: the first, the last and a sample drawn with a fixed seed
+    (so two runs, or two builds, with the same arguments write the same positions).  Pitch padding is never written."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, frames, rows, row_bytes in wl.outputs:
+        frames = frames[:max(1, DUMP_VALUES // (2 * row_bytes))]  # (a ring so long that two rows per frame would not fit: its first frames)
+        keep = max(2, DUMP_VALUES // (len(frames) * row_bytes))
+        if keep >= rows:
+            idx = np.arange(rows)
+        else:
+            rng = np.random.default_rng(1000)
+            idx = np.union1d([0, rows - 1], rng.choice(np.arange(1, rows - 1), keep - 2, replace=False))
+        sel = torch.from_numpy(idx).to(frames[0].device)
+        arr = torch.stack([f[:rows, :row_bytes].index_select(0, sel) for f in frames]).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        print(f"[dump] {name}.npy: {arr.shape} float32, rows {idx.size} of {rows} per frame", file=sys.stderr, flush=True)
+
+
 def other_configs(dev, main_wl):
     """Short (a few steps each, median of three blocks) measurements of BASELINE.json's other configs and of the per-Execute() dispatch mode, so
     the one JSON line also carries them.  Same ring discipline (device-resident, > Infinity Cache); informational only."""
     res = {}
     pci = device_pci(dev.index or 0)
     del main_wl.keep[:]
+    main_wl.outputs = []
     torch.cuda.empty_cache()
     for key, name, ring, mode, steps in (
             ("4k_nv12_rgb_one_dispatch_per_frame", "nv12_rgb_4k", 32, "single", 10),         # unmodified per-Execute() API
@@ -380,8 +413,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (default: WORLD_SIZE under torch.distributed.run, else 1)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed block of --steps steps is run this many times; the MEDIAN block is reported "
-                    "(ms_per_step, value, roofline), all of them in per_repeat_ms (SURVEY 8d: median of 5)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed block of --steps steps is run this many times; the MEDIAN block is reported "
+                    "(ms_per_step, value, roofline), all of them in per_repeat_ms (SURVEY 8d: median of 5).  Default 1 (exactly --steps timed "
+                    "steps), 5 with --full")
     ap.add_argument("--preheat-ms", type=float, default=300.0, help="untimed, declared pre-heat of the same dispatch before --warmup (0 = none)")
     ap.add_argument("--ring", type=int, default=32, help="distinct frame pairs in the ring (32 x 37.3 MB = 1.19 GB)")
     ap.add_argument("--variant", type=int, default=0)
@@ -391,20 +425,26 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--extra", action="store_true", help="also measure the other BASELINE configs / dispatch modes (adds 'other_configs'); "
                     "off by default so the default run launches ONE kernel shape and its rocprofv3 average is the headline's")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: --repeats 5 unless given, the CPU baseline (unless --no-cpu) "
+                    "and the other BASELINE configs (as --extra)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (a fixed, "
+                    "seeded sample of the ring's outputs, float32, <= 64 MB) as DIR/<name>.npy")
     ap.add_argument("--rehearse-host", action="store_true", help="control-flow rehearsal without a GPU (CPU test suite only): no conversion, "
                     "nothing measured, prints a line marked \"data\": \"rehearsal\"")
     ap.add_argument("--backend", default="nccl", help="process-group backend for N>1 (nccl = RCCL; gloo lets several ranks share one GPU for testing)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
 
     rank, world, local = sharding.env_rank()
     dist_on = world > 1
     if a.gpus is None:
         a.gpus = world  # a torchrun line that does not repeat --gpus: the launcher's WORLD_SIZE is the answer
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` typed by hand: become the launch line the driver uses (one rank per GPU); --standalone lets the c10d
-        # rendezvous pick its own free port (binding one here and handing the number over would race with other processes)
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1",
-                                  f"--nproc-per-node={a.gpus}", os.path.abspath(__file__)] + sys.argv[1:])
+        # `python bench.py --gpus N` typed by hand: run the launch line the driver uses (one rank per GPU) as a child process; --standalone
+        # lets the c10d rendezvous pick its own free port (binding one here and handing the number over would race with other processes)
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1",
+                                  f"--nproc-per-node={a.gpus}", os.path.abspath(__file__)] + sys.argv[1:]))
     if a.gpus != world:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE is {world}")
     if a.rehearse_host:
@@ -534,9 +574,11 @@ def main():
             out["rehearsal_units_per_s"], out["value"] = out["value"] * 1e9, None  # not a measurement of anything
             out["roofline"] = None
             out["config"] = {"workload": "host rehearsal of the multi-rank control flow: no conversion, nothing measured"}
-        if not a.no_cpu and world == 1 and a.workload == "nv12_rgb_4k" and not a.rehearse_host:
+        if a.dump_outputs and not a.rehearse_host:
+            dump_outputs(wl, a.dump_outputs)
+        if a.full and not a.no_cpu and world == 1 and a.workload == "nv12_rgb_4k" and not a.rehearse_host:
             out["cpu_baseline"] = cpu_baseline(wl)
-        if a.extra and world == 1 and a.workload == "nv12_rgb_4k" and a.variant == 0 and a.mode == "batch":
+        if (a.full or a.extra) and world == 1 and a.workload == "nv12_rgb_4k" and a.variant == 0 and a.mode == "batch":
             out["other_configs"] = other_configs(dev, wl)
         print(json.dumps(out), flush=True)
     if dist_on:

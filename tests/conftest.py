@@ -21,6 +21,17 @@ def native_test_build():
     return flags, out
 
 
+def compile_to(cmd, out):
+    """Run the compiler command `cmd`, whose output file is `out`, into a name of this process's own and rename that over `out`: pytest-xdist
+    workers that build the same harness at the same time then never write into, or load, a half-written file."""
+    import subprocess
+
+    tmp = f"{out}.{os.getpid()}.tmp"
+    subprocess.run([tmp if a == out else a for a in cmd], check=True)
+    os.replace(tmp, out)
+    return out
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 

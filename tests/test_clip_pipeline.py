@@ -1,5 +1,5 @@
 """tools/clip_pipeline.py — BASELINE config 1's runner (clip -> libav demux + software decode -> NV12 -> upload -> NV12->RGB) — exercised
-against the stub libav (tests/libav_stub): the bindings variant tests/_build/pynvcodec_stubav carries a PyFfmpegDecoder linked against a
+against the stub libav (tests/libav_stub): the bindings variant videoprocessingframework_amd/build/pynvcodec_stubav carries a PyFfmpegDecoder linked against a
 stand-in libav that "decodes" synthetic clips, so the runner's control flow, its decode leg and (with -m gpu) its whole chain run here,
 and every frame's CRC is compared with the ORACLE (decoded NV12 = the oracle's YUV420 -> NV12 of the stub's planes; RGB = the oracle's
 NV12 -> RGB of that).  Real bitstreams need real libav: where it exists the same command runs on tests/test.mp4 of the reference."""
@@ -21,9 +21,7 @@ TOOL = os.path.join(ROOT, "tools", "clip_pipeline.py")
 def _stub_pkg():
     from videoprocessingframework_amd import _build_bindings as bb
 
-    base = os.path.join(ROOT, "tests", "_build", "pynvcodec_stubav")
-    if os.path.isdir("/root/reference") or not os.path.isdir(base):   # build container: (re)build; GPU box: the prebuilt variant travels
-        base = bb.build_stub_libav_variant()
+    base = bb.build_stub_libav_variant()   # incremental: a no-op when build() already made it
     return base
 
 

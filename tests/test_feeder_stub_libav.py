@@ -36,10 +36,11 @@ def feeder():
     srcs = [os.path.join(CSRC, "feeder", "FfmpegFeeder.cpp"), os.path.join(STUB, "feeder_capi.cpp"), os.path.join(STUB, "stub_libav.c")]
     deps = srcs + [os.path.join(CSRC, "feeder", "FfmpegFeeder.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        from conftest import compile_to
         obj = os.path.join(OUT, "stub_libav.o")
-        subprocess.check_call(["gcc", "-std=c99", "-O1", "-fPIC", "-Wall", "-Wextra", "-Werror", f"-I{STUB}", "-c", srcs[2], "-o", obj])
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-Wall", "-Werror", f"-I{STUB}", f"-I{os.path.join(CSRC, 'tc')}",
-                               f"-I{os.path.join(CSRC, 'feeder')}", f"-I{os.path.join(ROOT, 'include')}", srcs[0], srcs[1], obj, "-Wl,-z,defs", "-o", so])
+        compile_to(["gcc", "-std=c99", "-O1", "-fPIC", "-Wall", "-Wextra", "-Werror", f"-I{STUB}", "-c", srcs[2], "-o", obj], obj)
+        compile_to(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-Wall", "-Werror", f"-I{STUB}", f"-I{os.path.join(CSRC, 'tc')}",
+                    f"-I{os.path.join(CSRC, 'feeder')}", f"-I{os.path.join(ROOT, 'include')}", srcs[0], srcs[1], obj, "-Wl,-z,defs", "-o", so], so)
     L = C.CDLL(so)
     L.feeder_open.restype = C.c_void_p
     L.feeder_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
@@ -161,7 +162,7 @@ def test_mid_stream_resolution_change_is_sized_from_the_frame(feeder, oracle):
 
 # ------------------------------------------------------------------------------------------------------------------------
 # the Python binding of the feeder (PyFfmpegDecoder, reference: src/PyNvCodec/src/PyFFMpegDecoder.cpp:37-70,220-268): the bindings are
-# built a second time with -DVPF_WITH_LIBAV against the stub (tests/_build/pynvcodec_stubav) and driven in a subprocess (a process
+# built a second time with -DVPF_WITH_LIBAV against the stub (videoprocessingframework_amd/build/pynvcodec_stubav) and driven in a subprocess (a process
 # can hold only one module named _PyNvCodec)
 # ------------------------------------------------------------------------------------------------------------------------
 _DECODER_SCRIPT = r"""
@@ -205,9 +206,7 @@ def _run_decoder(gpu):
 
     from videoprocessingframework_amd import _build_bindings as bb
 
-    base = os.path.join(ROOT, "tests", "_build", "pynvcodec_stubav")
-    if os.path.isdir("/root/reference") or not os.path.isdir(base):   # build container: (re)build; GPU box: the prebuilt variant travels
-        base = bb.build_stub_libav_variant()
+    base = bb.build_stub_libav_variant()   # incremental: a no-op when build() already made it
     r = subprocess.run([sys.executable, "-c", _DECODER_SCRIPT.format(base=base, gpu=gpu)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][0][7:])

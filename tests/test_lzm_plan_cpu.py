@@ -5,7 +5,6 @@
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +14,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lzp():
-    from conftest import native_test_build
+    from conftest import compile_to, native_test_build
     extra, out = native_test_build()
     so = os.path.join(out, "liblzm_plan_capi.so")
     src = os.path.join(ROOT, "tests", "c", "lzm_plan_capi.cpp")
     hdr = os.path.join(ROOT, "videoprocessingframework_amd", "csrc")
     deps = [src, os.path.join(hdr, "vpf_lzm_plan.h"), os.path.join(hdr, "vpf_plan_bounds.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", *extra, "-I", hdr, src, "-o", so, "-lm", "-pthread"], check=True)
+        compile_to(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", *extra, "-I", hdr, src, "-o", so, "-lm", "-pthread"], so)
     L = C.CDLL(so)
     L.lzp_plan.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.lzp_cache_new.restype = C.c_void_p

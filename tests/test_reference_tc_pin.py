@@ -9,8 +9,12 @@ oracle/_ref/libtc_ref.so.  These tests drive that library and this repo's PyNvCo
 
 What stays unpinned is NPP's arithmetic (closed source): the table NPP-function -> (matrix, range) below is SURVEY §8c's
 reading of NVIDIA's public NPP documentation.
+
+What the reference library answers is also recorded in tests/golden/reference_tc_pins.json (tests/golden/make_reference_pins.py): where
+oracle/_ref is absent the recording stands in for it; where it is present every live answer is checked against the recording as well.
 """
 import ctypes as C
+import json
 import os
 import sys
 
@@ -18,17 +22,19 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "_ref", "libtc_ref.so")
-if not os.path.exists(LIB):
-    pytest.skip("oracle/_ref/libtc_ref.so not built (needs /root/reference: make -C oracle ref_tc)", allow_module_level=True)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_tc_pins.json")
 sys.path.insert(0, os.path.join(ROOT, "videoprocessingframework_amd"))
 nvc = pytest.importorskip("PyNvCodec")
 
-REF = C.CDLL(LIB)
-REF.ref_convert_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
-REF.ref_surface_geometry.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.c_int]
+REF = C.CDLL(LIB) if os.path.exists(LIB) else None  # built by oracle/Makefile (`ref_tc`) where the reference tree is
+if REF is not None:
+    REF.ref_convert_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    REF.ref_surface_geometry.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.c_int]
+_PINS = []
 NAMES = "UNDEFINED Y RGB NV12 YUV420 RGB_PLANAR BGR YCBCR YUV444 RGB_32F RGB_32F_PLANAR YUV422 P10 P12 YUV444_10bit YUV420_10bit".split()
 PF = nvc.PixelFormat
 BT601, BT709, MPEG, JPEG = 0, 1, 0, 1
+SEPARATE_PLANES = ("YUV420", "YCBCR", "YUV422")  # the reference allocates these planes one by one
 
 # NPP entry point -> colour model, per NVIDIA's NPP documentation (SURVEY §8c [A1][A4][A5]): the "YCbCr" family is the
 # limited-range (MPEG) BT.601 model, the "YUV" family the full-range one, 709CSC limited / 709HDTV full range BT.709.
@@ -51,10 +57,40 @@ RELAYOUT = {  # no arithmetic on the samples: only accept / refuse is compared
     "nppiCopy_32f_C3P3R_Ctx", "nppiDivC_16u_C1RSfs_Ctx", "nppiConvert_16u8u_C1R_Ctx", "nppiRGBToGray_8u_C3C1R_Ctx", ""}
 
 
-def ref_probe(i, o, cs, cr):
+def live_probe(i, o, cs, cr):
     buf, seen = C.create_string_buffer(1024), C.c_int(-1)
     r = REF.ref_convert_probe(i, o, 64, 32, cs, cr, buf, 1024, C.byref(seen))
-    return r, buf.value.decode(), seen.value
+    return [r, buf.value.decode(), seen.value]
+
+
+def live_geometry(f, w, h):
+    out = (C.c_int64 * 64)()
+    rc = REF.ref_surface_geometry(f, w, h, out, 64)
+    v = [int(x) for x in out]
+    if rc == 0 and NAMES[f] in SEPARATE_PLANES:
+        for p in range(1, v[0]):
+            v[3 + 7 * p + 4] = None  # plane p's offset from plane 0: a difference of two heap addresses, not a property of the format
+    return [rc, v]
+
+
+def recorded(kind, key, live):
+    """the recorded answer of the reference library; checked against the live library where there is one"""
+    if not _PINS:
+        _PINS.append(json.load(open(GOLDEN)))
+    want = _PINS[0][kind][key]
+    if REF is not None:
+        assert live() == want, f"the recorded reference answer {kind} {key} is stale: tests/golden/make_reference_pins.py"
+    return want
+
+
+def ref_probe(i, o, cs, cr):
+    """(1 accepted / 0 refused / -1 no such converter, the NPP entry points it called, the format it produced)"""
+    return tuple(recorded("probe", f"{i},{o},{cs},{cr}", lambda: live_probe(i, o, cs, cr)))
+
+
+def ref_geometry(f, w, h):
+    """(0 / -1, the 64 values ref_surface_geometry fills in)"""
+    return tuple(recorded("geometry", f"{f},{w},{h}", lambda: live_geometry(f, w, h)))
 
 
 def test_converter_pairs_and_colour_model_selection_match_the_reference(capfd):
@@ -94,10 +130,10 @@ def test_converter_pairs_and_colour_model_selection_match_the_reference(capfd):
 def test_surface_geometry_matches_the_reference(w, h):
     nvc._UseHostAllocator(True)
     try:
-        out = (C.c_int64 * 64)()
         for f in range(1, 16):
             name = NAMES[f]
-            assert REF.ref_surface_geometry(f, w, h, out, 64) == 0, name
+            rc, out = ref_geometry(f, w, h)
+            assert rc == 0, name
             s = nvc.Surface.Make(getattr(PF, name), w, h, context=0)
             n = int(out[0])
             assert s.NumPlanes() == n, name
@@ -113,16 +149,16 @@ def test_surface_geometry_matches_the_reference(w, h):
                 assert s.HostSize() == out[1], (name, s.HostSize(), out[1])
                 assert s.PlanePtr(0).ElemSize() == out[2], name
             for p in range(n):
-                rw, rh, rpitch, rwb, roff, pw, ph = (int(v) for v in out[3 + 7 * p:10 + 7 * p])
+                rw, rh, rpitch, rwb, roff, pw, ph = out[3 + 7 * p:10 + 7 * p]
                 assert (s.Width(p), s.Height(p)) == (rw, rh), (name, p)
                 # plane p of a single-allocation format starts a whole number of rows after plane 0 in both libraries
-                if roff and roff % rpitch == 0 and name not in ("YUV420", "YCBCR", "YUV422"):
+                if name not in SEPARATE_PLANES and roff and roff % rpitch == 0:
                     mine = s.PlanePtr(p).GpuMem() - s.PlanePtr(0).GpuMem()
                     assert mine % s.Pitch(0) == 0 and mine // s.Pitch(0) == roff // rpitch, (name, p)
                 if p == 0:  # raw plane object: width in elements of the plane (RGB: 3W), height of the whole allocation
                     assert (s.PlanePtr(0).Width(), s.PlanePtr(0).Height()) == (pw, ph), (name, "raw plane 0")
         for f in (16, 17):  # NV12_PLANAR, GRAY12: no Surface class in the reference's factory
-            assert REF.ref_surface_geometry(f, w, h, out, 64) == -1
+            assert ref_geometry(f, w, h)[0] == -1
     finally:
         nvc._UseHostAllocator(False)
 
@@ -133,12 +169,13 @@ def test_odd_sizes_are_a_documented_divergence():
     the picture without chroma); this repo rounds chroma up so every luma sample has a chroma sample"""
     nvc._UseHostAllocator(True)
     try:
-        out = (C.c_int64 * 64)()
-        assert REF.ref_surface_geometry(3, 7, 5, out, 64) == 0      # NV12
+        rc, out = ref_geometry(3, 7, 5)
+        assert rc == 0      # NV12
         assert (out[3], out[4], out[10], out[11]) == (7, 4, 7, 2) and out[1] == 49
         s = nvc.Surface.Make(PF.NV12, 7, 5, context=0)
         assert (s.Width(0), s.Height(0), s.Width(1), s.Height(1)) == (7, 5, 7, 3)
-        assert REF.ref_surface_geometry(4, 7, 5, out, 64) == 0      # YUV420
+        rc, out = ref_geometry(4, 7, 5)
+        assert rc == 0      # YUV420
         assert (out[10], out[11]) == (3, 2) and out[1] == 35 + 2 * 6
         s = nvc.Surface.Make(PF.YUV420, 7, 5, context=0)
         assert (s.Width(1), s.Height(1)) == (4, 3) and s.HostSize() == 35 + 2 * 12

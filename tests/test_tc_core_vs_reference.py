@@ -1,17 +1,21 @@
 """Token/Task state machine: ours (videoprocessingframework_amd/csrc/tc/TC_CORE.hpp) against the REFERENCE's own
 TC_CORE compiled from /root/reference/src/TC/TC_CORE by oracle/Makefile into oracle/_ref/libtc_core_ref.so — the one
 part of the reference that builds without CUDA/NPP/libav.  The same C shim (oracle/ref_shim.cpp) is compiled against
-both headers and driven through identical random call sequences."""
+both headers and driven through identical random call sequences.  What the reference library does is also recorded in
+tests/golden/reference_tc_core_traces.json (tests/golden/make_reference_pins.py): where oracle/_ref is absent, ours is compared with the
+recording; where it is present, the live library is checked against the recording as well."""
 import ctypes as C
+import json
 import os
 import random
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libtc_core_ref.so")
 OURS = os.path.join(ROOT, "tests", "_build", "libtc_core_ours.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_tc_core_traces.json")
+SEEDS = range(12)
 
 
 def _load(path):
@@ -38,18 +42,26 @@ def _load(path):
     return L
 
 
-@pytest.fixture(scope="module")
-def libs():
+def load_ref():
+    """the reference's own TC_CORE where oracle/_ref holds it (oracle.build() makes it where the reference tree is), else None"""
     if not os.path.exists(REF):
         import oracle
-        oracle.build()
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref not built and /root/reference absent")
+        try:
+            oracle.build()
+        except Exception:  # noqa: BLE001  (no reference tree here: the recording stands in)
+            pass
+    return _load(REF) if os.path.exists(REF) else None
+
+
+@pytest.fixture(scope="module")
+def libs():
+    """(this repo's TC_CORE, the reference's or None)"""
     os.makedirs(os.path.dirname(OURS), exist_ok=True)
     src = os.path.join(ROOT, "oracle", "ref_shim.cpp")
     inc = os.path.join(ROOT, "videoprocessingframework_amd", "csrc", "tc")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", f"-I{inc}", src, "-o", OURS])
-    return _load(REF), _load(OURS)
+    from conftest import compile_to
+    compile_to(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", f"-I{inc}", src, "-o", OURS], OURS)
+    return _load(OURS), load_ref()
 
 
 class Driver:
@@ -94,25 +106,44 @@ class Driver:
             self.L.ref_token_del(t)
 
 
-@pytest.mark.parametrize("seed", range(12))
-def test_random_sequences_match_reference(libs, seed):
-    ref, ours = libs
+def _plain(v):
+    """an observable as JSON has it (tuples -> lists, the task name -> str)"""
+    if isinstance(v, (tuple, list)):
+        return [_plain(x) for x in v]
+    return v.decode() if isinstance(v, bytes) else v
+
+
+def trace(L, seed):
+    """every observable of random call sequence `seed` through library L: [initial state, [op, x, y, result] per call]"""
     rnd = random.Random(seed)
     ni, no = rnd.randint(0, 4), rnd.randint(0, 4)
     with_sync, run_ret = rnd.random() < 0.6, int(rnd.random() < 0.3)
-    a, b = Driver(ref, ni, no, with_sync, run_ret), Driver(ours, ni, no, with_sync, run_ret)
-    assert a.op("state") == b.op("state")
+    d = Driver(L, ni, no, with_sync, run_ret)
+    out = [_plain(d.op("state"))]
     for _ in range(300):
         name = rnd.choice(["set_in", "set_out", "get_in", "get_out", "clear_in", "clear_out", "exec", "state"])
         x, y = rnd.randint(-1, 5), rnd.randint(0, 6)  # token index (-1 = nullptr), slot (may be out of range)
-        assert a.op(name, x, y) == b.op(name, x, y), (name, x, y)
-    a.close()
-    b.close()
+        out.append([name, x, y, _plain(d.op(name, x, y))])
+    d.close()
+    return out
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_random_sequences_match_reference(libs, seed):
+    ours, ref = libs
+    want = json.load(open(GOLDEN))[str(seed)]
+    if ref is not None:
+        assert trace(ref, seed) == want, "the recorded reference traces are stale: tests/golden/make_reference_pins.py"
+    got = trace(ours, seed)
+    assert got[0] == want[0]
+    for g, w in zip(got[1:], want[1:]):
+        assert g == w, w[:3]
+    assert len(got) == len(want)
 
 
 def test_execute_semantics(libs):
     """Execute = Run then the sync callback, only when both callback and args are set (Task.cpp:50-57)."""
-    for L in libs:
+    for L in (L for L in libs if L is not None):
         d = Driver(L, 2, 1, True, 0)
         assert d.op("exec") == (0, 1, 1) and d.op("exec") == (0, 2, 2)
         d.close()

@@ -13,7 +13,7 @@ any-alignment kernel family (tuning 9) — and `--dump-crc FILE` writes the CRC-
 tests/test_clip_pipeline.py compares with the oracle (the oracle is test infrastructure: this tool never imports it).
 
 The decoder exists only where the bindings were built against libav (PyNvCodec.HAVE_LIBAV; this image has none).  `--pynvcodec DIR` points
-at another build of the package — the test suite passes tests/_build/pynvcodec_stubav, whose decoder is linked against the stub libav of
+at another build of the package — the test suite passes videoprocessingframework_amd/build/pynvcodec_stubav, whose decoder is linked against the stub libav of
 tests/libav_stub and "decodes" synthetic clips (`--clip synth:w=..,h=..,n=..`).
 
   python tools/clip_pipeline.py --clip tests/test.mp4 [--frames N] [--decode-only] [--gpu 0]

@@ -14,6 +14,7 @@ TC = os.path.join(B.CSRC, "tc")
 BND = os.path.join(B.CSRC, "bindings")
 OUT_DIR = os.path.join(B.PKG, "PyNvCodec")
 SOURCES = [os.path.join(TC, "MemoryInterfaces.cpp"), os.path.join(TC, "Tasks.cpp"), os.path.join(BND, "PyNvCodec.cpp")]
+STUB_BASE = os.path.join(B.OBJ, "pynvcodec_stubav")  # the stub-libav test variant (build_stub_libav_variant)
 
 
 def module_path() -> str:
@@ -68,18 +69,24 @@ def build(force: bool = False):
 
 def build_stub_libav_variant(force: bool = False) -> str:
     """TEST BUILD (tests/test_feeder_stub_libav.py): the same bindings with the optional PyFfmpegDecoder section compiled in
-    (-DVPF_WITH_LIBAV) and linked against tests/libav_stub/stub_libav.c instead of FFmpeg, into tests/_build/pynvcodec_stubav/PyNvCodec/.
-    Returns the directory to put on sys.path.  Never part of the product build."""
+    (-DVPF_WITH_LIBAV) and linked against tests/libav_stub/stub_libav.c instead of FFmpeg, into STUB_BASE/PyNvCodec/ (beside the build
+    objects: nothing is generated under tests/).  Returns the directory to put on sys.path.  Never part of the product build."""
+    import fcntl
     import shutil
     import subprocess
 
     stub = os.path.join(B.ROOT, "tests", "libav_stub")
-    base = os.path.join(B.ROOT, "tests", "_build", "pynvcodec_stubav")
+    base = STUB_BASE
     pkg = os.path.join(base, "PyNvCodec")
     os.makedirs(pkg, exist_ok=True)
-    shutil.copyfile(os.path.join(OUT_DIR, "__init__.py"), os.path.join(pkg, "__init__.py"))
-    stub_o = os.path.join(base, "stub_libav.o")
-    if force or B._newer(stub_o, [os.path.join(stub, "stub_libav.c")]):
-        subprocess.check_call(["gcc", "-std=c99", "-O1", "-fPIC", f"-I{stub}", "-c", os.path.join(stub, "stub_libav.c"), "-o", stub_o])
-    _build_module(pkg, "tcstub_", list(SOURCES) + [os.path.join(B.CSRC, "feeder", "FfmpegFeeder.cpp"), stub_o], ["-DVPF_WITH_LIBAV", f"-I{stub}"], [], B.PKG, force)
+    with open(os.path.join(base, ".build.lock"), "w") as lock:  # pytest-xdist workers must not rebuild (or rewrite) it at the same time
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        init_src, init_dst = os.path.join(OUT_DIR, "__init__.py"), os.path.join(pkg, "__init__.py")
+        if force or B._newer(init_dst, [init_src]):
+            shutil.copyfile(init_src, init_dst)
+        stub_o = os.path.join(base, "stub_libav.o")
+        if force or B._newer(stub_o, [os.path.join(stub, "stub_libav.c")]):
+            subprocess.check_call(["gcc", "-std=c99", "-O1", "-fPIC", f"-I{stub}", "-c", os.path.join(stub, "stub_libav.c"), "-o", stub_o])
+        _build_module(pkg, "tcstub_", list(SOURCES) + [os.path.join(B.CSRC, "feeder", "FfmpegFeeder.cpp"), stub_o], ["-DVPF_WITH_LIBAV", f"-I{stub}"], [],
+                      "$ORIGIN/../../..", force)  # STUB_BASE/PyNvCodec -> the package's libvpfhip.so, wherever the tree lies
     return base
