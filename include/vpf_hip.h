@@ -218,6 +218,31 @@ VPF_API vpf_status vpf_convert_resize_batch(const vpf_exec* exec, int src_fmt, i
                                             int color_range, vpf_size src_size, vpf_size dst_size, uint32_t n,
                                             const vpf_frame_io* frames);
 
+/*
+ * Fused NV12 / YUV420 -> bilinear resize -> normalised planar tensor (what a DNN consumes: float [N, 3, H, W]) in one pass.
+ * For every destination pixel and channel c, with u8[c] the byte vpf_convert_resize(..., RGB_PLANAR, ...) writes:
+ *   out[c] = round_to_dtype(fmaf(u8[c], scale[c], bias[c]))     one fp32 fused multiply-add, then round-to-nearest-even to f16 / bf16
+ * (torchvision's normalize(mean, std) after a division by 255: scale = 1 / (255 std), bias = -mean / std, both rounded to fp32).
+ * dst[0..2] are the three planes of the frame in output channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c] belong to
+ * output channel c): dst_size.width elements per row, `pitch` in bytes.  Plane pointers and pitches must be multiples of the element size
+ * and pitch >= width x element size (contiguous NCHW, a slice of a larger batch tensor and padded rows are all such planes).
+ * Unknown dtype or flag bits: VPF_ERR_UNSUPPORTED; a non-finite scale / bias or a misaligned plane: VPF_ERR_BAD_ARG.
+ */
+typedef enum vpf_tensor_dtype { VPF_TENSOR_F32 = 0, VPF_TENSOR_F16 = 1, VPF_TENSOR_BF16 = 2 } vpf_tensor_dtype;
+#define VPF_TENSOR_BGR 1u /* vpf_tensor_norm.flags: channel order B G R */
+typedef struct vpf_tensor_norm {
+  float scale[3];
+  float bias[3];
+  uint32_t dtype; /* vpf_tensor_dtype */
+  uint32_t flags; /* 0 or VPF_TENSOR_BGR */
+} vpf_tensor_norm;
+VPF_API vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                             const vpf_plane src[3], vpf_size dst_size, const vpf_plane dst[3], const vpf_tensor_norm* norm);
+/* The same over `n` same-shape frames; frames per dispatch as vpf_convert_resize_batch, counted with the tensor's real bytes (source +
+ * 3 x width x height x element size per frame). */
+VPF_API vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                   vpf_size dst_size, uint32_t n, const vpf_frame_io* frames, const vpf_tensor_norm* norm);
+
 VPF_API const char* vpf_status_string(int status);
 VPF_API const char* vpf_version(void);
 /* hipGetDeviceCount; 0 when no GPU / no driver (never fails). Replaces GetNumGpus

@@ -113,3 +113,50 @@ def surface_from_tensor(tensor: torch.Tensor, fmt=None):
     s = nvc.Surface.Wrap(f, int(w), int(h), int(pitch), tensor.data_ptr())
     s._owner = tensor
     return s
+
+
+_TENSOR_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # vpf_tensor_dtype
+
+
+def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
+    """NV12 / YUV420 surfaces -> the normalised float tensor [N, 3, H, W] a DNN consumes, in one pass of the fused kernels
+    (PySurfaceConvertResizer.ExecuteToTensor): the RGB_PLANAR bytes of resizer.ExecuteBatch, divided by 255 and normalised with
+    torchvision's mean / std (one fp32 fma per element, scale = 1 / (255 std), bias = -mean / std), rounded to `dtype` (float32, float16,
+    bfloat16).  mean / std are per output channel (B G R order when bgr=True).
+
+    `out`: a tensor to write into (dtype, device and shape must match, the last dimension contiguous; row, plane and frame strides are
+    free: a slice of a larger batch or padded rows work), else a new one on torch's current device.  The kernel runs on the resizer's
+    stream after torch's current stream has reached this call, and torch's current stream waits for it: the result can be used on the
+    current stream right away, no host synchronisation.  The surfaces themselves are ordered as for every Execute (the caller's business)."""
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"to_normalized_tensor: dtype must be one of {list(_TENSOR_DTYPES)}")
+    surfaces = list(surfaces)
+    n = len(surfaces)
+    w, h = resizer.DstSize()
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"to_normalized_tensor: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"to_normalized_tensor: out needs unit stride along W and non-overlapping rows, planes and frames, got strides "
+                             f"{out.stride()}")
+    if n == 0:
+        return out
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+        ok = resizer.ExecuteToTensor(surfaces, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
+                                     bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError("to_normalized_tensor: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out

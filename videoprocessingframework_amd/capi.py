@@ -29,7 +29,10 @@ EXPORTS = [
     "vpf_convert", "vpf_convert_batch", "vpf_convert_supported", "vpf_resize", "vpf_remap", "vpf_convert_resize",
     "vpf_convert_resize_batch", "vpf_resize_batch", "vpf_remap_batch", "vpf_resize_ws", "vpf_resize_batch_ws", "vpf_resize_workspace_bytes",
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
+    "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch",
 ]
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+TENSOR_BGR = 1
 
 
 class Workspace(C.Structure):
@@ -51,6 +54,35 @@ class Exec(C.Structure):
 
 class FrameIO(C.Structure):
     _fields_ = [("src", Plane * 3), ("dst", Plane * 3)]
+
+
+class TensorNorm(C.Structure):
+    """vpf_tensor_norm: out[c] = round_to_dtype(fmaf(u8[c], scale[c], bias[c])) (include/vpf_hip.h)"""
+    _fields_ = [("scale", C.c_float * 3), ("bias", C.c_float * 3), ("dtype", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def norm_params(mean, std):
+    """torchvision's normalize(mean, std) after a division by 255 as (scale, bias): scale = 1 / (255 std), bias = -mean / std, computed in
+    double and rounded to fp32 (the ctypes fields round).  std must be > 0 and every value finite."""
+    import math
+
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std need three values each")
+    if not all(math.isfinite(v) for v in mean + std) or min(std) <= 0:
+        raise ValueError("mean must be finite and std finite and > 0")
+    return [1.0 / (255.0 * s) for s in std], [-m / s for m, s in zip(mean, std)]
+
+
+def make_tensor_norm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None) -> TensorNorm:
+    """vpf_tensor_norm from mean / std (norm_params) or from raw scale / bias (passed through unchecked: the library validates them)"""
+    if scale is None:
+        scale, bias = norm_params(mean, std)
+    n = TensorNorm()
+    for c in range(3):
+        n.scale[c], n.bias[c] = scale[c], bias[c]
+    n.dtype, n.flags = dtype, TENSOR_BGR if bgr else 0
+    return n
 
 
 class VpfError(RuntimeError):
@@ -88,6 +120,9 @@ def lib() -> C.CDLL:
         L.vpf_resize_batch_ws.argtypes = [PE, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, C.POINTER(Workspace)]
         L.vpf_resize_workspace_bytes.argtypes = [C.c_int, C.c_int, Size, Size]
         L.vpf_resize_workspace_bytes.restype = C.c_uint64
+        PN = C.POINTER(TensorNorm)
+        L.vpf_convert_resize_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, Size, PP, PN]
+        L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
         L.vpf_status_string.argtypes = [C.c_int]
         L.vpf_status_string.restype = C.c_char_p
         L.vpf_version.restype = C.c_char_p
@@ -233,4 +268,20 @@ def convert_resize_batch(ex: Exec, src_fmt, dst_fmt, cs, cr, sw, sh, dw, dh, bat
                                         len(batch) if n is None else n, batch)
     if check:
         _check(st, "vpf_convert_resize_batch")
+    return st
+
+
+def convert_resize_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, src, dw, dh, dst, norm: TensorNorm, check=True) -> int:
+    """dst: the three planes (ptr, pitch in bytes) of the tensor frame in output channel order"""
+    st = lib().vpf_convert_resize_tensor(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), planes(src), Size(dw, dh), planes(dst), C.byref(norm))
+    if check:
+        _check(st, "vpf_convert_resize_tensor")
+    return st
+
+
+def convert_resize_tensor_batch(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, batch, norm: TensorNorm, n=None, check=True) -> int:
+    st = lib().vpf_convert_resize_tensor_batch(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), Size(dw, dh), len(batch) if n is None else n, batch,
+                                               C.byref(norm))
+    if check:
+        _check(st, "vpf_convert_resize_tensor_batch")
     return st

@@ -10,6 +10,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -126,7 +127,7 @@ class PySurfaceConvertResizer {
 
 public:
   PySurfaceConvertResizer(uint32_t sw, uint32_t sh, Pixel_Format in, uint32_t dw, uint32_t dh, Pixel_Format out, HipContext ctx, HipStream str)
-      : out_fmt_(out) {
+      : out_fmt_(out), task_dst_w_(dw), task_dst_h_(dh) {
     task_.reset(ConvertResizeSurface::Make(sw, sh, in, dw, dh, out, ctx, str));
     ctx_buf_.reset(Buffer::MakeOwnMem(sizeof(ColorspaceConversionContext)));
   }
@@ -151,6 +152,43 @@ public:
     for (auto& d : dst) b.push_back(d.get());
     return TASK_EXEC_SUCCESS == task_->RunBatch(a.data(), b.data(), (uint32_t)a.size(), cc.get());
   }
+  // additive: n surfaces -> a normalised planar tensor [n, 3, dh, dw] of f32 / f16 / bf16 at device address `dst` (vpf_convert_resize_tensor):
+  // element (i, c, y, x) at dst + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW).  mean / std are
+  // torchvision's (values of [0, 1] pixels), per output channel; scale = 1 / (255 std) and bias = -mean / std are computed in double.
+  bool ExecuteToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
+                       const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
+                       uint64_t plane_stride, uint64_t frame_stride) {
+    if (mean.size() != 3 || std.size() != 3) throw std::invalid_argument("mean and std need three values each");
+    vpf_tensor_norm norm;
+    std::memset(&norm, 0, sizeof(norm));
+    for (int c = 0; c < 3; c++) {
+      if (!std::isfinite(mean[c]) || !std::isfinite(std[c]) || !(std[c] > 0.0)) throw std::invalid_argument("mean must be finite and std finite and > 0");
+      norm.scale[c] = (float)(1.0 / (255.0 * std[c]));
+      norm.bias[c] = (float)(-mean[c] / std[c]);
+      if (!std::isfinite(norm.scale[c]) || !std::isfinite(norm.bias[c])) throw std::invalid_argument("mean / std give a scale or bias beyond fp32");
+    }
+    norm.dtype = dtype;
+    norm.flags = bgr ? VPF_TENSOR_BGR : 0u;
+    if (src.empty() || !dst) return false;
+    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
+    if (!row_pitch) row_pitch = dw * elem;
+    if (!plane_stride) plane_stride = dh * row_pitch;
+    if (!frame_stride) frame_stride = 3 * plane_stride;
+    if (row_pitch > 0xffffffffull) return false;
+    std::vector<Surface*> a;
+    std::vector<vpf_plane> planes(3 * src.size());
+    for (size_t i = 0; i < src.size(); i++) {
+      a.push_back(src[i].get());
+      for (int c = 0; c < 3; c++) {
+        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
+        planes[3 * i + c].pitch = (uint32_t)row_pitch;
+        planes[3 * i + c].reserved = 0;
+      }
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensor(a.data(), (uint32_t)a.size(), planes.data(), norm, cc.get());
+  }
+  size_t GetStream() const { return (size_t)task_->GetStream(); }
+  uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
 
 class PySurfaceResizer {
@@ -575,7 +613,12 @@ PYBIND11_MODULE(_PyNvCodec, m) {
       .def("Execute", &PySurfaceConvertResizer::Execute, py::arg("src"), py::arg("cc_ctx") = nullptr, py::keep_alive<0, 1>(),
            py::call_guard<py::gil_scoped_release>())
       .def("ExecuteBatch", &PySurfaceConvertResizer::ExecuteBatch, py::arg("src"), py::arg("dst"), py::arg("cc_ctx") = nullptr,
-           py::call_guard<py::gil_scoped_release>());
+           py::call_guard<py::gil_scoped_release>())
+      .def("ExecuteToTensor", &PySurfaceConvertResizer::ExecuteToTensor, py::arg("src"), py::arg("dst"), py::arg("dtype"), py::arg("mean"),
+           py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
+      .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 
   py::class_<PySurfaceResizer>(m, "PySurfaceResizer")
       .def(py::init([](uint32_t w, uint32_t h, Pixel_Format f, uint32_t gpu) { return new PySurfaceResizer(w, h, f, ctx_of((int)gpu), str_of((int)gpu)); }),

@@ -35,6 +35,62 @@ VPF_DEV void texel_rgb(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t x, uin
   rgb[2] = (float)sat_rne(__builtin_fmaf(yf, c.cy, k.bc));
 }
 
+// ------------------------------------------------------------------------------------------
+// The planar-tensor destination (FC_TENSOR, vpf_convert_resize_tensor): the store epilogue of every fused family.  Each family hands over
+// the 8-bit values FC_PLANAR would store (as floats: the same truncation, rounding or byte extraction that family uses for its bytes);
+// here they go through ONE fp32 fma per channel and a round-to-nearest-even conversion (v_cvt_f16_f32 under the default mode / the
+// compiler's v_cvt_pk_bf16_f32), then leave as 16 B (f32) or 8 B (f16 / bf16) per lane and channel where the row allows, else one element
+// at a time.  The dtype is a kernarg: a wave-uniform branch, one instantiation per family for the three dtypes.
+// ------------------------------------------------------------------------------------------
+template <int CAP>
+VPF_DEV TensorEpi epi_of(const BatchArgsT<CAP>&) { return TensorEpi{}; }  // 8-bit launches: never read
+template <int CAP>
+VPF_DEV TensorEpi epi_of(const BatchArgsTE<CAP>& a) { return a.e; }
+// `row` = byte address of row y of channel plane `ch` at column 0; u[] = the 8-bit values of columns x0 .. x0 + 3 (nv of them valid)
+template <bool NT>
+VPF_DEV void tensor_store4(uint8_t* row, uint32_t x0, const float u[4], const TensorEpi& e, int ch, bool vec, uint32_t nv) {
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) v[k] = __builtin_fmaf(u[k], e.scale[ch], e.bias[ch]);
+  if (e.dtype == VPF_TENSOR_F32) {
+    float* p = reinterpret_cast<float*>(row) + x0;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if (vec) stg<NT, f32x4>(p, f32x4{v[0], v[1], v[2], v[3]});
+    else for (uint32_t i = 0; i < nv; i++) p[i] = v[i];
+    return;
+  }
+  uint32_t h[4];
+  if (e.dtype == VPF_TENSOR_F16) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) h[k] = __builtin_bit_cast(uint16_t, (_Float16)v[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) h[k] = __builtin_bit_cast(uint16_t, (__bf16)v[k]);
+  }
+  uint16_t* p = reinterpret_cast<uint16_t*>(row) + x0;
+  if (vec) stg<NT, u32x2>(p, u32x2{h[0] | h[1] << 16, h[2] | h[3] << 16});
+  else for (uint32_t i = 0; i < nv; i++) p[i] = (uint16_t)h[i];
+}
+// eight consecutive f16 / bf16 elements per lane (k_convert_half): ONE 16-B store per lane, so a store instruction covers 1 KiB of the row
+// without holes (non-temporal, like the 8-bit planes).  (f32 rows go through LDS first: convert_half_task.)
+VPF_DEV void tensor_store8(uint8_t* row, uint32_t x0, const float u[8], const TensorEpi& e, int ch) {
+  uint32_t h[8];
+  if (e.dtype == VPF_TENSOR_F16) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) h[k] = __builtin_bit_cast(uint16_t, (_Float16)__builtin_fmaf(u[k], e.scale[ch], e.bias[ch]));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) h[k] = __builtin_bit_cast(uint16_t, (__bf16)__builtin_fmaf(u[k], e.scale[ch], e.bias[ch]));
+  }
+  stg<true, u32x4>(reinterpret_cast<uint16_t*>(row) + x0, u32x4{h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16});
+}
+// the FC_PLANAR store sections' values o[] (+ 0.5 added: truncation gives the byte) of channel ch, pixel k at o[k * stride]
+template <bool NT>
+VPF_DEV void tensor_store4_trunc(uint8_t* row, uint32_t x0, const float* o, int stride, const TensorEpi& e, int ch, bool vec, uint32_t nv) {
+  const float u[4] = {__builtin_truncf(o[0]), __builtin_truncf(o[stride]), __builtin_truncf(o[2 * stride]), __builtin_truncf(o[3 * stride])};
+  tensor_store4<NT>(row, x0, u, e, ch, vec, nv);
+}
+
 template <int SRC, int DST, class BA = BatchArgs>  // BA: the frame table's size (<= 32 / <= 128 frames: vpf_internal.h)
 __global__ __launch_bounds__(256) void k_convert_resize(const BA args, const Yuv2RgbCoef c, uint32_t sw,
                                                         uint32_t sh, uint32_t dw, uint32_t dh, float scx, float scy,
@@ -65,6 +121,9 @@ __global__ __launch_bounds__(256) void k_convert_resize(const BA args, const Yuv
       if (vec_ok && nv == 4) stg<false, uint32_t>(out, pack4_trunc(o[ch][0], o[ch][1], o[ch][2], o[ch][3]));
       else for (uint32_t i = 0; i < nv; i++) out[i] = (uint8_t)(uint32_t)(o[ch][i]);
     }
+  } else if constexpr (DST == FC_TENSOR) {
+    const TensorEpi e = epi_of(args);
+    for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, e, ch, vec_ok && nv == 4, nv);
   } else {
     const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -91,7 +150,7 @@ constexpr uint32_t kFusedRowBytes = 2048;  // cap; the launch sizes the strips f
 
 template <int SRC, int DST, int IT>
 VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, float scx,
-                                     float scy, int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by) {
+                                     float scy, int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by, const TensorEpi& te) {
   // per wave, NS strips of rowq x 16 B in dynamic LDS: 0,1 luma rows; 2,3 chroma rows (NV12: UV interleaved | YUV420: U);
   // 4,5 V rows (YUV420 only)
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -206,6 +265,11 @@ VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, u
         if (vec_ok && nv == 4) stg<false, uint32_t>(out, pack4<1>(v[ch][0], v[ch][1], v[ch][2], v[ch][3]));
         else for (uint32_t i = 0; i < nv; i++) out[i] = (uint8_t)sat_rne(v[ch][i]);
       }
+    } else if constexpr (DST == FC_TENSOR) {  // the byte is the conversion's own rounding here (v_cvt_pk_u8_f32)
+      for (int ch = 0; ch < 3; ch++) {
+        const float u[4] = {(float)sat_rne(v[ch][0]), (float)sat_rne(v[ch][1]), (float)sat_rne(v[ch][2]), (float)sat_rne(v[ch][3])};
+        tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec_ok && nv == 4, nv);
+      }
     } else {
       const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
       uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -258,6 +322,8 @@ VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, u
       if (vec_ok && nv == 4) stg<false, uint32_t>(out, pack4_trunc(o[ch][0], o[ch][1], o[ch][2], o[ch][3]));
       else for (uint32_t i = 0; i < nv; i++) out[i] = (uint8_t)(uint32_t)(o[ch][i]);
     }
+  } else if constexpr (DST == FC_TENSOR) {
+    for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, te, ch, vec_ok && nv == 4, nv);
   } else {
     const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -277,14 +343,14 @@ template <int SRC, int DST, int IT, class BA = BatchArgs>
 __global__ __launch_bounds__(256) void k_convert_resize_lds(const BA args, const Yuv2RgbCoef c, uint32_t sw, uint32_t sh,
                                                             uint32_t dw, uint32_t dh, float scx, float scy, int vec_ok, uint32_t rowq) {
   const BlockId b = picture_order();  // XCD-aware numbering (k_resize_common.h)
-  convert_resize_lds_task<SRC, DST, IT>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y);
+  convert_resize_lds_task<SRC, DST, IT>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y, epi_of(args));
 }
 // single-frame entry: scalar arguments, what the first loads need in front (see VPF_ONE_SRC_PARAMS in vpf_internal.h)
 template <int SRC, int DST, int IT>
 __global__ __launch_bounds__(256) void k_convert_resize_lds_one(const uint8_t* s0, const uint8_t* s1, uint32_t sp0, uint32_t sp1, uint32_t sw,
                                                                 uint32_t sh, uint32_t dw, uint32_t dh, float scx, float scy, uint32_t rowq,
                                                                 int vec_ok, const uint8_t* s2, uint32_t sp2, VPF_ONE_DST_PARAMS, const Yuv2RgbCoef c) {
-  convert_resize_lds_task<SRC, DST, IT>(VPF_ONE_FRAME, c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, blockIdx.x, blockIdx.y);
+  convert_resize_lds_task<SRC, DST, IT>(VPF_ONE_FRAME, c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, blockIdx.x, blockIdx.y, TensorEpi{});
 }
 
 
@@ -301,7 +367,7 @@ __global__ __launch_bounds__(256) void k_convert_resize_lds_one(const uint8_t* s
 // ------------------------------------------------------------------------------------------
 template <int SRC, int DST, int IT, int R>
 VPF_DEV void convert_resize_band_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, float scx,
-                                      float scy, int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by) {
+                                      float scy, int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by, const TensorEpi& te) {
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const uint32_t y0 = (by * 4 + wv) * R;
@@ -415,6 +481,9 @@ VPF_DEV void convert_resize_band_task(const FrameDesc& f, const Yuv2RgbCoef& c, 
           if (vec_ok && nv == 4) stg<false, uint32_t>(out, pack4_trunc(o[ch][0], o[ch][1], o[ch][2], o[ch][3]));
           else for (uint32_t i = 0; i < nv; i++) out[i] = (uint8_t)(uint32_t)(o[ch][i]);
         }
+      } else if constexpr (DST == FC_TENSOR) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, te, ch, vec_ok && nv == 4, nv);
       } else {
         constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
         uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -438,7 +507,7 @@ template <int SRC, int DST, int IT, int R, class BA = BatchArgs>
 __global__ __launch_bounds__(256) void k_convert_resize_band(const BA args, const Yuv2RgbCoef c, uint32_t sw, uint32_t sh,
                                                              uint32_t dw, uint32_t dh, float scx, float scy, int vec_ok, uint32_t rowq) {
   const BlockId b = picture_order();  // XCD-aware numbering (k_resize_common.h)
-  convert_resize_band_task<SRC, DST, IT, R>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y);
+  convert_resize_band_task<SRC, DST, IT, R>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y, epi_of(args));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -451,8 +520,8 @@ __global__ __launch_bounds__(256) void k_convert_resize_band(const BA args, cons
 // (packed) aligned destination rows.
 // ------------------------------------------------------------------------------------------
 template <int DST, int SRC>
-VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks) {
-  __shared__ u32x4 tile[DST == FC_PLANAR ? 1 : 4 * 96];  // 1.5 KiB per wave: 64 lanes x 24 packed bytes
+VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks, const TensorEpi& te) {
+  __shared__ u32x4 tile[DST == FC_PLANAR ? 1 : DST == FC_TENSOR ? 4 * 128 : 4 * 96];  // 1.5 KiB per wave: 64 lanes x 24 packed bytes (f32 tensor rows: 2 KiB)
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const uint32_t wt = blockIdx.x * 4 + wv;
   if (wt >= n_tasks) return;
@@ -490,6 +559,37 @@ VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_
 #pragma unroll
     for (int ch = 0; ch < 3; ch++)
       stg<true, u32x2>(f.d[ch] + (size_t)y * f.dp[ch] + xd, u32x2{gather4(o[ch][0], o[ch][1], o[ch][2], o[ch][3]), gather4(o[ch][4], o[ch][5], o[ch][6], o[ch][7])});
+  } else if constexpr (DST == FC_TENSOR) {  // eight whole pixels per lane (sw % 16 == 0), 16-B aligned rows: the vector stores only
+    // f32: 32 B per lane, so a 16-B store instruction would cover every other 16 B of the wave's 2 KiB and leave half-written lines to be
+    // merged (plain stores: 6.8 us per 4K -> 1080p frame against 3.9 for f16).  The wave's 512 pixels go through 2 KiB of LDS per channel
+    // instead and leave as two dense 1-KiB non-temporal stores, like the 8-bit rows.  f16 / bf16: one dense 16-B store per lane as they are.
+    u32x4* const t = tile + wv * 128;
+    const uint32_t xb = chunk * 512, dw = sw >> 1;  // the wave's first destination pixel; dw - xb is a multiple of 8
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      uint8_t* row = f.d[ch] + (size_t)y * f.dp[ch];
+      float u[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) u[i] = ubyte<1>(o[ch][i]);
+      if (te.dtype == VPF_TENSOR_F32) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = __builtin_fmaf(u[i], te.scale[ch], te.bias[ch]);
+        if (act) {
+          t[2 * lane] = u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+          t[2 * lane + 1] = u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])};
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int k = 0; k < 2; k++) {  // pixels xb + 4 idx .. + 3: written to LDS by lane idx / 2, which is active when they lie in the row
+          const uint32_t idx = 64 * k + lane;
+          if (xb + 4 * idx < dw) stg<true, u32x4>(reinterpret_cast<float*>(row) + xb + 4 * idx, t[idx]);
+        }
+        wave_lds_sync();  // this channel's LDS reads are done before the next channel's writes
+      } else if (act) {
+        tensor_store8(row, xd, u, te, ch);
+      }
+    }
   } else {
     constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint32_t* t = reinterpret_cast<uint32_t*>(tile + wv * 96);
@@ -515,12 +615,12 @@ VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_
 template <int DST, int SRC, class BA = BatchArgs>
 __global__ __launch_bounds__(256) void k_convert_half(const BA args, const Yuv2RgbCoef c, uint32_t sw, uint32_t dh,
                                                       uint32_t chunks_x, uint32_t n_tasks) {
-  convert_half_task<DST, SRC>(args.f[blockIdx.y], c, sw, dh, chunks_x, n_tasks);
+  convert_half_task<DST, SRC>(args.f[blockIdx.y], c, sw, dh, chunks_x, n_tasks, epi_of(args));
 }
 template <int DST, int SRC>  // single-frame entry: scalar arguments
 __global__ __launch_bounds__(256) void k_convert_half_one(VPF_ONE_SRC_PARAMS, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks,
                                                           VPF_ONE_DST_PARAMS, const Yuv2RgbCoef c) {
-  convert_half_task<DST, SRC>(VPF_ONE_FRAME, c, sw, dh, chunks_x, n_tasks);
+  convert_half_task<DST, SRC>(VPF_ONE_FRAME, c, sw, dh, chunks_x, n_tasks, TensorEpi{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -707,7 +807,7 @@ VPF_DEV void convert_unit8(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t cr
 }
 template <int SRC, int DST, int R>
 VPF_DEV void convert_strip_wg_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, float scx, float scy,
-                                   int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by) {
+                                   int vec_ok, uint32_t rowq, uint32_t bx, uint32_t by, const TensorEpi& te) {
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
   const uint32_t Y0 = by * (4 * R), xs = bx * 256;  // the grid covers the picture exactly: Y0 < dh, xs < dw
   const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
@@ -764,6 +864,9 @@ VPF_DEV void convert_strip_wg_task(const FrameDesc& f, const Yuv2RgbCoef& c, uin
         if (vec_ok && nv == 4) stg<false, uint32_t>(out, pack4_trunc(o[ch], o[3 + ch], o[6 + ch], o[9 + ch]));
         else for (uint32_t j = 0; j < nv; j++) out[j] = (uint8_t)(uint32_t)o[3 * j + ch];
       }
+    } else if constexpr (DST == FC_TENSOR) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec_ok && nv == 4, nv);
     } else {
       constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
       uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -785,11 +888,11 @@ __global__ __launch_bounds__(256) void k_convert_strip_wg(const BA args, const Y
                                                           float scx, float scy, int vec_ok, uint32_t rowq) {
   VPF_WAVE_TIMER(5);
   const BlockId b = picture_order();
-  convert_strip_wg_task<SRC, DST, R>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y);
+  convert_strip_wg_task<SRC, DST, R>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y, epi_of(args));
 }
 
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh,
-                                 uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh) {
+                                 uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te) {
   const float scx = (float)sw / (float)dw, scy = (float)sh / (float)dh;
   int vec_ok = 1;
   // up to 32 frames travel in the small frame table, more in the large one: two instantiations of every batch kernel (vpf_internal.h)
@@ -799,27 +902,40 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
 #define VPF_LAUNCH_BA(K, TARGS, GRID, BLK, LDS, ST, ...) do { \
     if (small) VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgs>), GRID, BLK, LDS, ST, as, __VA_ARGS__); \
     else VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsL>), GRID, BLK, LDS, ST, a, __VA_ARGS__); } while (0)
+  // FC_TENSOR: the same frame table with the epilogue behind it (BatchArgsTE); entries up to the next multiple of 8 are defined (vpf_abi.hip)
+  if (dst_fc == FC_TENSOR && (!te || n > (uint32_t)kMaxBatch)) return hipErrorInvalidValue;
+  const uint32_t ncopy = ((n + 7u) & ~7u) < (uint32_t)kMaxBatch ? ((n + 7u) & ~7u) : (uint32_t)kMaxBatch;
+#define VPF_LAUNCH_BAT(K, TARGS, GRID, BLK, LDS, ST, ...) do { \
+    if (small) { BatchArgsTE<kSmallBatch> t_; std::memcpy(t_.f, a.f, (ncopy < (uint32_t)kSmallBatch ? ncopy : (uint32_t)kSmallBatch) * sizeof(FrameDesc)); t_.e = *te; \
+                 VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kSmallBatch>>), GRID, BLK, LDS, ST, t_, __VA_ARGS__); } \
+    else { BatchArgsTE<kMaxBatch> t_; std::memcpy(t_.f, a.f, ncopy * sizeof(FrameDesc)); t_.e = *te; \
+           VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kMaxBatch>>), GRID, BLK, LDS, ST, t_, __VA_ARGS__); } } while (0)
+  // destination alignment the vector stores need: 4 px x element size per lane and plane (1-B elements: the 8-bit classes)
+  const uint32_t dmask = dst_fc == FC_TENSOR ? (te->dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
+  const int ndp = dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 3 : 1;
   const uint32_t rowb = lds_strip_bytes(1, sw, dw, a.f[0].s[0], a.f[0].sp[0], kFusedRowBytes);
   bool lds_ok = rowb != 0;
   for (uint32_t i = 0; i < n; i++) {
     const FrameDesc& f = a.f[i];
-    for (int k = 0; k < (dst_fc == FC_PLANAR ? 3 : 1); k++) vec_ok &= ((((uintptr_t)f.d[k] | f.dp[k]) & 3) == 0);
+    for (int k = 0; k < ndp; k++) vec_ok &= ((((uintptr_t)f.d[k] | f.dp[k]) & dmask) == 0);
     for (int k = 0; k < (src_fc == FC_NV12 ? 2 : 3); k++) lds_ok = lds_ok && !(((uintptr_t)f.s[k] | f.sp[k]) & 15);
   }
   // exact 2x from NV12: the quad-structured kernel (no taps, no gathers); tuning 40 / 9 keep the general kernels
   // (packed rows leave as 16-B stores: 3 * dw must be a multiple of 16)
-  if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
+  if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
     bool ok16 = true;
     for (uint32_t i = 0; i < n; i++)
-      for (int k = 0; k < (dst_fc == FC_PLANAR ? 3 : 1); k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (dst_fc == FC_PLANAR ? 7 : 15));
+      for (int k = 0; k < ndp; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (dst_fc == FC_PLANAR ? 7u : 15u));  // (FC_TENSOR: 16-B stores whatever the dtype)
     if (ok16) {
       const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
       dim3 hgrid((tasks + 3) / 4, n);
 #define VPF_HALF1(D, S) do { if (n == 1) VPF_LAUNCH((k_convert_half_one<D, S>), hgrid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), sw, dh, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c); \
                             else VPF_LAUNCH_BA(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks); } while (0)
-#define VPF_HALF(S) do { if (dst_fc == FC_RGB) VPF_HALF1(FC_RGB, S); else if (dst_fc == FC_BGR) VPF_HALF1(FC_BGR, S); else VPF_HALF1(FC_PLANAR, S); } while (0)
+#define VPF_HALFT(S) VPF_LAUNCH_BAT(k_convert_half, (FC_TENSOR, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
+#define VPF_HALF(S) do { if (dst_fc == FC_RGB) VPF_HALF1(FC_RGB, S); else if (dst_fc == FC_BGR) VPF_HALF1(FC_BGR, S); else if (dst_fc == FC_TENSOR) VPF_HALFT(S); else VPF_HALF1(FC_PLANAR, S); } while (0)
       if (src_fc == FC_NV12) VPF_HALF(FC_NV12); else VPF_HALF(FC_YUV420);
 #undef VPF_HALF
+#undef VPF_HALFT
 #undef VPF_HALF1
       return hipGetLastError();
     }
@@ -894,16 +1010,20 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
           dim3 wgrid((dw + 255) / 256, (dh + 4 * rw - 1) / (4 * rw), n);
 #define VPF_WG1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip_wg, (S, D, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
 #define VPF_WG(S, D) do { if (rw == 16) VPF_WG1(S, D, 16); else if (rw == 8) VPF_WG1(S, D, 8); else if (rw == 4) VPF_WG1(S, D, 4); else VPF_WG1(S, D, 2); } while (0)
-#define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else VPF_WG(S, FC_PLANAR); } while (0)
+#define VPF_WGT1(S, RR) VPF_LAUNCH_BAT(k_convert_strip_wg, (S, FC_TENSOR, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
+#define VPF_WGT(S) do { if (rw == 16) VPF_WGT1(S, 16); else if (rw == 8) VPF_WGT1(S, 8); else if (rw == 4) VPF_WGT1(S, 4); else VPF_WGT1(S, 2); } while (0)
+#define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else if (dst_fc == FC_TENSOR) VPF_WGT(S); else VPF_WG(S, FC_PLANAR); } while (0)
           if (src_fc == FC_NV12) VPF_WGD(FC_NV12); else VPF_WGD(FC_YUV420);
 #undef VPF_WGD
+#undef VPF_WGT
+#undef VPF_WGT1
 #undef VPF_WG
 #undef VPF_WG1
           return hipGetLastError();
         }
       }
 #ifdef VPF_LAB_FORMS
-      if (r && lds1 <= 64u * 1024u && conv_per_px <= 3.0) {
+      if (r && lds1 <= 64u * 1024u && conv_per_px <= 3.0 && dst_fc != FC_TENSOR) {  // (8-bit destinations only)
         dim3 sgrid((dw + 255) / 256, (dh + 4 * r - 1) / (4 * r), n);
 #define VPF_STRIP1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip, (S, D, RR), sgrid, dim3(256), lds1, st, c, sw, sh, dw, dh, scx, scy, vec_ok, (rowbytes / 16) | (srows << 16))
 #define VPF_STRIP(S, D) do { if (r == 8) VPF_STRIP1(S, D, 8); else if (r == 4) VPF_STRIP1(S, D, 4); else VPF_STRIP1(S, D, 2); } while (0)
@@ -928,9 +1048,13 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
       dim3 bgrid((dw + 255) / 256, (dh + 15) / 16, n);
 #define VPF_BAND1(S, D, I) VPF_LAUNCH_BA(k_convert_resize_band, (S, D, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
 #define VPF_BAND(S, D) do { if (rowb <= 1024) VPF_BAND1(S, D, 1); else VPF_BAND1(S, D, 2); } while (0)
-#define VPF_BANDD(S) do { if (dst_fc == FC_RGB) VPF_BAND(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_BAND(S, FC_BGR); else VPF_BAND(S, FC_PLANAR); } while (0)
+#define VPF_BANDT1(S, I) VPF_LAUNCH_BAT(k_convert_resize_band, (S, FC_TENSOR, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
+#define VPF_BANDT(S) do { if (rowb <= 1024) VPF_BANDT1(S, 1); else VPF_BANDT1(S, 2); } while (0)
+#define VPF_BANDD(S) do { if (dst_fc == FC_RGB) VPF_BAND(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_BAND(S, FC_BGR); else if (dst_fc == FC_TENSOR) VPF_BANDT(S); else VPF_BAND(S, FC_PLANAR); } while (0)
       if (src_fc == FC_NV12) VPF_BANDD(FC_NV12); else VPF_BANDD(FC_YUV420);
 #undef VPF_BANDD
+#undef VPF_BANDT
+#undef VPF_BANDT1
 #undef VPF_BAND
 #undef VPF_BAND1
       return hipGetLastError();
@@ -943,17 +1067,26 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
 #define VPF_GOL(S, D) do { if (rowb <= 1024) VPF_GOL1(S, D, 1); else VPF_GOL1(S, D, 2); } while (0)
 #define VPF_GO(S, D) VPF_LAUNCH_BA(k_convert_resize, (S, D), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
 #define VPF_PICK(S, D) do { if (lds_ok) VPF_GOL(S, D); else VPF_GO(S, D); } while (0)
-  if (src_fc == FC_NV12) {
+  // FC_TENSOR: the frame-table kernels for one frame too (no scalar-argument entry: the epilogue rides behind the table)
+#define VPF_GOLT(S) do { if (rowb <= 1024) VPF_LAUNCH_BAT(k_convert_resize_lds, (S, FC_TENSOR, 1), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); \
+                         else VPF_LAUNCH_BAT(k_convert_resize_lds, (S, FC_TENSOR, 2), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); } while (0)
+#define VPF_PICKT(S) do { if (lds_ok) VPF_GOLT(S); else VPF_LAUNCH_BAT(k_convert_resize, (S, FC_TENSOR), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok); } while (0)
+  if (dst_fc == FC_TENSOR) {
+    if (src_fc == FC_NV12) VPF_PICKT(FC_NV12); else if (src_fc == FC_YUV420) VPF_PICKT(FC_YUV420); else return hipErrorInvalidValue;
+  } else if (src_fc == FC_NV12) {
     if (dst_fc == FC_RGB) VPF_PICK(FC_NV12, FC_RGB); else if (dst_fc == FC_BGR) VPF_PICK(FC_NV12, FC_BGR); else VPF_PICK(FC_NV12, FC_PLANAR);
   } else if (src_fc == FC_YUV420) {
     if (dst_fc == FC_RGB) VPF_PICK(FC_YUV420, FC_RGB); else if (dst_fc == FC_BGR) VPF_PICK(FC_YUV420, FC_BGR); else VPF_PICK(FC_YUV420, FC_PLANAR);
   } else {
     return hipErrorInvalidValue;
   }
+#undef VPF_PICKT
+#undef VPF_GOLT
 #undef VPF_PICK
 #undef VPF_GO
 #undef VPF_GOL
 #undef VPF_GOL1
+#undef VPF_LAUNCH_BAT
 #undef VPF_LAUNCH_BA
 #undef VPF_UNPAREN
   return hipGetLastError();

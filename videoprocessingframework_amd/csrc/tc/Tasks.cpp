@@ -479,6 +479,31 @@ TaskExecStatus ConvertResizeSurface::RunBatch(Surface* const* ins, Surface* cons
   return TASK_EXEC_SUCCESS;
 }
 
+TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm,
+                                               const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensor");
+  if (!ins || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  std::vector<vpf_frame_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    Surface* s = ins[i];
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(s, io[i].src);
+    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_resize_tensor_batch(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+                                                        io.data(), &norm);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to convert + resize surfaces into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
+HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
+
 // ------------------------------------------------------------------------------------------ ResizeSurface
 struct ResizeSurface::Impl {
   Pixel_Format fmt;

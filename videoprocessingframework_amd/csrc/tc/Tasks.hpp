@@ -5,6 +5,7 @@
 // Every pixel is produced by libvpfhip (include/vpf_hip.h); there is no CPU path.
 #pragma once
 #include "MemoryInterfaces.hpp"
+#include "vpf_hip.h"
 
 namespace VPF {
 
@@ -48,6 +49,10 @@ public:
   ~ConvertResizeSurface() override;
   TaskExecStatus Run() final;  // asynchronous like ConvertSurface; null output = failure
   TaskExecStatus RunBatch(Surface* const* inputs, Surface* const* outputs, uint32_t n, const ColorspaceConversionContext* ctx);
+  // n same-shape surfaces -> n frames of a normalised planar tensor (vpf_convert_resize_tensor_batch): dst holds 3 n planes, frame i's
+  // channel planes at dst[3 i .. 3 i + 2] in output channel order; the same colour-context rules as Run / RunBatch
+  TaskExecStatus RunTensor(Surface* const* inputs, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
+  HipStream GetStream() const;  // the stream every Run* launches on
 
 private:
   static const uint32_t numInputs = 2U, numOutputs = 1U;

@@ -1,6 +1,7 @@
 // vpf_abi.hip — the C ABI of libvpfhip (include/vpf_hip.h): argument validation, format dispatch,
 // kernarg packing.  No CPU fallback of any kind: every success path ends in a HIP kernel launch.
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -437,6 +438,62 @@ vpf_status vpf_convert_resize(const vpf_exec* exec, int sf, int df, int cs, int 
   for (int k = 0; k < num_planes(sf); k++) io.src[k] = src[k];
   for (int k = 0; k < num_planes(df); k++) io.dst[k] = dst[k];
   return vpf_convert_resize_batch(exec, sf, df, cs, cr, ss, ds, 1, &io);
+}
+
+// The planar-tensor form of the fused path (include/vpf_hip.h): the RGB_PLANAR bytes through one fp32 fma per channel, stored as f32 / f16 / bf16.
+vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
+                                           const vpf_frame_io* frames, const vpf_tensor_norm* norm) {
+  const Mark mark("vpf_convert_resize_tensor_batch");
+  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !frames || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!planes_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
+    for (int k = 0; k < 3; k++) {
+      const vpf_plane& p = frames[i].dst[k];
+      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
+    }
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
+  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
+  te.dtype = norm->dtype;
+  const uint32_t per = frames_per_dispatch(frame_bytes(sf, ss) + 3ull * ds.width * ds.height * elem, true);  // the tensor's real bytes: 4x the 8-bit planes for f32
+  for (uint32_t base = 0; base < n; base += per) {
+    const uint32_t m = (n - base < per) ? n - base : per;
+    BatchArgsL a;
+    for (uint32_t i = 0; i < m; i++) {
+      vpf_plane d[3];
+      for (int k = 0; k < 3; k++) d[k] = frames[base + i].dst[bgr ? 2 - k : k];
+      fill_desc(a.f[i], frames[base + i].src, num_planes(sf), d, 3);
+    }
+    for (uint32_t i = m; i < ((m + 7u) & ~7u); i++) a.f[i] = a.f[0];
+    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), FC_TENSOR, c, ss.width, ss.height, m, a,
+                                               ds.width, ds.height, &te);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
+vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, const vpf_plane src[3], vpf_size ds,
+                                     const vpf_plane dst[3], const vpf_tensor_norm* norm) {
+  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!src || !dst) return VPF_ERR_BAD_ARG;
+  vpf_frame_io io;
+  std::memset(&io, 0, sizeof(io));
+  for (int k = 0; k < num_planes(sf); k++) io.src[k] = src[k];
+  for (int k = 0; k < 3; k++) io.dst[k] = dst[k];
+  return vpf_convert_resize_tensor_batch(exec, sf, cs, cr, ss, ds, 1, &io, norm);
 }
 
 const char* vpf_status_string(int s) {

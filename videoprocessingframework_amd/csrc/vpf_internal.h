@@ -72,6 +72,19 @@ enum FmtClass : int {
   FC_RGB = 3,     // packed R,G,B
   FC_BGR = 4,     // packed B,G,R
   FC_PLANAR = 5,  // three full planes R,G,B
+  FC_TENSOR = 6,  // three full planes of f32 / f16 / bf16: the FC_PLANAR bytes through one fma each (vpf_convert_resize_tensor)
+};
+// The epilogue of an FC_TENSOR launch: out[c] = to_dtype(fma(u8[c], scale[c], bias[c])).  It travels behind the frame table (BatchArgsTE), so
+// the 8-bit instantiations keep their kernarg layout.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
+struct TensorEpi {
+  float scale[3], bias[3];
+  uint32_t dtype;  // VPF_TENSOR_*: wave-uniform branch of the epilogue
+  uint32_t pad;
+};
+template <int CAP>
+struct BatchArgsTE {
+  FrameDesc f[CAP];
+  TensorEpi e;
 };
 
 // launchers (one per translation unit); all asynchronous on `st`
@@ -103,8 +116,9 @@ hipError_t launch_remap(hipStream_t st, uint32_t sw, uint32_t sh, const uint8_t*
                         uint32_t dh, uint8_t* dst, uint32_t dpitch);
 hipError_t launch_remap_batch(hipStream_t st, uint32_t sw, uint32_t sh, const float* xmap, uint32_t xpitch, const float* ymap, uint32_t ypitch,
                               uint32_t dw, uint32_t dh, uint32_t n, const BatchArgs& a);
+// dst_fc == FC_TENSOR takes `te` (the element size sets the destination alignment tests); every other class ignores it
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw,
-                                 uint32_t sh, uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh);
+                                 uint32_t sh, uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te = nullptr);
 
 int tuning(int key);
 
