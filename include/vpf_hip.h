@@ -243,6 +243,28 @@ VPF_API vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int src_fmt, 
 VPF_API vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
                                                    vpf_size dst_size, uint32_t n, const vpf_frame_io* frames, const vpf_tensor_norm* norm);
 
+/*
+ * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
+ * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
+ * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).
+ * For every element x of plane c, widened exactly to fp32 when f16 / bf16:
+ *   v  = x * scale[c] + bias[c]            two separately rounded fp32 operations (a multiply, then an add: not an fma)
+ *   q  = fminf(fmaxf(v, 0), 255)           IEEE maxNum / minNum: NaN -> 0, -inf -> 0, +inf -> 255
+ *   u8 = (uint8) rint(q)                   round to nearest, ties to even
+ * and the destination bytes are exactly those of vpf_convert(RGB_PLANAR -> YUV420, BT_601, color_range) on the three u8 planes, followed by
+ * vpf_convert(YUV420 -> NV12) for NV12 (chroma = the matrix rows applied to the mean of each 2x2 quad, edge quads replicated on odd sizes,
+ * NV12 chroma rows of 2 ceil(width / 2) bytes).  To undo torchvision's normalize(mean, std) of [0, 1] pixels: scale = 255 std, bias = 255 mean.
+ * Colour models: what vpf_convert(RGB_PLANAR, YUV420) accepts (BT.601, MPEG or JPEG range); anything else, a destination other than NV12 /
+ * YUV420, an unknown dtype or flag bit: VPF_ERR_UNSUPPORTED.  A null pointer, a non-finite scale / bias, a source pointer or pitch that is not
+ * a multiple of the element size, or pitch < width x element size: VPF_ERR_BAD_ARG.  Destinations: as vpf_convert (any alignment).
+ */
+VPF_API int vpf_tensor_convert_supported(int dst_fmt, int color_space, int color_range); /* host only */
+VPF_API vpf_status vpf_tensor_convert(const vpf_exec* exec, int dst_fmt, int color_space, int color_range, vpf_size size,
+                                      const vpf_plane src[3], const vpf_plane dst[3], const vpf_tensor_norm* denorm);
+/* The same over `n` same-shape frames (frames[i].src = the tensor planes, frames[i].dst = the picture), 32 frames per dispatch. */
+VPF_API vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int dst_fmt, int color_space, int color_range, vpf_size size,
+                                            uint32_t n, const vpf_frame_io* frames, const vpf_tensor_norm* denorm);
+
 VPF_API const char* vpf_status_string(int status);
 VPF_API const char* vpf_version(void);
 /* hipGetDeviceCount; 0 when no GPU / no driver (never fails). Replaces GetNumGpus

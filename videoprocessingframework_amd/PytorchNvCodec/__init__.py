@@ -160,3 +160,67 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
     if not ok:
         raise RuntimeError("to_normalized_tensor: the surfaces do not match the resizer (format / size) or the colour context was refused")
     return out
+
+
+def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None):
+    """A model's output -> NV12 / YUV420 surfaces for the encoder, in one pass (PyTensorToSurface.ExecuteBatch): `tensor` is [N, 3, H, W] or
+    [3, H, W] of float32 / float16 / bfloat16 on the device, normalised with torchvision's mean / std (per input plane; B G R planes when
+    bgr=True).  Every element goes through x * (255 std) + (255 mean) in fp32 (a multiply, then an add), is clamped to [0, 255] (NaN -> 0) and
+    rounded to nearest even; the surface bytes are those of PySurfaceConverter RGB_PLANAR -> YUV420 (-> NV12) on these planes (BT.601; JPEG
+    range unless cc_ctx says MPEG).
+
+    The tensor needs unit stride along W and positive row, plane and frame strides, rows at least W elements apart; beyond that the strides
+    are free (a slice of a larger batch, padded rows).  A zero stride (an expand()ed channel, frame or row) is refused with a ValueError:
+    call .contiguous() first.  The tensor must live on the converter's GPU.  Returns the list of surfaces: `out` (N surfaces of the
+    converter's size and format) if given, else new ones on that GPU.  The kernel runs on the converter's stream after torch's current stream
+    has reached this call, and torch's current stream waits for it: the surfaces can be used on the current stream right away, no host
+    synchronisation."""
+    try:
+        import PyNvCodec as nvc
+    except ImportError:  # package-relative import when used as videoprocessingframework_amd.PytorchNvCodec
+        from .. import PyNvCodec as nvc
+    if not isinstance(tensor, torch.Tensor) or tensor.dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"from_normalized_tensor: tensor must be a torch tensor of one of {list(_TENSOR_DTYPES)}")
+    if tensor.dim() == 3:
+        tensor = tensor.unsqueeze(0)
+    w, h = converter.Size()
+    if tensor.dim() != 4 or tuple(tensor.shape[1:]) != (3, h, w):
+        raise ValueError(f"from_normalized_tensor: tensor must have shape [N, 3, {h}, {w}] or [3, {h}, {w}], got {tuple(tensor.shape)}")
+    n = tensor.shape[0]
+    s0, s1, s2, s3 = tensor.stride()
+    # The binding reads a stride of 0 as "contiguous", so a zero (or negative) stride of a dimension that is really walked must not reach it;
+    # a dimension of one element is never walked, and goes down as 0 = default.
+    if (w > 1 and s3 != 1) or (h > 1 and s2 < w) or s1 <= 0 or (n > 1 and s0 <= 0):
+        raise ValueError(f"from_normalized_tensor: tensor needs unit stride along W, rows at least {w} elements apart and positive plane and frame "
+                         f"strides (an expanded tensor needs .contiguous() first), got strides {tensor.stride()}")
+    if h == 1:
+        s2 = 0
+    if n == 1:
+        s0 = 0
+    dev = converter.Device()
+    if not tensor.is_cuda or (dev >= 0 and tensor.device.index != dev):
+        raise ValueError(f"from_normalized_tensor: tensor must be a device tensor" + (f" on GPU {dev}" if dev >= 0 else "") + f", got one on {tensor.device}")
+    if out is not None:
+        out = list(out)
+        if len(out) != n:
+            raise ValueError(f"from_normalized_tensor: out must hold {n} surfaces, got {len(out)}")
+    if n == 0:
+        return []
+    elem = tensor.element_size()
+    with torch.cuda.device(tensor.device):
+        if out is None:
+            out = [nvc.Surface.Make(converter.Format(), w, h, dev if dev >= 0 else tensor.device.index) for _ in range(n)]
+        cur = torch.cuda.current_stream()
+        cs = int(converter.Stream())
+        side = torch.cuda.ExternalStream(cs) if cs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # whatever produced `tensor` on torch's stream comes first
+        ok = converter.ExecuteBatch(tensor.data_ptr(), out, _TENSOR_DTYPES[tensor.dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
+                                    bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+        if side is not None:
+            cur.wait_stream(side)
+            tensor.record_stream(side)  # the caching allocator must not hand the tensor's memory out before the converter has read it
+    if not ok:
+        raise RuntimeError("from_normalized_tensor: the surfaces do not match the converter (format / size), the tensor layout was refused or "
+                           "the colour context was refused")
+    return out

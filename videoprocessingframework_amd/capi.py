@@ -30,6 +30,7 @@ EXPORTS = [
     "vpf_convert_resize_batch", "vpf_resize_batch", "vpf_remap_batch", "vpf_resize_ws", "vpf_resize_batch_ws", "vpf_resize_workspace_bytes",
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch",
+    "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -72,6 +73,27 @@ def norm_params(mean, std):
     if not all(math.isfinite(v) for v in mean + std) or min(std) <= 0:
         raise ValueError("mean must be finite and std finite and > 0")
     return [1.0 / (255.0 * s) for s in std], [-m / s for m, s in zip(mean, std)]
+
+
+def denorm_params(mean, std):
+    """the way back (vpf_tensor_convert): a tensor normalised with torchvision's normalize(mean, std) of [0, 1] pixels -> 8-bit codes,
+    as (scale, bias): scale = 255 std, bias = 255 mean, computed in double and rounded to fp32 (the ctypes fields round).  std must be > 0
+    and every value finite."""
+    import math
+
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std need three values each")
+    if not all(math.isfinite(v) for v in mean + std) or min(std) <= 0:
+        raise ValueError("mean must be finite and std finite and > 0")
+    return [255.0 * s for s in std], [255.0 * m for m in mean]
+
+
+def make_tensor_denorm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None) -> TensorNorm:
+    """vpf_tensor_norm for vpf_tensor_convert from mean / std (denorm_params) or from raw scale / bias (passed through unchecked)"""
+    if scale is None:
+        scale, bias = denorm_params(mean, std)
+    return make_tensor_norm(dtype=dtype, bgr=bgr, scale=scale, bias=bias)
 
 
 def make_tensor_norm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None) -> TensorNorm:
@@ -123,6 +145,9 @@ def lib() -> C.CDLL:
         PN = C.POINTER(TensorNorm)
         L.vpf_convert_resize_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, Size, PP, PN]
         L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
+        L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
+        L.vpf_tensor_convert.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, PP, PN]
+        L.vpf_tensor_convert_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, C.c_uint32, PF, PN]
         L.vpf_status_string.argtypes = [C.c_int]
         L.vpf_status_string.restype = C.c_char_p
         L.vpf_version.restype = C.c_char_p
@@ -284,4 +309,23 @@ def convert_resize_tensor_batch(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, batch
                                                C.byref(norm))
     if check:
         _check(st, "vpf_convert_resize_tensor_batch")
+    return st
+
+
+def tensor_convert_supported(dst_fmt, cs, cr) -> bool:
+    return bool(lib().vpf_tensor_convert_supported(dst_fmt, cs, cr))
+
+
+def tensor_convert(ex: Exec, dst_fmt, cs, cr, w, h, src, dst, denorm: TensorNorm, check=True) -> int:
+    """src: the three planes (ptr, pitch in bytes) of the tensor frame in input channel order; dst: the NV12 / YUV420 planes"""
+    st = lib().vpf_tensor_convert(C.byref(ex), dst_fmt, cs, cr, Size(w, h), planes(src), planes(dst), C.byref(denorm))
+    if check:
+        _check(st, "vpf_tensor_convert")
+    return st
+
+
+def tensor_convert_batch(ex: Exec, dst_fmt, cs, cr, w, h, batch, denorm: TensorNorm, n=None, check=True) -> int:
+    st = lib().vpf_tensor_convert_batch(C.byref(ex), dst_fmt, cs, cr, Size(w, h), len(batch) if n is None else n, batch, C.byref(denorm))
+    if check:
+        _check(st, "vpf_tensor_convert_batch")
     return st

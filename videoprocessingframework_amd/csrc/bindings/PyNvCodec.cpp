@@ -191,6 +191,77 @@ public:
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
 
+// additive: a planar float tensor [n, 3, H, W] (f32 / f16 / bf16) at a device address -> NV12 / YUV420 surfaces in one pass (TensorToSurface)
+class PyTensorToSurface {
+  std::unique_ptr<TensorToSurface> task_;
+  Pixel_Format out_fmt_;
+  uint32_t w_, h_;
+  int dev_;
+
+  // mean / std are the ones the tensor was normalised with (torchvision's, values of [0, 1] pixels), per input plane: scale = 255 std and
+  // bias = 255 mean, computed in double and rounded to fp32
+  static vpf_tensor_norm denorm_of(uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, bool bgr) {
+    if (mean.size() != 3 || std.size() != 3) throw std::invalid_argument("mean and std need three values each");
+    vpf_tensor_norm d;
+    std::memset(&d, 0, sizeof(d));
+    for (int c = 0; c < 3; c++) {
+      if (!std::isfinite(mean[c]) || !std::isfinite(std[c]) || !(std[c] > 0.0)) throw std::invalid_argument("mean must be finite and std finite and > 0");
+      d.scale[c] = (float)(255.0 * std[c]);
+      d.bias[c] = (float)(255.0 * mean[c]);
+      if (!std::isfinite(d.scale[c]) || !std::isfinite(d.bias[c])) throw std::invalid_argument("mean / std give a scale or bias beyond fp32");
+    }
+    d.dtype = dtype;
+    d.flags = bgr ? VPF_TENSOR_BGR : 0u;
+    return d;
+  }
+  // element (i, c, y, x) at src + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW)
+  bool planes_of(uint64_t src, uint32_t dtype, size_t n, uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, std::vector<vpf_plane>& planes) const {
+    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2;
+    if (!row_pitch) row_pitch = w_ * elem;
+    if (!plane_stride) plane_stride = h_ * row_pitch;
+    if (!frame_stride) frame_stride = 3 * plane_stride;
+    if (!src || !n || row_pitch > 0xffffffffull) return false;
+    planes.resize(3 * n);
+    for (size_t i = 0; i < n; i++)
+      for (int c = 0; c < 3; c++) {
+        planes[3 * i + c].ptr = (void*)(uintptr_t)(src + i * frame_stride + c * plane_stride);
+        planes[3 * i + c].pitch = (uint32_t)row_pitch;
+        planes[3 * i + c].reserved = 0;
+      }
+    return true;
+  }
+
+public:
+  PyTensorToSurface(uint32_t w, uint32_t h, Pixel_Format out, HipContext ctx, HipStream str) : out_fmt_(out), w_(w), h_(h), dev_(DeviceOfContext(ctx)) {
+    task_.reset(TensorToSurface::Make(w, h, out, ctx, str));
+  }
+  int Device() const { return dev_; }  // the GPU the converter was built for; -1: whatever device is current
+  Pixel_Format GetFormat() const { return out_fmt_; }
+  size_t GetStream() const { return (size_t)task_->GetStream(); }
+  uint32_t Width() const { return w_; }
+  uint32_t Height() const { return h_; }
+  // one frame [3, H, W] -> a NON-OWNING alias of the task's single output surface (overwritten by the next Execute); failure = Empty()
+  std::shared_ptr<Surface> Execute(uint64_t src, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
+                                   std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch, uint64_t plane_stride) {
+    const vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
+    std::vector<vpf_plane> planes;
+    if (!planes_of(src, dtype, 1, row_pitch, plane_stride, 0, planes)) return empty_surface(out_fmt_);
+    Surface* out = task_->RunTensor(planes.data(), d, cc.get());
+    return out ? std::shared_ptr<Surface>(out->Clone()) : empty_surface(out_fmt_);
+  }
+  // frames [len(dst), 3, H, W] -> the caller's surfaces, one dispatch per 32 frames
+  bool ExecuteBatch(uint64_t src, const std::vector<std::shared_ptr<Surface>>& dst, uint32_t dtype, const std::vector<double>& mean,
+                    const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
+                    uint64_t plane_stride, uint64_t frame_stride) {
+    const vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
+    std::vector<vpf_plane> planes;
+    if (!planes_of(src, dtype, dst.size(), row_pitch, plane_stride, frame_stride, planes)) return false;
+    std::vector<Surface*> b;
+    for (auto& s : dst) b.push_back(s.get());
+    return TASK_EXEC_SUCCESS == task_->RunTensorBatch(planes.data(), b.data(), (uint32_t)b.size(), d, cc.get());
+  }
+};
+
 class PySurfaceResizer {
   std::unique_ptr<ResizeSurface> rs_;
   Pixel_Format fmt_;
@@ -619,6 +690,25 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>())
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
+
+  py::class_<PyTensorToSurface>(m, "PyTensorToSurface",
+                                "Additive: a planar float tensor [N, 3, H, W] (dtype 0 f32, 1 f16, 2 bf16) -> NV12 / YUV420 in one pass: denormalise, "
+                                "quantise (round to nearest even), BT.601 RGB -> YUV, 4:2:0; the bytes of PySurfaceConverter RGB_PLANAR -> YUV420 "
+                                "(-> NV12) on the quantised planes.")
+      .def(py::init([](uint32_t w, uint32_t h, Pixel_Format out, uint32_t gpu) { return new PyTensorToSurface(w, h, out, ctx_of((int)gpu), str_of((int)gpu)); }),
+           py::arg("width"), py::arg("height"), py::arg("dst_format"), py::arg("gpu_id"))
+      .def(py::init([](uint32_t w, uint32_t h, Pixel_Format out, size_t ctx, size_t str) { return new PyTensorToSurface(w, h, out, (HipContext)ctx, (HipStream)str); }),
+           py::arg("width"), py::arg("height"), py::arg("dst_format"), py::arg("context"), py::arg("stream"))
+      .def("Format", &PyTensorToSurface::GetFormat)
+      .def("Execute", &PyTensorToSurface::Execute, py::arg("src"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
+           py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0, py::keep_alive<0, 1>(),
+           py::call_guard<py::gil_scoped_release>())
+      .def("ExecuteBatch", &PyTensorToSurface::ExecuteBatch, py::arg("src"), py::arg("dst"), py::arg("dtype"), py::arg("mean"), py::arg("std"),
+           py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("Stream", &PyTensorToSurface::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
+      .def("Size", [](const PyTensorToSurface& t) { return py::make_tuple(t.Width(), t.Height()); }, "(width, height) of the frames")
+      .def("Device", &PyTensorToSurface::Device, "the GPU the converter was built for; -1: whatever device is current (a foreign context handle)");
 
   py::class_<PySurfaceResizer>(m, "PySurfaceResizer")
       .def(py::init([](uint32_t w, uint32_t h, Pixel_Format f, uint32_t gpu) { return new PySurfaceResizer(w, h, f, ctx_of((int)gpu), str_of((int)gpu)); }),

@@ -504,6 +504,73 @@ TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, 
 }
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
+// ------------------------------------------------------------------------------------------ TensorToSurface
+struct TensorToSurface::Impl {
+  const PairInfo* pair;  // rgb_planar_yuv420: the colour-context rule (RULE_RGB_YUV) and the name in its diagnostics
+  Pixel_Format out_fmt;
+  uint32_t w, h;
+  HipContext ctx;
+  HipStream str;
+  std::unique_ptr<Surface> out;
+};
+TensorToSurface::TensorToSurface(uint32_t w, uint32_t h, Pixel_Format out, HipContext ctx, HipStream str)
+    : Task("HipTensorToSurface", numInputs, numOutputs, nullptr, nullptr), pImpl() {
+  const PairInfo* p = find_pair(RGB_PLANAR, YUV420);
+  if (!p || (out != NV12 && out != YUV420) || !w || !h) {
+    std::stringstream ss;
+    ss << "Unsupported tensor conversion: to " << out << " " << w << "x" << h;
+    throw std::invalid_argument(ss.str());
+  }
+  pImpl.reset(new Impl{p, out, w, h, ctx, str, nullptr});
+  pImpl->out.reset(Surface::Make(out, w, h, ctx));
+}
+TensorToSurface::~TensorToSurface() {}
+TensorToSurface* TensorToSurface::Make(uint32_t w, uint32_t h, Pixel_Format out, HipContext ctx, HipStream str) {
+  return new TensorToSurface(w, h, out, ctx, str);
+}
+HipStream TensorToSurface::GetStream() const { return pImpl->str; }
+
+Surface* TensorToSurface::RunTensor(const vpf_plane src[3], const vpf_tensor_norm& denorm, const ColorspaceConversionContext* cc) {
+  const HipMark tick("TensorToSurface::RunTensor");
+  ClearOutputs();
+  if (!src || !pImpl->out || pImpl->out->Empty()) return nullptr;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return nullptr;
+  vpf_plane dst[3];
+  fill_planes(pImpl->out.get(), dst);
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_tensor_convert(&ex, pImpl->out_fmt, cs, cr, vpf_size{pImpl->w, pImpl->h}, src, dst, &denorm);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to convert a tensor into a surface. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return nullptr;
+  }
+  SetOutput(pImpl->out.get(), 0U);
+  return pImpl->out.get();
+}
+
+TaskExecStatus TensorToSurface::RunTensorBatch(const vpf_plane* src, Surface* const* outs, uint32_t n, const vpf_tensor_norm& denorm,
+                                               const ColorspaceConversionContext* cc) {
+  const HipMark tick("TensorToSurface::RunTensorBatch");
+  if (!src || !outs || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  std::vector<vpf_frame_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    Surface* d = outs[i];
+    if (!d || d->Empty() || d->PixelFormat() != pImpl->out_fmt || d->Width() != pImpl->w || d->Height() != pImpl->h) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    for (int k = 0; k < 3; k++) io[i].src[k] = src[3 * i + k];
+    fill_planes(d, io[i].dst);
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_tensor_convert_batch(&ex, pImpl->out_fmt, cs, cr, vpf_size{pImpl->w, pImpl->h}, n, io.data(), &denorm);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to convert tensors into surfaces. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------ ResizeSurface
 struct ResizeSurface::Impl {
   Pixel_Format fmt;

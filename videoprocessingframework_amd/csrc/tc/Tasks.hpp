@@ -61,6 +61,29 @@ private:
   ConvertResizeSurface(uint32_t sw, uint32_t sh, Pixel_Format in, uint32_t dw, uint32_t dh, Pixel_Format out, HipContext ctx, HipStream str);
 };
 
+// Additive (no reference counterpart): a planar float tensor frame (three planes of f32 / f16 / bf16, what a model writes) -> NV12 / YUV420
+// in one pass (vpf_tensor_convert): quantise to 8 bits, BT.601 RGB -> YUV, 4:2:0 mean.  The bytes are those of ConvertSurface RGB_PLANAR ->
+// YUV420 (-> NV12) on the quantised planes; the colour-context rules are that pair's (JPEG range without a context, BT.601 only).
+class TensorToSurface final : public Task {
+public:
+  // throws std::invalid_argument for a destination other than NV12 / YUV420 or an empty size
+  static TensorToSurface* Make(uint32_t width, uint32_t height, Pixel_Format outFormat, HipContext ctx, HipStream str);
+  ~TensorToSurface() override;
+  // one frame (src[0..2] = its channel planes in input order) into the task's own surface, asynchronous on the task's stream;
+  // nullptr = failure (refused colour context, refused planes), like a null output of ConvertSurface::Run
+  Surface* RunTensor(const vpf_plane src[3], const vpf_tensor_norm& denorm, const ColorspaceConversionContext* ctx);
+  // n frames (src holds 3 n planes, frame i's at src[3 i .. 3 i + 2]) into n caller-owned surfaces of the task's size and format
+  TaskExecStatus RunTensorBatch(const vpf_plane* src, Surface* const* outputs, uint32_t n, const vpf_tensor_norm& denorm,
+                                const ColorspaceConversionContext* ctx);
+  HipStream GetStream() const;  // the stream every Run* launches on
+
+private:
+  static const uint32_t numInputs = 0U, numOutputs = 1U;
+  struct Impl;
+  std::unique_ptr<Impl> pImpl;  // unique_ptr: a constructor that throws after allocating it (device OOM) frees it
+  TensorToSurface(uint32_t w, uint32_t h, Pixel_Format out, HipContext ctx, HipStream str);
+};
+
 class ResizeSurface final : public Task {
 public:
   static ResizeSurface* Make(uint32_t width, uint32_t height, Pixel_Format format, HipContext ctx, HipStream str);

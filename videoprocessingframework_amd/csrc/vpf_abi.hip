@@ -496,6 +496,65 @@ vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int c
   return vpf_convert_resize_tensor_batch(exec, sf, cs, cr, ss, ds, 1, &io, norm);
 }
 
+// Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
+int vpf_tensor_convert_supported(int df, int cs, int cr) {
+  return (df == VPF_FMT_NV12 || df == VPF_FMT_YUV420) && classify(VPF_FMT_RGB_PLANAR, VPF_FMT_YUV420, cs, cr) == FAM_RGB2YUV;
+}
+
+vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int df, int cs, int cr, vpf_size size, uint32_t n, const vpf_frame_io* frames,
+                                    const vpf_tensor_norm* denorm) {
+  const Mark mark("vpf_tensor_convert_batch");
+  if (!vpf_tensor_convert_supported(df, cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!denorm) return VPF_ERR_BAD_ARG;
+  if (denorm->dtype > VPF_TENSOR_BF16 || (denorm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(denorm->scale[c]) || !std::isfinite(denorm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !frames || !n || !dims_ok(size)) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = denorm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  for (uint32_t i = 0; i < n; i++) {
+    for (int k = 0; k < 3; k++) {
+      const vpf_plane& p = frames[i].src[k];
+      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)size.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
+    }
+    if (!planes_ok(df, size.width, frames[i].dst)) return VPF_ERR_BAD_ARG;
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Rgb2YuvCoef rc;
+  make_rgb2yuv(cr, &rc);
+  // the kernels read channel k (R G B) from plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
+  const bool bgr = (denorm->flags & VPF_TENSOR_BGR) != 0;
+  TensorPro tp;
+  std::memset(&tp, 0, sizeof(tp));
+  for (int k = 0; k < 3; k++) { tp.scale[k] = denorm->scale[bgr ? 2 - k : k]; tp.bias[k] = denorm->bias[bgr ? 2 - k : k]; }
+  tp.dtype = denorm->dtype;
+  const int nd = num_planes(df);
+  for (uint32_t base = 0; base < n; base += kSmallBatch) {
+    const uint32_t m = (n - base < (uint32_t)kSmallBatch) ? n - base : (uint32_t)kSmallBatch;
+    BatchArgs a;
+    for (uint32_t i = 0; i < m; i++) {
+      vpf_plane s[3];
+      for (int k = 0; k < 3; k++) s[k] = frames[base + i].src[bgr ? 2 - k : k];
+      fill_desc(a.f[i], s, 3, frames[base + i].dst, nd);
+    }
+    for (uint32_t i = m; i < (uint32_t)kSmallBatch; i++) a.f[i] = a.f[0];
+    const hipError_t e = launch_tensor_to_yuv(static_cast<hipStream_t>(exec->stream), df == VPF_FMT_NV12, rc, tp, size.width, size.height, m, a);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
+vpf_status vpf_tensor_convert(const vpf_exec* exec, int df, int cs, int cr, vpf_size size, const vpf_plane src[3], const vpf_plane dst[3],
+                              const vpf_tensor_norm* denorm) {
+  if (!vpf_tensor_convert_supported(df, cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!src || !dst) return VPF_ERR_BAD_ARG;
+  vpf_frame_io io;
+  std::memset(&io, 0, sizeof(io));
+  for (int k = 0; k < 3; k++) io.src[k] = src[k];
+  for (int k = 0; k < num_planes(df); k++) io.dst[k] = dst[k];
+  return vpf_tensor_convert_batch(exec, df, cs, cr, size, 1, &io, denorm);
+}
+
 const char* vpf_status_string(int s) {
   switch (s) {
     case VPF_OK: return "ok";

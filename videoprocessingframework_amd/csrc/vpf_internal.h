@@ -87,11 +87,22 @@ struct BatchArgsTE {
   TensorEpi e;
 };
 
+// The prologue of a tensor -> NV12 / YUV420 launch (vpf_tensor_convert): q[c] = rint(clamp(x[c] * scale[c] + bias[c], 0, 255)) feeds the RGB -> YUV
+// arithmetic.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
+struct TensorPro {
+  float scale[3], bias[3];
+  uint32_t dtype;  // VPF_TENSOR_*: template parameter of the fast kernel, wave-uniform branch of the quad kernel
+  uint32_t pad;
+};
+
 // launchers (one per translation unit); all asynchronous on `st`
 hipError_t launch_yuv_to_rgb(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t w,
                              uint32_t h, uint32_t n, const BatchArgs& a, int variant, bool dst_reused = false);
 hipError_t launch_rgb_to_yuv(hipStream_t st, int src_fc, int dst_fc /*FC_YUV444|FC_YUV420*/,
                              const Rgb2YuvCoef& c, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a);
+// three planes of f32 / f16 / bf16 (FrameDesc::s, R G B) -> NV12 (d[0], d[1]) or YUV420 (d[0..2]); k_rgb2yuv.hip
+hipError_t launch_tensor_to_yuv(hipStream_t st, bool nv12, const Rgb2YuvCoef& c, const TensorPro& t, uint32_t w, uint32_t h, uint32_t n,
+                                const BatchArgs& a);
 hipError_t launch_relayout(hipStream_t st, int src_fmt, int dst_fmt, uint32_t w, uint32_t h, uint32_t n,
                            const BatchArgs& a);
 hipError_t launch_resize(hipStream_t st, int channels, int interp, uint32_t sw, uint32_t sh, const uint8_t* src,
