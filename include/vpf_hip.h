@@ -244,6 +244,37 @@ VPF_API vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int src
                                                    vpf_size dst_size, uint32_t n, const vpf_frame_io* frames, const vpf_tensor_norm* norm);
 
 /*
+ * Fused multi-ROI crop + bilinear resize -> normalised planar tensor: `n` rectangles of decoded NV12 / YUV420 frames, each resized to the ONE
+ * size dst_size and normalised, in one dispatch (what a classifier / ReID / face network behind a detector consumes: float [K, 3, dh, dw]).
+ * A job = (the planes of a WHOLE frame of src_size = (W, H), rect = (x, y, w, h) in luma pixels of that frame, three destination planes);
+ * w, h >= 1, x + w <= W, y + h <= H, any integer x, y (odd ones too); many jobs may name the same frame.  For destination pixel (dx, dy), channel c:
+ *   tx = tap(dx, (float)w / (float)dw, w), ty = tap(dy, (float)h / (float)dh, h): vpf_resize(LINEAR)'s fp32 sampling — s = (d + 0.5) * scale - 0.5
+ *        clamped to [0, size - 1]; i0 = floor(s), i1 = min(i0 + 1, size - 1), f = s - i0 — on the RECTANGLE's size: taps clamp at the
+ *        rectangle's edges, nothing outside the rectangle contributes;
+ *   the four texels are frame pixels (x + tx.i0|i1, y + ty.i0|i1), each converted with vpf_convert's arithmetic for (src_fmt -> RGB_PLANAR,
+ *        color_space, color_range) including its 8-bit rounding; chroma is taken at absolute ((x + i) >> 1, (y + j) >> 1);
+ *   u8  = trunc(fma(fy, bot - top, top) + 0.5), top = fma(fx, p01 - p00, p00), bot = fma(fx, p11 - p10, p10);
+ *   out = round_to_dtype(fmaf(u8, scale[c], bias[c]))              exactly vpf_convert_resize_tensor's epilogue (dtype, VPF_TENSOR_BGR, plane rules).
+ * Equivalently u8 is the byte vpf_resize(RGB_PLANAR, LINEAR, (w, h) -> dst_size) writes when fed the planes of vpf_convert(frame -> RGB_PLANAR)
+ * advanced by y * pitch + x; with rect = the whole frame the output is bit-identical to vpf_convert_resize_tensor.
+ * `rois` is a HOST array, consumed before return; 96 jobs travel per job table, each table in at most two dispatches (jobs whose source window
+ * is converted once into LDS and blended from there, and jobs with large down-scale factors that convert per tap: identical bits).
+ * Unsupported format / matrix / dtype / flag: VPF_ERR_UNSUPPORTED as vpf_convert_resize_tensor.  Null pointers, n == 0, bad sizes, an empty
+ * rect, a rect that leaves the frame (no silent clipping), short pitches, misaligned planes, non-finite scale / bias: VPF_ERR_BAD_ARG — all
+ * checked before any device access.
+ */
+typedef struct vpf_rect {
+  uint32_t x, y, width, height;
+} vpf_rect;
+typedef struct vpf_roi_io {
+  vpf_plane src[3]; /* the WHOLE frame's planes */
+  vpf_plane dst[3];
+  vpf_rect rect;
+} vpf_roi_io; /* 112 bytes, no implicit padding */
+VPF_API vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                  vpf_size dst_size, uint32_t n, const vpf_roi_io* rois, const vpf_tensor_norm* norm);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

@@ -12,6 +12,8 @@ torch is plumbing here (allocation, streams); no pixel arithmetic happens in thi
 """
 from __future__ import annotations
 
+import operator
+
 import torch
 
 
@@ -159,6 +161,85 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
             cur.wait_stream(side)
     if not ok:
         raise RuntimeError("to_normalized_tensor: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out
+
+
+def _rois_list(rois, surfaces, fn):
+    """rois -> list of 5-tuples of Python ints, validated against the surfaces: ValueError for a device tensor, a non-integer dtype, a shape other
+    than [K, 5], a surface index out of range, an empty rectangle or one that leaves its surface"""
+    if isinstance(rois, torch.Tensor):
+        if rois.device.type != "cpu":
+            raise ValueError(f"{fn}: rois must live on the host (the job table is built on the CPU): pass rois.cpu()")
+        if rois.dtype.is_floating_point or rois.dtype.is_complex or rois.dtype == torch.bool:
+            raise ValueError(f"{fn}: rois must hold integers, got {rois.dtype}")
+        if rois.dim() != 2 or rois.shape[1] != 5:
+            raise ValueError(f"{fn}: a rois tensor must have shape [K, 5], got {tuple(rois.shape)}")
+        rois = rois.tolist()
+    elif hasattr(rois, "dtype") and hasattr(rois, "tolist"):  # numpy.ndarray
+        if getattr(rois.dtype, "kind", "") not in "iu":
+            raise ValueError(f"{fn}: rois must hold integers, got {rois.dtype}")
+        if rois.ndim != 2 or rois.shape[1] != 5:
+            raise ValueError(f"{fn}: a rois array must have shape [K, 5], got {tuple(rois.shape)}")
+        rois = rois.tolist()
+    out = []
+    for i, r in enumerate(rois):
+        r = tuple(r)
+        if len(r) != 5:
+            raise ValueError(f"{fn}: rois[{i}] must be (surface_index, x, y, w, h), got {r}")
+        try:
+            k, x, y, w, h = (operator.index(v) for v in r)  # Python and numpy integers; a float is refused, never truncated
+        except TypeError:
+            raise ValueError(f"{fn}: rois[{i}] must hold integers, got {r}") from None
+        if not 0 <= k < len(surfaces):
+            raise ValueError(f"{fn}: rois[{i}] names surface {k}, there are {len(surfaces)}")
+        sw, sh = surfaces[k].Width(), surfaces[k].Height()
+        if x < 0 or y < 0 or w < 1 or h < 1 or x + w > sw or y + h > sh:
+            raise ValueError(f"{fn}: rois[{i}] = (x {x}, y {y}, w {w}, h {h}) is empty or leaves its {sw} x {sh} surface (nothing is clipped silently)")
+        out.append((k, x, y, w, h))
+    return out
+
+
+def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
+    """K rectangles of NV12 / YUV420 surfaces -> the normalised float tensor [K, 3, dh, dw] a second-stage network (classifier, ReID, face net
+    behind a detector) consumes, in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteRoisToTensor, vpf_convert_resize_tensor_rois).
+    `rois`: a sequence of (surface_index, x, y, w, h) integer 5-tuples, or a CPU integer tensor / ndarray [K, 5]; x, y, w, h in luma pixels of
+    surfaces[surface_index], any integer offset (odd ones too), the rectangle inside the surface.  Every region is resized (bilinear, taps
+    clamped at the RECTANGLE's edges) to the resizer's destination size and normalised exactly as to_normalized_tensor does; a rectangle that
+    is the whole surface gives to_normalized_tensor's bits.
+
+    `out`, the returned tensor and the stream ordering: exactly as to_normalized_tensor.  ValueError for rois on the device (pass .cpu()), a
+    non-integer dtype, a bad surface index or a rectangle that is empty or leaves its surface.  K == 0 returns an empty tensor without a launch."""
+    fn = "rois_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    surfaces = list(surfaces)
+    jobs = _rois_list(rois, surfaces, fn)
+    n = len(jobs)
+    w, h = resizer.DstSize()
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    if n == 0:
+        return out
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+        ok = resizer.ExecuteRoisToTensor(surfaces, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
+                                         bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
     return out
 
 

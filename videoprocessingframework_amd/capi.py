@@ -29,7 +29,7 @@ EXPORTS = [
     "vpf_convert", "vpf_convert_batch", "vpf_convert_supported", "vpf_resize", "vpf_remap", "vpf_convert_resize",
     "vpf_convert_resize_batch", "vpf_resize_batch", "vpf_remap_batch", "vpf_resize_ws", "vpf_resize_batch_ws", "vpf_resize_workspace_bytes",
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
-    "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch",
+    "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
@@ -55,6 +55,15 @@ class Exec(C.Structure):
 
 class FrameIO(C.Structure):
     _fields_ = [("src", Plane * 3), ("dst", Plane * 3)]
+
+
+class Rect(C.Structure):
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class RoiIO(C.Structure):
+    """vpf_roi_io: one job of vpf_convert_resize_tensor_rois — the WHOLE source frame's planes, the destination planes, the rectangle"""
+    _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("rect", Rect)]
 
 
 class TensorNorm(C.Structure):
@@ -145,6 +154,7 @@ def lib() -> C.CDLL:
         PN = C.POINTER(TensorNorm)
         L.vpf_convert_resize_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, Size, PP, PN]
         L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
+        L.vpf_convert_resize_tensor_rois.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(RoiIO), PN]
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
         L.vpf_tensor_convert.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, PP, PN]
         L.vpf_tensor_convert_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, C.c_uint32, PF, PN]
@@ -309,6 +319,27 @@ def convert_resize_tensor_batch(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, batch
                                                C.byref(norm))
     if check:
         _check(st, "vpf_convert_resize_tensor_batch")
+    return st
+
+
+def make_rois(jobs) -> "C.Array[RoiIO]":
+    """jobs: list of (src_desc, dst_desc, (x, y, w, h)) with desc as in planes(); src_desc = the planes of the WHOLE frame"""
+    arr = (RoiIO * len(jobs))()
+    for i, (s, d, rect) in enumerate(jobs):
+        s, d = planes(s), planes(d)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+            arr[i].dst[k].ptr, arr[i].dst[k].pitch = d[k].ptr, d[k].pitch
+        arr[i].rect.x, arr[i].rect.y, arr[i].rect.width, arr[i].rect.height = rect
+    return arr
+
+
+def convert_resize_tensor_rois(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, rois, norm: TensorNorm, n=None, check=True) -> int:
+    """rois: RoiIO array from make_rois(); every rectangle resized to dw x dh and normalised, 96 jobs per job table"""
+    st = lib().vpf_convert_resize_tensor_rois(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), Size(dw, dh), len(rois) if n is None else n, rois,
+                                              C.byref(norm) if norm is not None else None)
+    if check:
+        _check(st, "vpf_convert_resize_tensor_rois")
     return st
 
 

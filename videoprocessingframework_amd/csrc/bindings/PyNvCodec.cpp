@@ -10,6 +10,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -155,9 +156,7 @@ public:
   // additive: n surfaces -> a normalised planar tensor [n, 3, dh, dw] of f32 / f16 / bf16 at device address `dst` (vpf_convert_resize_tensor):
   // element (i, c, y, x) at dst + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW).  mean / std are
   // torchvision's (values of [0, 1] pixels), per output channel; scale = 1 / (255 std) and bias = -mean / std are computed in double.
-  bool ExecuteToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
-                       const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
-                       uint64_t plane_stride, uint64_t frame_stride) {
+  static vpf_tensor_norm norm_of(uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, bool bgr) {
     if (mean.size() != 3 || std.size() != 3) throw std::invalid_argument("mean and std need three values each");
     vpf_tensor_norm norm;
     std::memset(&norm, 0, sizeof(norm));
@@ -169,6 +168,12 @@ public:
     }
     norm.dtype = dtype;
     norm.flags = bgr ? VPF_TENSOR_BGR : 0u;
+    return norm;
+  }
+  bool ExecuteToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
+                       const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
+                       uint64_t plane_stride, uint64_t frame_stride) {
+    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
     if (src.empty() || !dst) return false;
     const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
     if (!row_pitch) row_pitch = dw * elem;
@@ -186,6 +191,36 @@ public:
       }
     }
     return TASK_EXEC_SUCCESS == task_->RunTensor(a.data(), (uint32_t)a.size(), planes.data(), norm, cc.get());
+  }
+  // additive: K rectangles of surfaces -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_resize_tensor_rois):
+  // rois[i] = (surface index, x, y, w, h) in luma pixels, any integer offset, inside the surface; tensor layout and mean / std as ExecuteToTensor
+  bool ExecuteRoisToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<std::array<int64_t, 5>>& rois, uint64_t dst, uint32_t dtype,
+                           const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr,
+                           uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride) {
+    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || rois.empty() || !dst) return false;
+    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
+    if (!row_pitch) row_pitch = dw * elem;
+    if (!plane_stride) plane_stride = dh * row_pitch;
+    if (!frame_stride) frame_stride = 3 * plane_stride;
+    if (row_pitch > 0xffffffffull) return false;
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    std::vector<uint32_t> index(rois.size());
+    std::vector<vpf_rect> rects(rois.size());
+    std::vector<vpf_plane> planes(3 * rois.size());
+    for (size_t i = 0; i < rois.size(); i++) {
+      for (int k = 0; k < 5; k++)
+        if (rois[i][k] < 0 || rois[i][k] > 0xffffffffll) return false;
+      index[i] = (uint32_t)rois[i][0];
+      rects[i] = vpf_rect{(uint32_t)rois[i][1], (uint32_t)rois[i][2], (uint32_t)rois[i][3], (uint32_t)rois[i][4]};
+      for (int c = 0; c < 3; c++) {
+        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
+        planes[3 * i + c].pitch = (uint32_t)row_pitch;
+        planes[3 * i + c].reserved = 0;
+      }
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensorRois(a.data(), (uint32_t)a.size(), index.data(), rects.data(), (uint32_t)rois.size(), planes.data(), norm, cc.get());
   }
   size_t GetStream() const { return (size_t)task_->GetStream(); }
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
@@ -688,6 +723,11 @@ PYBIND11_MODULE(_PyNvCodec, m) {
       .def("ExecuteToTensor", &PySurfaceConvertResizer::ExecuteToTensor, py::arg("src"), py::arg("dst"), py::arg("dtype"), py::arg("mean"),
            py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0,
            py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("ExecuteRoisToTensor", &PySurfaceConvertResizer::ExecuteRoisToTensor, py::arg("surfaces"), py::arg("rois"), py::arg("ptr"), py::arg("dtype"),
+           py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>(),
+           "K rectangles (surface_index, x, y, w, h) of the surfaces, each resized to the task's destination size and normalised, into a planar tensor "
+           "[K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one dispatch per 96 regions")
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 

@@ -1,0 +1,219 @@
+// k_convert_roi.hip — fused multi-ROI crop + bilinear resize of NV12 / YUV420 into a normalised planar tensor (gfx950):
+// vpf_convert_resize_tensor_rois.  One dispatch serves many jobs; a job = (whole source frame, rectangle at ANY integer offset, three
+// destination planes), every job with scale factors of its own (RoiDesc, vpf_internal.h).  Grid z = job.
+//   k_roi_strip    the staged form: a workgroup owns (job, 16 destination rows, 256 destination columns); it converts that band's source
+//                  window once into an LDS strip of four-byte RGB pixels (the strip of k_convert_strip_wg) and blends from bytes
+//   k_roi_gather   per-tap texel_rgb: jobs whose window does not pay or does not fit (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
+// Definition (include/vpf_hip.h): taps are make_tap<LINEAR> on the RECTANGLE's size (they clamp at its edges), texels are frame pixels
+// (x + i, y + j) converted with vpf_convert's arithmetic — chroma at absolute ((x + i) >> 1, (y + j) >> 1) —, then bilerp, truncation
+// and the tensor epilogue.  Both kernels run exactly those fp32 operations in that order: identical bits.
+#include "k_bilinear_blend.h"
+#include "k_fused_common.h"
+
+namespace vpf {
+
+// loads of any alignment: a rectangle starts at an arbitrary byte of an arbitrarily aligned plane (the backend keeps them one
+// global_load_dword / _dwordx2: gfx950 global memory takes unaligned addresses)
+typedef u32x2 u32x2_any __attribute__((aligned(1)));
+typedef uint32_t u32_any __attribute__((aligned(1)));
+
+constexpr int kRoiBandRows = 4;  // destination rows per wave of the staged form: a workgroup's strip serves 16 rows x 256 columns
+
+// ------------------------------------------------------------------------------------------
+// The staged form.  convert_strip_wg_task (k_convert_resize.hip) with per-job geometry: the strip's pixels are ABSOLUTE frame pixels
+// [base_px, ..) x rows [y + R_lo, y + R_hi], base_px = the even pixel at or below the first tap (a conversion unit = 8 pixels x 2 luma
+// rows under ONE chroma row, so units start on chroma pairs of the frame, whatever the parity of the rectangle's corner); the blend
+// addresses them through rectangle-relative taps.  A unit that would read past the frame's right edge takes byte loads clamped to the
+// row's last sample instead of the 8-byte ones (its surplus pixels are converted and never blended): no byte outside the frame's own
+// rows is read.  Rows need no clamp: every row of the window lies in the rectangle, every chroma row under it in the frame.
+// ------------------------------------------------------------------------------------------
+template <int SRC>
+__global__ __launch_bounds__(256) void k_roi_strip(const RoiArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t dw, uint32_t dh, uint32_t dmask,
+                                                   uint32_t lds_bytes) {
+  constexpr int R = kRoiBandRows;
+  const RoiDesc& J = args.j[blockIdx.z];
+  const FrameDesc& f = J.f;
+  const uint32_t rx = J.x, ry = J.y, rw = J.w, rh = J.h;
+  const float scx = J.scx, scy = J.scy;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
+  const uint32_t Y0 = blockIdx.y * (4 * R), xs = blockIdx.x * 256;  // the grid covers the destination exactly: Y0 < dh, xs < dw
+  const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
+  const uint32_t first = rx + make_tap<VPF_INTERP_LINEAR>(xs, scx, rw).i0, last = rx + make_tap<VPF_INTERP_LINEAR>(xe, scx, rw).i1;  // frame pixels
+  const uint32_t base_px = first & ~1u;
+  const uint32_t R_lo_rel = __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y0, scy, rh).i0);
+  const uint32_t R_lo = ry + R_lo_rel, R_hi = ry + __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y1, scy, rh).i1);  // frame rows
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  const uint32_t c_lo = R_lo >> 1, ncr = (R_hi >> 1) - c_lo + 1, ng = ((last - base_px) >> 3) + 1, units = ncr * ng;
+  const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
+  if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, launch_convert_resize_rois)
+  const uint32_t cw = (W + 1) >> 1;
+  const float rng = 1.0f / (float)ng;
+  // unit u -> (chroma row ci = u / ng, group g): (u + 0.5) / ng is at least 0.5 / ng from an integer, far more than the fp32 error for u < 2^14
+  struct Unit { bool act = false, ra = false, rb = false; uint8_t* w = nullptr; u32x2 ya = {0u, 0u}, yb = {0u, 0u}, cq = {0u, 0u}; uint32_t vq = 0; };
+  auto bytes8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  // samples i0 .. i0 + 7 of a row of n, indices clamped to n - 1
+    uint32_t d[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t i = i0 + k < n ? i0 + k : n - 1;
+      d[k >> 2] |= (uint32_t)row[i] << (8 * (k & 3));
+    }
+    return u32x2{d[0], d[1]};
+  };
+  auto fetch = [&](uint32_t u, Unit& q) {
+    q.act = u < units;
+    if (!q.act) return;
+    const uint32_t ci = (uint32_t)(((float)u + 0.5f) * rng), g = u - ci * ng;
+    const uint32_t crow = c_lo + ci, px0 = base_px + 8 * g, r0 = 2 * crow;
+    q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  // (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window)
+    const uint8_t* const y0p = f.s[0] + (size_t)r0 * f.sp[0];
+    const uint8_t* const c1p = f.s[1] + (size_t)crow * f.sp[1];
+    if (px0 + 8 <= W) {
+      if constexpr (SRC == FC_NV12) {
+        q.cq = *reinterpret_cast<const u32x2_any*>(c1p + px0);
+      } else {
+        q.cq = u32x2{*reinterpret_cast<const u32_any*>(c1p + (px0 >> 1)), 0u};
+        q.vq = *reinterpret_cast<const u32_any*>(f.s[2] + (size_t)crow * f.sp[2] + (px0 >> 1));
+      }
+      if (q.ra) q.ya = *reinterpret_cast<const u32x2_any*>(y0p + px0);
+      if (q.rb) q.yb = *reinterpret_cast<const u32x2_any*>(y0p + f.sp[0] + px0);
+    } else {  // the unit that holds the frame's right edge
+      if constexpr (SRC == FC_NV12) {
+        uint32_t d[2] = {0u, 0u};  // U V pairs of chroma samples (px0 >> 1) .. + 3
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;
+          d[k >> 1] |= ((uint32_t)c1p[2 * i] | (uint32_t)c1p[2 * i + 1] << 8) << (16 * (k & 1));
+        }
+        q.cq = u32x2{d[0], d[1]};
+      } else {
+        q.cq = u32x2{bytes8(c1p, px0 >> 1, cw)[0], 0u};
+        q.vq = bytes8(f.s[2] + (size_t)crow * f.sp[2], px0 >> 1, cw)[0];
+      }
+      if (q.ra) q.ya = bytes8(y0p, px0, W);
+      if (q.rb) q.yb = bytes8(y0p + f.sp[0], px0, W);
+    }
+    // strip byte of (row r0, px0); r0 may be R_lo - 1 (that row is not written then: only row r0 + 1 is) — a signed offset
+    q.w = strip + ((int32_t)(r0 - R_lo) * (int32_t)rowbytes + (int32_t)(4 * (px0 - base_px)));
+  };
+  for (uint32_t u0 = tid; u0 < units; u0 += 512) {  // two units per lane in flight
+    Unit q0, q1;
+    fetch(u0, q0);
+    fetch(u0 + 256, q1);
+    __builtin_amdgcn_sched_barrier(0);  // both units' loads are requested before the first conversion
+    if (q0.act) convert_unit8<SRC>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);
+    if (q1.act) convert_unit8<SRC>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);
+  }
+  __syncthreads();
+  const uint32_t ya = Y0 + wv * R;
+  if (ya > Y1) return;
+  const uint32_t yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;
+  const Tap row_taps = band_row_taps(ya, yb, scy, rh);  // every lane of the wave still active here
+  const uint32_t x0 = xs + lane * 4;
+  if (x0 >= dw) return;
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const ColTapsX T = make_col_taps_x(base_px - rx, x0, dw, rw, scx);  // tap offsets from the strip's first pixel (frame pixel base_px = rectangle pixel base_px - x, modulo 2^32)
+  const TensorEpi te = args.e;
+  band_blend_rows<3, R>(strip, rowbytes, R_lo_rel, ya, yb, row_taps, T, [&](uint32_t y, const float* o) {  // o: pixel-major R G B, + 0.5 added
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec, nv);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// The gather form: k_convert_resize with per-job geometry (four lanes-rows x 64 lanes x 4 pixels per workgroup).
+// ------------------------------------------------------------------------------------------
+template <int SRC>
+__global__ __launch_bounds__(256) void k_roi_gather(const RoiArgs args, const Yuv2RgbCoef c, uint32_t dw, uint32_t dh, uint32_t dmask) {
+  const RoiDesc& J = args.j[blockIdx.z];
+  const FrameDesc& f = J.f;
+  const uint32_t x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  const uint32_t y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x0 >= dw || y >= dh) return;
+  const Tap ty = make_tap<VPF_INTERP_LINEAR>(y, J.scy, J.h);
+  float o[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const Tap tx = make_tap<VPF_INTERP_LINEAR>((x0 + k < dw) ? x0 + k : dw - 1, J.scx, J.w);
+    float p00[3], p01[3], p10[3], p11[3];
+    texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i0, p00);
+    texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i0, p01);
+    texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i1, p10);
+    texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i1, p11);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) o[ch][k] = bilerp(p00[ch], p01[ch], p10[ch], p11[ch], tx.f, ty.f);
+  }
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, args.e, ch, vec, nv);
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side.  The strip a staged job needs is WALKED with the kernel's own fp32 tap arithmetic (vpf_lin_i0 = make_tap's i0), chunk by
+// chunk and band by band, like vpf_band_rows_exact: a bound that is a row short would be silent corruption.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t kRoiStripMax = 53u * 1024u;  // three workgroups per CU (160 KiB)
+struct RoiStripNeed {
+  uint32_t bytes;  // rows x row bytes of the job's largest workgroup strip
+  double conv;     // source pixels converted per destination pixel (the gather form converts four)
+};
+static RoiStripNeed roi_strip_need(const RoiDesc& j, uint32_t dw, uint32_t dh) {
+  uint32_t rowbytes = 0, rows = 0;
+  for (uint32_t xs = 0; xs < dw; xs += 256) {
+    const uint32_t xe = xs + 255 < dw - 1 ? xs + 255 : dw - 1;
+    const uint32_t i0 = vpf_lin_i0(xe, j.scx, j.w);
+    const uint32_t first = j.x + vpf_lin_i0(xs, j.scx, j.w), last = j.x + (i0 + 1 < j.w ? i0 + 1 : j.w - 1);
+    const uint32_t rb = 32u * (((last - (first & ~1u)) >> 3) + 1u) + 16u;
+    rowbytes = rb > rowbytes ? rb : rowbytes;
+  }
+  for (uint32_t ya = 0; ya < dh; ya += 4 * kRoiBandRows) {
+    const uint32_t yb = ya + 4 * kRoiBandRows - 1 < dh - 1 ? ya + 4 * kRoiBandRows - 1 : dh - 1;
+    const uint32_t lo = vpf_lin_i0(ya, j.scy, j.h), hi0 = vpf_lin_i0(yb, j.scy, j.h), hi = hi0 + 1 < j.h ? hi0 + 1 : j.h - 1;
+    rows = hi - lo + 1 > rows ? hi - lo + 1 : rows;
+  }
+  const uint32_t cols = dw < 256 ? dw : 256, brows = dh < 4 * kRoiBandRows ? dh : 4 * kRoiBandRows;
+  return RoiStripNeed{rows * rowbytes, (double)rows * (rowbytes / 4) / ((double)cols * brows)};
+}
+
+hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
+                                      uint32_t dh, const TensorEpi& te) {
+  if (!n || n > (uint32_t)kRoiBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420)) return hipErrorInvalidValue;
+  const uint32_t dmask = te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need
+  // staged: the window fits a strip that leaves three workgroups per CU and converts at most three source pixels per destination pixel
+  // (the measured break-even of the strip against the per-tap kernels, launch_convert_resize); everything else gathers
+  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
+  RoiArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
+  std::memset(&as, 0, sizeof(as));
+  std::memset(&ag, 0, sizeof(ag));
+  as.e = ag.e = te;
+  uint32_t ns = 0, ngat = 0, lds = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : roi_strip_need(jobs[i], dw, dh);
+    if (!all_gather && need.bytes <= kRoiStripMax && need.conv <= 3.0) {
+      as.j[ns++] = jobs[i];
+      lds = need.bytes > lds ? need.bytes : lds;
+    } else {
+      ag.j[ngat++] = jobs[i];
+    }
+  }
+  if (ns) {
+    const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
+    if (src_fc == FC_NV12) VPF_LAUNCH((k_roi_strip<FC_NV12>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds);
+    else VPF_LAUNCH((k_roi_strip<FC_YUV420>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (ngat) {
+    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
+    if (src_fc == FC_NV12) VPF_LAUNCH((k_roi_gather<FC_NV12>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask);
+    else VPF_LAUNCH((k_roi_gather<FC_YUV420>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+}  // namespace vpf

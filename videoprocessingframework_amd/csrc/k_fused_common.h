@@ -1,0 +1,132 @@
+// k_fused_common.h — what the fused convert + resize translation units (k_convert_resize.hip, k_convert_roi.hip) share: the per-texel conversion,
+// the planar-tensor store epilogue, and the 8-pixel conversion unit of the workgroup-shared RGB strips.
+#ifndef VPF_K_FUSED_COMMON_H_
+#define VPF_K_FUSED_COMMON_H_
+#include "k_bilinear_blend.h"
+
+namespace vpf {
+
+// ------------------------------------------------------------------------------------------
+// (Stores: plain here — non-temporal stores measured 1.44 -> 1.61 us per 4K -> 720p frame in the batched fused kernel,
+// while the unfused resize kernels gain from them on large outputs: 1080p -> 4K 16.0 -> 13.8 us.)
+// fused NV12 / YUV420 -> bilinear -> RGB / BGR / RGB_PLANAR.  Defined as convert-then-resize: each of
+// the four source texels is converted to 8-bit RGB with exactly vpf_convert's arithmetic (including
+// its rounding), then interpolated — bit-identical to running the two kernels back to back, but the
+// 3 B/px intermediate never exists: 12.4 MB read + 2.8 MB written instead of 65 MB for 4K -> 720p.
+// ------------------------------------------------------------------------------------------
+template <int SRC>
+VPF_DEV void texel_rgb(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t x, uint32_t y, float* rgb) {
+  const float yf = (float)f.s[0][(size_t)y * f.sp[0] + x];
+  float u, v;
+  if constexpr (SRC == FC_NV12) {
+    const uint8_t* p = f.s[1] + (size_t)(y >> 1) * f.sp[1] + 2 * (x >> 1);
+    u = p[0]; v = p[1];
+  } else {
+    u = f.s[1][(size_t)(y >> 1) * f.sp[1] + (x >> 1)]; v = f.s[2][(size_t)(y >> 1) * f.sp[2] + (x >> 1)];
+  }
+  const Chroma k = chroma_terms(c, u, v);
+  rgb[0] = (float)sat_rne(__builtin_fmaf(yf, c.cy, k.rc));
+  rgb[1] = (float)sat_rne(__builtin_fmaf(yf, c.cy, k.gc));
+  rgb[2] = (float)sat_rne(__builtin_fmaf(yf, c.cy, k.bc));
+}
+
+// ------------------------------------------------------------------------------------------
+// The planar-tensor destination (FC_TENSOR, vpf_convert_resize_tensor): the store epilogue of every fused family.  Each family hands over
+// the 8-bit values FC_PLANAR would store (as floats: the same truncation, rounding or byte extraction that family uses for its bytes);
+// here they go through ONE fp32 fma per channel and a round-to-nearest-even conversion (v_cvt_f16_f32 under the default mode / the
+// compiler's v_cvt_pk_bf16_f32), then leave as 16 B (f32) or 8 B (f16 / bf16) per lane and channel where the row allows, else one element
+// at a time.  The dtype is a kernarg: a wave-uniform branch, one instantiation per family for the three dtypes.
+// ------------------------------------------------------------------------------------------
+template <int CAP>
+VPF_DEV TensorEpi epi_of(const BatchArgsT<CAP>&) { return TensorEpi{}; }  // 8-bit launches: never read
+template <int CAP>
+VPF_DEV TensorEpi epi_of(const BatchArgsTE<CAP>& a) { return a.e; }
+// `row` = byte address of row y of channel plane `ch` at column 0; u[] = the 8-bit values of columns x0 .. x0 + 3 (nv of them valid)
+template <bool NT>
+VPF_DEV void tensor_store4(uint8_t* row, uint32_t x0, const float u[4], const TensorEpi& e, int ch, bool vec, uint32_t nv) {
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) v[k] = __builtin_fmaf(u[k], e.scale[ch], e.bias[ch]);
+  if (e.dtype == VPF_TENSOR_F32) {
+    float* p = reinterpret_cast<float*>(row) + x0;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if (vec) stg<NT, f32x4>(p, f32x4{v[0], v[1], v[2], v[3]});
+    else for (uint32_t i = 0; i < nv; i++) p[i] = v[i];
+    return;
+  }
+  uint32_t h[4];
+  if (e.dtype == VPF_TENSOR_F16) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) h[k] = __builtin_bit_cast(uint16_t, (_Float16)v[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) h[k] = __builtin_bit_cast(uint16_t, (__bf16)v[k]);
+  }
+  uint16_t* p = reinterpret_cast<uint16_t*>(row) + x0;
+  if (vec) stg<NT, u32x2>(p, u32x2{h[0] | h[1] << 16, h[2] | h[3] << 16});
+  else for (uint32_t i = 0; i < nv; i++) p[i] = (uint16_t)h[i];
+}
+// eight consecutive f16 / bf16 elements per lane (k_convert_half): ONE 16-B store per lane, so a store instruction covers 1 KiB of the row
+// without holes (non-temporal, like the 8-bit planes).  (f32 rows go through LDS first: convert_half_task.)
+VPF_DEV void tensor_store8(uint8_t* row, uint32_t x0, const float u[8], const TensorEpi& e, int ch) {
+  uint32_t h[8];
+  if (e.dtype == VPF_TENSOR_F16) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) h[k] = __builtin_bit_cast(uint16_t, (_Float16)__builtin_fmaf(u[k], e.scale[ch], e.bias[ch]));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) h[k] = __builtin_bit_cast(uint16_t, (__bf16)__builtin_fmaf(u[k], e.scale[ch], e.bias[ch]));
+  }
+  stg<true, u32x4>(reinterpret_cast<uint16_t*>(row) + x0, u32x4{h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16});
+}
+// the FC_PLANAR store sections' values o[] (+ 0.5 added: truncation gives the byte) of channel ch, pixel k at o[k * stride]
+template <bool NT>
+VPF_DEV void tensor_store4_trunc(uint8_t* row, uint32_t x0, const float* o, int stride, const TensorEpi& e, int ch, bool vec, uint32_t nv) {
+  const float u[4] = {__builtin_truncf(o[0]), __builtin_truncf(o[stride]), __builtin_truncf(o[2 * stride]), __builtin_truncf(o[3 * stride])};
+  tensor_store4<NT>(row, x0, u, e, ch, vec, nv);
+}
+
+// One conversion unit of the workgroup-shared strips (k_convert_strip_wg, k_roi_strip): 8 pixels x 2 luma rows under one chroma row -> four-byte
+// R G B x pixels in LDS.
+template <int SRC>
+VPF_DEV void convert_unit8(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t crow, uint32_t px0, bool row_a, bool row_b, uint8_t* wa /* strip byte of (row 2 crow, px0) */,
+                           uint32_t rowbytes, u32x2 ya, u32x2 yb, u32x2 cq, uint32_t vq) {
+  (void)f; (void)crow; (void)px0;
+  uint32_t uv[2];  // U V U V bytes of pixel pairs 0, 1 | 2, 3
+  if constexpr (SRC == FC_NV12) {
+    uv[0] = cq[0]; uv[1] = cq[1];
+  } else {
+    uv[0] = __builtin_amdgcn_perm(vq, cq[0], 0x05010400u); uv[1] = __builtin_amdgcn_perm(vq, cq[0], 0x07030602u);
+  }
+  Chroma k[4];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    k[2 * j] = chroma_terms(c, ubyte<0>(uv[j]), ubyte<1>(uv[j]));
+    k[2 * j + 1] = chroma_terms(c, ubyte<2>(uv[j]), ubyte<3>(uv[j]));
+  }
+#pragma unroll
+  for (int hf = 0; hf < 2; hf++) {
+    if (!(hf ? row_b : row_a)) continue;
+    const u32x2 yq = hf ? yb : ya;
+    uint32_t d[8];  // 8 px -> 8 dwords R G B x (px4 strips, k_bilinear_blend.h), vpf_convert's rounding (v_cvt_pk_u8_f32): three cvt per pixel as for packed bytes
+#pragma unroll
+    for (int j = 0; j < 2; j++) {  // (the pixel-pair form of convert_strip_task: same IEEE fma per component as convert4 -> same bits)
+      const uint32_t yd = yq[j];
+      const f32x2 cy2 = {c.cy, c.cy}, ya2 = {ubyte<0>(yd), ubyte<1>(yd)}, yb2 = {ubyte<2>(yd), ubyte<3>(yd)};
+      const Chroma &ka = k[2 * j], &kb = k[2 * j + 1];
+      const f32x2 ra = __builtin_elementwise_fma(ya2, cy2, f32x2{ka.rc, ka.rc}), ga = __builtin_elementwise_fma(ya2, cy2, f32x2{ka.gc, ka.gc}),
+                  ba = __builtin_elementwise_fma(ya2, cy2, f32x2{ka.bc, ka.bc});
+      const f32x2 rb = __builtin_elementwise_fma(yb2, cy2, f32x2{kb.rc, kb.rc}), gb = __builtin_elementwise_fma(yb2, cy2, f32x2{kb.gc, kb.gc}),
+                  bb = __builtin_elementwise_fma(yb2, cy2, f32x2{kb.bc, kb.bc});
+      d[4 * j] = pack3(ra[0], ga[0], ba[0]);
+      d[4 * j + 1] = pack3(ra[1], ga[1], ba[1]);
+      d[4 * j + 2] = pack3(rb[0], gb[0], bb[0]);
+      d[4 * j + 3] = pack3(rb[1], gb[1], bb[1]);
+    }
+    u32x4* w = reinterpret_cast<u32x4*>(wa + (hf ? rowbytes : 0u));
+    w[0] = u32x4{d[0], d[1], d[2], d[3]}; w[1] = u32x4{d[4], d[5], d[6], d[7]};
+  }
+}
+
+}  // namespace vpf
+#endif  // VPF_K_FUSED_COMMON_H_

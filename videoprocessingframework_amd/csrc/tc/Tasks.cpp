@@ -502,6 +502,33 @@ TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, 
   }
   return TASK_EXEC_SUCCESS;
 }
+TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, uint32_t n,
+                                                   const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorRois");
+  if (!frames || !n_frames || !frame_index || !rects || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  for (uint32_t i = 0; i < n_frames; i++) {
+    Surface* s = frames[i];
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+  }
+  std::vector<vpf_roi_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(frames[frame_index[i]], io[i].src);
+    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    io[i].rect = rects[i];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_resize_tensor_rois(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+                                                       io.data(), &norm);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to convert + resize regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
 // ------------------------------------------------------------------------------------------ TensorToSurface

@@ -52,6 +52,11 @@ public:
   // n same-shape surfaces -> n frames of a normalised planar tensor (vpf_convert_resize_tensor_batch): dst holds 3 n planes, frame i's
   // channel planes at dst[3 i .. 3 i + 2] in output channel order; the same colour-context rules as Run / RunBatch
   TaskExecStatus RunTensor(Surface* const* inputs, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
+  // n rectangles of surfaces -> n frames of a normalised planar tensor (vpf_convert_resize_tensor_rois): job i takes rects[i] (luma pixels, any
+  // integer offset, inside the surface) of frames[frame_index[i]] and writes dst[3 i .. 3 i + 2]; every surface has the task's source format
+  // and size, every job the task's destination size.  The same colour-context rules as RunTensor.
+  TaskExecStatus RunTensorRois(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, uint32_t n,
+                               const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on
 
 private:

@@ -496,6 +496,55 @@ vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int c
   return vpf_convert_resize_tensor_batch(exec, sf, cs, cr, ss, ds, 1, &io, norm);
 }
 
+// Many rectangles of decoded frames -> one batch of normalised planes (include/vpf_hip.h): per-job geometry, kRoiBatch jobs per job table,
+// each table at most two dispatches (k_convert_roi.hip).
+vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
+                                          const vpf_roi_io* rois, const vpf_tensor_norm* norm) {
+  const Mark mark("vpf_convert_resize_tensor_rois");
+  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !rois || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  for (uint32_t i = 0; i < n; i++) {
+    const vpf_rect& r = rois[i].rect;
+    if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
+    if (!planes_ok(sf, ss.width, rois[i].src)) return VPF_ERR_BAD_ARG;
+    for (int k = 0; k < 3; k++) {
+      const vpf_plane& p = rois[i].dst[k];
+      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
+    }
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
+  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
+  te.dtype = norm->dtype;
+  RoiDesc jobs[kRoiBatch];
+  for (uint32_t base = 0; base < n; base += kRoiBatch) {
+    const uint32_t m = (n - base < (uint32_t)kRoiBatch) ? n - base : (uint32_t)kRoiBatch;
+    for (uint32_t i = 0; i < m; i++) {
+      const vpf_roi_io& io = rois[base + i];
+      vpf_plane d[3];
+      for (int k = 0; k < 3; k++) d[k] = io.dst[bgr ? 2 - k : k];
+      RoiDesc& j = jobs[i];
+      fill_desc(j.f, io.src, num_planes(sf), d, 3);
+      j.x = io.rect.x; j.y = io.rect.y; j.w = io.rect.width; j.h = io.rect.height;
+      j.scx = (float)j.w / (float)ds.width; j.scy = (float)j.h / (float)ds.height;
+    }
+    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
 int vpf_tensor_convert_supported(int df, int cs, int cr) {
   return (df == VPF_FMT_NV12 || df == VPF_FMT_YUV420) && classify(VPF_FMT_RGB_PLANAR, VPF_FMT_YUV420, cs, cr) == FAM_RGB2YUV;

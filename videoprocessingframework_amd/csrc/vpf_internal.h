@@ -87,6 +87,21 @@ struct BatchArgsTE {
   TensorEpi e;
 };
 
+// The job table of a multi-ROI launch (vpf_convert_resize_tensor_rois, k_convert_roi.hip): per job the planes of the WHOLE source frame and
+// of the destination, the rectangle in luma pixels of the frame, and the job's own scale factors (computed on the host as every launcher
+// does: (float)w / (float)dw).  96 jobs x 96 B + the epilogue = the 9 248 B of BatchArgsTE<kMaxBatch>, the largest argument block measured.
+constexpr int kRoiBatch = 96;
+struct RoiDesc {
+  FrameDesc f;
+  uint32_t x, y, w, h;
+  float scx, scy;
+};
+struct RoiArgs {
+  RoiDesc j[kRoiBatch];
+  TensorEpi e;
+};
+static_assert(sizeof(RoiDesc) == 96 && sizeof(RoiArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the ROI job table must not outgrow the largest frame table");
+
 // The prologue of a tensor -> NV12 / YUV420 launch (vpf_tensor_convert): q[c] = rint(clamp(x[c] * scale[c] + bias[c], 0, 255)) feeds the RGB -> YUV
 // arithmetic.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
 struct TensorPro {
@@ -130,6 +145,9 @@ hipError_t launch_remap_batch(hipStream_t st, uint32_t sw, uint32_t sh, const fl
 // dst_fc == FC_TENSOR takes `te` (the element size sets the destination alignment tests); every other class ignores it
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw,
                                  uint32_t sh, uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te = nullptr);
+// n <= kRoiBatch jobs on frames `W` pixels wide -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); k_convert_roi.hip
+hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
+                                      uint32_t dh, const TensorEpi& te);
 
 int tuning(int key);
 
