@@ -275,6 +275,49 @@ VPF_API vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int src_
                                                   vpf_size dst_size, uint32_t n, const vpf_roi_io* rois, const vpf_tensor_norm* norm);
 
 /*
+ * Fused multi-ROI affine warp -> normalised planar tensor: `n` crops of decoded NV12 / YUV420 frames that are NOT axis-aligned (aligned faces, rotated
+ * text boxes, oriented detections, flips, shears), each sampled through a 2 x 3 matrix of its own into the ONE size dst_size and normalised, in
+ * one dispatch: float [K, 3, dh, dw].  A job = (the planes of a WHOLE frame of src_size = (W, H), m[6] = (m00 m01 m02; m10 m11 m12), three
+ * destination planes).  The matrix is the INVERSE map: it takes a destination pixel to source coordinates in luma pixels of that frame; coordinates
+ * are pixel indices, the convention of vpf_remap's maps.  For destination pixel (dx, dy), channel c — every operation a separately rounded fp32
+ * operation in this order, no fma:
+ *   sx = (m00 * (float)dx + m01 * (float)dy) + m02,  sy = (m10 * (float)dx + m11 * (float)dy) + m12;
+ *   VPF_WARP_CONSTANT: the pixel is in range when sx >= 0 && sx <= (float)(W - 1) && sy >= 0 && sy <= (float)(H - 1) (vpf_remap's test: -0.0 is in
+ *        range); a pixel out of range takes u8[c] = border[c], unblended (border[c] belongs to OUTPUT channel c, like scale[c] and bias[c]);
+ *   VPF_WARP_REPLICATE: sx = min(max(sx, 0), W - 1), sy = min(max(sy, 0), H - 1) first, so every pixel is in range;
+ *   in range: x0 = (int)sx, x1 = min(x0 + 1, W - 1), fx = sx - (float)x0, likewise y (vpf_remap's sampling); the four texels are frame pixels
+ *        (x0|x1, y0|y1), each converted with vpf_convert's arithmetic for (src_fmt -> RGB_PLANAR, color_space, color_range) including its 8-bit
+ *        rounding, chroma taken at (x >> 1, y >> 1);
+ *   u8  = trunc(fma(fy, bot - top, top) + 0.5), top = fma(fx, p01 - p00, p00), bot = fma(fx, p11 - p10, p10);
+ *   out = round_to_dtype(fmaf(u8, scale[c], bias[c]))              exactly vpf_convert_resize_tensor's epilogue (dtype, VPF_TENSOR_BGR, plane rules).
+ * Equivalently u8 is the byte vpf_remap(RGB) writes when its source is vpf_convert(frame -> RGB), its maps hold the sx, sy above and its
+ * destination was pre-filled with `border`.  Resize and remap use different coordinate conventions: a caller who wants vpf_resize's sampling of
+ * a rectangle (x, y, w, h) folds it into the matrix (m00 = s, m02 = 0.5 s - 0.5 + x with s = w / dw); bit-equality with
+ * vpf_convert_resize_tensor_rois is not promised for such matrices.  A job whose footprint lies wholly outside the frame is legal: it writes the
+ * border (the edge pixels under REPLICATE).
+ * `jobs` is a HOST array, consumed before return; 96 jobs travel per job table, each table in at most two dispatches (jobs whose tiles' source
+ * windows are converted once into LDS and blended from there, and jobs that convert per tap — down-scales: identical bits).
+ * opts == NULL means VPF_WARP_CONSTANT with border 0 0 0.  Unsupported format / matrix / dtype / flag as vpf_convert_resize_tensor, or an unknown
+ * border mode: VPF_ERR_UNSUPPORTED.  Null pointers, n == 0, bad sizes, short pitches, misaligned planes, non-finite scale / bias, non-zero
+ * reserved fields, a matrix coefficient that is not finite or exceeds 2^24 in magnitude (so sx, sy stay finite and no NaN arises):
+ * VPF_ERR_BAD_ARG — all checked before any device access.
+ */
+#define VPF_WARP_CONSTANT 0u
+#define VPF_WARP_REPLICATE 1u
+typedef struct vpf_warp_io {
+  vpf_plane src[3]; /* the WHOLE frame's planes */
+  vpf_plane dst[3];
+  float m[6]; /* m00 m01 m02 m10 m11 m12: destination pixel -> source coordinates */
+} vpf_warp_io; /* 120 bytes, no implicit padding */
+typedef struct vpf_warp_opts {
+  uint32_t border_mode; /* VPF_WARP_* */
+  uint8_t border[3];    /* per output channel, VPF_WARP_CONSTANT */
+  uint8_t reserved;     /* must be 0 */
+} vpf_warp_opts; /* 8 bytes */
+VPF_API vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size, vpf_size dst_size,
+                                           uint32_t n, const vpf_warp_io* jobs, const vpf_tensor_norm* norm, const vpf_warp_opts* opts);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

@@ -243,6 +243,100 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
     return out
 
 
+_WARP_MODES = {"constant": 0, "replicate": 1}
+
+
+def _matrices_list(matrices, fn):
+    """matrices -> list of six-float lists (rounded to float32 once): ValueError for a device tensor, a non-float dtype, a shape other than
+    [K, 2, 3], a coefficient that is not finite or exceeds 2^24 in magnitude"""
+    import numpy as np
+
+    if isinstance(matrices, torch.Tensor):
+        if matrices.device.type != "cpu":
+            raise ValueError(f"{fn}: matrices must live on the host (the job table is built on the CPU): pass matrices.cpu()")
+        if not matrices.dtype.is_floating_point:
+            raise ValueError(f"{fn}: matrices must hold floats, got {matrices.dtype}")
+        arr = matrices.detach().to(torch.float64).numpy()
+    else:
+        arr = np.asarray(matrices)
+        if arr.size and arr.dtype.kind != "f" and not (arr.dtype.kind in "iu" and not hasattr(matrices, "dtype")):
+            raise ValueError(f"{fn}: matrices must hold floats, got {arr.dtype}")
+    if arr.size == 0 and arr.ndim <= 1:
+        arr = arr.reshape(0, 2, 3)
+    if arr.ndim != 3 or tuple(arr.shape[1:]) != (2, 3):
+        raise ValueError(f"{fn}: matrices must have shape [K, 2, 3], got {tuple(arr.shape)}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        arr = arr.astype(np.float32)
+    if not bool((np.abs(arr) <= np.float32(2.0 ** 24)).all()):
+        raise ValueError(f"{fn}: every matrix coefficient must be finite and at most 2^24 in magnitude")
+    return [[float(v) for v in m.reshape(6)] for m in arr]
+
+
+def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None) -> torch.Tensor:
+    """K affine warps of NV12 / YUV420 surfaces -> the normalised float tensor [K, 3, dh, dw] a network behind a detector consumes (aligned faces,
+    rotated text boxes, oriented detections), in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteWarpsToTensor, vpf_convert_warp_tensor).
+    `matrices`: a host [K, 2, 3] float tensor, ndarray or nested sequence (float64 is rounded to float32 once); matrices[i] is the INVERSE map of
+    job i: it takes a destination pixel (dx, dy) to source coordinates in luma pixels of surfaces[surface_index[i]], the convention of remap's
+    maps.  Pixels that fall outside the surface take `border` (per output channel, 0..255) under border_mode "constant" and the nearest edge
+    pixel under "replicate".  Normalisation, `out`, the returned tensor and the stream ordering: exactly as to_normalized_tensor.
+
+    ValueError for matrices on the device (pass .cpu()), a wrong shape, a non-float dtype, a coefficient that is not finite or exceeds 2^24, a
+    bad surface index, a border value outside 0..255, an unknown mode.  K == 0 returns an empty tensor without a launch."""
+    fn = "warps_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    if border_mode not in _WARP_MODES:
+        raise ValueError(f"{fn}: border_mode must be one of {list(_WARP_MODES)}, got {border_mode!r}")
+    try:
+        border = [operator.index(v) for v in border]
+    except TypeError:
+        raise ValueError(f"{fn}: border must hold three integers, got {border!r}") from None
+    if len(border) != 3 or any(not 0 <= v <= 255 for v in border):
+        raise ValueError(f"{fn}: border must hold three values in 0..255, got {border}")
+    surfaces = list(surfaces)
+    jobs = _matrices_list(matrices, fn)
+    if isinstance(surface_index, torch.Tensor):
+        if surface_index.device.type != "cpu":
+            raise ValueError(f"{fn}: surface_index must live on the host: pass surface_index.cpu()")
+        surface_index = surface_index.tolist()
+    try:
+        index = [operator.index(v) for v in surface_index]
+    except TypeError:
+        raise ValueError(f"{fn}: surface_index must hold integers") from None
+    if len(index) != len(jobs):
+        raise ValueError(f"{fn}: {len(index)} surface indices for {len(jobs)} matrices")
+    for i, k in enumerate(index):
+        if not 0 <= k < len(surfaces):
+            raise ValueError(f"{fn}: surface_index[{i}] names surface {k}, there are {len(surfaces)}")
+    n = len(jobs)
+    w, h = resizer.DstSize()
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    if n == 0:
+        return out
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+        ok = resizer.ExecuteWarpsToTensor(surfaces, index, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
+                                          cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem)
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out
+
+
 def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None):
     """A model's output -> NV12 / YUV420 surfaces for the encoder, in one pass (PyTensorToSurface.ExecuteBatch): `tensor` is [N, 3, H, W] or
     [3, H, W] of float32 / float16 / bfloat16 on the device, normalised with torchvision's mean / std (per input plane; B G R planes when

@@ -29,7 +29,7 @@ EXPORTS = [
     "vpf_convert", "vpf_convert_batch", "vpf_convert_supported", "vpf_resize", "vpf_remap", "vpf_convert_resize",
     "vpf_convert_resize_batch", "vpf_resize_batch", "vpf_remap_batch", "vpf_resize_ws", "vpf_resize_batch_ws", "vpf_resize_workspace_bytes",
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
-    "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois",
+    "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
@@ -64,6 +64,19 @@ class Rect(C.Structure):
 class RoiIO(C.Structure):
     """vpf_roi_io: one job of vpf_convert_resize_tensor_rois — the WHOLE source frame's planes, the destination planes, the rectangle"""
     _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("rect", Rect)]
+
+
+class WarpIO(C.Structure):
+    """vpf_warp_io: one job of vpf_convert_warp_tensor — the WHOLE source frame's planes, the destination planes, the inverse 2 x 3 matrix"""
+    _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("m", C.c_float * 6)]
+
+
+class WarpOpts(C.Structure):
+    """vpf_warp_opts: border mode (WARP_CONSTANT / WARP_REPLICATE) and the border bytes per output channel"""
+    _fields_ = [("border_mode", C.c_uint32), ("border", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+WARP_CONSTANT, WARP_REPLICATE = 0, 1
 
 
 class TensorNorm(C.Structure):
@@ -155,6 +168,7 @@ def lib() -> C.CDLL:
         L.vpf_convert_resize_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, Size, PP, PN]
         L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
         L.vpf_convert_resize_tensor_rois.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(RoiIO), PN]
+        L.vpf_convert_warp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(WarpIO), PN, C.POINTER(WarpOpts)]
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
         L.vpf_tensor_convert.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, PP, PN]
         L.vpf_tensor_convert_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, C.c_uint32, PF, PN]
@@ -340,6 +354,38 @@ def convert_resize_tensor_rois(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, rois, 
                                               C.byref(norm) if norm is not None else None)
     if check:
         _check(st, "vpf_convert_resize_tensor_rois")
+    return st
+
+
+def make_warps(jobs) -> "C.Array[WarpIO]":
+    """jobs: list of (src_desc, dst_desc, m) with desc as in planes(); src_desc = the planes of the WHOLE frame, m = six floats
+    (m00 m01 m02 m10 m11 m12) or a 2 x 3 nested sequence: destination pixel -> source coordinates"""
+    arr = (WarpIO * len(jobs))()
+    for i, (s, d, m) in enumerate(jobs):
+        s, d = planes(s), planes(d)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+            arr[i].dst[k].ptr, arr[i].dst[k].pitch = d[k].ptr, d[k].pitch
+        flat = [v for row in m for v in row] if len(m) == 2 else list(m)
+        for k in range(6):
+            arr[i].m[k] = flat[k]
+    return arr
+
+
+def make_warp_opts(border_mode=WARP_CONSTANT, border=(0, 0, 0)) -> WarpOpts:
+    o = WarpOpts()
+    o.border_mode = border_mode
+    for k in range(3):
+        o.border[k] = border[k]
+    return o
+
+
+def convert_warp_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, warps, norm: TensorNorm, opts: WarpOpts = None, n=None, check=True) -> int:
+    """warps: WarpIO array from make_warps(); every job sampled through its matrix into dw x dh and normalised, 96 jobs per job table"""
+    st = lib().vpf_convert_warp_tensor(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), Size(dw, dh), len(warps) if n is None else n, warps,
+                                       C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_warp_tensor")
     return st
 
 

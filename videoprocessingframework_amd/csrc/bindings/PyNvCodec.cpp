@@ -222,6 +222,44 @@ public:
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorRois(a.data(), (uint32_t)a.size(), index.data(), rects.data(), (uint32_t)rois.size(), planes.data(), norm, cc.get());
   }
+  // additive: K affine warps of surfaces -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_warp_tensor):
+  // warps[i] = (surface index, m00, m01, m02, m10, m11, m12), the inverse matrix (destination pixel -> source luma pixel coordinates);
+  // border per output channel, border_mode 0 = constant, 1 = replicate; tensor layout and mean / std as ExecuteToTensor
+  bool ExecuteWarpsToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<int64_t>& index, const std::vector<std::array<float, 6>>& matrices,
+                            uint64_t dst, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
+                            std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode,
+                            uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride) {
+    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || index.empty() || index.size() != matrices.size() || !dst) return false;
+    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
+    if (!row_pitch) row_pitch = dw * elem;
+    if (!plane_stride) plane_stride = dh * row_pitch;
+    if (!frame_stride) frame_stride = 3 * plane_stride;
+    if (row_pitch > 0xffffffffull) return false;
+    vpf_warp_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    opts.border_mode = border_mode;
+    for (int c = 0; c < 3; c++) {
+      if (border[c] < 0 || border[c] > 255) return false;
+      opts.border[c] = (uint8_t)border[c];
+    }
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    std::vector<uint32_t> idx(index.size());
+    std::vector<float> m(6 * index.size());
+    std::vector<vpf_plane> planes(3 * index.size());
+    for (size_t i = 0; i < index.size(); i++) {
+      if (index[i] < 0 || index[i] > 0xffffffffll) return false;
+      idx[i] = (uint32_t)index[i];
+      for (int k = 0; k < 6; k++) m[6 * i + k] = matrices[i][k];
+      for (int c = 0; c < 3; c++) {
+        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
+        planes[3 * i + c].pitch = (uint32_t)row_pitch;
+        planes[3 * i + c].reserved = 0;
+      }
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensorWarps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
+  }
   size_t GetStream() const { return (size_t)task_->GetStream(); }
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
@@ -728,6 +766,13 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>(),
            "K rectangles (surface_index, x, y, w, h) of the surfaces, each resized to the task's destination size and normalised, into a planar tensor "
            "[K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one dispatch per 96 regions")
+      .def("ExecuteWarpsToTensor", &PySurfaceConvertResizer::ExecuteWarpsToTensor, py::arg("surfaces"), py::arg("surface_index"), py::arg("matrices"),
+           py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>(),
+           "K affine warps of the surfaces: job i samples surfaces[surface_index[i]] through the inverse 2 x 3 matrix matrices[i] (six floats) into the "
+           "task's destination size, normalised, into a planar tensor [K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one "
+           "dispatch per 96 regions")
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 

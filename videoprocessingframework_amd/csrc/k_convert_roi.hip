@@ -12,11 +12,6 @@
 
 namespace vpf {
 
-// loads of any alignment: a rectangle starts at an arbitrary byte of an arbitrarily aligned plane (the backend keeps them one
-// global_load_dword / _dwordx2: gfx950 global memory takes unaligned addresses)
-typedef u32x2 u32x2_any __attribute__((aligned(1)));
-typedef uint32_t u32_any __attribute__((aligned(1)));
-
 constexpr int kRoiBandRows = 4;  // destination rows per wave of the staged form: a workgroup's strip serves 16 rows x 256 columns
 
 // ------------------------------------------------------------------------------------------
@@ -46,63 +41,7 @@ __global__ __launch_bounds__(256) void k_roi_strip(const RoiArgs args, const Yuv
   const uint32_t c_lo = R_lo >> 1, ncr = (R_hi >> 1) - c_lo + 1, ng = ((last - base_px) >> 3) + 1, units = ncr * ng;
   const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
   if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, launch_convert_resize_rois)
-  const uint32_t cw = (W + 1) >> 1;
-  const float rng = 1.0f / (float)ng;
-  // unit u -> (chroma row ci = u / ng, group g): (u + 0.5) / ng is at least 0.5 / ng from an integer, far more than the fp32 error for u < 2^14
-  struct Unit { bool act = false, ra = false, rb = false; uint8_t* w = nullptr; u32x2 ya = {0u, 0u}, yb = {0u, 0u}, cq = {0u, 0u}; uint32_t vq = 0; };
-  auto bytes8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  // samples i0 .. i0 + 7 of a row of n, indices clamped to n - 1
-    uint32_t d[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const uint32_t i = i0 + k < n ? i0 + k : n - 1;
-      d[k >> 2] |= (uint32_t)row[i] << (8 * (k & 3));
-    }
-    return u32x2{d[0], d[1]};
-  };
-  auto fetch = [&](uint32_t u, Unit& q) {
-    q.act = u < units;
-    if (!q.act) return;
-    const uint32_t ci = (uint32_t)(((float)u + 0.5f) * rng), g = u - ci * ng;
-    const uint32_t crow = c_lo + ci, px0 = base_px + 8 * g, r0 = 2 * crow;
-    q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  // (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window)
-    const uint8_t* const y0p = f.s[0] + (size_t)r0 * f.sp[0];
-    const uint8_t* const c1p = f.s[1] + (size_t)crow * f.sp[1];
-    if (px0 + 8 <= W) {
-      if constexpr (SRC == FC_NV12) {
-        q.cq = *reinterpret_cast<const u32x2_any*>(c1p + px0);
-      } else {
-        q.cq = u32x2{*reinterpret_cast<const u32_any*>(c1p + (px0 >> 1)), 0u};
-        q.vq = *reinterpret_cast<const u32_any*>(f.s[2] + (size_t)crow * f.sp[2] + (px0 >> 1));
-      }
-      if (q.ra) q.ya = *reinterpret_cast<const u32x2_any*>(y0p + px0);
-      if (q.rb) q.yb = *reinterpret_cast<const u32x2_any*>(y0p + f.sp[0] + px0);
-    } else {  // the unit that holds the frame's right edge
-      if constexpr (SRC == FC_NV12) {
-        uint32_t d[2] = {0u, 0u};  // U V pairs of chroma samples (px0 >> 1) .. + 3
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;
-          d[k >> 1] |= ((uint32_t)c1p[2 * i] | (uint32_t)c1p[2 * i + 1] << 8) << (16 * (k & 1));
-        }
-        q.cq = u32x2{d[0], d[1]};
-      } else {
-        q.cq = u32x2{bytes8(c1p, px0 >> 1, cw)[0], 0u};
-        q.vq = bytes8(f.s[2] + (size_t)crow * f.sp[2], px0 >> 1, cw)[0];
-      }
-      if (q.ra) q.ya = bytes8(y0p, px0, W);
-      if (q.rb) q.yb = bytes8(y0p + f.sp[0], px0, W);
-    }
-    // strip byte of (row r0, px0); r0 may be R_lo - 1 (that row is not written then: only row r0 + 1 is) — a signed offset
-    q.w = strip + ((int32_t)(r0 - R_lo) * (int32_t)rowbytes + (int32_t)(4 * (px0 - base_px)));
-  };
-  for (uint32_t u0 = tid; u0 < units; u0 += 512) {  // two units per lane in flight
-    Unit q0, q1;
-    fetch(u0, q0);
-    fetch(u0 + 256, q1);
-    __builtin_amdgcn_sched_barrier(0);  // both units' loads are requested before the first conversion
-    if (q0.act) convert_unit8<SRC>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);
-    if (q1.act) convert_unit8<SRC>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);
-  }
+  VPF_STRIP_FILL_WINDOW  // (k_fused_common.h: shared with k_warp_strip)
   __syncthreads();
   const uint32_t ya = Y0 + wv * R;
   if (ya > Y1) return;

@@ -1,0 +1,265 @@
+// k_convert_warp.hip — fused multi-ROI affine warp of NV12 / YUV420 into a normalised planar tensor (gfx950): vpf_convert_warp_tensor.
+// One dispatch serves many jobs; a job = (whole source frame, inverse 2 x 3 matrix, three destination planes) (WarpDesc, vpf_internal.h).
+// Grid = (destination tiles of 32 x 32, job); a lane owns four consecutive pixels of one row, a workgroup 8 lanes x 32 rows.
+//   k_warp_strip    the staged form: the workgroup takes the bounding box of its tile's taps from the tile's four corners, converts that
+//                   source window once into an LDS strip of four-byte RGB pixels (VPF_STRIP_FILL_WINDOW, the fill stage of k_roi_strip) and
+//                   blends every pixel from bytes at per-pixel taps
+//   k_warp_gather   per-tap texel_rgb: jobs whose tile windows do not fit 64 KiB of LDS (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
+// Definition (include/vpf_hip.h): sx = (m00 dx + m01 dy) + m02, sy likewise, every operation rounded on its own (-ffp-contract=off), then
+// vpf_remap's range test and sampling on frame pixels converted with vpf_convert's arithmetic, bilerp, truncation, the tensor epilogue.
+// Both kernels run exactly those fp32 operations in that order: identical bits.
+#include <cmath>
+
+#include "k_bilinear_blend.h"
+#include "k_fused_common.h"
+
+namespace vpf {
+
+// Destination tile of a workgroup: 1024 pixels, four per lane.  Close to square keeps a rotated footprint's bounding box small; 32 x 32 measured
+// against 64 x 16 and 16 x 64 (builds with -DVPF_WARP_TILE_W= -DVPF_WARP_TILE_H=, tools/warp_kernel_ab.py).
+#ifndef VPF_WARP_TILE_W
+#define VPF_WARP_TILE_W 32
+#define VPF_WARP_TILE_H 32
+#endif
+constexpr uint32_t kWarpTileW = VPF_WARP_TILE_W, kWarpTileH = VPF_WARP_TILE_H, kWarpLanesX = kWarpTileW / 4;
+static_assert(kWarpTileW * kWarpTileH == 1024 && kWarpTileW % 4 == 0, "a workgroup of 256 lanes x 4 pixels covers one tile");
+
+// ------------------------------------------------------------------------------------------
+// Coordinates: host and device run the same separately rounded fp32 operations (the host sizes the strips with them).
+// ------------------------------------------------------------------------------------------
+struct WarpXY { float sx, sy; };
+__host__ __device__ __forceinline__ WarpXY warp_xy(const float* m, uint32_t dx, uint32_t dy, bool rep, float wmax, float hmax) {
+  const float fx = (float)dx, fy = (float)dy;
+  float sx = (m[0] * fx + m[1] * fy) + m[2];
+  float sy = (m[3] * fx + m[4] * fy) + m[5];
+  if (rep) {  // a max, then a min
+    sx = fminf(fmaxf(sx, 0.f), wmax);
+    sy = fminf(fmaxf(sy, 0.f), hmax);
+  }
+  return WarpXY{sx, sy};
+}
+// The source window of a destination tile [xs, xe] x [ys, ye]: rounding is monotonic, so sx and sy are monotonic in dx for fixed dy and in dy
+// for fixed dx (clamped or not) and their extremes over the tile lie at its four corners, exactly.  Every in-range pixel of the tile has
+// x_lo <= x0, x1 <= x_hi and y_lo <= y0, y1 <= y_hi; `empty`: no pixel of the tile is in range.
+struct WarpWin {
+  uint32_t x_lo, x_hi, y_lo, y_hi;
+  bool empty;
+};
+__host__ __device__ __forceinline__ WarpWin warp_window(const float* m, uint32_t xs, uint32_t xe, uint32_t ys, uint32_t ye, bool rep, uint32_t W,
+                                                        uint32_t H) {
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  const WarpXY a = warp_xy(m, xs, ys, rep, wmax, hmax), b = warp_xy(m, xe, ys, rep, wmax, hmax), c = warp_xy(m, xs, ye, rep, wmax, hmax),
+               d = warp_xy(m, xe, ye, rep, wmax, hmax);
+  const float xmin = fminf(fminf(a.sx, b.sx), fminf(c.sx, d.sx)), xmax = fmaxf(fmaxf(a.sx, b.sx), fmaxf(c.sx, d.sx));
+  const float ymin = fminf(fminf(a.sy, b.sy), fminf(c.sy, d.sy)), ymax = fmaxf(fmaxf(a.sy, b.sy), fmaxf(c.sy, d.sy));
+  WarpWin w{0u, 0u, 0u, 0u, !(xmax >= 0.f && xmin <= wmax && ymax >= 0.f && ymin <= hmax)};
+  if (w.empty) return w;
+  w.x_lo = (uint32_t)(int)fmaxf(xmin, 0.f);
+  w.y_lo = (uint32_t)(int)fmaxf(ymin, 0.f);
+  const uint32_t xh = (uint32_t)(int)fminf(xmax, wmax), yh = (uint32_t)(int)fminf(ymax, hmax);
+  w.x_hi = xh + 1 < W ? xh + 1 : W - 1;
+  w.y_hi = yh + 1 < H ? yh + 1 : H - 1;
+  return w;
+}
+// the strip of a window: whole conversion units from the even pixel at or below x_lo, rows y_lo .. y_hi (the layout of k_roi_strip)
+struct WarpStrip { uint32_t base_px, ng, rowbytes, rows, bytes; };
+__host__ __device__ __forceinline__ WarpStrip warp_strip(const WarpWin& w) {
+  WarpStrip s;
+  s.base_px = w.x_lo & ~1u;
+  s.ng = ((w.x_hi - s.base_px) >> 3) + 1;
+  s.rowbytes = 32u * s.ng + 16u;  // 16-B unit writes force a pitch of whole four-dword slots; the odd slot keeps rows of ng = 4 k units off one bank
+  s.rows = w.y_hi - w.y_lo + 1;
+  s.bytes = s.rows * s.rowbytes;
+  return s;
+}
+
+VPF_DEV bool warp_rep(const TensorEpi& e) { return (e.pad >> 24) == VPF_WARP_REPLICATE; }
+VPF_DEV float warp_border(const TensorEpi& e, int ch) { return (float)((e.pad >> (8 * ch)) & 0xffu); }
+
+// four pixels of a lane through the per-tap form, stored through the tensor epilogue
+template <int SRC>
+VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorEpi& te, uint32_t W, uint32_t H, uint32_t dw, uint32_t dmask, uint32_t x0,
+                          uint32_t y) {
+  const FrameDesc& f = J.f;
+  const bool rep = warp_rep(te);
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  float u[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const WarpXY s = warp_xy(J.m, (x0 + k < dw) ? x0 + k : dw - 1, y, rep, wmax, hmax);
+    const bool in = s.sx >= 0.f && s.sx <= wmax && s.sy >= 0.f && s.sy <= hmax;
+    const float cx = __builtin_amdgcn_fmed3f(s.sx, 0.f, wmax), cy = __builtin_amdgcn_fmed3f(s.sy, 0.f, hmax);  // == sx, sy when in range
+    const uint32_t xa = (uint32_t)(int)cx, ya = (uint32_t)(int)cy;
+    const uint32_t xb = xa + 1 < W ? xa + 1 : W - 1, yb = ya + 1 < H ? ya + 1 : H - 1;
+    const float fx = cx - (float)xa, fy = cy - (float)ya;
+    float p00[3], p01[3], p10[3], p11[3];
+    texel_rgb<SRC>(f, c, xa, ya, p00);
+    texel_rgb<SRC>(f, c, xb, ya, p01);
+    texel_rgb<SRC>(f, c, xa, yb, p10);
+    texel_rgb<SRC>(f, c, xb, yb, p11);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const float v = __builtin_truncf(bilerp(p00[ch], p01[ch], p10[ch], p11[ch], fx, fy));
+      u[ch][k] = in ? v : warp_border(te, ch);
+    }
+  }
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+}
+
+// ------------------------------------------------------------------------------------------
+// The staged form.  The window is wave-uniform (block indices and kernel arguments only).  A tile whose window is empty writes the border; a
+// tile whose strip would not fit the LDS it was given — never: the launcher's bound covers every tile (warp_need) — takes the per-tap
+// form instead of writing from a short strip.
+// ------------------------------------------------------------------------------------------
+template <int SRC>
+__global__ __launch_bounds__(256) void k_warp_strip(const WarpArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
+                                                    uint32_t dmask, uint32_t lds_bytes) {
+  const WarpDesc& J = args.j[blockIdx.z];
+  const FrameDesc& f = J.f;
+  const TensorEpi te = args.e;
+  const bool rep = warp_rep(te);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t xs = blockIdx.x * kWarpTileW, ys = blockIdx.y * kWarpTileH;  // the grid covers the destination exactly: xs < dw, ys < dh
+  const uint32_t xe = (xs + kWarpTileW - 1 < dw - 1) ? xs + kWarpTileW - 1 : dw - 1, ye = (ys + kWarpTileH - 1 < dh - 1) ? ys + kWarpTileH - 1 : dh - 1;
+  const uint32_t x0 = xs + (tid % kWarpLanesX) * 4, y = ys + tid / kWarpLanesX;
+  const bool mine = x0 < dw && y < dh;
+  WarpWin w = warp_window(J.m, xs, xe, ys, ye, rep, W, H);
+  w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
+  w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  if (w.empty) {  // (CONSTANT only: a clamped coordinate is always in range)
+    if (!mine) return;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const float b = warp_border(te, ch), u[4] = {b, b, b, b};
+      tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec, nv);
+    }
+    return;
+  }
+  const WarpStrip S = warp_strip(w);
+  if (S.bytes > lds_bytes) {
+    if (mine) warp_gather4<SRC>(J, c, te, W, H, dw, dmask, x0, y);
+    return;
+  }
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  {  // the names VPF_STRIP_FILL_WINDOW takes from its scope
+    const uint32_t base_px = S.base_px, R_lo = w.y_lo, R_hi = w.y_hi, c_lo = R_lo >> 1, ng = S.ng, units = ((R_hi >> 1) - c_lo + 1) * ng, rowbytes = S.rowbytes;
+    VPF_STRIP_FILL_WINDOW
+  }
+  __syncthreads();
+  if (!mine) return;
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  const float xlf = (float)w.x_lo, xhf = (float)w.x_hi, ylf = (float)w.y_lo, yhf = (float)w.y_hi;
+  float u[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const WarpXY s = warp_xy(J.m, (x0 + k < dw) ? x0 + k : dw - 1, y, rep, wmax, hmax);
+    const bool in = s.sx >= 0.f && s.sx <= wmax && s.sy >= 0.f && s.sy <= hmax;
+    // an in-range coordinate lies inside the window, so pulling it to the window leaves it unchanged; every other one reads some pixel of
+    // the strip and is replaced by the border.  x1 = min(x0 + 1, x_hi) is min(x0 + 1, W - 1) for an in-range pixel (x_hi = min(floor + 1, W - 1)).
+    const float cx = __builtin_amdgcn_fmed3f(s.sx, xlf, xhf), cy = __builtin_amdgcn_fmed3f(s.sy, ylf, yhf);
+    const uint32_t xa = (uint32_t)(int)cx, ya = (uint32_t)(int)cy;
+    const uint32_t xb = xa + 1 < w.x_hi ? xa + 1 : w.x_hi, yb = ya + 1 < w.y_hi ? ya + 1 : w.y_hi;
+    const float fx = cx - (float)xa, fy = cy - (float)ya;
+    const uint8_t* const ra = strip + (ya - w.y_lo) * S.rowbytes, * const rb = strip + (yb - w.y_lo) * S.rowbytes;
+    const uint32_t oa = 4 * (xa - S.base_px), ob = 4 * (xb - S.base_px);
+    const uint32_t q00 = *reinterpret_cast<const uint32_t*>(ra + oa), q01 = *reinterpret_cast<const uint32_t*>(ra + ob);
+    const uint32_t q10 = *reinterpret_cast<const uint32_t*>(rb + oa), q11 = *reinterpret_cast<const uint32_t*>(rb + ob);
+    const float v[3] = {__builtin_truncf(bilerp(ubyte<0>(q00), ubyte<0>(q01), ubyte<0>(q10), ubyte<0>(q11), fx, fy)),
+                        __builtin_truncf(bilerp(ubyte<1>(q00), ubyte<1>(q01), ubyte<1>(q10), ubyte<1>(q11), fx, fy)),
+                        __builtin_truncf(bilerp(ubyte<2>(q00), ubyte<2>(q01), ubyte<2>(q10), ubyte<2>(q11), fx, fy))};
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) u[ch][k] = in ? v[ch] : warp_border(te, ch);
+  }
+  for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+}
+
+// ------------------------------------------------------------------------------------------
+// The gather form: the same tile and lane assignment, four texel_rgb per pixel.
+// ------------------------------------------------------------------------------------------
+template <int SRC>
+__global__ __launch_bounds__(256) void k_warp_gather(const WarpArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
+                                                     uint32_t dmask) {
+  const uint32_t x0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, y = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
+  if (x0 >= dw || y >= dh) return;
+  warp_gather4<SRC>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side.  The dynamic LDS of a dispatch is an UPPER BOUND of every tile's strip, from the matrix alone, O(1) per job (a walk over every
+// tile's corners cost ~10 ns per tile and bounded the whole call).  Along one axis a tile of tw x th pixels spans at most
+// |r0| (tw - 1) + |r1| (th - 1) in exact arithmetic; each fp32 coordinate is off by at most 2^-23 (|r0| dx + |r1| dy + |r2|) (three roundings
+// of half an ulp of values no larger than that sum), taken four times over here; x_hi - x_lo + 1 <= floor(xmax) - floor(xmin) + 2 <= span + 3;
+// a clamp (REPLICATE, the frame) only shrinks a window.  The kernel compares the strip it computes with the bytes it was given and takes the
+// per-tap path for a tile that would not fit, so a bound that were ever short costs time, not pixels.
+// ------------------------------------------------------------------------------------------
+// Policy (measured): the staged form wherever a tile's strip fits kWarpStripMax, the per-tap form otherwise.  Kernel time of the staged
+// form is 0.50-0.82 x the per-tap form's in every case whose strip fits, 2.86 x down-scales at 15 degrees (about 12 source pixels converted per
+// destination pixel) included: no break-even in converted pixels is reached before the strip outgrows the LDS, so there is none in the policy.
+// 64 KiB (two workgroups per CU, the most a launch takes without an attribute) against 53 KiB (three): every case that fits 53 KiB runs the same
+// either way, and 2.7 x at 45 degrees (62 KiB) takes 0.585 us per region staged against 0.754 per tap.
+#ifndef VPF_WARP_STRIP_MAX_KIB
+#define VPF_WARP_STRIP_MAX_KIB 64
+#endif
+constexpr uint32_t kWarpStripMax = VPF_WARP_STRIP_MAX_KIB * 1024u;
+struct WarpNeed {
+  uint32_t bytes;  // upper bound of the job's largest tile strip
+};
+static WarpNeed warp_need(const WarpDesc& j, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
+  auto count = [&](const float* r, uint32_t S) {  // pixels of a tile's window along one axis, at most
+    const double span = std::fabs((double)r[0]) * (tw - 1) + std::fabs((double)r[1]) * (th - 1);
+    const double err = 4.0 * 0x1p-23 * (std::fabs((double)r[0]) * dw + std::fabs((double)r[1]) * dh + std::fabs((double)r[2]));
+    const double n = std::floor(span + 2.0 * err) + 3.0;
+    return n < (double)S ? (uint32_t)n : S;
+  };
+  const uint32_t nx = count(j.m, W), rows = count(j.m + 3, H);
+  uint32_t ng = (nx >> 3) + 1;  // the strip starts on the even pixel at or below x_lo
+  const uint32_t ng_max = ((W - 1) >> 3) + 1;
+  ng = ng < ng_max ? ng : ng_max;
+  return WarpNeed{rows * (32u * ng + 16u)};
+}
+
+hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
+                               uint32_t dh, const TensorEpi& te) {
+  if (!n || n > (uint32_t)kWarpBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420)) return hipErrorInvalidValue;
+  const uint32_t dmask = te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need
+  const int tune = tuning(VPF_TUNE_NV12_RGB_VARIANT);
+  const bool all_gather = tune == 9;
+  WarpArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
+  std::memset(&as, 0, sizeof(as));
+  std::memset(&ag, 0, sizeof(ag));
+  as.e = ag.e = te;
+  uint32_t ns = 0, ngat = 0, lds = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const WarpNeed need = all_gather ? WarpNeed{0u} : warp_need(jobs[i], W, H, dw, dh);
+    if (!all_gather && need.bytes <= kWarpStripMax) {
+      as.j[ns++] = jobs[i];
+      lds = need.bytes > lds ? need.bytes : lds;
+    } else {
+      ag.j[ngat++] = jobs[i];
+    }
+  }
+  const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
+  if (ns) {
+    if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_strip<FC_NV12>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
+    else VPF_LAUNCH((k_warp_strip<FC_YUV420>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (ngat) {
+    if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_gather<FC_NV12>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
+    else VPF_LAUNCH((k_warp_gather<FC_YUV420>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+}  // namespace vpf

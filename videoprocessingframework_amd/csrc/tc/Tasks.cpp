@@ -529,6 +529,34 @@ TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint3
   }
   return TASK_EXEC_SUCCESS;
 }
+TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
+                                                    const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
+                                                    const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorWarps");
+  if (!frames || !n_frames || !frame_index || !matrices || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  for (uint32_t i = 0; i < n_frames; i++) {
+    Surface* s = frames[i];
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+  }
+  std::vector<vpf_warp_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(frames[frame_index[i]], io[i].src);
+    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    for (int k = 0; k < 6; k++) io[i].m[k] = matrices[6 * i + k];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_warp_tensor(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(),
+                                                &norm, opts);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to warp regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
 // ------------------------------------------------------------------------------------------ TensorToSurface

@@ -57,6 +57,12 @@ public:
   // and size, every job the task's destination size.  The same colour-context rules as RunTensor.
   TaskExecStatus RunTensorRois(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, uint32_t n,
                                const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
+  // n affine warps of surfaces -> n frames of a normalised planar tensor (vpf_convert_warp_tensor): job i samples frames[frame_index[i]] through
+  // the inverse matrix matrices[6 i .. 6 i + 5] (m00 m01 m02 m10 m11 m12: destination pixel -> source coordinates in luma pixels) and writes
+  // dst[3 i .. 3 i + 2]; every surface has the task's source format and size, every job the task's destination size; opts == nullptr:
+  // VPF_WARP_CONSTANT with border 0 0 0.  The same colour-context rules as RunTensor.
+  TaskExecStatus RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
+                                const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on
 
 private:

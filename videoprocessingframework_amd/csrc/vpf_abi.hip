@@ -545,6 +545,62 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
   return VPF_OK;
 }
 
+// Many affine warps of decoded frames -> one batch of normalised planes (include/vpf_hip.h): per-job matrices, kWarpBatch jobs per job table,
+// each table at most two dispatches (k_convert_warp.hip).
+vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_warp_io* jobs,
+                                   const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
+  const Mark mark("vpf_convert_warp_tensor");
+  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
+  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  for (uint32_t i = 0; i < n; i++) {
+    for (int k = 0; k < 6; k++)
+      if (!(std::fabs(jobs[i].m[k]) <= 16777216.0f)) return VPF_ERR_BAD_ARG;  // NaN and infinities fail the comparison too
+    if (!planes_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
+    for (int k = 0; k < num_planes(sf); k++)
+      if (jobs[i].src[k].reserved) return VPF_ERR_BAD_ARG;
+    for (int k = 0; k < 3; k++) {
+      const vpf_plane& p = jobs[i].dst[k];
+      if (!p.ptr || p.reserved || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
+    }
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their border bytes here
+  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
+  te.dtype = norm->dtype;
+  if (opts) {
+    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->border[bgr ? 2 - k : k] << (8 * k);
+    te.pad |= opts->border_mode << 24;
+  }
+  WarpDesc table[kWarpBatch];
+  for (uint32_t base = 0; base < n; base += kWarpBatch) {
+    const uint32_t m = (n - base < (uint32_t)kWarpBatch) ? n - base : (uint32_t)kWarpBatch;
+    for (uint32_t i = 0; i < m; i++) {
+      const vpf_warp_io& io = jobs[base + i];
+      vpf_plane d[3];
+      for (int k = 0; k < 3; k++) d[k] = io.dst[bgr ? 2 - k : k];
+      fill_desc(table[i].f, io.src, num_planes(sf), d, 3);
+      for (int k = 0; k < 6; k++) table[i].m[k] = io.m[k];
+    }
+    const hipError_t e = launch_convert_warp(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
+                                             ds.height, te);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
 int vpf_tensor_convert_supported(int df, int cs, int cr) {
   return (df == VPF_FMT_NV12 || df == VPF_FMT_YUV420) && classify(VPF_FMT_RGB_PLANAR, VPF_FMT_YUV420, cs, cr) == FAM_RGB2YUV;

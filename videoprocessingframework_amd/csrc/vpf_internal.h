@@ -102,6 +102,21 @@ struct RoiArgs {
 };
 static_assert(sizeof(RoiDesc) == 96 && sizeof(RoiArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the ROI job table must not outgrow the largest frame table");
 
+// The job table of a multi-ROI affine warp (vpf_convert_warp_tensor, k_convert_warp.hip): per job the planes of the WHOLE source frame and of the
+// destination and the inverse matrix m = (m00 m01 m02; m10 m11 m12), destination pixel -> source coordinates in luma pixels.  96 B like RoiDesc,
+// so the same 96 jobs per table.  The three border bytes (kernel channel order R G B) and the border mode travel in TensorEpi::pad:
+// pad = border[0] | border[1] << 8 | border[2] << 16 | mode << 24.
+constexpr int kWarpBatch = 96;
+struct WarpDesc {
+  FrameDesc f;
+  float m[6];
+};
+struct WarpArgs {
+  WarpDesc j[kWarpBatch];
+  TensorEpi e;
+};
+static_assert(sizeof(WarpDesc) == 96 && sizeof(WarpArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the warp job table must not outgrow the largest frame table");
+
 // The prologue of a tensor -> NV12 / YUV420 launch (vpf_tensor_convert): q[c] = rint(clamp(x[c] * scale[c] + bias[c], 0, 255)) feeds the RGB -> YUV
 // arithmetic.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
 struct TensorPro {
@@ -148,6 +163,10 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
 // n <= kRoiBatch jobs on frames `W` pixels wide -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); k_convert_roi.hip
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
                                       uint32_t dh, const TensorEpi& te);
+// n <= kWarpBatch jobs on frames of W x H pixels -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); `te.pad`
+// carries border and mode (WarpArgs); k_convert_warp.hip
+hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
+                               uint32_t dh, const TensorEpi& te);
 
 int tuning(int key);
 
