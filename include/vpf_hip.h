@@ -227,6 +227,16 @@ VPF_API vpf_status vpf_convert_resize_batch(const vpf_exec* exec, int src_fmt, i
  * output channel c): dst_size.width elements per row, `pitch` in bytes.  Plane pointers and pitches must be multiples of the element size
  * and pitch >= width x element size (contiguous NCHW, a slice of a larger batch tensor and padded rows are all such planes).
  * Unknown dtype or flag bits: VPF_ERR_UNSUPPORTED; a non-finite scale / bias or a misaligned plane: VPF_ERR_BAD_ARG.
+ *
+ * 10 / 12-bit sources: src_fmt = VPF_FMT_P10 / VPF_FMT_P12 (16-bit MSB-aligned semi-planar, what HEVC Main10 / AV1 / HDR decoders hand over) is
+ * accepted by this entry, its batch form, vpf_convert_resize_tensor_rois and vpf_convert_warp_tensor — and by these four only.  src[0] = Y, W samples
+ * of 2 bytes per row; src[1] = interleaved U V, 2 ceil(W / 2) samples per row, ceil(H / 2) rows; `pitch` in bytes; plane pointers and pitches
+ * must be multiples of 2 (else VPF_ERR_BAD_ARG, like short pitches).  Every luma and chroma sample v is first replaced by
+ * min(255, (v + 128) >> 8) — what vpf_convert(P10 | P12 -> NV12) writes; P10 and P12 are the same code: the low bits take part in the rounding —
+ * and everything downstream is the NV12 definition: the output is bit-identical to the same entry for VPF_FMT_NV12 on the planes
+ * vpf_convert(P10 | P12 -> NV12) writes for that frame, without that pass over the whole frame.  This is deliberately NOT a full-precision
+ * conversion (the 10 bits fed into the matrix): that would be a definition with nothing to test it against.  vpf_convert_resize(_batch),
+ * vpf_convert_supported and vpf_resize answer for P10 / P12 as before.
  */
 typedef enum vpf_tensor_dtype { VPF_TENSOR_F32 = 0, VPF_TENSOR_F16 = 1, VPF_TENSOR_BF16 = 2 } vpf_tensor_dtype;
 #define VPF_TENSOR_BGR 1u /* vpf_tensor_norm.flags: channel order B G R */
@@ -244,7 +254,9 @@ VPF_API vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int src
                                                    vpf_size dst_size, uint32_t n, const vpf_frame_io* frames, const vpf_tensor_norm* norm);
 
 /*
- * Fused multi-ROI crop + bilinear resize -> normalised planar tensor: `n` rectangles of decoded NV12 / YUV420 frames, each resized to the ONE
+ * Fused multi-ROI crop + bilinear resize -> normalised planar tensor: `n` rectangles of decoded NV12 / YUV420 frames (or P10 / P12 ones,
+ * narrowed to 8 bits at the load: "10 / 12-bit sources" at vpf_convert_resize_tensor — a region costs the bytes it touches, not a pass over the
+ * whole 16-bit frame), each resized to the ONE
  * size dst_size and normalised, in one dispatch (what a classifier / ReID / face network behind a detector consumes: float [K, 3, dh, dw]).
  * A job = (the planes of a WHOLE frame of src_size = (W, H), rect = (x, y, w, h) in luma pixels of that frame, three destination planes);
  * w, h >= 1, x + w <= W, y + h <= H, any integer x, y (odd ones too); many jobs may name the same frame.  For destination pixel (dx, dy), channel c:
@@ -275,7 +287,8 @@ VPF_API vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int src_
                                                   vpf_size dst_size, uint32_t n, const vpf_roi_io* rois, const vpf_tensor_norm* norm);
 
 /*
- * Fused multi-ROI affine warp -> normalised planar tensor: `n` crops of decoded NV12 / YUV420 frames that are NOT axis-aligned (aligned faces, rotated
+ * Fused multi-ROI affine warp -> normalised planar tensor: `n` crops of decoded NV12 / YUV420 frames (or P10 / P12 ones, narrowed to 8 bits at the
+ * load: "10 / 12-bit sources" at vpf_convert_resize_tensor) that are NOT axis-aligned (aligned faces, rotated
  * text boxes, oriented detections, flips, shears), each sampled through a 2 x 3 matrix of its own into the ONE size dst_size and normalised, in
  * one dispatch: float [K, 3, dh, dw].  A job = (the planes of a WHOLE frame of src_size = (W, H), m[6] = (m00 m01 m02; m10 m11 m12), three
  * destination planes).  The matrix is the INVERSE map: it takes a destination pixel to source coordinates in luma pixels of that frame; coordinates

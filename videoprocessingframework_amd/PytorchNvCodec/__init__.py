@@ -121,7 +121,7 @@ _TENSOR_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # vpf_
 
 
 def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
-    """NV12 / YUV420 surfaces -> the normalised float tensor [N, 3, H, W] a DNN consumes, in one pass of the fused kernels
+    """NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [N, 3, H, W] a DNN consumes, in one pass of the fused kernels
     (PySurfaceConvertResizer.ExecuteToTensor): the RGB_PLANAR bytes of resizer.ExecuteBatch, divided by 255 and normalised with
     torchvision's mean / std (one fp32 fma per element, scale = 1 / (255 std), bias = -mean / std), rounded to `dtype` (float32, float16,
     bfloat16).  mean / std are per output channel (B G R order when bgr=True).
@@ -200,7 +200,7 @@ def _rois_list(rois, surfaces, fn):
 
 
 def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
-    """K rectangles of NV12 / YUV420 surfaces -> the normalised float tensor [K, 3, dh, dw] a second-stage network (classifier, ReID, face net
+    """K rectangles of NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [K, 3, dh, dw] a second-stage network (classifier, ReID, face net
     behind a detector) consumes, in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteRoisToTensor, vpf_convert_resize_tensor_rois).
     `rois`: a sequence of (surface_index, x, y, w, h) integer 5-tuples, or a CPU integer tensor / ndarray [K, 5]; x, y, w, h in luma pixels of
     surfaces[surface_index], any integer offset (odd ones too), the rectangle inside the surface.  Every region is resized (bilinear, taps
@@ -273,7 +273,7 @@ def _matrices_list(matrices, fn):
 
 
 def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None) -> torch.Tensor:
-    """K affine warps of NV12 / YUV420 surfaces -> the normalised float tensor [K, 3, dh, dw] a network behind a detector consumes (aligned faces,
+    """K affine warps of NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [K, 3, dh, dw] a network behind a detector consumes (aligned faces,
     rotated text boxes, oriented detections), in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteWarpsToTensor, vpf_convert_warp_tensor).
     `matrices`: a host [K, 2, 3] float tensor, ndarray or nested sequence (float64 is rounded to float32 once); matrices[i] is the INVERSE map of
     job i: it takes a destination pixel (dx, dy) to source coordinates in luma pixels of surfaces[surface_index[i]], the convention of remap's

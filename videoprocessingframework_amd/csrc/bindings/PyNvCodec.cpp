@@ -742,7 +742,10 @@ PYBIND11_MODULE(_PyNvCodec, m) {
 
   py::class_<PySurfaceConvertResizer>(m, "PySurfaceConvertResizer",
                                       "Additive: NV12 / YUV420 -> bilinear resize -> RGB / BGR / RGB_PLANAR in one pass; bit-identical to "
-                                      "PySurfaceConverter followed by PySurfaceResizer (bilinear).")
+                                      "PySurfaceConverter followed by PySurfaceResizer (bilinear).  P10 / P12 sources construct too, for ExecuteToTensor / "
+                                      "ExecuteRoisToTensor / ExecuteWarpsToTensor only: every 16-bit sample is narrowed to min(255, (v + 128) >> 8) (the bytes of "
+                                      "PySurfaceConverter P10 -> NV12) at the load, then NV12's path; Execute / ExecuteBatch of such an instance refuse (Empty() "
+                                      "surface / False, with a message): the 8-bit outputs take 8-bit sources.")
       .def(py::init([](uint32_t sw, uint32_t sh, Pixel_Format in, uint32_t dw, uint32_t dh, Pixel_Format out, uint32_t gpu) {
              return new PySurfaceConvertResizer(sw, sh, in, dw, dh, out, ctx_of((int)gpu), str_of((int)gpu));
            }),

@@ -440,6 +440,9 @@ __global__ __launch_bounds__(256) void k_convert_resize_band(const BA args, cons
 // destination pixel instead of ~120 in the general kernel.  Bit-identical to it (same fma order on the same values).
 // Requires NV12 or YUV420 (chroma planes 8-B aligned), sw == 2 dw, sh == 2 dh, sw % 16 == 0 (% 32 for packed outputs), 16-B aligned source rows, 8-B (planar) / 16-B
 // (packed) aligned destination rows.
+// FC_P16 (P10 / P12, FC_TENSOR only): the lane's 16 luma samples of each row and its 8 U V pairs are 32 B each at byte 2 xs — two 16-B loads,
+// narrowed to the dwordx4 the body works on.  Requires sw == 2 dw, sh == 2 dh, sw % 16 == 0, 16-B aligned luma and chroma planes and pitches
+// (an active lane has xs + 16 <= sw: its loads end inside the rows' own samples), 16-B aligned destination rows.
 // ------------------------------------------------------------------------------------------
 template <int DST, int SRC>
 VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks, const TensorEpi& te) {
@@ -457,9 +460,19 @@ VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_
   // VALU per destination pixel — the kernel was VALU-bound (tools/gpu_pmc_fused.sh 3840 2160 1920 1080).
   uint32_t o[3][8];  // channel value of destination pixel i in byte 1
   if (act) {
-    const u32x4 ya = ldg<true, u32x4>(f.s[0] + (size_t)(2 * y) * f.sp[0] + xs);
-    const u32x4 yb = ldg<true, u32x4>(f.s[0] + (size_t)(2 * y + 1) * f.sp[0] + xs);
-    const u32x4 uv = load_uv16<SRC, true>(f, y, xs);
+    u32x4 ya, yb, uv;
+    if constexpr (SRC == FC_P16) {
+      const uint8_t* const pa = f.s[0] + (size_t)(2 * y) * f.sp[0] + 2 * (size_t)xs;
+      const uint8_t* const pb = f.s[0] + (size_t)(2 * y + 1) * f.sp[0] + 2 * (size_t)xs;
+      const uint8_t* const pc = f.s[1] + (size_t)y * f.sp[1] + 2 * (size_t)xs;
+      const u32x4 a0 = ldg<true, u32x4>(pa), a1 = ldg<true, u32x4>(pa + 16), b0 = ldg<true, u32x4>(pb), b1 = ldg<true, u32x4>(pb + 16);
+      const u32x4 c0 = ldg<true, u32x4>(pc), c1 = ldg<true, u32x4>(pc + 16);
+      ya = p16x16_to_8(a0, a1); yb = p16x16_to_8(b0, b1); uv = p16x16_to_8(c0, c1);
+    } else {
+      ya = ldg<true, u32x4>(f.s[0] + (size_t)(2 * y) * f.sp[0] + xs);
+      yb = ldg<true, u32x4>(f.s[0] + (size_t)(2 * y + 1) * f.sp[0] + xs);
+      uv = load_uv16<SRC, true>(f, y, xs);
+    }
     auto avg = [](const float* t, const float* b, int i) { return __builtin_amdgcn_udot4(pack4<1>(t[i], t[i + 1], b[i], b[i + 1]), 0x40404040u, 128u, false); };
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -711,14 +724,23 @@ VPF_DEV void convert_strip_wg_task(const FrameDesc& f, const Yuv2RgbCoef& c, uin
     q.crow = c_lo + ci; q.px0 = base_px + 8 * g;
     const uint32_t r0 = 2 * q.crow;
     q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  // (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window)
-    if constexpr (SRC == FC_NV12) {
-      q.cq = ldg<false, u32x2>(f.s[1] + (size_t)q.crow * f.sp[1] + q.px0);
+    if constexpr (SRC == FC_P16) {
+      // 16-bit samples: the unit's 8 luma samples and its 4 U V pairs are 16 B each at byte 2 px0 of their rows, aligned (the launcher requires
+      // 16-B aligned planes and pitches; px0 is a multiple of 8), narrowed to the dwords of the 8-bit unit.  px0 + 8 <= sw (sw % 8 == 0, px0 <=
+      // last < sw), so luma bytes end at or before 2 sw and chroma bytes at or before 4 (sw / 2): no byte outside the frame's own rows is read.
+      q.cq = p16x8_to_8(ldg<false, u32x4>(f.s[1] + (size_t)q.crow * f.sp[1] + 2 * (size_t)q.px0));
+      if (q.ra) q.ya = p16x8_to_8(ldg<false, u32x4>(f.s[0] + (size_t)r0 * f.sp[0] + 2 * (size_t)q.px0));
+      if (q.rb) q.yb = p16x8_to_8(ldg<false, u32x4>(f.s[0] + (size_t)(r0 + 1) * f.sp[0] + 2 * (size_t)q.px0));
     } else {
-      q.cq = u32x2{ldg<false, uint32_t>(f.s[1] + (size_t)q.crow * f.sp[1] + (q.px0 >> 1)), 0u};
-      q.vq = ldg<false, uint32_t>(f.s[2] + (size_t)q.crow * f.sp[2] + (q.px0 >> 1));
+      if constexpr (SRC == FC_NV12) {
+        q.cq = ldg<false, u32x2>(f.s[1] + (size_t)q.crow * f.sp[1] + q.px0);
+      } else {
+        q.cq = u32x2{ldg<false, uint32_t>(f.s[1] + (size_t)q.crow * f.sp[1] + (q.px0 >> 1)), 0u};
+        q.vq = ldg<false, uint32_t>(f.s[2] + (size_t)q.crow * f.sp[2] + (q.px0 >> 1));
+      }
+      if (q.ra) q.ya = ldg<false, u32x2>(f.s[0] + (size_t)r0 * f.sp[0] + q.px0);
+      if (q.rb) q.yb = ldg<false, u32x2>(f.s[0] + (size_t)(r0 + 1) * f.sp[0] + q.px0);
     }
-    if (q.ra) q.ya = ldg<false, u32x2>(f.s[0] + (size_t)r0 * f.sp[0] + q.px0);
-    if (q.rb) q.yb = ldg<false, u32x2>(f.s[0] + (size_t)(r0 + 1) * f.sp[0] + q.px0);
     // strip byte of (row r0, px0); r0 may be R_lo - 1 (that row is not written then: only row r0 + 1 is) — a signed offset
     q.w = strip + ((int32_t)(r0 - R_lo) * (int32_t)rowbytes + (int32_t)(4 * (q.px0 - base_px)));
   };
@@ -727,8 +749,9 @@ VPF_DEV void convert_strip_wg_task(const FrameDesc& f, const Yuv2RgbCoef& c, uin
     fetch(u0, q0);
     fetch(u0 + 256, q1);
     __builtin_amdgcn_sched_barrier(0);  // both units' loads are requested before the first conversion
-    if (q0.act) convert_unit8<SRC>(f, c, q0.crow, q0.px0, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);
-    if (q1.act) convert_unit8<SRC>(f, c, q1.crow, q1.px0, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);
+    constexpr int USRC = SRC == FC_P16 ? (int)FC_NV12 : SRC;  // 16-bit samples were narrowed at the load
+    if (q0.act) convert_unit8<USRC>(f, c, q0.crow, q0.px0, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);
+    if (q1.act) convert_unit8<USRC>(f, c, q1.crow, q1.px0, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);
   }
   __syncthreads();
   const uint32_t ya = Y0 + wv * R;
@@ -803,6 +826,28 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
     for (int k = 0; k < ndp; k++) vec_ok &= ((((uintptr_t)f.d[k] | f.dp[k]) & dmask) == 0);
     for (int k = 0; k < (src_fc == FC_NV12 ? 2 : 3); k++) lds_ok = lds_ok && !(((uintptr_t)f.s[k] | f.sp[k]) & 15);
   }
+  // 16-bit sources (FC_P16: P10 / P12, into FC_TENSOR only).  Policy: exact 2x -> k_convert_half; the workgroup strip under the wconv rule of
+  // the 8-bit sources below; everything else -> the gather form.  The per-tap LDS kernels stage raw bytes and have no 16-bit instantiation
+  // (DESIGN 4.10, 8).  VPF_TUNE_NV12_RGB_VARIANT = 9 / 40 / 49 keep the gather form.
+  const int p16_v = tuning(VPF_TUNE_NV12_RGB_VARIANT);
+  const bool p16_general = p16_v == 9 || p16_v == 40 || p16_v == 49;
+  bool p16_a16 = src_fc == FC_P16;  // 16-B aligned source planes and pitches: what the aligned 16-B loads of the half and strip kernels need
+  if (src_fc == FC_P16) {
+    if (dst_fc != FC_TENSOR) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n; i++)
+      for (int k = 0; k < 2; k++) p16_a16 = p16_a16 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 15);
+    if (sw == 2 * dw && sh == 2 * dh && sw % 16 == 0 && p16_a16 && !p16_general) {
+      bool ok16 = true;
+      for (uint32_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & 15u);
+      if (ok16) {
+        const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
+        dim3 hgrid((tasks + 3) / 4, n);
+        VPF_LAUNCH_BAT(k_convert_half, (FC_TENSOR, FC_P16), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks);
+        return hipGetLastError();
+      }
+    }
+  }
   // exact 2x from NV12: the quad-structured kernel (no taps, no gathers); tuning 40 / 9 keep the general kernels
   // (packed rows leave as 16-B stores: 3 * dw must be a multiple of 16)
   if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
@@ -827,10 +872,10 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
   // axis keep the kernels below (their zero-weight shortcuts skip whole rows / taps)
   {
     const bool odd_x = sw % dw == 0 && ((sw / dw) & 1), odd_y = sh % dh == 0 && ((sh / dh) & 1);
-    bool ok8 = (src_fc == FC_NV12 || src_fc == FC_YUV420) && sw % 8 == 0 && !odd_x && !odd_y && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 &&
+    bool ok8 = (src_fc == FC_NV12 || src_fc == FC_YUV420 || (src_fc == FC_P16 && p16_a16)) && sw % 8 == 0 && !odd_x && !odd_y && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 &&
                tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9 && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 49 && sw < (1u << 22) && sh < (1u << 22);
     for (uint32_t i = 0; i < n && ok8; i++)
-      for (int k = 0; k < (src_fc == FC_NV12 ? 2 : 3); k++) ok8 = ok8 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 7);
+      for (int k = 0; k < (src_fc == FC_YUV420 ? 3 : 2); k++) ok8 = ok8 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 7);
     if (ok8) {
 #ifdef VPF_LAB_FORMS  // the per-wave strips of rounds 2-4 (k_convert_strip): variant 47, and where the workgroup strips do not apply
       const uint32_t rowbytes = vpf_bound_fused_rowbytes(scx);  // a wave's source span + alignment + tap-window slack (vpf_plan_bounds.h)
@@ -896,7 +941,7 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
 #define VPF_WGT1(S, RR) VPF_LAUNCH_BAT(k_convert_strip_wg, (S, FC_TENSOR, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
 #define VPF_WGT(S) do { if (rw == 16) VPF_WGT1(S, 16); else if (rw == 8) VPF_WGT1(S, 8); else if (rw == 4) VPF_WGT1(S, 4); else VPF_WGT1(S, 2); } while (0)
 #define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else if (dst_fc == FC_TENSOR) VPF_WGT(S); else VPF_WG(S, FC_PLANAR); } while (0)
-          if (src_fc == FC_NV12) VPF_WGD(FC_NV12); else VPF_WGD(FC_YUV420);
+          if (src_fc == FC_NV12) VPF_WGD(FC_NV12); else if (src_fc == FC_P16) VPF_WGT(FC_P16); else VPF_WGD(FC_YUV420);
 #undef VPF_WGD
 #undef VPF_WGT
 #undef VPF_WGT1
@@ -919,6 +964,11 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
       }
 #endif  // VPF_LAB_FORMS
     }
+  }
+  if (src_fc == FC_P16) {  // everything else from 16-bit sources: the gather form
+    dim3 ggrid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
+    VPF_LAUNCH_BAT(k_convert_resize, (FC_P16, FC_TENSOR), ggrid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok);
+    return hipGetLastError();
   }
   const uint32_t lds = 4 * (src_fc == FC_NV12 ? 4 : 6) * rowb;
   // factors beyond ~2x on a launch that covers the chip with four rows per wave: the per-tap kernel as a row band (k_convert_resize_band);

@@ -7,6 +7,7 @@
 // Definition (include/vpf_hip.h): taps are make_tap<LINEAR> on the RECTANGLE's size (they clamp at its edges), texels are frame pixels
 // (x + i, y + j) converted with vpf_convert's arithmetic — chroma at absolute ((x + i) >> 1, (y + j) >> 1) —, then bilerp, truncation
 // and the tensor epilogue.  Both kernels run exactly those fp32 operations in that order: identical bits.
+// P10 / P12 frames (FC_P16) take the same two kernels: their 16-bit samples are narrowed to 8 bits at the load (k_fused_common.h).
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
 
@@ -120,7 +121,7 @@ static RoiStripNeed roi_strip_need(const RoiDesc& j, uint32_t dw, uint32_t dh) {
 
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
                                       uint32_t dh, const TensorEpi& te) {
-  if (!n || n > (uint32_t)kRoiBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420)) return hipErrorInvalidValue;
+  if (!n || n > (uint32_t)kRoiBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
   const uint32_t dmask = te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need
   // staged: the window fits a strip that leaves three workgroups per CU and converts at most three source pixels per destination pixel
   // (the measured break-even of the strip against the per-tap kernels, launch_convert_resize); everything else gathers
@@ -142,6 +143,7 @@ hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbC
   if (ns) {
     const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
     if (src_fc == FC_NV12) VPF_LAUNCH((k_roi_strip<FC_NV12>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds);
+    else if (src_fc == FC_P16) VPF_LAUNCH((k_roi_strip<FC_P16>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds);
     else VPF_LAUNCH((k_roi_strip<FC_YUV420>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -149,6 +151,7 @@ hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbC
   if (ngat) {
     const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
     if (src_fc == FC_NV12) VPF_LAUNCH((k_roi_gather<FC_NV12>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask);
+    else if (src_fc == FC_P16) VPF_LAUNCH((k_roi_gather<FC_P16>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask);
     else VPF_LAUNCH((k_roi_gather<FC_YUV420>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask);
     return hipGetLastError();
   }

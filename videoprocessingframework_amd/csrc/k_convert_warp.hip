@@ -8,6 +8,7 @@
 // Definition (include/vpf_hip.h): sx = (m00 dx + m01 dy) + m02, sy likewise, every operation rounded on its own (-ffp-contract=off), then
 // vpf_remap's range test and sampling on frame pixels converted with vpf_convert's arithmetic, bilerp, truncation, the tensor epilogue.
 // Both kernels run exactly those fp32 operations in that order: identical bits.
+// P10 / P12 frames (FC_P16) take the same two kernels: their 16-bit samples are narrowed to 8 bits at the load (k_fused_common.h).
 #include <cmath>
 
 #include "k_bilinear_blend.h"
@@ -229,7 +230,7 @@ static WarpNeed warp_need(const WarpDesc& j, uint32_t W, uint32_t H, uint32_t dw
 
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
                                uint32_t dh, const TensorEpi& te) {
-  if (!n || n > (uint32_t)kWarpBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420)) return hipErrorInvalidValue;
+  if (!n || n > (uint32_t)kWarpBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
   const uint32_t dmask = te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need
   const int tune = tuning(VPF_TUNE_NV12_RGB_VARIANT);
   const bool all_gather = tune == 9;
@@ -250,12 +251,14 @@ hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c,
   const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
   if (ns) {
     if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_strip<FC_NV12>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
+    else if (src_fc == FC_P16) VPF_LAUNCH((k_warp_strip<FC_P16>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
     else VPF_LAUNCH((k_warp_strip<FC_YUV420>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (ngat) {
     if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_gather<FC_NV12>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
+    else if (src_fc == FC_P16) VPF_LAUNCH((k_warp_gather<FC_P16>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
     else VPF_LAUNCH((k_warp_gather<FC_YUV420>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
     return hipGetLastError();
   }

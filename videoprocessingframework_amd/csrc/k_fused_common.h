@@ -6,6 +6,12 @@
 
 namespace vpf {
 
+// loads of any alignment: a rectangle starts at an arbitrary byte of an arbitrarily aligned plane (the backend keeps them one
+// global_load_dword / _dwordx2 / _dwordx4: gfx950 global memory takes unaligned addresses)
+typedef u32x2 u32x2_any __attribute__((aligned(1)));
+typedef uint32_t u32_any __attribute__((aligned(1)));
+typedef u32x4 u32x4_any __attribute__((aligned(1)));  // (FC_P16 rows: always 2-B aligned, vpf_abi.hip)
+
 // ------------------------------------------------------------------------------------------
 // (Stores: plain here — non-temporal stores measured 1.44 -> 1.61 us per 4K -> 720p frame in the batched fused kernel,
 // while the unfused resize kernels gain from them on large outputs: 1080p -> 4K 16.0 -> 13.8 us.)
@@ -14,15 +20,22 @@ namespace vpf {
 // its rounding), then interpolated — bit-identical to running the two kernels back to back, but the
 // 3 B/px intermediate never exists: 12.4 MB read + 2.8 MB written instead of 65 MB for 4K -> 720p.
 // ------------------------------------------------------------------------------------------
+// FC_P16 (P10 / P12): one 2-B load for Y, one 4-B load for the U V pair (2-B aligned), both narrowed to 8 bits (p16_to_8) — then the same chain.
 template <int SRC>
 VPF_DEV void texel_rgb(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t x, uint32_t y, float* rgb) {
-  const float yf = (float)f.s[0][(size_t)y * f.sp[0] + x];
-  float u, v;
-  if constexpr (SRC == FC_NV12) {
-    const uint8_t* p = f.s[1] + (size_t)(y >> 1) * f.sp[1] + 2 * (x >> 1);
-    u = p[0]; v = p[1];
+  float yf, u, v;
+  if constexpr (SRC == FC_P16) {
+    yf = (float)p16_to_8(*reinterpret_cast<const uint16_t*>(f.s[0] + (size_t)y * f.sp[0] + 2 * (size_t)x));
+    const uint32_t d = *reinterpret_cast<const u32_any*>(f.s[1] + (size_t)(y >> 1) * f.sp[1] + 4 * (size_t)(x >> 1));
+    u = (float)p16_to_8((uint16_t)(d & 0xffffu)); v = (float)p16_to_8((uint16_t)(d >> 16));
   } else {
-    u = f.s[1][(size_t)(y >> 1) * f.sp[1] + (x >> 1)]; v = f.s[2][(size_t)(y >> 1) * f.sp[2] + (x >> 1)];
+    yf = (float)f.s[0][(size_t)y * f.sp[0] + x];
+    if constexpr (SRC == FC_NV12) {
+      const uint8_t* p = f.s[1] + (size_t)(y >> 1) * f.sp[1] + 2 * (x >> 1);
+      u = p[0]; v = p[1];
+    } else {
+      u = f.s[1][(size_t)(y >> 1) * f.sp[1] + (x >> 1)]; v = f.s[2][(size_t)(y >> 1) * f.sp[2] + (x >> 1)];
+    }
   }
   const Chroma k = chroma_terms(c, u, v);
   rgb[0] = (float)sat_rne(__builtin_fmaf(yf, c.cy, k.rc));
@@ -87,7 +100,7 @@ VPF_DEV void tensor_store4_trunc(uint8_t* row, uint32_t x0, const float* o, int 
 }
 
 // One conversion unit of the workgroup-shared strips (k_convert_strip_wg, k_roi_strip): 8 pixels x 2 luma rows under one chroma row -> four-byte
-// R G B x pixels in LDS.
+// R G B x pixels in LDS.  (FC_P16 sources narrow their samples at the load and come here as FC_NV12.)
 template <int SRC>
 VPF_DEV void convert_unit8(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t crow, uint32_t px0, bool row_a, bool row_b, uint8_t* wa /* strip byte of (row 2 crow, px0) */,
                            uint32_t rowbytes, u32x2 ya, u32x2 yb, u32x2 cq, uint32_t vq) {
@@ -128,14 +141,13 @@ VPF_DEV void convert_unit8(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t cr
   }
 }
 
-// loads of any alignment: a rectangle starts at an arbitrary byte of an arbitrarily aligned plane (the backend keeps them one
-// global_load_dword / _dwordx2: gfx950 global memory takes unaligned addresses)
-typedef u32x2 u32x2_any __attribute__((aligned(1)));
-typedef uint32_t u32_any __attribute__((aligned(1)));
-
 // The fill stage of the staged per-job kernels (k_roi_strip, k_warp_strip): the workgroup's 256 lanes convert the source window of ABSOLUTE frame
 // pixels [base_px, base_px + 8 ng) x rows [R_lo, R_hi] into the strip, whole conversion units at a time with loads of any alignment; the unit that
 // holds the frame's right edge takes clamped byte loads, so no byte outside the frame's own rows is read.  The caller synchronises afterwards.
+// FC_P16: a unit's 8 luma samples and its 4 U V pairs are 16 B each at byte 2 px0 of their rows (px0 even: chroma pair px0 / 2 starts at byte
+// 4 (px0 / 2)), loaded at any 2-B alignment and narrowed to the two dwords the 8-bit unit takes.  The whole-unit loads run under the same
+// condition px0 + 8 <= W: luma bytes [2 px0, 2 px0 + 16) end at or before 2 W, chroma bytes at 4 (px0 / 2 + 4) <= 4 ceil(W / 2) — inside the
+// rows' own samples.  The right-edge unit takes 2-B sample loads with indices clamped to the row's last sample (pair), as the 8-bit code does.
 // A statement macro, not a function: its text is k_roi_strip's original fill stage, so that kernel's code object is unchanged.  It expands in
 // a template <int SRC> kernel and uses these names of the enclosing scope: f (FrameDesc), c (Yuv2RgbCoef), W (frame width), strip (uint8_t*),
 // base_px (even), R_lo, R_hi (frame rows), c_lo = R_lo >> 1, ng (units per row), units = chroma rows x ng, rowbytes, tid.
@@ -161,7 +173,34 @@ typedef uint32_t u32_any __attribute__((aligned(1)));
     q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  /* (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window) */                             \
     const uint8_t* const y0p = f.s[0] + (size_t)r0 * f.sp[0];                                                                                            \
     const uint8_t* const c1p = f.s[1] + (size_t)crow * f.sp[1];                                                                                          \
-    if (px0 + 8 <= W) {                                                                                                                                  \
+    if constexpr (SRC == FC_P16) {                                                                                                                       \
+      (void)bytes8;                                                                                                                                      \
+      auto words8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  /* 16-bit samples i0 .. i0 + 7 of a row of n, clamped to n - 1, narrowed */      \
+        uint32_t d[2] = {0u, 0u};                                                                                                                        \
+  _Pragma("unroll")                                                                                                                                      \
+        for (int k = 0; k < 8; k++) {                                                                                                                    \
+          const uint32_t i = i0 + k < n ? i0 + k : n - 1;                                                                                                \
+          d[k >> 2] |= (uint32_t)p16_to_8(reinterpret_cast<const uint16_t*>(row)[i]) << (8 * (k & 3));                                                   \
+        }                                                                                                                                                \
+        return u32x2{d[0], d[1]};                                                                                                                        \
+      };                                                                                                                                                 \
+      if (px0 + 8 <= W) {                                                                                                                                \
+        q.cq = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(c1p + 2 * (size_t)px0));                                                                   \
+        if (q.ra) q.ya = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + 2 * (size_t)px0));                                                         \
+        if (q.rb) q.yb = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + f.sp[0] + 2 * (size_t)px0));                                               \
+      } else {  /* the unit that holds the frame's right edge */                                                                                         \
+        uint32_t d[2] = {0u, 0u};  /* U V pairs of chroma samples (px0 >> 1) .. + 3 */                                                                   \
+  _Pragma("unroll")                                                                                                                                      \
+        for (int k = 0; k < 4; k++) {                                                                                                                    \
+          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;                                                                              \
+          const uint16_t* const pc = reinterpret_cast<const uint16_t*>(c1p);                                                                             \
+          d[k >> 1] |= ((uint32_t)p16_to_8(pc[2 * i]) | (uint32_t)p16_to_8(pc[2 * i + 1]) << 8) << (16 * (k & 1));                                       \
+        }                                                                                                                                                \
+        q.cq = u32x2{d[0], d[1]};                                                                                                                        \
+        if (q.ra) q.ya = words8(y0p, px0, W);                                                                                                            \
+        if (q.rb) q.yb = words8(y0p + f.sp[0], px0, W);                                                                                                  \
+      }                                                                                                                                                  \
+    } else if (px0 + 8 <= W) {                                                                                                                           \
       if constexpr (SRC == FC_NV12) {                                                                                                                    \
         q.cq = *reinterpret_cast<const u32x2_any*>(c1p + px0);                                                                                           \
       } else {                                                                                                                                           \
@@ -194,8 +233,8 @@ typedef uint32_t u32_any __attribute__((aligned(1)));
     fetch(u0, q0);                                                                                                                                       \
     fetch(u0 + 256, q1);                                                                                                                                 \
     __builtin_amdgcn_sched_barrier(0);  /* both units' loads are requested before the first conversion */                                                \
-    if (q0.act) convert_unit8<SRC>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);                                              \
-    if (q1.act) convert_unit8<SRC>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);                                              \
+    if (q0.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);             \
+    if (q1.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);             \
   }                                                                                                                                                     
 
 }  // namespace vpf

@@ -13,11 +13,6 @@
 
 namespace vpf {
 
-VPF_DEV uint8_t p16_to_8(uint16_t v) {  // (v + 128) >> 8 saturated: nppiDivC_16u(256) round-to-nearest + Convert_16u8u
-  uint32_t r = ((uint32_t)v + 128u) >> 8;
-  return (uint8_t)(r > 255u ? 255u : r);
-}
-
 // ------------------------------------------------------------------------------------------
 // NV12 <-> YUV420: one lane = 16 luma px x 2 rows + 8 chroma pairs.
 // fast path: w % 16 == 0, h even, Y/UV planes 16-B aligned, U/V planes 8-B aligned.

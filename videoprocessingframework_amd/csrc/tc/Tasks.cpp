@@ -404,23 +404,29 @@ TaskExecStatus ConvertSurface::RunBatch(Surface* const* ins, Surface* const* out
 
 // ------------------------------------------------------------------------------------------ ConvertResizeSurface
 struct ConvertResizeSurface::Impl {
-  const PairInfo* pair;
+  const PairInfo* pair;  // the colour-context rule and the name in diagnostics; for P10 / P12 sources the NV12 pair with the same output
+  Pixel_Format in;       // what the surfaces must be (pair->in for the 8-bit sources)
   uint32_t sw, sh, dw, dh;
   HipContext ctx;
   HipStream str;
   std::unique_ptr<Surface> out;
+  bool p16() const { return in == P10 || in == P12; }  // tensor entries only: the 8-bit outputs take 8-bit sources
 };
+static const char* const kP16Refusal =
+    "fused conversion + resize: the 8-bit outputs take 8-bit sources (NV12 / YUV420); P10 / P12 surfaces feed the tensor entries "
+    "(ExecuteToTensor, ExecuteRoisToTensor, ExecuteWarpsToTensor)";
 ConvertResizeSurface::ConvertResizeSurface(uint32_t sw, uint32_t sh, Pixel_Format in, uint32_t dw, uint32_t dh, Pixel_Format out,
                                            HipContext ctx, HipStream str)
     : Task("HipConvertResizeSurface", numInputs, numOutputs, nullptr, nullptr), pImpl() {
-  const PairInfo* p = find_pair(in, out);
-  const bool fusable = p && (in == NV12 || in == YUV420) && (out == RGB || out == BGR || out == RGB_PLANAR);
+  const bool in16 = in == P10 || in == P12;  // narrowed to 8 bits at the load, then NV12's arithmetic: NV12's colour-context rule
+  const PairInfo* p = find_pair(in16 ? NV12 : in, out);
+  const bool fusable = p && (in == NV12 || in == YUV420 || in16) && (out == RGB || out == BGR || out == RGB_PLANAR);
   if (!fusable || !sw || !sh || !dw || !dh) {
     std::stringstream ss;
     ss << "Unsupported fused conversion + resize: " << in << " to " << out;
     throw std::invalid_argument(ss.str());
   }
-  pImpl.reset(new Impl{p, sw, sh, dw, dh, ctx, str, nullptr});
+  pImpl.reset(new Impl{p, in, sw, sh, dw, dh, ctx, str, nullptr});
   pImpl->out.reset(Surface::Make(out, dw, dh, ctx));
 }
 ConvertResizeSurface::~ConvertResizeSurface() {}
@@ -435,9 +441,13 @@ TaskExecStatus ConvertResizeSurface::Run() {
   const ColorspaceConversionContext* cc = nullptr;
   if (auto* b = static_cast<Buffer*>(GetInput(1))) cc = b->GetDataAs<ColorspaceConversionContext>();
   if (!in || in->Empty() || !pImpl->out || pImpl->out->Empty()) return TASK_EXEC_SUCCESS;
-  if (in->PixelFormat() != pImpl->pair->in || in->Width() != pImpl->sw || in->Height() != pImpl->sh) {
+  if (pImpl->p16()) {
+    std::cerr << kP16Refusal << std::endl;
+    return TASK_EXEC_SUCCESS;
+  }
+  if (in->PixelFormat() != pImpl->in || in->Width() != pImpl->sw || in->Height() != pImpl->sh) {
     std::cerr << "fused " << pImpl->pair->name << ": input surface is " << PixelFormatName(in->PixelFormat()) << " " << in->Width()
-              << "x" << in->Height() << ", task was built for " << PixelFormatName(pImpl->pair->in) << " " << pImpl->sw << "x"
+              << "x" << in->Height() << ", task was built for " << PixelFormatName(pImpl->in) << " " << pImpl->sw << "x"
               << pImpl->sh << std::endl;
     return TASK_EXEC_SUCCESS;
   }
@@ -458,12 +468,16 @@ TaskExecStatus ConvertResizeSurface::Run() {
 }
 TaskExecStatus ConvertResizeSurface::RunBatch(Surface* const* ins, Surface* const* outs, uint32_t n, const ColorspaceConversionContext* cc) {
   if (!ins || !outs || !n) return TASK_EXEC_FAIL;
+  if (pImpl->p16()) {
+    std::cerr << kP16Refusal << std::endl;
+    return TASK_EXEC_FAIL;
+  }
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
   std::vector<vpf_frame_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
     Surface *s = ins[i], *d = outs[i];
-    if (!s || !d || s->Empty() || d->Empty() || s->PixelFormat() != pImpl->pair->in || d->PixelFormat() != pImpl->pair->out ||
+    if (!s || !d || s->Empty() || d->Empty() || s->PixelFormat() != pImpl->in || d->PixelFormat() != pImpl->pair->out ||
         s->Width() != pImpl->sw || s->Height() != pImpl->sh || d->Width() != pImpl->dw || d->Height() != pImpl->dh)
       return TASK_EXEC_FAIL;
     fill_planes(s, io[i].src);
@@ -488,13 +502,13 @@ TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, 
   std::vector<vpf_frame_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
     Surface* s = ins[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(s, io[i].src);
     for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
-  const vpf_status st = vpf_convert_resize_tensor_batch(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+  const vpf_status st = vpf_convert_resize_tensor_batch(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
                                                         io.data(), &norm);
   if (st != VPF_OK) {
     std::cerr << "Failed to convert + resize surfaces into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
@@ -510,7 +524,7 @@ TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint3
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
   for (uint32_t i = 0; i < n_frames; i++) {
     Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
   }
   std::vector<vpf_roi_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
@@ -521,7 +535,7 @@ TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint3
     io[i].rect = rects[i];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
-  const vpf_status st = vpf_convert_resize_tensor_rois(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+  const vpf_status st = vpf_convert_resize_tensor_rois(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
                                                        io.data(), &norm);
   if (st != VPF_OK) {
     std::cerr << "Failed to convert + resize regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
@@ -538,7 +552,7 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
   for (uint32_t i = 0; i < n_frames; i++) {
     Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->pair->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
   }
   std::vector<vpf_warp_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
@@ -549,7 +563,7 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
     for (int k = 0; k < 6; k++) io[i].m[k] = matrices[6 * i + k];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
-  const vpf_status st = vpf_convert_warp_tensor(&ex, pImpl->pair->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(),
+  const vpf_status st = vpf_convert_warp_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(),
                                                 &norm, opts);
   if (st != VPF_OK) {
     std::cerr << "Failed to warp regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;

@@ -42,6 +42,9 @@ private:
 // Additive (no reference counterpart; SURVEY §8 R1 "(ii) fused NV12 -> bilinear -> RGB"): convert and bilinear-resize in
 // one pass, bit-identical to ConvertSurface followed by ResizeSurface but without the full-size RGB intermediate.
 // Sources NV12 / YUV420, destinations RGB / BGR / RGB_PLANAR; colour-context rules are those of the unfused pair.
+// P10 / P12 sources construct too, for the tensor entries only (RunTensor, RunTensorRois, RunTensorWarps: every 16-bit sample is narrowed to
+// min(255, (v + 128) >> 8), what ConvertSurface P10 -> NV12 writes, then NV12's path with the NV12 pair's colour-context rule); Run and
+// RunBatch of such a task refuse with a message: the 8-bit outputs take 8-bit sources.
 class ConvertResizeSurface final : public Task {
 public:
   static ConvertResizeSurface* Make(uint32_t src_width, uint32_t src_height, Pixel_Format inFormat, uint32_t dst_width,

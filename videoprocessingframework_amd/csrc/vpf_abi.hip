@@ -153,6 +153,25 @@ static int yuv_src_class(int f) {
     default: return -1;
   }
 }
+// The sources of the fused TENSOR entries (vpf_convert_resize_tensor(_batch), _rois, vpf_convert_warp_tensor): the 8-bit 4:2:0 formats and
+// P10 / P12, whose 16-bit samples the kernels narrow at the load.  A mapping of its own: classify() and the 8-bit fused entries keep
+// yuv_src_class(), so vpf_convert_supported(P10, RGB ..) and vpf_convert_resize(P10 ..) answer as before.
+static int tensor_src_class(int f) {
+  switch (f) {
+    case VPF_FMT_NV12: return FC_NV12;
+    case VPF_FMT_YUV420: return FC_YUV420;
+    case VPF_FMT_P10: case VPF_FMT_P12: return FC_P16;
+    default: return -1;
+  }
+}
+// planes_ok, and for the 16-bit formats 2-B aligned pointers and pitches
+static bool tensor_src_ok(int f, uint32_t w, const vpf_plane* p) {
+  if (!planes_ok(f, w, p)) return false;
+  if (f == VPF_FMT_P10 || f == VPF_FMT_P12)
+    for (int k = 0; k < 2; k++)
+      if (((uintptr_t)p[k].ptr | p[k].pitch) & 1) return false;
+  return true;
+}
 static int rgb_class(int f) {
   switch (f) {
     case VPF_FMT_RGB: return FC_RGB;
@@ -444,7 +463,7 @@ vpf_status vpf_convert_resize(const vpf_exec* exec, int sf, int df, int cs, int 
 vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
                                            const vpf_frame_io* frames, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_batch");
-  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
   if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
   for (int c = 0; c < 3; c++)
@@ -452,7 +471,7 @@ vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs,
   if (!exec || !frames || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
   for (uint32_t i = 0; i < n; i++) {
-    if (!planes_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
     for (int k = 0; k < 3; k++) {
       const vpf_plane& p = frames[i].dst[k];
       if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
@@ -478,7 +497,7 @@ vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs,
       fill_desc(a.f[i], frames[base + i].src, num_planes(sf), d, 3);
     }
     for (uint32_t i = m; i < ((m + 7u) & ~7u); i++) a.f[i] = a.f[0];
-    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), FC_TENSOR, c, ss.width, ss.height, m, a,
+    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), FC_TENSOR, c, ss.width, ss.height, m, a,
                                                ds.width, ds.height, &te);
     if (e != hipSuccess) return status_of(e);
   }
@@ -487,7 +506,7 @@ vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs,
 
 vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, const vpf_plane src[3], vpf_size ds,
                                      const vpf_plane dst[3], const vpf_tensor_norm* norm) {
-  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
   vpf_frame_io io;
   std::memset(&io, 0, sizeof(io));
@@ -501,7 +520,7 @@ vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int c
 vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
                                           const vpf_roi_io* rois, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_rois");
-  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
   if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
   for (int c = 0; c < 3; c++)
@@ -511,7 +530,7 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
   for (uint32_t i = 0; i < n; i++) {
     const vpf_rect& r = rois[i].rect;
     if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
-    if (!planes_ok(sf, ss.width, rois[i].src)) return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, rois[i].src)) return VPF_ERR_BAD_ARG;
     for (int k = 0; k < 3; k++) {
       const vpf_plane& p = rois[i].dst[k];
       if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
@@ -539,7 +558,7 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
       j.x = io.rect.x; j.y = io.rect.y; j.w = io.rect.width; j.h = io.rect.height;
       j.scx = (float)j.w / (float)ds.width; j.scy = (float)j.h / (float)ds.height;
     }
-    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te);
+    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -550,7 +569,7 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
 vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_warp_io* jobs,
                                    const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
   const Mark mark("vpf_convert_warp_tensor");
-  if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
   if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
   if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
@@ -562,7 +581,7 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
   for (uint32_t i = 0; i < n; i++) {
     for (int k = 0; k < 6; k++)
       if (!(std::fabs(jobs[i].m[k]) <= 16777216.0f)) return VPF_ERR_BAD_ARG;  // NaN and infinities fail the comparison too
-    if (!planes_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
     for (int k = 0; k < num_planes(sf); k++)
       if (jobs[i].src[k].reserved) return VPF_ERR_BAD_ARG;
     for (int k = 0; k < 3; k++) {
@@ -594,7 +613,7 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
       fill_desc(table[i].f, io.src, num_planes(sf), d, 3);
       for (int k = 0; k < 6; k++) table[i].m[k] = io.m[k];
     }
-    const hipError_t e = launch_convert_warp(static_cast<hipStream_t>(exec->stream), yuv_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
+    const hipError_t e = launch_convert_warp(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
                                              ds.height, te);
     if (e != hipSuccess) return status_of(e);
   }

@@ -145,6 +145,25 @@ VPF_DEV u32x4 load_uv16(const FrameDesc& f, uint32_t rp, uint32_t x) {
   }
 }
 
+// 16-bit MSB-aligned samples (P10 / P12) -> 8 bits: (v + 128) >> 8 saturated: nppiDivC_16u(256) round-to-nearest + Convert_16u8u
+// (k_relayout.hip's P10 / P12 -> NV12 and the 16-bit source class of the fused kernels: the same narrowing)
+VPF_DEV uint8_t p16_to_8(uint16_t v) {
+  uint32_t r = ((uint32_t)v + 128u) >> 8;
+  return (uint8_t)(r > 255u ? 255u : r);
+}
+// the packed form: two dwords of two samples each -> their four bytes in one dword.  A saturating 16-bit add of 128 (v_pk_add_u16 .. clamp)
+// leaves min(255, (v + 128) >> 8) in the high byte of every half — 0xff80 .. 0xffff stop at 0xffff, whose high byte is the saturated 255 —
+// and one v_perm_b32 collects the four high bytes.
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+VPF_DEV uint32_t p16x4_to_8(uint32_t lo, uint32_t hi) {
+  const u16x2 r = {128, 128};
+  const uint32_t a = __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(u16x2, lo), r));
+  const uint32_t b = __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(u16x2, hi), r));
+  return __builtin_amdgcn_perm(b, a, 0x07050301u);
+}
+VPF_DEV u32x2 p16x8_to_8(u32x4 v) { return u32x2{p16x4_to_8(v[0], v[1]), p16x4_to_8(v[2], v[3])}; }                      // 8 samples (16 B) -> 8 bytes
+VPF_DEV u32x4 p16x16_to_8(u32x4 a, u32x4 b) { return u32x4{p16x4_to_8(a[0], a[1]), p16x4_to_8(a[2], a[3]), p16x4_to_8(b[0], b[1]), p16x4_to_8(b[2], b[3])}; }  // 16 samples -> 16 bytes
+
 // make one wave's LDS writes visible to its own other lanes (wave-private tiles: no workgroup barrier needed)
 VPF_DEV void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

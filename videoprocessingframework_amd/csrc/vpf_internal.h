@@ -73,6 +73,8 @@ enum FmtClass : int {
   FC_BGR = 4,     // packed B,G,R
   FC_PLANAR = 5,  // three full planes R,G,B
   FC_TENSOR = 6,  // three full planes of f32 / f16 / bf16: the FC_PLANAR bytes through one fma each (vpf_convert_resize_tensor)
+  FC_P16 = 7,     // P10 / P12: Y + interleaved UV of 16-bit MSB-aligned samples, 4:2:0 — a SOURCE class of the fused tensor entries only: every
+                  // sample is narrowed to 8 bits at the load (p16_to_8, vpf_device.h), from there the code is FC_NV12's
 };
 // The epilogue of an FC_TENSOR launch: out[c] = to_dtype(fma(u8[c], scale[c], bias[c])).  It travels behind the frame table (BatchArgsTE), so
 // the 8-bit instantiations keep their kernarg layout.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
