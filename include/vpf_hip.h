@@ -237,14 +237,24 @@ VPF_API vpf_status vpf_convert_resize_batch(const vpf_exec* exec, int src_fmt, i
  * vpf_convert(P10 | P12 -> NV12) writes for that frame, without that pass over the whole frame.  This is deliberately NOT a full-precision
  * conversion (the 10 bits fed into the matrix): that would be a definition with nothing to test it against.  vpf_convert_resize(_batch),
  * vpf_convert_supported and vpf_resize answer for P10 / P12 as before.
+ *
+ * Channels-last (NHWC, torch.channels_last) tensors: flags | VPF_TENSOR_NHWC, accepted by this entry, its batch form,
+ * vpf_convert_resize_tensor_rois, vpf_convert_warp_tensor (destination) and vpf_tensor_convert(_batch) (source), for every source format, dtype
+ * and channel order they take.  dst[0] (src[0] on the way back) is then the ONE interleaved plane of the frame or job: element (y, x, c) lies at
+ * ptr + y * pitch + (3 x + c) * element size, c in output channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c], bias[c] and the warp's
+ * border[c] belong to channel c as ever).  dst[1] and dst[2] are ignored and may be zero.  ptr and pitch must be multiples of the element size
+ * and pitch >= 3 x width x element size (else VPF_ERR_BAD_ARG).  Element (y, x, c) is bit for bit the element (c, y, x) the same call writes
+ * without the flag, and vpf_tensor_convert's output is bit for bit the planar call's on the de-interleaved planes.  Flag bits other than
+ * VPF_TENSOR_BGR | VPF_TENSOR_NHWC (2 included): VPF_ERR_UNSUPPORTED.
  */
 typedef enum vpf_tensor_dtype { VPF_TENSOR_F32 = 0, VPF_TENSOR_F16 = 1, VPF_TENSOR_BF16 = 2 } vpf_tensor_dtype;
-#define VPF_TENSOR_BGR 1u /* vpf_tensor_norm.flags: channel order B G R */
+#define VPF_TENSOR_BGR 1u  /* vpf_tensor_norm.flags: channel order B G R */
+#define VPF_TENSOR_NHWC 4u /* vpf_tensor_norm.flags: one interleaved plane [H, W, 3] per frame instead of three planes */
 typedef struct vpf_tensor_norm {
   float scale[3];
   float bias[3];
   uint32_t dtype; /* vpf_tensor_dtype */
-  uint32_t flags; /* 0 or VPF_TENSOR_BGR */
+  uint32_t flags; /* 0 or any of VPF_TENSOR_BGR | VPF_TENSOR_NHWC */
 } vpf_tensor_norm;
 VPF_API vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
                                              const vpf_plane src[3], vpf_size dst_size, const vpf_plane dst[3], const vpf_tensor_norm* norm);

@@ -13,6 +13,7 @@ torch is plumbing here (allocation, streams); no pixel arithmetic happens in thi
 from __future__ import annotations
 
 import operator
+from typing import TYPE_CHECKING, overload
 
 import torch
 
@@ -119,8 +120,48 @@ def surface_from_tensor(tensor: torch.Tensor, fmt=None):
 
 _TENSOR_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # vpf_tensor_dtype
 
+if TYPE_CHECKING:  # the two call forms of the four tensor functions: the planar one, unchanged, and the one that names the memory layout
+    @overload
+    def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor: ...
+    @overload
+    def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None, *, channels_last: bool) -> torch.Tensor: ...
+    @overload
+    def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor: ...
+    @overload
+    def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None, *, channels_last: bool) -> torch.Tensor: ...
+    @overload
+    def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None) -> torch.Tensor: ...
+    @overload
+    def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, *, channels_last: bool) -> torch.Tensor: ...
+    @overload
+    def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None) -> list: ...
+    @overload
+    def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None, *, channels_last: bool) -> list: ...
 
-def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
+
+def _channels_last_strides(fn, t, what):
+    """(frame, row) strides in elements of a logical [N, 3, H, W] tensor in torch.channels_last memory: strides (s0, 1, s2, 3) with s2 >= 3 W and
+    s0 >= H s2 (a slice of a larger batch and padded rows qualify); ValueError naming the strides otherwise.  Dimensions of one element are
+    never walked: their strides are not looked at."""
+    n, _, h, w = t.shape
+    s0, s1, s2, s3 = t.stride()
+    if s1 != 1 or (w > 1 and s3 != 3) or (h > 1 and s2 < 3 * w) or (n > 1 and s0 < h * (s2 if h > 1 else 3 * w)):
+        raise ValueError(f"{fn}: channels_last=True needs {what} in torch.channels_last memory format: strides (s0, 1, s2, 3) with s2 >= {3 * w} and "
+                         f"s0 >= {h} * s2, got strides {tuple(t.stride())}")
+    return (s0 if n > 1 else 0), (s2 if h > 1 else 0)
+
+
+def _channels_last_out(fn, out, n, h, w, dtype):
+    """the destination of a channels_last=True call: a new [n, 3, h, w] tensor in torch.channels_last memory format, or the checked `out`"""
+    if out is None:
+        return torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()), memory_format=torch.channels_last)
+    if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+        raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    _channels_last_strides(fn, out, "out")
+    return out
+
+
+def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
     """NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [N, 3, H, W] a DNN consumes, in one pass of the fused kernels
     (PySurfaceConvertResizer.ExecuteToTensor): the RGB_PLANAR bytes of resizer.ExecuteBatch, divided by 255 and normalised with
     torchvision's mean / std (one fp32 fma per element, scale = 1 / (255 std), bias = -mean / std), rounded to `dtype` (float32, float16,
@@ -129,13 +170,21 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
     `out`: a tensor to write into (dtype, device and shape must match, the last dimension contiguous; row, plane and frame strides are
     free: a slice of a larger batch or padded rows work), else a new one on torch's current device.  The kernel runs on the resizer's
     stream after torch's current stream has reached this call, and torch's current stream waits for it: the result can be used on the
-    current stream right away, no host synchronisation.  The surfaces themselves are ordered as for every Execute (the caller's business)."""
+    current stream right away, no host synchronisation.  The surfaces themselves are ordered as for every Execute (the caller's business).
+
+    channels_last=True (here, in rois_to_normalized_tensor and in warps_to_normalized_tensor): the same values, written by the kernels straight
+    into torch.channels_last memory (NHWC) — the returned tensor still has the logical shape [N, 3, H, W], and
+    is_contiguous(memory_format=torch.channels_last) holds for a new one.  `out` then needs strides (s0, 1, s2, 3) with s2 >= 3 W and
+    s0 >= H s2 (a slice of a channels-last batch and padded rows qualify), else ValueError.  The layout is what this argument says, never
+    inferred from the strides of `out`."""
     if dtype not in _TENSOR_DTYPES:
         raise ValueError(f"to_normalized_tensor: dtype must be one of {list(_TENSOR_DTYPES)}")
     surfaces = list(surfaces)
     n = len(surfaces)
     w, h = resizer.DstSize()
-    if out is None:
+    if channels_last:
+        out = _channels_last_out("to_normalized_tensor", out, n, h, w, dtype)
+    elif out is None:
         out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
     else:
         if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
@@ -149,6 +198,8 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
         return out
     elem = out.element_size()
     s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides("to_normalized_tensor", out, "out"), 0
     with torch.cuda.device(out.device):
         cur = torch.cuda.current_stream()
         rs = int(resizer.Stream())
@@ -156,7 +207,7 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
         if side is not None:
             side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
         ok = resizer.ExecuteToTensor(surfaces, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
-                                     bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+                                     bool(bgr), s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
         if side is not None:
             cur.wait_stream(side)
     if not ok:
@@ -199,7 +250,7 @@ def _rois_list(rois, surfaces, fn):
     return out
 
 
-def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None) -> torch.Tensor:
+def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
     """K rectangles of NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [K, 3, dh, dw] a second-stage network (classifier, ReID, face net
     behind a detector) consumes, in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteRoisToTensor, vpf_convert_resize_tensor_rois).
     `rois`: a sequence of (surface_index, x, y, w, h) integer 5-tuples, or a CPU integer tensor / ndarray [K, 5]; x, y, w, h in luma pixels of
@@ -207,7 +258,7 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
     clamped at the RECTANGLE's edges) to the resizer's destination size and normalised exactly as to_normalized_tensor does; a rectangle that
     is the whole surface gives to_normalized_tensor's bits.
 
-    `out`, the returned tensor and the stream ordering: exactly as to_normalized_tensor.  ValueError for rois on the device (pass .cpu()), a
+    `out`, channels_last, the returned tensor and the stream ordering: exactly as to_normalized_tensor.  ValueError for rois on the device (pass .cpu()), a
     non-integer dtype, a bad surface index or a rectangle that is empty or leaves its surface.  K == 0 returns an empty tensor without a launch."""
     fn = "rois_to_normalized_tensor"
     if dtype not in _TENSOR_DTYPES:
@@ -216,7 +267,9 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
     jobs = _rois_list(rois, surfaces, fn)
     n = len(jobs)
     w, h = resizer.DstSize()
-    if out is None:
+    if channels_last:
+        out = _channels_last_out(fn, out, n, h, w, dtype)
+    elif out is None:
         out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
     else:
         if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
@@ -228,6 +281,8 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
         return out
     elem = out.element_size()
     s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
     with torch.cuda.device(out.device):
         cur = torch.cuda.current_stream()
         rs = int(resizer.Stream())
@@ -235,7 +290,7 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
         if side is not None:
             side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
         ok = resizer.ExecuteRoisToTensor(surfaces, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
-                                         bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+                                         bool(bgr), s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
         if side is not None:
             cur.wait_stream(side)
     if not ok:
@@ -272,13 +327,13 @@ def _matrices_list(matrices, fn):
     return [[float(v) for v in m.reshape(6)] for m in arr]
 
 
-def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None) -> torch.Tensor:
+def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
     """K affine warps of NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [K, 3, dh, dw] a network behind a detector consumes (aligned faces,
     rotated text boxes, oriented detections), in one dispatch per 96 regions (PySurfaceConvertResizer.ExecuteWarpsToTensor, vpf_convert_warp_tensor).
     `matrices`: a host [K, 2, 3] float tensor, ndarray or nested sequence (float64 is rounded to float32 once); matrices[i] is the INVERSE map of
     job i: it takes a destination pixel (dx, dy) to source coordinates in luma pixels of surfaces[surface_index[i]], the convention of remap's
     maps.  Pixels that fall outside the surface take `border` (per output channel, 0..255) under border_mode "constant" and the nearest edge
-    pixel under "replicate".  Normalisation, `out`, the returned tensor and the stream ordering: exactly as to_normalized_tensor.
+    pixel under "replicate".  Normalisation, `out`, channels_last, the returned tensor and the stream ordering: exactly as to_normalized_tensor.
 
     ValueError for matrices on the device (pass .cpu()), a wrong shape, a non-float dtype, a coefficient that is not finite or exceeds 2^24, a
     bad surface index, a border value outside 0..255, an unknown mode.  K == 0 returns an empty tensor without a launch."""
@@ -310,7 +365,9 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
             raise ValueError(f"{fn}: surface_index[{i}] names surface {k}, there are {len(surfaces)}")
     n = len(jobs)
     w, h = resizer.DstSize()
-    if out is None:
+    if channels_last:
+        out = _channels_last_out(fn, out, n, h, w, dtype)
+    elif out is None:
         out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
     else:
         if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
@@ -322,6 +379,8 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
         return out
     elem = out.element_size()
     s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
     with torch.cuda.device(out.device):
         cur = torch.cuda.current_stream()
         rs = int(resizer.Stream())
@@ -329,7 +388,7 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
         if side is not None:
             side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
         ok = resizer.ExecuteWarpsToTensor(surfaces, index, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
-                                          cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem)
+                                          cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
         if side is not None:
             cur.wait_stream(side)
     if not ok:
@@ -337,7 +396,7 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
     return out
 
 
-def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None):
+def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None, channels_last=False):
     """A model's output -> NV12 / YUV420 surfaces for the encoder, in one pass (PyTensorToSurface.ExecuteBatch): `tensor` is [N, 3, H, W] or
     [3, H, W] of float32 / float16 / bfloat16 on the device, normalised with torchvision's mean / std (per input plane; B G R planes when
     bgr=True).  Every element goes through x * (255 std) + (255 mean) in fp32 (a multiply, then an add), is clamped to [0, 255] (NaN -> 0) and
@@ -349,7 +408,12 @@ def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None,
     call .contiguous() first.  The tensor must live on the converter's GPU.  Returns the list of surfaces: `out` (N surfaces of the
     converter's size and format) if given, else new ones on that GPU.  The kernel runs on the converter's stream after torch's current stream
     has reached this call, and torch's current stream waits for it: the surfaces can be used on the current stream right away, no host
-    synchronisation."""
+    synchronisation.
+
+    channels_last=True: `tensor` (still of logical shape [N, 3, H, W]) lies in torch.channels_last memory — what a channels-last model
+    returns — and is read as it is, without a .contiguous() copy: strides (s0, 1, s2, 3) with s2 >= 3 W and s0 >= H s2, anything else is a
+    ValueError.  The surfaces are byte for byte those of the planar call on tensor.contiguous().  The layout is what this argument says, never
+    inferred from the strides."""
     try:
         import PyNvCodec as nvc
     except ImportError:  # package-relative import when used as videoprocessingframework_amd.PytorchNvCodec
@@ -363,9 +427,11 @@ def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None,
         raise ValueError(f"from_normalized_tensor: tensor must have shape [N, 3, {h}, {w}] or [3, {h}, {w}], got {tuple(tensor.shape)}")
     n = tensor.shape[0]
     s0, s1, s2, s3 = tensor.stride()
+    if channels_last:
+        (s0, s2), s1, s3 = _channels_last_strides("from_normalized_tensor", tensor, "the tensor"), 1, 1
     # The binding reads a stride of 0 as "contiguous", so a zero (or negative) stride of a dimension that is really walked must not reach it;
     # a dimension of one element is never walked, and goes down as 0 = default.
-    if (w > 1 and s3 != 1) or (h > 1 and s2 < w) or s1 <= 0 or (n > 1 and s0 <= 0):
+    if not channels_last and ((w > 1 and s3 != 1) or (h > 1 and s2 < w) or s1 <= 0 or (n > 1 and s0 <= 0)):
         raise ValueError(f"from_normalized_tensor: tensor needs unit stride along W, rows at least {w} elements apart and positive plane and frame "
                          f"strides (an expanded tensor needs .contiguous() first), got strides {tensor.stride()}")
     if h == 1:
@@ -391,7 +457,7 @@ def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None,
         if side is not None:
             side.wait_stream(cur)  # whatever produced `tensor` on torch's stream comes first
         ok = converter.ExecuteBatch(tensor.data_ptr(), out, _TENSOR_DTYPES[tensor.dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
-                                    bool(bgr), s2 * elem, s1 * elem, s0 * elem)
+                                    bool(bgr), s2 * elem, (0 if channels_last else s1) * elem, s0 * elem, bool(channels_last))
         if side is not None:
             cur.wait_stream(side)
             tensor.record_stream(side)  # the caching allocator must not hand the tensor's memory out before the converter has read it

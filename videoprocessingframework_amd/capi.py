@@ -34,6 +34,7 @@ EXPORTS = [
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
+TENSOR_NHWC = 4  # one interleaved plane [H, W, 3] per frame (dst[0] / src[0]) instead of three planes
 
 
 class Workspace(C.Structure):
@@ -111,21 +112,21 @@ def denorm_params(mean, std):
     return [255.0 * s for s in std], [255.0 * m for m in mean]
 
 
-def make_tensor_denorm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None) -> TensorNorm:
+def make_tensor_denorm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None, nhwc=False) -> TensorNorm:
     """vpf_tensor_norm for vpf_tensor_convert from mean / std (denorm_params) or from raw scale / bias (passed through unchecked)"""
     if scale is None:
         scale, bias = denorm_params(mean, std)
-    return make_tensor_norm(dtype=dtype, bgr=bgr, scale=scale, bias=bias)
+    return make_tensor_norm(dtype=dtype, bgr=bgr, scale=scale, bias=bias, nhwc=nhwc)
 
 
-def make_tensor_norm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None) -> TensorNorm:
+def make_tensor_norm(mean=None, std=None, dtype=TENSOR_F32, bgr=False, scale=None, bias=None, nhwc=False) -> TensorNorm:
     """vpf_tensor_norm from mean / std (norm_params) or from raw scale / bias (passed through unchecked: the library validates them)"""
     if scale is None:
         scale, bias = norm_params(mean, std)
     n = TensorNorm()
     for c in range(3):
         n.scale[c], n.bias[c] = scale[c], bias[c]
-    n.dtype, n.flags = dtype, TENSOR_BGR if bgr else 0
+    n.dtype, n.flags = dtype, (TENSOR_BGR if bgr else 0) | (TENSOR_NHWC if nhwc else 0)
     return n
 
 

@@ -77,6 +77,30 @@ std::shared_ptr<Surface> make_surface(Pixel_Format f, uint32_t w, uint32_t h, Hi
 }
 std::shared_ptr<Surface> empty_surface(Pixel_Format f) { return std::shared_ptr<Surface>(Surface::Make(f)); }
 
+// The planes of `n` tensor frames of w x h at device address `base`, as the Task layer's tensor entries take them.  Planar: three per frame,
+// element (i, c, y, x) at base + i frame_stride + c plane_stride + y row_pitch + x elem (strides in bytes, 0 = contiguous NCHW).  channels_last:
+// ONE per frame, element (i, c, y, x) at base + i frame_stride + y row_pitch + (3 x + c) elem (plane_stride ignored, 0 = contiguous NHWC), and
+// VPF_TENSOR_NHWC is set in `norm`.
+bool tensor_planes(uint64_t base, uint32_t dtype, size_t n, uint64_t w, uint64_t h, uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride,
+                   bool channels_last, vpf_tensor_norm& norm, std::vector<vpf_plane>& planes) {
+  const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2;
+  if (!row_pitch) row_pitch = (channels_last ? 3 : 1) * w * elem;
+  if (channels_last) plane_stride = 0;
+  else if (!plane_stride) plane_stride = h * row_pitch;
+  if (!frame_stride) frame_stride = channels_last ? h * row_pitch : 3 * plane_stride;
+  if (row_pitch > 0xffffffffull) return false;
+  const size_t per = channels_last ? 1 : 3;
+  if (channels_last) norm.flags |= VPF_TENSOR_NHWC;
+  planes.resize(per * n);
+  for (size_t i = 0; i < n; i++)
+    for (size_t c = 0; c < per; c++) {
+      planes[per * i + c].ptr = (void*)(uintptr_t)(base + i * frame_stride + c * plane_stride);
+      planes[per * i + c].pitch = (uint32_t)row_pitch;
+      planes[per * i + c].reserved = 0;
+    }
+  return true;
+}
+
 // host-memory "device" allocator: lets CPU-only unit tests build Surfaces (geometry, dispatch, error paths)
 void* host_alloc(size_t n, int, void*) { return std::calloc(n ? n : 1, 1); }
 void host_free(void* p, int, void*) { std::free(p); }
@@ -153,6 +177,9 @@ public:
     for (auto& d : dst) b.push_back(d.get());
     return TASK_EXEC_SUCCESS == task_->RunBatch(a.data(), b.data(), (uint32_t)a.size(), cc.get());
   }
+  // channels_last (every *ToTensor entry): the tensor is [n, dh, dw, 3] in memory (torch.channels_last of a logical [n, 3, dh, dw]): element
+  // (i, c, y, x) at dst + i frame_stride + y row_pitch + (3 x + c) elem; plane_stride is ignored, row_pitch 0 = 3 dw elem, frame_stride 0 = dh row_pitch;
+  // ONE plane per frame / job goes to the Task layer (VPF_TENSOR_NHWC)
   // additive: n surfaces -> a normalised planar tensor [n, 3, dh, dw] of f32 / f16 / bf16 at device address `dst` (vpf_convert_resize_tensor):
   // element (i, c, y, x) at dst + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW).  mean / std are
   // torchvision's (values of [0, 1] pixels), per output channel; scale = 1 / (255 std) and bias = -mean / std are computed in double.
@@ -172,53 +199,33 @@ public:
   }
   bool ExecuteToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
                        const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
-                       uint64_t plane_stride, uint64_t frame_stride) {
-    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+                       uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
     if (src.empty() || !dst) return false;
-    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
-    if (!row_pitch) row_pitch = dw * elem;
-    if (!plane_stride) plane_stride = dh * row_pitch;
-    if (!frame_stride) frame_stride = 3 * plane_stride;
-    if (row_pitch > 0xffffffffull) return false;
     std::vector<Surface*> a;
-    std::vector<vpf_plane> planes(3 * src.size());
-    for (size_t i = 0; i < src.size(); i++) {
-      a.push_back(src[i].get());
-      for (int c = 0; c < 3; c++) {
-        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
-        planes[3 * i + c].pitch = (uint32_t)row_pitch;
-        planes[3 * i + c].reserved = 0;
-      }
-    }
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, src.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    for (size_t i = 0; i < src.size(); i++) a.push_back(src[i].get());
     return TASK_EXEC_SUCCESS == task_->RunTensor(a.data(), (uint32_t)a.size(), planes.data(), norm, cc.get());
   }
   // additive: K rectangles of surfaces -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_resize_tensor_rois):
   // rois[i] = (surface index, x, y, w, h) in luma pixels, any integer offset, inside the surface; tensor layout and mean / std as ExecuteToTensor
   bool ExecuteRoisToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<std::array<int64_t, 5>>& rois, uint64_t dst, uint32_t dtype,
                            const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr,
-                           uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride) {
-    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+                           uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
     if (src.empty() || rois.empty() || !dst) return false;
-    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
-    if (!row_pitch) row_pitch = dw * elem;
-    if (!plane_stride) plane_stride = dh * row_pitch;
-    if (!frame_stride) frame_stride = 3 * plane_stride;
-    if (row_pitch > 0xffffffffull) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, rois.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
     std::vector<Surface*> a;
     for (auto& s : src) a.push_back(s.get());
     std::vector<uint32_t> index(rois.size());
     std::vector<vpf_rect> rects(rois.size());
-    std::vector<vpf_plane> planes(3 * rois.size());
     for (size_t i = 0; i < rois.size(); i++) {
       for (int k = 0; k < 5; k++)
         if (rois[i][k] < 0 || rois[i][k] > 0xffffffffll) return false;
       index[i] = (uint32_t)rois[i][0];
       rects[i] = vpf_rect{(uint32_t)rois[i][1], (uint32_t)rois[i][2], (uint32_t)rois[i][3], (uint32_t)rois[i][4]};
-      for (int c = 0; c < 3; c++) {
-        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
-        planes[3 * i + c].pitch = (uint32_t)row_pitch;
-        planes[3 * i + c].reserved = 0;
-      }
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorRois(a.data(), (uint32_t)a.size(), index.data(), rects.data(), (uint32_t)rois.size(), planes.data(), norm, cc.get());
   }
@@ -228,14 +235,11 @@ public:
   bool ExecuteWarpsToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<int64_t>& index, const std::vector<std::array<float, 6>>& matrices,
                             uint64_t dst, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
                             std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode,
-                            uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride) {
-    const vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+                            uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
     if (src.empty() || index.empty() || index.size() != matrices.size() || !dst) return false;
-    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2, dw = task_dst_w_, dh = task_dst_h_;
-    if (!row_pitch) row_pitch = dw * elem;
-    if (!plane_stride) plane_stride = dh * row_pitch;
-    if (!frame_stride) frame_stride = 3 * plane_stride;
-    if (row_pitch > 0xffffffffull) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, index.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
     vpf_warp_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.border_mode = border_mode;
@@ -247,16 +251,10 @@ public:
     for (auto& s : src) a.push_back(s.get());
     std::vector<uint32_t> idx(index.size());
     std::vector<float> m(6 * index.size());
-    std::vector<vpf_plane> planes(3 * index.size());
     for (size_t i = 0; i < index.size(); i++) {
       if (index[i] < 0 || index[i] > 0xffffffffll) return false;
       idx[i] = (uint32_t)index[i];
       for (int k = 0; k < 6; k++) m[6 * i + k] = matrices[i][k];
-      for (int c = 0; c < 3; c++) {
-        planes[3 * i + c].ptr = (void*)(uintptr_t)(dst + i * frame_stride + c * plane_stride);
-        planes[3 * i + c].pitch = (uint32_t)row_pitch;
-        planes[3 * i + c].reserved = 0;
-      }
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorWarps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
   }
@@ -287,21 +285,11 @@ class PyTensorToSurface {
     d.flags = bgr ? VPF_TENSOR_BGR : 0u;
     return d;
   }
-  // element (i, c, y, x) at src + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW)
-  bool planes_of(uint64_t src, uint32_t dtype, size_t n, uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, std::vector<vpf_plane>& planes) const {
-    const uint64_t elem = dtype == VPF_TENSOR_F32 ? 4 : 2;
-    if (!row_pitch) row_pitch = w_ * elem;
-    if (!plane_stride) plane_stride = h_ * row_pitch;
-    if (!frame_stride) frame_stride = 3 * plane_stride;
-    if (!src || !n || row_pitch > 0xffffffffull) return false;
-    planes.resize(3 * n);
-    for (size_t i = 0; i < n; i++)
-      for (int c = 0; c < 3; c++) {
-        planes[3 * i + c].ptr = (void*)(uintptr_t)(src + i * frame_stride + c * plane_stride);
-        planes[3 * i + c].pitch = (uint32_t)row_pitch;
-        planes[3 * i + c].reserved = 0;
-      }
-    return true;
+  // element (i, c, y, x) at src + i frame_stride + c plane_stride + y row_pitch + x elem (bytes; 0 = contiguous NCHW); channels_last: tensor_planes
+  bool planes_of(uint64_t src, uint32_t dtype, size_t n, uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last,
+                 vpf_tensor_norm& d, std::vector<vpf_plane>& planes) const {
+    if (!src || !n) return false;
+    return tensor_planes(src, dtype, n, w_, h_, row_pitch, plane_stride, frame_stride, channels_last, d, planes);
   }
 
 public:
@@ -315,20 +303,22 @@ public:
   uint32_t Height() const { return h_; }
   // one frame [3, H, W] -> a NON-OWNING alias of the task's single output surface (overwritten by the next Execute); failure = Empty()
   std::shared_ptr<Surface> Execute(uint64_t src, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
-                                   std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch, uint64_t plane_stride) {
-    const vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
+                                   std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch, uint64_t plane_stride,
+                                   bool channels_last) {
+    vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
     std::vector<vpf_plane> planes;
-    if (!planes_of(src, dtype, 1, row_pitch, plane_stride, 0, planes)) return empty_surface(out_fmt_);
+    if (!planes_of(src, dtype, 1, row_pitch, plane_stride, 0, channels_last, d, planes)) return empty_surface(out_fmt_);
+    planes.resize(3);  // (RunTensor takes src[3]; channels_last reads src[0] only)
     Surface* out = task_->RunTensor(planes.data(), d, cc.get());
     return out ? std::shared_ptr<Surface>(out->Clone()) : empty_surface(out_fmt_);
   }
   // frames [len(dst), 3, H, W] -> the caller's surfaces, one dispatch per 32 frames
   bool ExecuteBatch(uint64_t src, const std::vector<std::shared_ptr<Surface>>& dst, uint32_t dtype, const std::vector<double>& mean,
                     const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, uint64_t row_pitch,
-                    uint64_t plane_stride, uint64_t frame_stride) {
-    const vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
+                    uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm d = denorm_of(dtype, mean, std, bgr);
     std::vector<vpf_plane> planes;
-    if (!planes_of(src, dtype, dst.size(), row_pitch, plane_stride, frame_stride, planes)) return false;
+    if (!planes_of(src, dtype, dst.size(), row_pitch, plane_stride, frame_stride, channels_last, d, planes)) return false;
     std::vector<Surface*> b;
     for (auto& s : dst) b.push_back(s.get());
     return TASK_EXEC_SUCCESS == task_->RunTensorBatch(planes.data(), b.data(), (uint32_t)b.size(), d, cc.get());
@@ -763,16 +753,16 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("ExecuteToTensor", &PySurfaceConvertResizer::ExecuteToTensor, py::arg("src"), py::arg("dst"), py::arg("dtype"), py::arg("mean"),
            py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0,
-           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>())
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>())
       .def("ExecuteRoisToTensor", &PySurfaceConvertResizer::ExecuteRoisToTensor, py::arg("surfaces"), py::arg("rois"), py::arg("ptr"), py::arg("dtype"),
            py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
-           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>(),
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
            "K rectangles (surface_index, x, y, w, h) of the surfaces, each resized to the task's destination size and normalised, into a planar tensor "
            "[K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one dispatch per 96 regions")
       .def("ExecuteWarpsToTensor", &PySurfaceConvertResizer::ExecuteWarpsToTensor, py::arg("surfaces"), py::arg("surface_index"), py::arg("matrices"),
            py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
            py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
-           py::arg("frame_stride") = 0, py::call_guard<py::gil_scoped_release>(),
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
            "K affine warps of the surfaces: job i samples surfaces[surface_index[i]] through the inverse 2 x 3 matrix matrices[i] (six floats) into the "
            "task's destination size, normalised, into a planar tensor [K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one "
            "dispatch per 96 regions")
@@ -789,11 +779,11 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            py::arg("width"), py::arg("height"), py::arg("dst_format"), py::arg("context"), py::arg("stream"))
       .def("Format", &PyTensorToSurface::GetFormat)
       .def("Execute", &PyTensorToSurface::Execute, py::arg("src"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
-           py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0, py::keep_alive<0, 1>(),
+           py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0, py::arg("channels_last") = false, py::keep_alive<0, 1>(),
            py::call_guard<py::gil_scoped_release>())
       .def("ExecuteBatch", &PyTensorToSurface::ExecuteBatch, py::arg("src"), py::arg("dst"), py::arg("dtype"), py::arg("mean"), py::arg("std"),
            py::arg("cc_ctx") = nullptr, py::arg("bgr") = false, py::arg("row_pitch") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0,
-           py::call_guard<py::gil_scoped_release>())
+           py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>())
       .def("Stream", &PyTensorToSurface::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("Size", [](const PyTensorToSurface& t) { return py::make_tuple(t.Width(), t.Height()); }, "(width, height) of the frames")
       .def("Device", &PyTensorToSurface::Device, "the GPU the converter was built for; -1: whatever device is current (a foreign context handle)");

@@ -46,6 +46,10 @@ __global__ __launch_bounds__(256) void k_convert_resize(const BA args, const Yuv
   } else if constexpr (DST == FC_TENSOR) {
     const TensorEpi e = epi_of(args);
     for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, e, ch, vec_ok && nv == 4, nv);
+  } else if constexpr (DST == FC_TENSOR_NHWC) {
+    const TensorEpi e = epi_of(args);
+    tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, &o[0][0], 4, 1, e, vec_ok && nv == 4, nv,
+                                    __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
   } else {
     const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -192,6 +196,13 @@ VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, u
         const float u[4] = {(float)sat_rne(v[ch][0]), (float)sat_rne(v[ch][1]), (float)sat_rne(v[ch][2]), (float)sat_rne(v[ch][3])};
         tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec_ok && nv == 4, nv);
       }
+    } else if constexpr (DST == FC_TENSOR_NHWC) {
+      float u[3][4];
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) u[ch][k] = (float)sat_rne(v[ch][k]);
+      tensor_store_nhwc<false, 4>(f.d[0] + (size_t)y * f.dp[0], x0, u, te, vec_ok && nv == 4, nv, wv, lane);
     } else {
       const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
       uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -246,6 +257,8 @@ VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, u
     }
   } else if constexpr (DST == FC_TENSOR) {
     for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, te, ch, vec_ok && nv == 4, nv);
+  } else if constexpr (DST == FC_TENSOR_NHWC) {
+    tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, &o[0][0], 4, 1, te, vec_ok && nv == 4, nv, wv, lane);
   } else {
     const int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -406,6 +419,8 @@ VPF_DEV void convert_resize_band_task(const FrameDesc& f, const Yuv2RgbCoef& c, 
       } else if constexpr (DST == FC_TENSOR) {
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, te, ch, vec_ok && nv == 4, nv);
+      } else if constexpr (DST == FC_TENSOR_NHWC) {
+        tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, &o[0][0], 4, 1, te, vec_ok && nv == 4, nv, wv, lane);
       } else {
         constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
         uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -446,7 +461,7 @@ __global__ __launch_bounds__(256) void k_convert_resize_band(const BA args, cons
 // ------------------------------------------------------------------------------------------
 template <int DST, int SRC>
 VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks, const TensorEpi& te) {
-  __shared__ u32x4 tile[DST == FC_PLANAR ? 1 : DST == FC_TENSOR ? 4 * 128 : 4 * 96];  // 1.5 KiB per wave: 64 lanes x 24 packed bytes (f32 tensor rows: 2 KiB)
+  __shared__ u32x4 tile[DST == FC_PLANAR || DST == FC_TENSOR_NHWC ? 1 : DST == FC_TENSOR ? 4 * 128 : 4 * 96];  // 1.5 KiB per wave: 64 lanes x 24 packed bytes (f32 tensor rows: 2 KiB)
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const uint32_t wt = blockIdx.x * 4 + wv;
   if (wt >= n_tasks) return;
@@ -525,6 +540,14 @@ VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_
         tensor_store8(row, xd, u, te, ch);
       }
     }
+  } else if constexpr (DST == FC_TENSOR_NHWC) {  // eight whole pixels per lane, a 16-B aligned plane and pitch: 96 / 48 contiguous bytes per lane
+    if (!act) return;
+    float u[3][8];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+      for (int i = 0; i < 8; i++) u[ch][i] = ubyte<1>(o[ch][i]);
+    tensor_store_nhwc<true, 8>(f.d[0] + (size_t)y * f.dp[0], xd, u, te, true, 8u, wv, lane);
   } else {
     constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
     uint32_t* t = reinterpret_cast<uint32_t*>(tile + wv * 96);
@@ -773,6 +796,8 @@ VPF_DEV void convert_strip_wg_task(const FrameDesc& f, const Yuv2RgbCoef& c, uin
     } else if constexpr (DST == FC_TENSOR) {
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec_ok && nv == 4, nv);
+    } else if constexpr (DST == FC_TENSOR_NHWC) {
+      tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, o, 1, 3, te, vec_ok && nv == 4, nv, wv, lane);
     } else {
       constexpr int a = (DST == FC_BGR) ? 2 : 0, b = (DST == FC_BGR) ? 0 : 2;
       uint8_t* out = f.d[0] + (size_t)y * f.dp[0] + 3 * (size_t)x0;
@@ -809,15 +834,24 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
     if (small) VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgs>), GRID, BLK, LDS, ST, as, __VA_ARGS__); \
     else VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsL>), GRID, BLK, LDS, ST, a, __VA_ARGS__); } while (0)
   // FC_TENSOR: the same frame table with the epilogue behind it (BatchArgsTE); entries up to the next multiple of 8 are defined (vpf_abi.hip)
-  if (dst_fc == FC_TENSOR && (!te || n > (uint32_t)kMaxBatch)) return hipErrorInvalidValue;
+  // FC_TENSOR_NHWC: the same launches with the other destination class (VPF_TDST): the family is picked exactly as for FC_TENSOR, only the
+  // destination alignment test differs — one plane, whose vector stores are 16-B ones whatever the dtype
+  const bool nhwc = dst_fc == FC_TENSOR_NHWC, tens = dst_fc == FC_TENSOR || nhwc;
+  if (tens && (!te || n > (uint32_t)kMaxBatch)) return hipErrorInvalidValue;
+#define VPF_TDST(M, ...) do { if (nhwc) M(FC_TENSOR_NHWC, __VA_ARGS__); else M(FC_TENSOR, __VA_ARGS__); } while (0)
   const uint32_t ncopy = ((n + 7u) & ~7u) < (uint32_t)kMaxBatch ? ((n + 7u) & ~7u) : (uint32_t)kMaxBatch;
+  // FC_TENSOR_NHWC: where the launch has room, a staging area for the waves' interleaved rows behind the kernel's own dynamic LDS, named in the
+  // epilogue (nhwc_stage_plan, vpf_internal.h); stage_npx = pixels per lane of the kernel about to be launched
+  uint32_t stage_npx = 4;
 #define VPF_LAUNCH_BAT(K, TARGS, GRID, BLK, LDS, ST, ...) do { \
-    if (small) { BatchArgsTE<kSmallBatch> t_; std::memcpy(t_.f, a.f, (ncopy < (uint32_t)kSmallBatch ? ncopy : (uint32_t)kSmallBatch) * sizeof(FrameDesc)); t_.e = *te; \
-                 VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kSmallBatch>>), GRID, BLK, LDS, ST, t_, __VA_ARGS__); } \
-    else { BatchArgsTE<kMaxBatch> t_; std::memcpy(t_.f, a.f, ncopy * sizeof(FrameDesc)); t_.e = *te; \
-           VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kMaxBatch>>), GRID, BLK, LDS, ST, t_, __VA_ARGS__); } } while (0)
+    TensorEpi e_ = *te; \
+    const uint32_t l_ = nhwc ? nhwc_stage_plan(*te, (uint32_t)(LDS), stage_npx, &e_) : (uint32_t)(LDS); \
+    if (small) { BatchArgsTE<kSmallBatch> t_; std::memcpy(t_.f, a.f, (ncopy < (uint32_t)kSmallBatch ? ncopy : (uint32_t)kSmallBatch) * sizeof(FrameDesc)); t_.e = e_; \
+                 VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kSmallBatch>>), GRID, BLK, l_, ST, t_, __VA_ARGS__); } \
+    else { BatchArgsTE<kMaxBatch> t_; std::memcpy(t_.f, a.f, ncopy * sizeof(FrameDesc)); t_.e = e_; \
+           VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kMaxBatch>>), GRID, BLK, l_, ST, t_, __VA_ARGS__); } } while (0)
   // destination alignment the vector stores need: 4 px x element size per lane and plane (1-B elements: the 8-bit classes)
-  const uint32_t dmask = dst_fc == FC_TENSOR ? (te->dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
+  const uint32_t dmask = nhwc ? 15u : dst_fc == FC_TENSOR ? (te->dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
   const int ndp = dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 3 : 1;
   const uint32_t rowb = lds_strip_bytes(1, sw, dw, a.f[0].s[0], a.f[0].sp[0], kFusedRowBytes);
   bool lds_ok = rowb != 0;
@@ -833,24 +867,27 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
   const bool p16_general = p16_v == 9 || p16_v == 40 || p16_v == 49;
   bool p16_a16 = src_fc == FC_P16;  // 16-B aligned source planes and pitches: what the aligned 16-B loads of the half and strip kernels need
   if (src_fc == FC_P16) {
-    if (dst_fc != FC_TENSOR) return hipErrorInvalidValue;
+    if (!tens) return hipErrorInvalidValue;
     for (uint32_t i = 0; i < n; i++)
       for (int k = 0; k < 2; k++) p16_a16 = p16_a16 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 15);
     if (sw == 2 * dw && sh == 2 * dh && sw % 16 == 0 && p16_a16 && !p16_general) {
       bool ok16 = true;
       for (uint32_t i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & 15u);
+        for (int k = 0; k < ndp; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & 15u);
       if (ok16) {
         const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
         dim3 hgrid((tasks + 3) / 4, n);
-        VPF_LAUNCH_BAT(k_convert_half, (FC_TENSOR, FC_P16), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks);
+#define VPF_HALFP(D, S) VPF_LAUNCH_BAT(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
+        stage_npx = 8;
+        VPF_TDST(VPF_HALFP, FC_P16);
+#undef VPF_HALFP
         return hipGetLastError();
       }
     }
   }
   // exact 2x from NV12: the quad-structured kernel (no taps, no gathers); tuning 40 / 9 keep the general kernels
   // (packed rows leave as 16-B stores: 3 * dw must be a multiple of 16)
-  if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
+  if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR || tens ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
     bool ok16 = true;
     for (uint32_t i = 0; i < n; i++)
       for (int k = 0; k < ndp; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (dst_fc == FC_PLANAR ? 7u : 15u));  // (FC_TENSOR: 16-B stores whatever the dtype)
@@ -859,8 +896,9 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
       dim3 hgrid((tasks + 3) / 4, n);
 #define VPF_HALF1(D, S) do { if (n == 1) VPF_LAUNCH((k_convert_half_one<D, S>), hgrid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), sw, dh, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c); \
                             else VPF_LAUNCH_BA(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks); } while (0)
-#define VPF_HALFT(S) VPF_LAUNCH_BAT(k_convert_half, (FC_TENSOR, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
-#define VPF_HALF(S) do { if (dst_fc == FC_RGB) VPF_HALF1(FC_RGB, S); else if (dst_fc == FC_BGR) VPF_HALF1(FC_BGR, S); else if (dst_fc == FC_TENSOR) VPF_HALFT(S); else VPF_HALF1(FC_PLANAR, S); } while (0)
+#define VPF_HALFT(D, S) VPF_LAUNCH_BAT(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
+#define VPF_HALF(S) do { if (dst_fc == FC_RGB) VPF_HALF1(FC_RGB, S); else if (dst_fc == FC_BGR) VPF_HALF1(FC_BGR, S); else if (tens) VPF_TDST(VPF_HALFT, S); else VPF_HALF1(FC_PLANAR, S); } while (0)
+      stage_npx = 8;
       if (src_fc == FC_NV12) VPF_HALF(FC_NV12); else VPF_HALF(FC_YUV420);
 #undef VPF_HALF
 #undef VPF_HALFT
@@ -938,12 +976,14 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
           dim3 wgrid((dw + 255) / 256, (dh + 4 * rw - 1) / (4 * rw), n);
 #define VPF_WG1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip_wg, (S, D, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
 #define VPF_WG(S, D) do { if (rw == 16) VPF_WG1(S, D, 16); else if (rw == 8) VPF_WG1(S, D, 8); else if (rw == 4) VPF_WG1(S, D, 4); else VPF_WG1(S, D, 2); } while (0)
-#define VPF_WGT1(S, RR) VPF_LAUNCH_BAT(k_convert_strip_wg, (S, FC_TENSOR, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
-#define VPF_WGT(S) do { if (rw == 16) VPF_WGT1(S, 16); else if (rw == 8) VPF_WGT1(S, 8); else if (rw == 4) VPF_WGT1(S, 4); else VPF_WGT1(S, 2); } while (0)
-#define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else if (dst_fc == FC_TENSOR) VPF_WGT(S); else VPF_WG(S, FC_PLANAR); } while (0)
+#define VPF_WGT1(D, S, RR) VPF_LAUNCH_BAT(k_convert_strip_wg, (S, D, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
+#define VPF_WGT2(D, S) do { if (rw == 16) VPF_WGT1(D, S, 16); else if (rw == 8) VPF_WGT1(D, S, 8); else if (rw == 4) VPF_WGT1(D, S, 4); else VPF_WGT1(D, S, 2); } while (0)
+#define VPF_WGT(S) VPF_TDST(VPF_WGT2, S)
+#define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else if (tens) VPF_WGT(S); else VPF_WG(S, FC_PLANAR); } while (0)
           if (src_fc == FC_NV12) VPF_WGD(FC_NV12); else if (src_fc == FC_P16) VPF_WGT(FC_P16); else VPF_WGD(FC_YUV420);
 #undef VPF_WGD
 #undef VPF_WGT
+#undef VPF_WGT2
 #undef VPF_WGT1
 #undef VPF_WG
 #undef VPF_WG1
@@ -951,7 +991,7 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
         }
       }
 #ifdef VPF_LAB_FORMS
-      if (r && lds1 <= 64u * 1024u && conv_per_px <= 3.0 && dst_fc != FC_TENSOR) {  // (8-bit destinations only)
+      if (r && lds1 <= 64u * 1024u && conv_per_px <= 3.0 && !tens) {  // (8-bit destinations only)
         dim3 sgrid((dw + 255) / 256, (dh + 4 * r - 1) / (4 * r), n);
 #define VPF_STRIP1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip, (S, D, RR), sgrid, dim3(256), lds1, st, c, sw, sh, dw, dh, scx, scy, vec_ok, (rowbytes / 16) | (srows << 16))
 #define VPF_STRIP(S, D) do { if (r == 8) VPF_STRIP1(S, D, 8); else if (r == 4) VPF_STRIP1(S, D, 4); else VPF_STRIP1(S, D, 2); } while (0)
@@ -967,7 +1007,9 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
   }
   if (src_fc == FC_P16) {  // everything else from 16-bit sources: the gather form
     dim3 ggrid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
-    VPF_LAUNCH_BAT(k_convert_resize, (FC_P16, FC_TENSOR), ggrid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok);
+#define VPF_GATP(D, S) VPF_LAUNCH_BAT(k_convert_resize, (S, D), ggrid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
+    VPF_TDST(VPF_GATP, FC_P16);
+#undef VPF_GATP
     return hipGetLastError();
   }
   const uint32_t lds = 4 * (src_fc == FC_NV12 ? 4 : 6) * rowb;
@@ -981,12 +1023,14 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
       dim3 bgrid((dw + 255) / 256, (dh + 15) / 16, n);
 #define VPF_BAND1(S, D, I) VPF_LAUNCH_BA(k_convert_resize_band, (S, D, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
 #define VPF_BAND(S, D) do { if (rowb <= 1024) VPF_BAND1(S, D, 1); else VPF_BAND1(S, D, 2); } while (0)
-#define VPF_BANDT1(S, I) VPF_LAUNCH_BAT(k_convert_resize_band, (S, FC_TENSOR, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
-#define VPF_BANDT(S) do { if (rowb <= 1024) VPF_BANDT1(S, 1); else VPF_BANDT1(S, 2); } while (0)
-#define VPF_BANDD(S) do { if (dst_fc == FC_RGB) VPF_BAND(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_BAND(S, FC_BGR); else if (dst_fc == FC_TENSOR) VPF_BANDT(S); else VPF_BAND(S, FC_PLANAR); } while (0)
+#define VPF_BANDT1(D, S, I) VPF_LAUNCH_BAT(k_convert_resize_band, (S, D, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
+#define VPF_BANDT2(D, S) do { if (rowb <= 1024) VPF_BANDT1(D, S, 1); else VPF_BANDT1(D, S, 2); } while (0)
+#define VPF_BANDT(S) VPF_TDST(VPF_BANDT2, S)
+#define VPF_BANDD(S) do { if (dst_fc == FC_RGB) VPF_BAND(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_BAND(S, FC_BGR); else if (tens) VPF_BANDT(S); else VPF_BAND(S, FC_PLANAR); } while (0)
       if (src_fc == FC_NV12) VPF_BANDD(FC_NV12); else VPF_BANDD(FC_YUV420);
 #undef VPF_BANDD
 #undef VPF_BANDT
+#undef VPF_BANDT2
 #undef VPF_BANDT1
 #undef VPF_BAND
 #undef VPF_BAND1
@@ -1001,10 +1045,11 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
 #define VPF_GO(S, D) VPF_LAUNCH_BA(k_convert_resize, (S, D), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
 #define VPF_PICK(S, D) do { if (lds_ok) VPF_GOL(S, D); else VPF_GO(S, D); } while (0)
   // FC_TENSOR: the frame-table kernels for one frame too (no scalar-argument entry: the epilogue rides behind the table)
-#define VPF_GOLT(S) do { if (rowb <= 1024) VPF_LAUNCH_BAT(k_convert_resize_lds, (S, FC_TENSOR, 1), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); \
-                         else VPF_LAUNCH_BAT(k_convert_resize_lds, (S, FC_TENSOR, 2), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); } while (0)
-#define VPF_PICKT(S) do { if (lds_ok) VPF_GOLT(S); else VPF_LAUNCH_BAT(k_convert_resize, (S, FC_TENSOR), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok); } while (0)
-  if (dst_fc == FC_TENSOR) {
+#define VPF_GOLT(D, S) do { if (rowb <= 1024) VPF_LAUNCH_BAT(k_convert_resize_lds, (S, D, 1), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); \
+                            else VPF_LAUNCH_BAT(k_convert_resize_lds, (S, D, 2), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); } while (0)
+#define VPF_GATT(D, S) VPF_LAUNCH_BAT(k_convert_resize, (S, D), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
+#define VPF_PICKT(S) do { if (lds_ok) VPF_TDST(VPF_GOLT, S); else VPF_TDST(VPF_GATT, S); } while (0)
+  if (tens) {
     if (src_fc == FC_NV12) VPF_PICKT(FC_NV12); else if (src_fc == FC_YUV420) VPF_PICKT(FC_YUV420); else return hipErrorInvalidValue;
   } else if (src_fc == FC_NV12) {
     if (dst_fc == FC_RGB) VPF_PICK(FC_NV12, FC_RGB); else if (dst_fc == FC_BGR) VPF_PICK(FC_NV12, FC_BGR); else VPF_PICK(FC_NV12, FC_PLANAR);
@@ -1014,11 +1059,13 @@ hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Y
     return hipErrorInvalidValue;
   }
 #undef VPF_PICKT
+#undef VPF_GATT
 #undef VPF_GOLT
 #undef VPF_PICK
 #undef VPF_GO
 #undef VPF_GOL
 #undef VPF_GOL1
+#undef VPF_TDST
 #undef VPF_LAUNCH_BAT
 #undef VPF_LAUNCH_BA
 #undef VPF_UNPAREN

@@ -77,8 +77,18 @@ __host__ __device__ __forceinline__ WarpStrip warp_strip(const WarpWin& w) {
 VPF_DEV bool warp_rep(const TensorEpi& e) { return (e.pad >> 24) == VPF_WARP_REPLICATE; }
 VPF_DEV float warp_border(const TensorEpi& e, int ch) { return (float)((e.pad >> (8 * ch)) & 0xffu); }
 
+// the lane's four pixels u[ch][k] through the tensor epilogue.  FC_TENSOR_NHWC: per-lane vector stores — a tile row is 8 lanes, 384 B of f32, so a
+// store instruction of a wave covers eight rows' runs whatever the form; nothing to stage
+template <int DST>
+VPF_DEV void warp_store4(const FrameDesc& f, uint32_t x0, uint32_t y, const float (&u)[3][4], const TensorEpi& te, bool vec, uint32_t nv) {
+  if constexpr (DST == FC_TENSOR_NHWC) {
+    tensor_store_nhwc<false, 4>(f.d[0] + (size_t)y * f.dp[0], x0, u, te, vec, nv, kNoStage, 0u);
+  } else {
+    for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+  }
+}
 // four pixels of a lane through the per-tap form, stored through the tensor epilogue
-template <int SRC>
+template <int SRC, int DST = FC_TENSOR>
 VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorEpi& te, uint32_t W, uint32_t H, uint32_t dw, uint32_t dmask, uint32_t x0,
                           uint32_t y) {
   const FrameDesc& f = J.f;
@@ -107,8 +117,8 @@ VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorE
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
   bool vec = nv == 4;
 #pragma unroll
-  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
-  for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  warp_store4<DST>(f, x0, y, u, te, vec, nv);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -116,70 +126,18 @@ VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorE
 // tile whose strip would not fit the LDS it was given — never: the launcher's bound covers every tile (warp_need) — takes the per-tap
 // form instead of writing from a short strip.
 // ------------------------------------------------------------------------------------------
+// (DST = FC_TENSOR: three planes per job, k_warp_strip; FC_TENSOR_NHWC: one interleaved plane, k_warp_strip_nhwc)
 template <int SRC>
 __global__ __launch_bounds__(256) void k_warp_strip(const WarpArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
                                                     uint32_t dmask, uint32_t lds_bytes) {
-  const WarpDesc& J = args.j[blockIdx.z];
-  const FrameDesc& f = J.f;
-  const TensorEpi te = args.e;
-  const bool rep = warp_rep(te);
-  const uint32_t tid = threadIdx.x;
-  const uint32_t xs = blockIdx.x * kWarpTileW, ys = blockIdx.y * kWarpTileH;  // the grid covers the destination exactly: xs < dw, ys < dh
-  const uint32_t xe = (xs + kWarpTileW - 1 < dw - 1) ? xs + kWarpTileW - 1 : dw - 1, ye = (ys + kWarpTileH - 1 < dh - 1) ? ys + kWarpTileH - 1 : dh - 1;
-  const uint32_t x0 = xs + (tid % kWarpLanesX) * 4, y = ys + tid / kWarpLanesX;
-  const bool mine = x0 < dw && y < dh;
-  WarpWin w = warp_window(J.m, xs, xe, ys, ye, rep, W, H);
-  w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
-  w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
-  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < 3; ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
-  if (w.empty) {  // (CONSTANT only: a clamped coordinate is always in range)
-    if (!mine) return;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-      const float b = warp_border(te, ch), u[4] = {b, b, b, b};
-      tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec, nv);
-    }
-    return;
-  }
-  const WarpStrip S = warp_strip(w);
-  if (S.bytes > lds_bytes) {
-    if (mine) warp_gather4<SRC>(J, c, te, W, H, dw, dmask, x0, y);
-    return;
-  }
-  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
-  {  // the names VPF_STRIP_FILL_WINDOW takes from its scope
-    const uint32_t base_px = S.base_px, R_lo = w.y_lo, R_hi = w.y_hi, c_lo = R_lo >> 1, ng = S.ng, units = ((R_hi >> 1) - c_lo + 1) * ng, rowbytes = S.rowbytes;
-    VPF_STRIP_FILL_WINDOW
-  }
-  __syncthreads();
-  if (!mine) return;
-  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
-  const float xlf = (float)w.x_lo, xhf = (float)w.x_hi, ylf = (float)w.y_lo, yhf = (float)w.y_hi;
-  float u[3][4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const WarpXY s = warp_xy(J.m, (x0 + k < dw) ? x0 + k : dw - 1, y, rep, wmax, hmax);
-    const bool in = s.sx >= 0.f && s.sx <= wmax && s.sy >= 0.f && s.sy <= hmax;
-    // an in-range coordinate lies inside the window, so pulling it to the window leaves it unchanged; every other one reads some pixel of
-    // the strip and is replaced by the border.  x1 = min(x0 + 1, x_hi) is min(x0 + 1, W - 1) for an in-range pixel (x_hi = min(floor + 1, W - 1)).
-    const float cx = __builtin_amdgcn_fmed3f(s.sx, xlf, xhf), cy = __builtin_amdgcn_fmed3f(s.sy, ylf, yhf);
-    const uint32_t xa = (uint32_t)(int)cx, ya = (uint32_t)(int)cy;
-    const uint32_t xb = xa + 1 < w.x_hi ? xa + 1 : w.x_hi, yb = ya + 1 < w.y_hi ? ya + 1 : w.y_hi;
-    const float fx = cx - (float)xa, fy = cy - (float)ya;
-    const uint8_t* const ra = strip + (ya - w.y_lo) * S.rowbytes, * const rb = strip + (yb - w.y_lo) * S.rowbytes;
-    const uint32_t oa = 4 * (xa - S.base_px), ob = 4 * (xb - S.base_px);
-    const uint32_t q00 = *reinterpret_cast<const uint32_t*>(ra + oa), q01 = *reinterpret_cast<const uint32_t*>(ra + ob);
-    const uint32_t q10 = *reinterpret_cast<const uint32_t*>(rb + oa), q11 = *reinterpret_cast<const uint32_t*>(rb + ob);
-    const float v[3] = {__builtin_truncf(bilerp(ubyte<0>(q00), ubyte<0>(q01), ubyte<0>(q10), ubyte<0>(q11), fx, fy)),
-                        __builtin_truncf(bilerp(ubyte<1>(q00), ubyte<1>(q01), ubyte<1>(q10), ubyte<1>(q11), fx, fy)),
-                        __builtin_truncf(bilerp(ubyte<2>(q00), ubyte<2>(q01), ubyte<2>(q10), ubyte<2>(q11), fx, fy))};
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) u[ch][k] = in ? v[ch] : warp_border(te, ch);
-  }
-  for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+  constexpr int DST = FC_TENSOR;
+#include "k_convert_warp_strip_body.h"
+}
+template <int SRC>
+__global__ __launch_bounds__(256) void k_warp_strip_nhwc(const WarpArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
+                                                    uint32_t dmask, uint32_t lds_bytes) {
+  constexpr int DST = FC_TENSOR_NHWC;  // one interleaved plane per job
+#include "k_convert_warp_strip_body.h"
 }
 
 // ------------------------------------------------------------------------------------------
@@ -191,6 +149,13 @@ __global__ __launch_bounds__(256) void k_warp_gather(const WarpArgs args, const 
   const uint32_t x0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, y = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
   if (x0 >= dw || y >= dh) return;
   warp_gather4<SRC>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
+}
+template <int SRC>
+__global__ __launch_bounds__(256) void k_warp_gather_nhwc(const WarpArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
+                                                          uint32_t dmask) {
+  const uint32_t x0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, y = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
+  if (x0 >= dw || y >= dh) return;
+  warp_gather4<SRC, FC_TENSOR_NHWC>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -229,9 +194,9 @@ static WarpNeed warp_need(const WarpDesc& j, uint32_t W, uint32_t H, uint32_t dw
 }
 
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
-                               uint32_t dh, const TensorEpi& te) {
+                               uint32_t dh, const TensorEpi& te, bool nhwc) {
   if (!n || n > (uint32_t)kWarpBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
-  const uint32_t dmask = te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need
+  const uint32_t dmask = nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B)
   const int tune = tuning(VPF_TUNE_NV12_RGB_VARIANT);
   const bool all_gather = tune == 9;
   WarpArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
@@ -250,16 +215,18 @@ hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c,
   }
   const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
   if (ns) {
-    if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_strip<FC_NV12>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
-    else if (src_fc == FC_P16) VPF_LAUNCH((k_warp_strip<FC_P16>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
-    else VPF_LAUNCH((k_warp_strip<FC_YUV420>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds);
+#define VPF_WARPS(S) do { if (nhwc) VPF_LAUNCH((k_warp_strip_nhwc<S>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds); \
+                          else VPF_LAUNCH((k_warp_strip<S>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds); } while (0)
+    if (src_fc == FC_NV12) VPF_WARPS(FC_NV12); else if (src_fc == FC_P16) VPF_WARPS(FC_P16); else VPF_WARPS(FC_YUV420);
+#undef VPF_WARPS
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (ngat) {
-    if (src_fc == FC_NV12) VPF_LAUNCH((k_warp_gather<FC_NV12>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
-    else if (src_fc == FC_P16) VPF_LAUNCH((k_warp_gather<FC_P16>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
-    else VPF_LAUNCH((k_warp_gather<FC_YUV420>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask);
+#define VPF_WARPG(S) do { if (nhwc) VPF_LAUNCH((k_warp_gather_nhwc<S>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask); \
+                          else VPF_LAUNCH((k_warp_gather<S>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask); } while (0)
+    if (src_fc == FC_NV12) VPF_WARPG(FC_NV12); else if (src_fc == FC_P16) VPF_WARPG(FC_P16); else VPF_WARPG(FC_YUV420);
+#undef VPF_WARPG
     return hipGetLastError();
   }
   return hipSuccess;

@@ -99,6 +99,122 @@ VPF_DEV void tensor_store4_trunc(uint8_t* row, uint32_t x0, const float* o, int 
   tensor_store4<NT>(row, x0, u, e, ch, vec, nv);
 }
 
+// ------------------------------------------------------------------------------------------
+// The channels-last destination (FC_TENSOR_NHWC, VPF_TENSOR_NHWC): the same values in ONE interleaved plane, element (y, x, c) at row y + (3 x + c)
+// elements.  A lane holds all three channels of its NPX pixels (4; 8 in k_convert_half), so its 3 NPX elements are one contiguous run: 48 / 96 B of
+// f32, 24 / 48 B of f16 / bf16.  The same fma and the same conversions as tensor_store4 / tensor_store8, then one of three store forms:
+//   element stores     unaligned planes and row tails (nv < NPX), as tensor_store4 does;
+//   per-lane vectors   16-B stores (12-B ones for the 24 B of four 16-bit pixels): every store instruction of a wave writes every third 16 B of its span;
+//   dense              the wave's run (64 lanes x 3 NPX elements, one row) goes through wave-private LDS (wave_lds_sync, no workgroup barrier) and
+//                      leaves as store instructions that each cover 1 KiB of the row without holes.  The LAUNCHER decides (nhwc_stage_plan,
+//                      vpf_internal.h): it appends the staging area to the launch's dynamic LDS and names its place in TensorEpi::dtype; without
+//                      one the kernel stores per lane.  Measured: dense wins for f32 in every family and for the half kernel's
+//                      16-bit rows; four 16-bit pixels per lane leave faster as two 12-B stores.
+// B G R order: the host swapped scale / bias (kernel channel order) and set kEpiSwapRB; kernel channel ch goes to slot 2 - ch (wave-uniform).
+// ------------------------------------------------------------------------------------------
+typedef uint32_t u32x3_a8 __attribute__((ext_vector_type(3), aligned(8)));
+// `row` = byte address of row y of the plane at column 0; u[ch][k] = the 8-bit value of kernel channel ch of column x0 + k (nv of the NPX columns
+// valid); `vec`: nv == NPX and a 16-B aligned plane and pitch; `wv`, `lane`: the wave's index in its workgroup and the lane's place in the wave's run
+// of the row (x0 = first column of the run + NPX lane); wv = kNoStage: the lanes of a wave are not one run of a row (the warp kernels' tiles).
+// Every lane of the wave that is still active calls this together, and the active lanes are lanes 0 .. nact - 1 (lanes right of the row's end
+// have left: every family drops them before its epilogue).
+constexpr uint32_t kNoStage = ~0u;
+template <bool NT, int NPX>
+VPF_DEV void tensor_store_nhwc(uint8_t* row, uint32_t x0, const float (&u)[3][NPX], const TensorEpi& e, bool vec, uint32_t nv, uint32_t wv, uint32_t lane) {
+  const bool swap = (e.dtype & kEpiSwapRB) != 0;
+  const uint32_t dtype = e.dtype & kEpiDtypeMask, stage_q = (e.dtype & kEpiStageMask) >> kEpiStageShift;
+  float v[NPX][3];  // slot order
+#pragma unroll
+  for (int k = 0; k < NPX; k++) {
+    const float a = __builtin_fmaf(u[0][k], e.scale[0], e.bias[0]), b = __builtin_fmaf(u[2][k], e.scale[2], e.bias[2]);
+    v[k][0] = swap ? b : a;
+    v[k][1] = __builtin_fmaf(u[1][k], e.scale[1], e.bias[1]);
+    v[k][2] = swap ? a : b;
+  }
+  constexpr int ND = 3 * NPX;  // dwords of a lane's run: ND of f32, ND / 2 of f16 / bf16
+  uint32_t d[ND];
+  const bool f32 = dtype == VPF_TENSOR_F32;
+  if (f32) {
+#pragma unroll
+    for (int i = 0; i < ND; i++) d[i] = __float_as_uint(v[i / 3][i % 3]);
+  } else {
+    uint32_t h[ND];
+    if (dtype == VPF_TENSOR_F16) {
+#pragma unroll
+      for (int i = 0; i < ND; i++) h[i] = __builtin_bit_cast(uint16_t, (_Float16)v[i / 3][i % 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < ND; i++) h[i] = __builtin_bit_cast(uint16_t, (__bf16)v[i / 3][i % 3]);
+    }
+#pragma unroll
+    for (int i = 0; i < ND / 2; i++) d[i] = h[2 * i] | h[2 * i + 1] << 16;
+#pragma unroll
+    for (int i = ND / 2; i < ND; i++) d[i] = 0u;
+  }
+  const uint32_t elem = f32 ? 4u : 2u;
+  uint8_t* const p = row + (size_t)x0 * 3u * elem;
+  // dense: every lane of the wave still here takes the vector path (an active lane has all its NPX columns inside the row then)
+  if (wv != kNoStage && stage_q != 0 && __builtin_amdgcn_ballot_w64(!vec) == 0) {
+    const uint32_t nd = f32 ? (uint32_t)ND : (uint32_t)(ND / 2);  // dwords per lane
+    u32x4* const stage = dyn_strip + (stage_q - 1) + wv * (16 * nd);  // 64 lanes x nd dwords per wave, behind the kernel's own dynamic LDS
+    uint32_t* const sd = reinterpret_cast<uint32_t*>(stage);
+    if (f32) {
+#pragma unroll
+      for (int j = 0; j < ND / 4; j++) stage[(ND / 4) * lane + j] = u32x4{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < ND / 4; j++) *reinterpret_cast<u32x2*>(sd + (ND / 2) * lane + 2 * j) = u32x2{d[2 * j], d[2 * j + 1]};
+    }
+    wave_lds_sync();
+    // The nact active lanes wrote the run's first `total` = nact nd dwords (a multiple of 2), all inside the row; the same lanes store them: store
+    // k of lane l takes the 16-B unit k nact + l, so every store instruction covers nact x 16 contiguous bytes (1 KiB of a full wave).  Dword
+    // 4 idx of the run is 16-B aligned in memory: the run starts at a multiple of 64 NPX columns of a 16-B aligned row.
+    const uint32_t nact = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true)), total = nact * nd;
+    uint8_t* const wrow = row + (size_t)(x0 - (uint32_t)NPX * lane) * 3u * elem;
+#pragma unroll
+    for (int k = 0; k < ND / 4; k++) {
+      const uint32_t idx = nact * k + lane;
+      if (4 * idx + 4 <= total) stg<NT, u32x4>(wrow + 16 * (size_t)idx, stage[idx]);
+      else if (4 * idx + 2 <= total) stg<NT, u32x2>(wrow + 16 * (size_t)idx, *reinterpret_cast<const u32x2*>(sd + 4 * idx));
+    }
+    wave_lds_sync();  // these LDS reads are done before the wave's next row overwrites the buffer
+    return;
+  }
+  if (vec) {
+    if (f32) {
+#pragma unroll
+      for (int j = 0; j < ND / 4; j++) stg<NT, u32x4>(p + 16 * j, u32x4{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]});
+    } else if constexpr (NPX % 8 == 0) {
+#pragma unroll
+      for (int j = 0; j < ND / 8; j++) stg<NT, u32x4>(p + 16 * j, u32x4{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]});
+    } else {  // 24 B at a multiple of 8: two 12-B stores
+#pragma unroll
+      for (int j = 0; j < ND / 6; j++) stg<NT, u32x3_a8>(p + 12 * j, u32x3_a8{d[3 * j], d[3 * j + 1], d[3 * j + 2]});
+    }
+    return;
+  }
+  if (f32) {
+#pragma unroll
+    for (int i = 0; i < ND; i++)
+      if ((uint32_t)i < 3 * nv) reinterpret_cast<uint32_t*>(p)[i] = d[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < ND; i++)
+      if ((uint32_t)i < 3 * nv) reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)(i & 1 ? d[i >> 1] >> 16 : d[i >> 1]);
+  }
+}
+// the FC_PLANAR store sections' values o[] (+ 0.5 added: truncation gives the byte): channel ch of pixel k at o[ch * cs + k * ps]
+template <bool NT>
+VPF_DEV void tensor_store4_nhwc_trunc(uint8_t* row, uint32_t x0, const float* o, int cs, int ps, const TensorEpi& e, bool vec, uint32_t nv, uint32_t wv,
+                                      uint32_t lane) {
+  float u[3][4];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) u[ch][k] = __builtin_truncf(o[ch * cs + k * ps]);
+  tensor_store_nhwc<NT, 4>(row, x0, u, e, vec, nv, wv, lane);
+}
+
 // One conversion unit of the workgroup-shared strips (k_convert_strip_wg, k_roi_strip): 8 pixels x 2 luma rows under one chroma row -> four-byte
 // R G B x pixels in LDS.  (FC_P16 sources narrow their samples at the load and come here as FC_NV12.)
 template <int SRC>

@@ -505,7 +505,8 @@ TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, 
     if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(s, io[i].src);
-    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
+    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_resize_tensor_batch(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
@@ -531,7 +532,8 @@ TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint3
     if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(frames[frame_index[i]], io[i].src);
-    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
+    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
     io[i].rect = rects[i];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
@@ -559,7 +561,8 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
     if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(frames[frame_index[i]], io[i].src);
-    for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
+    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
     for (int k = 0; k < 6; k++) io[i].m[k] = matrices[6 * i + k];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
@@ -628,7 +631,8 @@ TaskExecStatus TensorToSurface::RunTensorBatch(const vpf_plane* src, Surface* co
     Surface* d = outs[i];
     if (!d || d->Empty() || d->PixelFormat() != pImpl->out_fmt || d->Width() != pImpl->w || d->Height() != pImpl->h) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
-    for (int k = 0; k < 3; k++) io[i].src[k] = src[3 * i + k];
+    if (denorm.flags & VPF_TENSOR_NHWC) io[i].src[0] = src[i];  // one interleaved plane per frame
+    else for (int k = 0; k < 3; k++) io[i].src[k] = src[3 * i + k];
     fill_planes(d, io[i].dst);
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);

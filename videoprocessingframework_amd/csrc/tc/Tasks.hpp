@@ -53,7 +53,8 @@ public:
   TaskExecStatus Run() final;  // asynchronous like ConvertSurface; null output = failure
   TaskExecStatus RunBatch(Surface* const* inputs, Surface* const* outputs, uint32_t n, const ColorspaceConversionContext* ctx);
   // n same-shape surfaces -> n frames of a normalised planar tensor (vpf_convert_resize_tensor_batch): dst holds 3 n planes, frame i's
-  // channel planes at dst[3 i .. 3 i + 2] in output channel order; the same colour-context rules as Run / RunBatch
+  // channel planes at dst[3 i .. 3 i + 2] in output channel order; the same colour-context rules as Run / RunBatch.  With VPF_TENSOR_NHWC in
+  // norm.flags (here, in RunTensorRois and in RunTensorWarps) dst holds n planes: dst[i] is the one interleaved plane of frame / job i
   TaskExecStatus RunTensor(Surface* const* inputs, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
   // n rectangles of surfaces -> n frames of a normalised planar tensor (vpf_convert_resize_tensor_rois): job i takes rects[i] (luma pixels, any
   // integer offset, inside the surface) of frames[frame_index[i]] and writes dst[3 i .. 3 i + 2]; every surface has the task's source format
@@ -86,7 +87,8 @@ public:
   // one frame (src[0..2] = its channel planes in input order) into the task's own surface, asynchronous on the task's stream;
   // nullptr = failure (refused colour context, refused planes), like a null output of ConvertSurface::Run
   Surface* RunTensor(const vpf_plane src[3], const vpf_tensor_norm& denorm, const ColorspaceConversionContext* ctx);
-  // n frames (src holds 3 n planes, frame i's at src[3 i .. 3 i + 2]) into n caller-owned surfaces of the task's size and format
+  // n frames (src holds 3 n planes, frame i's at src[3 i .. 3 i + 2]; with VPF_TENSOR_NHWC in denorm.flags n planes, frame i's interleaved
+  // plane at src[i]; RunTensor then reads src[0] only) into n caller-owned surfaces of the task's size and format
   TaskExecStatus RunTensorBatch(const vpf_plane* src, Surface* const* outputs, uint32_t n, const vpf_tensor_norm& denorm,
                                 const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on

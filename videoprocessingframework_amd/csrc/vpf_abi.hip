@@ -459,23 +459,38 @@ vpf_status vpf_convert_resize(const vpf_exec* exec, int sf, int df, int cs, int 
   return vpf_convert_resize_batch(exec, sf, df, cs, cr, ss, ds, 1, &io);
 }
 
+// The planes of a tensor frame or job: three of `width` elements per row, or with VPF_TENSOR_NHWC the ONE interleaved plane p[0] of 3 x width
+// elements per row (p[1], p[2] are not looked at).  Pointers and pitches are multiples of the element size.
+static bool tensor_planes_ok(const vpf_plane* p, bool nhwc, uint32_t width, uint32_t elem, bool reserved_zero = false) {
+  for (int k = 0; k < (nhwc ? 1 : 3); k++) {
+    if (!p[k].ptr || (reserved_zero && p[k].reserved) || (uint64_t)p[k].pitch < (uint64_t)width * elem * (nhwc ? 3u : 1u) ||
+        (((uintptr_t)p[k].ptr | p[k].pitch) & (elem - 1)))
+      return false;
+  }
+  return true;
+}
+// the planes the kernels take: kernel channel k (R G B) -> plane k, B G R order swaps planes 0 and 2; NHWC: the one plane (the kernel swaps slots)
+static int tensor_planes(const vpf_plane* p, bool nhwc, bool bgr, vpf_plane out[3]) {
+  if (nhwc) { out[0] = p[0]; return 1; }
+  for (int k = 0; k < 3; k++) out[k] = p[bgr ? 2 - k : k];
+  return 3;
+}
+
 // The planar-tensor form of the fused path (include/vpf_hip.h): the RGB_PLANAR bytes through one fp32 fma per channel, stored as f32 / f16 / bf16.
 vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
                                            const vpf_frame_io* frames, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_batch");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
   for (int c = 0; c < 3; c++)
     if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
   if (!exec || !frames || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
   for (uint32_t i = 0; i < n; i++) {
     if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
-    for (int k = 0; k < 3; k++) {
-      const vpf_plane& p = frames[i].dst[k];
-      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
-    }
+    if (!tensor_planes_ok(frames[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
@@ -486,18 +501,18 @@ vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs,
   TensorEpi te;
   std::memset(&te, 0, sizeof(te));
   for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype;
+  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
   const uint32_t per = frames_per_dispatch(frame_bytes(sf, ss) + 3ull * ds.width * ds.height * elem, true);  // the tensor's real bytes: 4x the 8-bit planes for f32
   for (uint32_t base = 0; base < n; base += per) {
     const uint32_t m = (n - base < per) ? n - base : per;
     BatchArgsL a;
     for (uint32_t i = 0; i < m; i++) {
       vpf_plane d[3];
-      for (int k = 0; k < 3; k++) d[k] = frames[base + i].dst[bgr ? 2 - k : k];
-      fill_desc(a.f[i], frames[base + i].src, num_planes(sf), d, 3);
+      const int nd = tensor_planes(frames[base + i].dst, nhwc, bgr, d);
+      fill_desc(a.f[i], frames[base + i].src, num_planes(sf), d, nd);
     }
     for (uint32_t i = m; i < ((m + 7u) & ~7u); i++) a.f[i] = a.f[0];
-    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), FC_TENSOR, c, ss.width, ss.height, m, a,
+    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), nhwc ? FC_TENSOR_NHWC : FC_TENSOR, c, ss.width, ss.height, m, a,
                                                ds.width, ds.height, &te);
     if (e != hipSuccess) return status_of(e);
   }
@@ -522,19 +537,17 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
   const Mark mark("vpf_convert_resize_tensor_rois");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
   for (int c = 0; c < 3; c++)
     if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
   if (!exec || !rois || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
   for (uint32_t i = 0; i < n; i++) {
     const vpf_rect& r = rois[i].rect;
     if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
     if (!tensor_src_ok(sf, ss.width, rois[i].src)) return VPF_ERR_BAD_ARG;
-    for (int k = 0; k < 3; k++) {
-      const vpf_plane& p = rois[i].dst[k];
-      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
-    }
+    if (!tensor_planes_ok(rois[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
@@ -545,20 +558,20 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
   TensorEpi te;
   std::memset(&te, 0, sizeof(te));
   for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype;
+  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
   RoiDesc jobs[kRoiBatch];
   for (uint32_t base = 0; base < n; base += kRoiBatch) {
     const uint32_t m = (n - base < (uint32_t)kRoiBatch) ? n - base : (uint32_t)kRoiBatch;
     for (uint32_t i = 0; i < m; i++) {
       const vpf_roi_io& io = rois[base + i];
       vpf_plane d[3];
-      for (int k = 0; k < 3; k++) d[k] = io.dst[bgr ? 2 - k : k];
+      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
       RoiDesc& j = jobs[i];
-      fill_desc(j.f, io.src, num_planes(sf), d, 3);
+      fill_desc(j.f, io.src, num_planes(sf), d, nd);
       j.x = io.rect.x; j.y = io.rect.y; j.w = io.rect.width; j.h = io.rect.height;
       j.scx = (float)j.w / (float)ds.width; j.scy = (float)j.h / (float)ds.height;
     }
-    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te);
+    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te, nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -571,23 +584,21 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
   const Mark mark("vpf_convert_warp_tensor");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
   if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
   if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
   for (int c = 0; c < 3; c++)
     if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
   if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
   for (uint32_t i = 0; i < n; i++) {
     for (int k = 0; k < 6; k++)
       if (!(std::fabs(jobs[i].m[k]) <= 16777216.0f)) return VPF_ERR_BAD_ARG;  // NaN and infinities fail the comparison too
     if (!tensor_src_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
     for (int k = 0; k < num_planes(sf); k++)
       if (jobs[i].src[k].reserved) return VPF_ERR_BAD_ARG;
-    for (int k = 0; k < 3; k++) {
-      const vpf_plane& p = jobs[i].dst[k];
-      if (!p.ptr || p.reserved || (uint64_t)p.pitch < (uint64_t)ds.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
-    }
+    if (!tensor_planes_ok(jobs[i].dst, nhwc, ds.width, elem, true)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
@@ -598,7 +609,7 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
   TensorEpi te;
   std::memset(&te, 0, sizeof(te));
   for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype;
+  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
   if (opts) {
     for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->border[bgr ? 2 - k : k] << (8 * k);
     te.pad |= opts->border_mode << 24;
@@ -609,12 +620,12 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
     for (uint32_t i = 0; i < m; i++) {
       const vpf_warp_io& io = jobs[base + i];
       vpf_plane d[3];
-      for (int k = 0; k < 3; k++) d[k] = io.dst[bgr ? 2 - k : k];
-      fill_desc(table[i].f, io.src, num_planes(sf), d, 3);
+      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
+      fill_desc(table[i].f, io.src, num_planes(sf), d, nd);
       for (int k = 0; k < 6; k++) table[i].m[k] = io.m[k];
     }
     const hipError_t e = launch_convert_warp(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
-                                             ds.height, te);
+                                             ds.height, te, nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -630,16 +641,14 @@ vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int df, int cs, int cr
   const Mark mark("vpf_tensor_convert_batch");
   if (!vpf_tensor_convert_supported(df, cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!denorm) return VPF_ERR_BAD_ARG;
-  if (denorm->dtype > VPF_TENSOR_BF16 || (denorm->flags & ~VPF_TENSOR_BGR)) return VPF_ERR_UNSUPPORTED;
+  if (denorm->dtype > VPF_TENSOR_BF16 || (denorm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
   for (int c = 0; c < 3; c++)
     if (!std::isfinite(denorm->scale[c]) || !std::isfinite(denorm->bias[c])) return VPF_ERR_BAD_ARG;
   if (!exec || !frames || !n || !dims_ok(size)) return VPF_ERR_BAD_ARG;
   const uint32_t elem = denorm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (denorm->flags & VPF_TENSOR_NHWC) != 0;
   for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < 3; k++) {
-      const vpf_plane& p = frames[i].src[k];
-      if (!p.ptr || (uint64_t)p.pitch < (uint64_t)size.width * elem || (((uintptr_t)p.ptr | p.pitch) & (elem - 1))) return VPF_ERR_BAD_ARG;
-    }
+    if (!tensor_planes_ok(frames[i].src, nhwc, size.width, elem)) return VPF_ERR_BAD_ARG;
     if (!planes_ok(df, size.width, frames[i].dst)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
@@ -652,17 +661,18 @@ vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int df, int cs, int cr
   std::memset(&tp, 0, sizeof(tp));
   for (int k = 0; k < 3; k++) { tp.scale[k] = denorm->scale[bgr ? 2 - k : k]; tp.bias[k] = denorm->bias[bgr ? 2 - k : k]; }
   tp.dtype = denorm->dtype;
+  tp.pad = nhwc && bgr ? 1u : 0u;
   const int nd = num_planes(df);
   for (uint32_t base = 0; base < n; base += kSmallBatch) {
     const uint32_t m = (n - base < (uint32_t)kSmallBatch) ? n - base : (uint32_t)kSmallBatch;
     BatchArgs a;
     for (uint32_t i = 0; i < m; i++) {
       vpf_plane s[3];
-      for (int k = 0; k < 3; k++) s[k] = frames[base + i].src[bgr ? 2 - k : k];
-      fill_desc(a.f[i], s, 3, frames[base + i].dst, nd);
+      const int ns = tensor_planes(frames[base + i].src, nhwc, bgr, s);
+      fill_desc(a.f[i], s, ns, frames[base + i].dst, nd);
     }
     for (uint32_t i = m; i < (uint32_t)kSmallBatch; i++) a.f[i] = a.f[0];
-    const hipError_t e = launch_tensor_to_yuv(static_cast<hipStream_t>(exec->stream), df == VPF_FMT_NV12, rc, tp, size.width, size.height, m, a);
+    const hipError_t e = launch_tensor_to_yuv(static_cast<hipStream_t>(exec->stream), df == VPF_FMT_NV12, rc, tp, size.width, size.height, m, a, nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;

@@ -75,14 +75,41 @@ enum FmtClass : int {
   FC_TENSOR = 6,  // three full planes of f32 / f16 / bf16: the FC_PLANAR bytes through one fma each (vpf_convert_resize_tensor)
   FC_P16 = 7,     // P10 / P12: Y + interleaved UV of 16-bit MSB-aligned samples, 4:2:0 — a SOURCE class of the fused tensor entries only: every
                   // sample is narrowed to 8 bits at the load (p16_to_8, vpf_device.h), from there the code is FC_NV12's
+  FC_TENSOR_NHWC = 8,  // FC_TENSOR's elements in ONE interleaved plane per frame (VPF_TENSOR_NHWC): element (y, x, c) at d[0] + y dp[0] + (3 x + c) elem
 };
 // The epilogue of an FC_TENSOR launch: out[c] = to_dtype(fma(u8[c], scale[c], bias[c])).  It travels behind the frame table (BatchArgsTE), so
 // the 8-bit instantiations keep their kernarg layout.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
+// FC_TENSOR_NHWC has one plane, so B G R order cannot be a swap of planes there: the host still swaps the parameters (scale / bias / border stay
+// in kernel channel order) and sets kEpiSwapRB in `dtype`; the epilogue then puts kernel channel ch into slot 2 - ch (wave-uniform).  FC_TENSOR
+// launches never carry the bit: their kernels compare `dtype` as a whole.
+constexpr uint32_t kEpiSwapRB = 0x80000000u;
+// ... and where the launch has room, the wave's interleaved row leaves through LDS as dense stores (k_fused_common.h): bits 8 .. 20 of `dtype` = 1 +
+// the offset of the staging area in the launch's dynamic LDS, in 16-B units (0: none, store per lane).  Per wave 64 lanes x 3 NPX elements.
+constexpr uint32_t kEpiDtypeMask = 0xffu, kEpiStageShift = 8, kEpiStageMask = 0x1fffu << kEpiStageShift;
+// Which rows take the dense form: 1 = f32 rows, 2 = f16 / bf16 rows of the families with four pixels per lane, 4 = f16 / bf16 rows of
+// k_convert_half (eight pixels per lane).  Measured per family with builds of mask 0 and 7 (profiles/r11_tensor_nhwc.txt): without
+// 1 f32 rows are 4-37 % slower in the 4-px families and ~8 x slower in k_convert_half; with 2 the 16-bit rows of the strip and per-tap kernels
+// are slower (two 12-B stores per lane beat 8-B LDS writes plus 1.5 dense stores); without 4 k_convert_half's 16-bit rows are ~1.6 x slower.
+#ifndef VPF_NHWC_DENSE
+#define VPF_NHWC_DENSE (1 | 4)
+#endif
 struct TensorEpi {
   float scale[3], bias[3];
-  uint32_t dtype;  // VPF_TENSOR_*: wave-uniform branch of the epilogue
+  uint32_t dtype;  // VPF_TENSOR_*: wave-uniform branch of the epilogue (FC_TENSOR_NHWC: | kEpiSwapRB)
   uint32_t pad;
 };
+static_assert(sizeof(TensorEpi) == 32, "the epilogue rides behind the frame and job tables: its size is part of their layout");
+// The staging plan of an FC_TENSOR_NHWC launch whose kernel uses `lds` bytes of dynamic LDS itself and gives a lane `npx` pixels: the epilogue to
+// pass (e with the area's place) and the dynamic LDS to ask for.  No room under the 64 KiB a workgroup may take: no staging, the same kernel.
+inline uint32_t nhwc_stage_plan(const TensorEpi& te, uint32_t lds, uint32_t npx, TensorEpi* e) {
+  *e = te;
+  const uint32_t dt = te.dtype & kEpiDtypeMask;
+  const bool want = dt == VPF_TENSOR_F32 ? ((VPF_NHWC_DENSE) & 1) != 0 : ((VPF_NHWC_DENSE) & (npx == 8 ? 4 : 2)) != 0;
+  const uint32_t bytes = 4u * 64u * 3u * npx * (dt == VPF_TENSOR_F32 ? 4u : 2u);
+  if (!want || (lds & 15u) || lds + bytes > 64u * 1024u) return lds;
+  e->dtype |= (lds / 16u + 1u) << kEpiStageShift;
+  return lds + bytes;
+}
 template <int CAP>
 struct BatchArgsTE {
   FrameDesc f[CAP];
@@ -124,7 +151,7 @@ static_assert(sizeof(WarpDesc) == 96 && sizeof(WarpArgs) <= sizeof(BatchArgsTE<k
 struct TensorPro {
   float scale[3], bias[3];
   uint32_t dtype;  // VPF_TENSOR_*: template parameter of the fast kernel, wave-uniform branch of the quad kernel
-  uint32_t pad;
+  uint32_t pad;    // the NHWC kernels: 1 = kernel channel ch is read from slot 2 - ch of the interleaved plane (B G R order); else 0
 };
 
 // launchers (one per translation unit); all asynchronous on `st`
@@ -133,8 +160,9 @@ hipError_t launch_yuv_to_rgb(hipStream_t st, int src_fc, int dst_fc, const Yuv2R
 hipError_t launch_rgb_to_yuv(hipStream_t st, int src_fc, int dst_fc /*FC_YUV444|FC_YUV420*/,
                              const Rgb2YuvCoef& c, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a);
 // three planes of f32 / f16 / bf16 (FrameDesc::s, R G B) -> NV12 (d[0], d[1]) or YUV420 (d[0..2]); k_rgb2yuv.hip
+// nhwc: ONE interleaved plane of w x 3 elements per row (FrameDesc::s[0]; t.pad = 1 for B G R order) instead of the three planes
 hipError_t launch_tensor_to_yuv(hipStream_t st, bool nv12, const Rgb2YuvCoef& c, const TensorPro& t, uint32_t w, uint32_t h, uint32_t n,
-                                const BatchArgs& a);
+                                const BatchArgs& a, bool nhwc = false);
 hipError_t launch_relayout(hipStream_t st, int src_fmt, int dst_fmt, uint32_t w, uint32_t h, uint32_t n,
                            const BatchArgs& a);
 hipError_t launch_resize(hipStream_t st, int channels, int interp, uint32_t sw, uint32_t sh, const uint8_t* src,
@@ -159,16 +187,17 @@ hipError_t launch_remap(hipStream_t st, uint32_t sw, uint32_t sh, const uint8_t*
                         uint32_t dh, uint8_t* dst, uint32_t dpitch);
 hipError_t launch_remap_batch(hipStream_t st, uint32_t sw, uint32_t sh, const float* xmap, uint32_t xpitch, const float* ymap, uint32_t ypitch,
                               uint32_t dw, uint32_t dh, uint32_t n, const BatchArgs& a);
-// dst_fc == FC_TENSOR takes `te` (the element size sets the destination alignment tests); every other class ignores it
+// dst_fc == FC_TENSOR / FC_TENSOR_NHWC take `te` (the element size sets the destination alignment tests); every other class ignores it
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw,
                                  uint32_t sh, uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te = nullptr);
 // n <= kRoiBatch jobs on frames `W` pixels wide -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); k_convert_roi.hip
+// (nhwc: FC_TENSOR_NHWC planes, one per job, here and in launch_convert_warp)
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
-                                      uint32_t dh, const TensorEpi& te);
+                                      uint32_t dh, const TensorEpi& te, bool nhwc = false);
 // n <= kWarpBatch jobs on frames of W x H pixels -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); `te.pad`
 // carries border and mode (WarpArgs); k_convert_warp.hip
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
-                               uint32_t dh, const TensorEpi& te);
+                               uint32_t dh, const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 
