@@ -10,10 +10,9 @@
 // P10 / P12 frames (FC_P16) take the same two kernels: their 16-bit samples are narrowed to 8 bits at the load (k_fused_common.h).
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "vpf_job_bounds.h"  // kRoiBandRows, roi_strip_need, the policy's limits: shared with the CPU property test
 
 namespace vpf {
-
-constexpr int kRoiBandRows = 4;  // destination rows per wave of the staged form: a workgroup's strip serves 16 rows x 256 columns
 
 // ------------------------------------------------------------------------------------------
 // The staged form.  convert_strip_wg_task (k_convert_resize.hip) with per-job geometry: the strip's pixels are ABSOLUTE frame pixels
@@ -53,31 +52,9 @@ __global__ __launch_bounds__(256, 4) void k_roi_gather_nhwc(const RoiArgs args, 
 
 // ------------------------------------------------------------------------------------------
 // Host side.  The strip a staged job needs is WALKED with the kernel's own fp32 tap arithmetic (vpf_lin_i0 = make_tap's i0), chunk by
-// chunk and band by band, like vpf_band_rows_exact: a bound that is a row short would be silent corruption.
+// chunk and band by band, like vpf_band_rows_exact: a bound that is a row short would be silent corruption (roi_strip_need,
+// vpf_job_bounds.h; tests/test_job_bounds_cpu.py).
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kRoiStripMax = 53u * 1024u;  // three workgroups per CU (160 KiB)
-struct RoiStripNeed {
-  uint32_t bytes;  // rows x row bytes of the job's largest workgroup strip
-  double conv;     // source pixels converted per destination pixel (the gather form converts four)
-};
-static RoiStripNeed roi_strip_need(const RoiDesc& j, uint32_t dw, uint32_t dh) {
-  uint32_t rowbytes = 0, rows = 0;
-  for (uint32_t xs = 0; xs < dw; xs += 256) {
-    const uint32_t xe = xs + 255 < dw - 1 ? xs + 255 : dw - 1;
-    const uint32_t i0 = vpf_lin_i0(xe, j.scx, j.w);
-    const uint32_t first = j.x + vpf_lin_i0(xs, j.scx, j.w), last = j.x + (i0 + 1 < j.w ? i0 + 1 : j.w - 1);
-    const uint32_t rb = 32u * (((last - (first & ~1u)) >> 3) + 1u) + 16u;
-    rowbytes = rb > rowbytes ? rb : rowbytes;
-  }
-  for (uint32_t ya = 0; ya < dh; ya += 4 * kRoiBandRows) {
-    const uint32_t yb = ya + 4 * kRoiBandRows - 1 < dh - 1 ? ya + 4 * kRoiBandRows - 1 : dh - 1;
-    const uint32_t lo = vpf_lin_i0(ya, j.scy, j.h), hi0 = vpf_lin_i0(yb, j.scy, j.h), hi = hi0 + 1 < j.h ? hi0 + 1 : j.h - 1;
-    rows = hi - lo + 1 > rows ? hi - lo + 1 : rows;
-  }
-  const uint32_t cols = dw < 256 ? dw : 256, brows = dh < 4 * kRoiBandRows ? dh : 4 * kRoiBandRows;
-  return RoiStripNeed{rows * rowbytes, (double)rows * (rowbytes / 4) / ((double)cols * brows)};
-}
-
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
                                       uint32_t dh, const TensorEpi& te, bool nhwc) {
   if (!n || n > (uint32_t)kRoiBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
@@ -91,8 +68,9 @@ hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbC
   as.e = ag.e = te;  // (one interleaved plane: the staging plan of each dispatch follows below, nhwc_stage_plan)
   uint32_t ns = 0, ngat = 0, lds = 0;
   for (uint32_t i = 0; i < n; i++) {
-    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : roi_strip_need(jobs[i], dw, dh);
-    if (!all_gather && need.bytes <= kRoiStripMax && need.conv <= 3.0) {
+    const RoiDesc& j = jobs[i];
+    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : roi_strip_need(j.x, j.w, j.h, j.scx, j.scy, dw, dh);
+    if (!all_gather && roi_job_staged(need)) {
       as.j[ns++] = jobs[i];
       lds = need.bytes > lds ? need.bytes : lds;
     } else {

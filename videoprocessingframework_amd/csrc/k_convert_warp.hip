@@ -13,66 +13,12 @@
 
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "vpf_job_bounds.h"
 
 namespace vpf {
 
-// Destination tile of a workgroup: 1024 pixels, four per lane.  Close to square keeps a rotated footprint's bounding box small; 32 x 32 measured
-// against 64 x 16 and 16 x 64 (builds with -DVPF_WARP_TILE_W= -DVPF_WARP_TILE_H=, tools/warp_kernel_ab.py).
-#ifndef VPF_WARP_TILE_W
-#define VPF_WARP_TILE_W 32
-#define VPF_WARP_TILE_H 32
-#endif
-constexpr uint32_t kWarpTileW = VPF_WARP_TILE_W, kWarpTileH = VPF_WARP_TILE_H, kWarpLanesX = kWarpTileW / 4;
-static_assert(kWarpTileW * kWarpTileH == 1024 && kWarpTileW % 4 == 0, "a workgroup of 256 lanes x 4 pixels covers one tile");
-
-// ------------------------------------------------------------------------------------------
-// Coordinates: host and device run the same separately rounded fp32 operations (the host sizes the strips with them).
-// ------------------------------------------------------------------------------------------
-struct WarpXY { float sx, sy; };
-__host__ __device__ __forceinline__ WarpXY warp_xy(const float* m, uint32_t dx, uint32_t dy, bool rep, float wmax, float hmax) {
-  const float fx = (float)dx, fy = (float)dy;
-  float sx = (m[0] * fx + m[1] * fy) + m[2];
-  float sy = (m[3] * fx + m[4] * fy) + m[5];
-  if (rep) {  // a max, then a min
-    sx = fminf(fmaxf(sx, 0.f), wmax);
-    sy = fminf(fmaxf(sy, 0.f), hmax);
-  }
-  return WarpXY{sx, sy};
-}
-// The source window of a destination tile [xs, xe] x [ys, ye]: rounding is monotonic, so sx and sy are monotonic in dx for fixed dy and in dy
-// for fixed dx (clamped or not) and their extremes over the tile lie at its four corners, exactly.  Every in-range pixel of the tile has
-// x_lo <= x0, x1 <= x_hi and y_lo <= y0, y1 <= y_hi; `empty`: no pixel of the tile is in range.
-struct WarpWin {
-  uint32_t x_lo, x_hi, y_lo, y_hi;
-  bool empty;
-};
-__host__ __device__ __forceinline__ WarpWin warp_window(const float* m, uint32_t xs, uint32_t xe, uint32_t ys, uint32_t ye, bool rep, uint32_t W,
-                                                        uint32_t H) {
-  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
-  const WarpXY a = warp_xy(m, xs, ys, rep, wmax, hmax), b = warp_xy(m, xe, ys, rep, wmax, hmax), c = warp_xy(m, xs, ye, rep, wmax, hmax),
-               d = warp_xy(m, xe, ye, rep, wmax, hmax);
-  const float xmin = fminf(fminf(a.sx, b.sx), fminf(c.sx, d.sx)), xmax = fmaxf(fmaxf(a.sx, b.sx), fmaxf(c.sx, d.sx));
-  const float ymin = fminf(fminf(a.sy, b.sy), fminf(c.sy, d.sy)), ymax = fmaxf(fmaxf(a.sy, b.sy), fmaxf(c.sy, d.sy));
-  WarpWin w{0u, 0u, 0u, 0u, !(xmax >= 0.f && xmin <= wmax && ymax >= 0.f && ymin <= hmax)};
-  if (w.empty) return w;
-  w.x_lo = (uint32_t)(int)fmaxf(xmin, 0.f);
-  w.y_lo = (uint32_t)(int)fmaxf(ymin, 0.f);
-  const uint32_t xh = (uint32_t)(int)fminf(xmax, wmax), yh = (uint32_t)(int)fminf(ymax, hmax);
-  w.x_hi = xh + 1 < W ? xh + 1 : W - 1;
-  w.y_hi = yh + 1 < H ? yh + 1 : H - 1;
-  return w;
-}
-// the strip of a window: whole conversion units from the even pixel at or below x_lo, rows y_lo .. y_hi (the layout of k_roi_strip)
-struct WarpStrip { uint32_t base_px, ng, rowbytes, rows, bytes; };
-__host__ __device__ __forceinline__ WarpStrip warp_strip(const WarpWin& w) {
-  WarpStrip s;
-  s.base_px = w.x_lo & ~1u;
-  s.ng = ((w.x_hi - s.base_px) >> 3) + 1;
-  s.rowbytes = 32u * s.ng + 16u;  // 16-B unit writes force a pitch of whole four-dword slots; the odd slot keeps rows of ng = 4 k units off one bank
-  s.rows = w.y_hi - w.y_lo + 1;
-  s.bytes = s.rows * s.rowbytes;
-  return s;
-}
+// The tile (kWarpTileW x kWarpTileH), the coordinates (warp_xy), a tile's source window and strip (warp_window, warp_strip) and the launcher's bound
+// (warp_need, kWarpStripMax) stand in vpf_job_bounds.h: host, device and the CPU property test (tests/test_job_bounds_cpu.py) share them.
 
 VPF_DEV bool warp_rep(const TensorEpi& e) { return (e.pad >> 24) == VPF_WARP_REPLICATE; }
 VPF_DEV float warp_border(const TensorEpi& e, int ch) { return (float)((e.pad >> (8 * ch)) & 0xffu); }
@@ -159,40 +105,9 @@ __global__ __launch_bounds__(256) void k_warp_gather_nhwc(const WarpArgs args, c
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  The dynamic LDS of a dispatch is an UPPER BOUND of every tile's strip, from the matrix alone, O(1) per job (a walk over every
-// tile's corners cost ~10 ns per tile and bounded the whole call).  Along one axis a tile of tw x th pixels spans at most
-// |r0| (tw - 1) + |r1| (th - 1) in exact arithmetic; each fp32 coordinate is off by at most 2^-23 (|r0| dx + |r1| dy + |r2|) (three roundings
-// of half an ulp of values no larger than that sum), taken four times over here; x_hi - x_lo + 1 <= floor(xmax) - floor(xmin) + 2 <= span + 3;
-// a clamp (REPLICATE, the frame) only shrinks a window.  The kernel compares the strip it computes with the bytes it was given and takes the
-// per-tap path for a tile that would not fit, so a bound that were ever short costs time, not pixels.
+// Host side.  The dynamic LDS of a dispatch is an UPPER BOUND of every tile's strip, from the matrix alone, O(1) per job: warp_need and the
+// policy's limit kWarpStripMax, vpf_job_bounds.h.
 // ------------------------------------------------------------------------------------------
-// Policy (measured): the staged form wherever a tile's strip fits kWarpStripMax, the per-tap form otherwise.  Kernel time of the staged
-// form is 0.50-0.82 x the per-tap form's in every case whose strip fits, 2.86 x down-scales at 15 degrees (about 12 source pixels converted per
-// destination pixel) included: no break-even in converted pixels is reached before the strip outgrows the LDS, so there is none in the policy.
-// 64 KiB (two workgroups per CU, the most a launch takes without an attribute) against 53 KiB (three): every case that fits 53 KiB runs the same
-// either way, and 2.7 x at 45 degrees (62 KiB) takes 0.585 us per region staged against 0.754 per tap.
-#ifndef VPF_WARP_STRIP_MAX_KIB
-#define VPF_WARP_STRIP_MAX_KIB 64
-#endif
-constexpr uint32_t kWarpStripMax = VPF_WARP_STRIP_MAX_KIB * 1024u;
-struct WarpNeed {
-  uint32_t bytes;  // upper bound of the job's largest tile strip
-};
-static WarpNeed warp_need(const WarpDesc& j, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
-  const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
-  auto count = [&](const float* r, uint32_t S) {  // pixels of a tile's window along one axis, at most
-    const double span = std::fabs((double)r[0]) * (tw - 1) + std::fabs((double)r[1]) * (th - 1);
-    const double err = 4.0 * 0x1p-23 * (std::fabs((double)r[0]) * dw + std::fabs((double)r[1]) * dh + std::fabs((double)r[2]));
-    const double n = std::floor(span + 2.0 * err) + 3.0;
-    return n < (double)S ? (uint32_t)n : S;
-  };
-  const uint32_t nx = count(j.m, W), rows = count(j.m + 3, H);
-  uint32_t ng = (nx >> 3) + 1;  // the strip starts on the even pixel at or below x_lo
-  const uint32_t ng_max = ((W - 1) >> 3) + 1;
-  ng = ng < ng_max ? ng : ng_max;
-  return WarpNeed{rows * (32u * ng + 16u)};
-}
-
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
                                uint32_t dh, const TensorEpi& te, bool nhwc) {
   if (!n || n > (uint32_t)kWarpBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
@@ -205,7 +120,7 @@ hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c,
   as.e = ag.e = te;
   uint32_t ns = 0, ngat = 0, lds = 0;
   for (uint32_t i = 0; i < n; i++) {
-    const WarpNeed need = all_gather ? WarpNeed{0u} : warp_need(jobs[i], W, H, dw, dh);
+    const WarpNeed need = all_gather ? WarpNeed{0u} : warp_need(jobs[i].m, W, H, dw, dh);
     if (!all_gather && need.bytes <= kWarpStripMax) {
       as.j[ns++] = jobs[i];
       lds = need.bytes > lds ? need.bytes : lds;
