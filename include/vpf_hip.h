@@ -297,6 +297,51 @@ VPF_API vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int src_
                                                   vpf_size dst_size, uint32_t n, const vpf_roi_io* rois, const vpf_tensor_norm* norm);
 
 /*
+ * Letterbox into the tensor — fused multi-ROI crop + bilinear resize with PLACEMENT and PADDING: vpf_convert_resize_tensor_rois with a destination
+ * rectangle per job.  What a detector-style network takes first (resize to fit, centre, pad the rest with a constant: YOLO's 114-grey letterbox),
+ * and what ReID / face / OCR crops padded to the input aspect need behind it: `n` jobs of K different aspect ratios in one dispatch.
+ * A job = (the planes of a WHOLE frame of src_size = (W, H), rect = (x, y, w, h) in luma pixels of that frame — vpf_roi_io.rect's rules —, the
+ * planes of the WHOLE dst_size = (dw, dh) of this job, dst_rect = (ix, iy, iw, ih) in destination pixels: where the picture goes); iw, ih >= 1,
+ * ix + iw <= dw, iy + ih <= dh; different jobs may have different dst_rects.  For destination pixel (dx, dy) of the plane, channel c:
+ *   inside  (ix <= dx < ix + iw && iy <= dy < iy + ih): u8[c] is the byte vpf_convert_resize_tensor_rois defines for rect -> (iw, ih) at pixel
+ *        (dx - ix, dy - iy): tx = tap(dx - ix, (float)w / (float)iw, w), ty = tap(dy - iy, (float)h / (float)ih, h) on the RECTANGLE's size (taps
+ *        clamp at the rectangle's edges), the four texels frame pixels (x + tx.i0|i1, y + ty.i0|i1) converted with vpf_convert's arithmetic, chroma
+ *        at absolute ((x + i) >> 1, (y + j) >> 1), u8 = trunc(fma(fy, bot - top, top) + 0.5) with the same top and bot;
+ *   outside: u8[c] = pad[c], unblended (pad[c] belongs to OUTPUT channel c, like scale[c], bias[c] and the warp's border[c]);
+ *   out = round_to_dtype(fmaf(u8[c], scale[c], bias[c]))           exactly vpf_convert_resize_tensor's epilogue (dtype, flags, plane rules).
+ * Equivalently: every plane of the job filled with the epilogue of `pad`, then vpf_convert_resize_tensor_rois(dst_size = (iw, ih)) on the job's
+ * planes advanced by iy * pitch + ix * element size (3 * ix elements with VPF_TENSOR_NHWC) — bit-identical to that, without the misaligned slice and
+ * without writing the picture's elements twice.  With dst_rect = (0, 0, dw, dh) the output is bit-identical to vpf_convert_resize_tensor_rois.
+ * Every element of every job's dst_size planes is written exactly once, and nothing else is written.
+ * It accepts what the ROI entry accepts: NV12 / YUV420 / P10 / P12 sources (16-bit samples narrowed at the load), f32 / f16 / bf16,
+ * VPF_TENSOR_BGR, VPF_TENSOR_NHWC (dst[0] = the one interleaved plane of the job), the same colour rules.  `jobs` is a HOST array, consumed before
+ * return; 82 jobs travel per job table, each table in at most two dispatches (jobs whose source window is converted once into LDS and blended from
+ * there, and jobs with large down-scale factors that convert per tap: identical bits).  opts == NULL means pad 0 0 0.
+ * Refusals are the ROI entry's, plus VPF_ERR_BAD_ARG for an empty dst_rect, a dst_rect that leaves dst_size (no silent clipping) and a non-zero
+ * `reserved` — all checked before any device access.
+ *
+ * vpf_letterbox_fit (host only, callable without a GPU): the aspect-preserving, centred dst_rect of a w x h rectangle inside dw x dh, in integer
+ * arithmetic with 64-bit products.  w * dh >= h * dw (width-limited): iw = dw, ih = clamp((2 h dw + w) / (2 w), 1, dh) (round half up); otherwise
+ * ih = dh, iw = clamp((2 w dh + h) / (2 h), 1, dw); ix = (dw - iw) / 2, iy = (dh - ih) / 2, rounded down.  1920 x 1080 into 640 x 640 gives
+ * (0, 140, 640, 360).  A zero size gives (0, 0, 0, 0).  Destination pixel x_dst of the picture shows frame coordinate
+ * x_frame = rect.x + (x_dst - ix + 0.5) * w / iw - 0.5 (likewise y): the way back for a detector's boxes.
+ */
+typedef struct vpf_letterbox_io {
+  vpf_plane src[3];  /* the WHOLE frame's planes */
+  vpf_plane dst[3];  /* the WHOLE dst_size planes of this job (one plane with VPF_TENSOR_NHWC) */
+  vpf_rect rect;     /* source rectangle, luma pixels of the frame (vpf_roi_io.rect's rules) */
+  vpf_rect dst_rect; /* where the picture goes inside dst_size, destination pixels */
+} vpf_letterbox_io; /* 128 bytes, no implicit padding */
+typedef struct vpf_letterbox_opts {
+  uint8_t pad[3];   /* per output channel */
+  uint8_t reserved; /* must be 0 */
+} vpf_letterbox_opts; /* 4 bytes */
+VPF_API vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                vpf_size dst_size, uint32_t n, const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm,
+                                                const vpf_letterbox_opts* opts);
+VPF_API vpf_rect vpf_letterbox_fit(vpf_size src, vpf_size dst); /* host only */
+
+/*
  * Fused multi-ROI affine warp -> normalised planar tensor: `n` crops of decoded NV12 / YUV420 frames (or P10 / P12 ones, narrowed to 8 bits at the
  * load: "10 / 12-bit sources" at vpf_convert_resize_tensor) that are NOT axis-aligned (aligned faces, rotated
  * text boxes, oriented detections, flips, shears), each sampled through a 2 x 3 matrix of its own into the ONE size dst_size and normalised, in

@@ -396,6 +396,110 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
     return out
 
 
+def _dst_rects_list(dst_rects, n, w, h, fn):
+    """dst_rects -> list of n 4-tuples of Python ints inside the w x h destination: ValueError for a device tensor, a non-integer dtype, another
+    length than the rois', an empty rectangle or one that leaves the destination"""
+    if isinstance(dst_rects, torch.Tensor):
+        if dst_rects.device.type != "cpu":
+            raise ValueError(f"{fn}: dst_rects must live on the host (the job table is built on the CPU): pass dst_rects.cpu()")
+        if dst_rects.dtype.is_floating_point or dst_rects.dtype.is_complex or dst_rects.dtype == torch.bool:
+            raise ValueError(f"{fn}: dst_rects must hold integers, got {dst_rects.dtype}")
+        dst_rects = dst_rects.tolist()
+    elif hasattr(dst_rects, "dtype") and hasattr(dst_rects, "tolist"):  # numpy.ndarray
+        if getattr(dst_rects.dtype, "kind", "") not in "iu":
+            raise ValueError(f"{fn}: dst_rects must hold integers, got {dst_rects.dtype}")
+        dst_rects = dst_rects.tolist()
+    dst_rects = list(dst_rects)
+    if len(dst_rects) != n:
+        raise ValueError(f"{fn}: {len(dst_rects)} dst_rects for {n} rois")
+    out = []
+    for i, r in enumerate(dst_rects):
+        r = tuple(r)
+        try:
+            if len(r) != 4:
+                raise TypeError
+            ix, iy, iw, ih = (operator.index(v) for v in r)
+        except TypeError:
+            raise ValueError(f"{fn}: dst_rects[{i}] must be four integers (ix, iy, iw, ih), got {r}") from None
+        if ix < 0 or iy < 0 or iw < 1 or ih < 1 or ix + iw > w or iy + ih > h:
+            raise ValueError(f"{fn}: dst_rects[{i}] = (ix {ix}, iy {iy}, iw {iw}, ih {ih}) is empty or leaves the {w} x {h} destination")
+        out.append((ix, iy, iw, ih))
+    return out
+
+
+def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_rects=None, pad=(114, 114, 114), dtype=torch.float32, bgr=False, out=None,
+                                   cc_ctx=None, channels_last=False):
+    """Letterbox: K rectangles of NV12 / YUV420 (or P10 / P12) surfaces, each resized into a rectangle of its own inside its [3, dh, dw] frame and the
+    rest of the frame padded with a constant — the aspect-preserving input of a detector (YOLO's 114-grey letterbox) and of ReID / face / OCR networks
+    that take padded crops —, normalised, in one dispatch per 82 jobs (PySurfaceConvertResizer.ExecuteLetterboxToTensor, vpf_convert_letterbox_tensor).
+    `rois` as in rois_to_normalized_tensor; None: one job per surface, the whole frame.  `dst_rects`: per job (ix, iy, iw, ih) in destination pixels,
+    inside the resizer's destination size (a sequence of integer 4-tuples or a CPU integer tensor / ndarray [K, 4]); None: the aspect-preserving,
+    centred fit of each job's rectangle (PyNvCodec.LetterboxFit: integer arithmetic, round half up).  `pad`: three values 0..255, per output channel
+    (B G R order when bgr=True), written THROUGH the normalisation like every pixel.
+
+    Returns (tensor, placement): the [K, 3, dh, dw] tensor and a CPU int64 tensor [K, 4] of the destination rectangles used.  Inside its rectangle a
+    job holds the bits rois_to_normalized_tensor gives for a resizer of size (iw, ih); a dst_rect that is the whole destination gives
+    rois_to_normalized_tensor's bits.  The map back to frame coordinates, for a detector's boxes (likewise y with rect.y, iy, h, ih):
+        x_frame = rect.x + (x_dst - ix + 0.5) * w / iw - 0.5
+
+    `out`, channels_last and the stream ordering: exactly as to_normalized_tensor.  ValueError for what rois_to_normalized_tensor refuses, for a pad
+    that is not three integers in 0..255, for rois and dst_rects of different lengths and for a dst_rect that is empty or leaves the destination.
+    K == 0 returns an empty tensor and an empty placement without a launch."""
+    fn = "letterbox_to_normalized_tensor"
+    try:
+        import PyNvCodec as nvc
+    except ImportError:  # package-relative import when used as videoprocessingframework_amd.PytorchNvCodec
+        from .. import PyNvCodec as nvc
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    try:
+        pad = [operator.index(v) for v in pad]
+    except TypeError:
+        raise ValueError(f"{fn}: pad must hold three integers, got {pad!r}") from None
+    if len(pad) != 3 or any(not 0 <= v <= 255 for v in pad):
+        raise ValueError(f"{fn}: pad must hold three values in 0..255, got {pad}")
+    surfaces = list(surfaces)
+    if rois is None:
+        rois = [(i, 0, 0, s.Width(), s.Height()) for i, s in enumerate(surfaces)]
+    jobs = _rois_list(rois, surfaces, fn)
+    n = len(jobs)
+    w, h = resizer.DstSize()
+    if dst_rects is None:
+        rects = [tuple(int(v) for v in nvc.LetterboxFit(j[3], j[4], w, h)) for j in jobs]
+    else:
+        rects = _dst_rects_list(dst_rects, n, w, h, fn)
+    placement = torch.tensor(rects, dtype=torch.int64).reshape(n, 4)
+    if channels_last:
+        out = _channels_last_out(fn, out, n, h, w, dtype)
+    elif out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    if n == 0:
+        return out, placement
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+        ok = resizer.ExecuteLetterboxToTensor(surfaces, jobs, rects, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
+                                              cc_ctx, bool(bgr), pad, s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out, placement
+
+
 def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None, channels_last=False):
     """A model's output -> NV12 / YUV420 surfaces for the encoder, in one pass (PyTensorToSurface.ExecuteBatch): `tensor` is [N, 3, H, W] or
     [3, H, W] of float32 / float16 / bfloat16 on the device, normalised with torchvision's mean / std (per input plane; B G R planes when

@@ -31,6 +31,7 @@ EXPORTS = [
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
+    "vpf_convert_letterbox_tensor", "vpf_letterbox_fit",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -78,6 +79,17 @@ class WarpOpts(C.Structure):
 
 
 WARP_CONSTANT, WARP_REPLICATE = 0, 1
+
+
+class LetterboxIO(C.Structure):
+    """vpf_letterbox_io: one job of vpf_convert_letterbox_tensor — the WHOLE source frame's planes, the WHOLE destination planes, the source
+    rectangle and where the picture goes inside the destination"""
+    _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("rect", Rect), ("dst_rect", Rect)]
+
+
+class LetterboxOpts(C.Structure):
+    """vpf_letterbox_opts: the pad bytes per output channel"""
+    _fields_ = [("pad", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
 class TensorNorm(C.Structure):
@@ -170,6 +182,10 @@ def lib() -> C.CDLL:
         L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
         L.vpf_convert_resize_tensor_rois.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(RoiIO), PN]
         L.vpf_convert_warp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(WarpIO), PN, C.POINTER(WarpOpts)]
+        L.vpf_convert_letterbox_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(LetterboxIO), PN,
+                                                   C.POINTER(LetterboxOpts)]
+        L.vpf_letterbox_fit.argtypes = [Size, Size]
+        L.vpf_letterbox_fit.restype = Rect
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
         L.vpf_tensor_convert.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, PP, PP, PN]
         L.vpf_tensor_convert_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, C.c_uint32, PF, PN]
@@ -387,6 +403,43 @@ def convert_warp_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, warps, norm: 
                                        C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
     if check:
         _check(st, "vpf_convert_warp_tensor")
+    return st
+
+
+def letterbox_fit(w, h, dw, dh):
+    """vpf_letterbox_fit: the aspect-preserving, centred placement (ix, iy, iw, ih) of a w x h rectangle inside dw x dh (host only)"""
+    r = lib().vpf_letterbox_fit(Size(w, h), Size(dw, dh))
+    return (r.x, r.y, r.width, r.height)
+
+
+def make_letterbox_jobs(jobs) -> "C.Array[LetterboxIO]":
+    """jobs: list of (src_desc, dst_desc, (x, y, w, h), (ix, iy, iw, ih)) with desc as in planes(); src_desc = the planes of the WHOLE frame,
+    dst_desc = the WHOLE destination planes of the job"""
+    arr = (LetterboxIO * len(jobs))()
+    for i, (s, d, rect, dst_rect) in enumerate(jobs):
+        s, d = planes(s), planes(d)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+            arr[i].dst[k].ptr, arr[i].dst[k].pitch = d[k].ptr, d[k].pitch
+        arr[i].rect.x, arr[i].rect.y, arr[i].rect.width, arr[i].rect.height = rect
+        arr[i].dst_rect.x, arr[i].dst_rect.y, arr[i].dst_rect.width, arr[i].dst_rect.height = dst_rect
+    return arr
+
+
+def make_letterbox_opts(pad=(0, 0, 0)) -> LetterboxOpts:
+    o = LetterboxOpts()
+    for k in range(3):
+        o.pad[k] = pad[k]
+    return o
+
+
+def convert_letterbox_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, jobs, norm: TensorNorm, opts: LetterboxOpts = None, n=None, check=True) -> int:
+    """jobs: LetterboxIO array from make_letterbox_jobs(); every rectangle resized into its dst_rect of the dw x dh planes, the rest padded, 82
+    jobs per job table"""
+    st = lib().vpf_convert_letterbox_tensor(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), Size(dw, dh), len(jobs) if n is None else n, jobs,
+                                            C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_letterbox_tensor")
     return st
 
 

@@ -258,6 +258,41 @@ public:
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorWarps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
   }
+  // additive: K letterbox jobs -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_letterbox_tensor): rois[i] as
+  // ExecuteRoisToTensor, dst_rects[i] = (ix, iy, iw, ih) where that region's picture goes inside dw x dh, `pad` (per output channel) everywhere else;
+  // std::invalid_argument (ValueError) for a pad value outside 0..255 and for rois / dst_rects of different lengths
+  bool ExecuteLetterboxToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<std::array<int64_t, 5>>& rois,
+                                const std::vector<std::array<int64_t, 4>>& dst_rects, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
+                                const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::vector<int64_t>& pad,
+                                uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (pad.size() != 3) throw std::invalid_argument("pad needs three values");
+    vpf_letterbox_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    for (int c = 0; c < 3; c++) {
+      if (pad[c] < 0 || pad[c] > 255) throw std::invalid_argument("pad values must lie in 0..255");
+      opts.pad[c] = (uint8_t)pad[c];
+    }
+    if (rois.size() != dst_rects.size()) throw std::invalid_argument("rois and dst_rects must have the same length");
+    if (src.empty() || rois.empty() || !dst) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, rois.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    std::vector<uint32_t> index(rois.size());
+    std::vector<vpf_rect> rects(rois.size()), drects(rois.size());
+    for (size_t i = 0; i < rois.size(); i++) {
+      for (int k = 0; k < 5; k++)
+        if (rois[i][k] < 0 || rois[i][k] > 0xffffffffll) return false;
+      for (int k = 0; k < 4; k++)
+        if (dst_rects[i][k] < 0 || dst_rects[i][k] > 0xffffffffll) return false;
+      index[i] = (uint32_t)rois[i][0];
+      rects[i] = vpf_rect{(uint32_t)rois[i][1], (uint32_t)rois[i][2], (uint32_t)rois[i][3], (uint32_t)rois[i][4]};
+      drects[i] = vpf_rect{(uint32_t)dst_rects[i][0], (uint32_t)dst_rects[i][1], (uint32_t)dst_rects[i][2], (uint32_t)dst_rects[i][3]};
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensorLetterbox(a.data(), (uint32_t)a.size(), index.data(), rects.data(), drects.data(), (uint32_t)rois.size(),
+                                                          planes.data(), norm, &opts, cc.get());
+  }
   size_t GetStream() const { return (size_t)task_->GetStream(); }
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
@@ -766,6 +801,13 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "K affine warps of the surfaces: job i samples surfaces[surface_index[i]] through the inverse 2 x 3 matrix matrices[i] (six floats) into the "
            "task's destination size, normalised, into a planar tensor [K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one "
            "dispatch per 96 regions")
+      .def("ExecuteLetterboxToTensor", &PySurfaceConvertResizer::ExecuteLetterboxToTensor, py::arg("surfaces"), py::arg("rois"), py::arg("dst_rects"),
+           py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("pad") = std::vector<int64_t>{0, 0, 0}, py::arg("row_stride") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0,
+           py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
+           "K letterbox jobs: rectangle rois[i] = (surface_index, x, y, w, h) resized into dst_rects[i] = (ix, iy, iw, ih) of its [3, dh, dw] frame of the "
+           "planar tensor at device address ptr, pad (per output channel, 0..255) everywhere else in the frame, normalised (strides in bytes, 0 = "
+           "contiguous); one dispatch per 82 regions.  ValueError for a bad pad and for rois / dst_rects of different lengths")
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 
@@ -892,6 +934,11 @@ PYBIND11_MODULE(_PyNvCodec, m) {
         },
         py::arg("src_format"), py::arg("dst_format"), py::arg("cc_ctx") = nullptr,
         "(color_space, color_range) the converter would use for this pair and context, or None if it refuses the combination");
+  m.def("LetterboxFit", [](uint32_t w, uint32_t h, uint32_t dw, uint32_t dh) {
+          const vpf_rect r = vpf_letterbox_fit(vpf_size{w, h}, vpf_size{dw, dh});
+          return py::make_tuple(r.x, r.y, r.width, r.height);
+        }, py::arg("w"), py::arg("h"), py::arg("dw"), py::arg("dh"),
+        "additive: (ix, iy, iw, ih), the aspect-preserving, centred placement of a w x h rectangle inside dw x dh (vpf_letterbox_fit; host only)");
   m.def("KernelLibraryVersion", []() { return std::string(vpf_version()); });
   m.def("AllocPinned",
         [](size_t nbytes) {

@@ -1,0 +1,216 @@
+// k_convert_letterbox.hip — fused multi-ROI crop + bilinear resize of NV12 / YUV420 (P10 / P12) with PLACEMENT and PADDING into a normalised tensor
+// (gfx950): vpf_convert_letterbox_tensor.  The ROI entry (k_convert_roi.hip) with a destination rectangle per job: the rectangle of the frame is
+// resized to iw x ih and lands at (ix, iy) of the job's dw x dh planes, every other element of the planes takes the pad value (LetterboxDesc,
+// vpf_internal.h).  One dispatch serves many jobs with rectangles, pictures and placements of their own.  Grid z = job.
+//   k_lb_strip    the staged form: a workgroup owns (job, 16 rows, 256 columns) of the destination PLANE — not of the picture: a lane's four
+//                 pixels start at a multiple of four columns of the plane, so an aligned tensor keeps its 16-B / 8-B stores whatever ix is.
+//                 A tile that misses the picture stores the pad and leaves (no load, no strip, no barrier); a tile that meets it clips its
+//                 column and row range to the picture, converts the taps' source window once into an LDS strip of four-byte RGB pixels
+//                 (VPF_STRIP_FILL_WINDOW, the fill stage of k_roi_strip) and blends from bytes, choosing per pixel between blend and pad
+//   k_lb_gather   per-tap texel_rgb: jobs whose window does not pay or does not fit (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
+// Definition (include/vpf_hip.h): inside the picture the byte vpf_convert_resize_tensor_rois defines for rect -> (iw, ih) at (dx - ix, dy - iy) —
+// make_tap<LINEAR> on the rectangle with scale (float)w / (float)iw, frame texels at absolute coordinates, bilerp, truncation —, outside pad[c];
+// then the tensor epilogue.  Both kernels run exactly the ROI kernels' fp32 operations in their order on the picture: identical bits.
+#include "k_bilinear_blend.h"
+#include "k_fused_common.h"
+#include "vpf_job_bounds.h"  // kRoiBandRows, letterbox_strip_need, the policy's limits: shared with the CPU property test
+
+namespace vpf {
+
+VPF_DEV float lb_pad(const TensorEpi& e, int ch) { return (float)((e.pad >> (8 * ch)) & 0xffu); }
+
+// the lane's four pixels u[ch][k] (8-bit values) of plane row y through the tensor epilogue; wv, lane: tensor_store_nhwc's (a wave's lanes are one
+// run of a row in both kernels)
+template <int DST>
+VPF_DEV void lb_store4(const FrameDesc& f, uint32_t x0, uint32_t y, const float (&u)[3][4], const TensorEpi& te, bool vec, uint32_t nv, uint32_t wv,
+                       uint32_t lane) {
+  if constexpr (DST == FC_TENSOR_NHWC) {
+    tensor_store_nhwc<false, 4>(f.d[0] + (size_t)y * f.dp[0], x0, u, te, vec, nv, wv, lane);
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
+  }
+}
+// rows ya .. yb of the lane's four columns, except rows ra .. rb (ra > rb: none excepted), take the pad.  The values do not depend on the row: their
+// epilogue (one fma and one conversion per channel) is computed once per lane, the loop stores.
+template <int DST>
+VPF_DEV void lb_pad_rows(const FrameDesc& f, uint32_t x0, uint32_t ya, uint32_t yb, uint32_t ra, uint32_t rb, const TensorEpi& te, bool vec,
+                         uint32_t nv, uint32_t wv, uint32_t lane) {
+  float u[3][4];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) u[ch][k] = lb_pad(te, ch);
+  for (uint32_t y = ya; y <= yb; y++) {
+    if (y >= ra && y <= rb) continue;
+    lb_store4<DST>(f, x0, y, u, te, vec, nv, wv, lane);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The staged form: k_roi_strip's strip (ABSOLUTE frame pixels [base_px, ..) x rows [y + R_lo, y + R_hi], whole conversion units, the frame's
+// right-edge unit through clamped byte loads) for the part of the picture that the tile holds.  Tile, clip and the tile's miss are functions of the
+// block indices and the job alone: workgroup-uniform, decided before the barrier.
+// ------------------------------------------------------------------------------------------
+template <int SRC, int DST>  // DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane
+__global__ __launch_bounds__(256) void k_lb_strip(const LetterboxArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t dw, uint32_t dh, uint32_t dmask,
+                                                  uint32_t lds_bytes) {
+  constexpr int R = kRoiBandRows;
+  const LetterboxDesc& L = args.j[blockIdx.z];
+  const RoiDesc& J = L.r;
+  const FrameDesc& f = J.f;
+  const uint32_t rx = J.x, ry = J.y, rw = J.w, rh = J.h;
+  const float scx = J.scx, scy = J.scy;
+  const uint32_t ix = L.ix, iy = L.iy, ixe = ix + L.iw - 1, iye = iy + L.ih - 1;  // the picture's first and last column and row on the plane
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
+  const uint32_t Y0 = blockIdx.y * (4 * R), xs = blockIdx.x * 256;  // the grid covers the destination plane exactly: Y0 < dh, xs < dw
+  const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
+  const TensorEpi te = args.e;
+  const uint32_t ya = Y0 + wv * R, yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;  // the wave's rows of the plane
+  const uint32_t x0 = xs + lane * 4;                                           // the lane's columns of the plane: a multiple of four
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;                               // (x0 < dw where it is used)
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  if (xs > ixe || xe < ix || Y0 > iye || Y1 < iy) {  // the tile misses the picture: pad, nothing converted
+    if (ya > Y1 || x0 >= dw) return;
+    lb_pad_rows<DST>(f, x0, ya, yb, 1u, 0u, te, vec, nv, wv, lane);
+    return;
+  }
+  // the tile's columns and rows of the PICTURE
+  const uint32_t cxs = (xs > ix ? xs : ix) - ix, cxe = (xe < ixe ? xe : ixe) - ix, cys = (Y0 > iy ? Y0 : iy) - iy, cye = (Y1 < iye ? Y1 : iye) - iy;
+  const uint32_t first = rx + make_tap<VPF_INTERP_LINEAR>(cxs, scx, rw).i0, last = rx + make_tap<VPF_INTERP_LINEAR>(cxe, scx, rw).i1;  // frame pixels
+  const uint32_t base_px = first & ~1u;
+  const uint32_t R_lo_rel = __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(cys, scy, rh).i0);
+  const uint32_t R_lo = ry + R_lo_rel, R_hi = ry + __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(cye, scy, rh).i1);  // frame rows
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  const uint32_t c_lo = R_lo >> 1, ncr = (R_hi >> 1) - c_lo + 1, ng = ((last - base_px) >> 3) + 1, units = ncr * ng;
+  const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
+  if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, letterbox_strip_need)
+  VPF_STRIP_FILL_WINDOW  // (k_fused_common.h: shared with k_roi_strip and k_warp_strip)
+  __syncthreads();
+  if (ya > Y1) return;
+  const uint32_t ra = ya > iy ? ya : iy, rb = yb < iye ? yb : iye;  // the wave's rows inside the picture (none: ra > rb)
+  const bool rows_in = ra <= rb;
+  const Tap row_taps = band_row_taps(rows_in ? ra - iy : cys, rows_in ? rb - iy : cys, scy, rh);  // every lane of the wave still active here
+  if (x0 >= dw) return;
+  lb_pad_rows<DST>(f, x0, ya, yb, ra, rb, te, vec, nv, wv, lane);
+  if (!rows_in) return;
+  // Column taps, as make_col_taps_x gives them for picture column x0 + k - ix; a column outside the picture takes the taps of the tile's nearest
+  // picture column — inside the strip — and its blend is dropped for the pad below.
+  ColTapsX T;
+  bool in[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t x = x0 + k;
+    in[k] = x >= ix && x <= ixe;
+    const uint32_t px = x < ix + cxs ? cxs : (x > ix + cxe ? cxe : x - ix);
+    const Tap t = make_tap<VPF_INTERP_LINEAR>(px, scx, rw);
+    T.a[k] = 4u * (t.i0 - (base_px - rx));  // (frame pixel base_px = rectangle pixel base_px - rx, modulo 2^32)
+    T.f[k] = t.f;
+  }
+  const float pad[3] = {lb_pad(te, 0), lb_pad(te, 1), lb_pad(te, 2)};
+  band_blend_rows<3, R>(strip, rowbytes, R_lo_rel, ra - iy, rb - iy, row_taps, T, [&](uint32_t y, const float* o) {  // o: pixel-major R G B, + 0.5 added
+    float u[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) u[ch][k] = in[k] ? __builtin_truncf(o[3 * k + ch]) : pad[ch];
+    lb_store4<DST>(f, x0, y + iy, u, te, vec, nv, wv, lane);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// The gather form: k_roi_gather on the plane (four rows x 64 lanes x 4 pixels per workgroup, a wave = one row).  A lane whose four
+// columns miss the picture loads nothing; a wave whose row or columns miss it branches over the conversion as a whole.
+// ------------------------------------------------------------------------------------------
+template <int SRC, int DST>  // (FC_TENSOR_NHWC: four waves per SIMD asked for, as k_roi_gather_nhwc)
+__global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gather(const LetterboxArgs args, const Yuv2RgbCoef c, uint32_t dw,
+                                                                                    uint32_t dh, uint32_t dmask) {
+  const LetterboxDesc& L = args.j[blockIdx.z];
+  const RoiDesc& J = L.r;
+  const FrameDesc& f = J.f;
+  const uint32_t x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  const uint32_t y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x0 >= dw || y >= dh) return;
+  const uint32_t ix = L.ix, iy = L.iy, ixe = ix + L.iw - 1, iye = iy + L.ih - 1;
+  const bool row_in = y >= iy && y <= iye;
+  const Tap ty = make_tap<VPF_INTERP_LINEAR>(row_in ? y - iy : 0u, J.scy, J.h);
+  float u[3][4];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) u[ch][k] = lb_pad(args.e, ch);
+  if (row_in && x0 + 3 >= ix && x0 <= ixe) {  // the lane holds picture: all four pixels' texels in flight together, as k_roi_gather has them
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t x = x0 + k;  // (a column right of the plane is right of the picture: pad, not stored)
+      // a column outside the picture takes the taps of the nearest picture column — texels of the rectangle — and keeps the pad
+      const Tap tx = make_tap<VPF_INTERP_LINEAR>(x < ix ? 0u : (x > ixe ? ixe - ix : x - ix), J.scx, J.w);
+      float p00[3], p01[3], p10[3], p11[3];
+      texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i0, p00);
+      texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i0, p01);
+      texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i1, p10);
+      texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i1, p11);
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        const float v = __builtin_truncf(bilerp(p00[ch], p01[ch], p10[ch], p11[ch], tx.f, ty.f));
+        u[ch][k] = x >= ix && x <= ixe ? v : u[ch][k];
+      }
+    }
+  }
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  lb_store4<DST>(f, x0, y, u, args.e, vec, nv, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side.  launch_convert_resize_rois with the plane-laid walk: the strip a staged job needs is WALKED with the kernel's own fp32 tap
+// arithmetic over the tiles that meet the picture (letterbox_strip_need, vpf_job_bounds.h; tests/test_letterbox_bounds_cpu.py).  The policy is
+// the ROI kernels' (roi_job_staged: kRoiStripMax, kRoiConvMax).
+// ------------------------------------------------------------------------------------------
+hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
+                                    uint32_t dh, const TensorEpi& te, bool nhwc) {
+  if (!n || n > (uint32_t)kLetterboxBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
+  const uint32_t dmask = nhwc || (te.dtype & kEpiDtypeMask) == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane (one interleaved plane: 16 B)
+  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
+  LetterboxArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
+  std::memset(&as, 0, sizeof(as));
+  std::memset(&ag, 0, sizeof(ag));
+  as.e = ag.e = te;
+  uint32_t ns = 0, ngat = 0, lds = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const LetterboxDesc& j = jobs[i];
+    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : letterbox_strip_need(j.r.x, j.r.w, j.r.h, j.r.scx, j.r.scy, j.ix, j.iy, j.iw, j.ih, dw, dh);
+    if (!all_gather && roi_job_staged(need)) {
+      as.j[ns++] = jobs[i];
+      lds = need.bytes > lds ? need.bytes : lds;
+    } else {
+      ag.j[ngat++] = jobs[i];
+    }
+  }
+  if (ns) {
+    const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
+    const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &as.e) : lds;  // the strip, then the waves' staging area where both fit
+#define VPF_LBS(S) do { if (nhwc) VPF_LAUNCH((k_lb_strip<S, FC_TENSOR_NHWC>), grid, dim3(256), lds_all, st, as, c, W, dw, dh, dmask, lds); \
+                        else VPF_LAUNCH((k_lb_strip<S, FC_TENSOR>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds); } while (0)
+    if (src_fc == FC_NV12) VPF_LBS(FC_NV12); else if (src_fc == FC_P16) VPF_LBS(FC_P16); else VPF_LBS(FC_YUV420);
+#undef VPF_LBS
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (ngat) {
+    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
+    const uint32_t lds_g = nhwc ? nhwc_stage_plan(te, 0u, 4, &ag.e) : 0u;
+#define VPF_LBG(S) do { if (nhwc) VPF_LAUNCH((k_lb_gather<S, FC_TENSOR_NHWC>), grid, dim3(256), lds_g, st, ag, c, dw, dh, dmask); \
+                        else VPF_LAUNCH((k_lb_gather<S, FC_TENSOR>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask); } while (0)
+    if (src_fc == FC_NV12) VPF_LBG(FC_NV12); else if (src_fc == FC_P16) VPF_LBG(FC_P16); else VPF_LBG(FC_YUV420);
+#undef VPF_LBG
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+}  // namespace vpf

@@ -574,6 +574,36 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
   }
   return TASK_EXEC_SUCCESS;
 }
+TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects,
+                                                        const vpf_rect* dst_rects, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm,
+                                                        const vpf_letterbox_opts* opts, const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorLetterbox");
+  if (!frames || !n_frames || !frame_index || !rects || !dst_rects || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  for (uint32_t i = 0; i < n_frames; i++) {
+    Surface* s = frames[i];
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+  }
+  std::vector<vpf_letterbox_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(frames[frame_index[i]], io[i].src);
+    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
+    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    io[i].rect = rects[i];
+    io[i].dst_rect = dst_rects[i];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_letterbox_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+                                                     io.data(), &norm, opts);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to letterbox regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
 // ------------------------------------------------------------------------------------------ TensorToSurface

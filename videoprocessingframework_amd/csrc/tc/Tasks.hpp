@@ -67,6 +67,12 @@ public:
   // VPF_WARP_CONSTANT with border 0 0 0.  The same colour-context rules as RunTensor.
   TaskExecStatus RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                 const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
+  // n letterbox jobs (vpf_convert_letterbox_tensor): job i resizes rects[i] of frames[frame_index[i]] into dst_rects[i] (destination pixels, inside
+  // the task's destination size) of the planes dst[3 i .. 3 i + 2] and writes the pad everywhere else in them; opts == nullptr: pad 0 0 0.
+  // RunTensorRois' colour-context rules; the entry cuts the jobs into job tables.
+  TaskExecStatus RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, const vpf_rect* dst_rects,
+                                    uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts,
+                                    const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on
 
 private:

@@ -577,6 +577,77 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
   return VPF_OK;
 }
 
+// The aspect-preserving placement of a w x h picture inside dw x dh (include/vpf_hip.h): integers only, 64-bit products.
+vpf_rect vpf_letterbox_fit(vpf_size src, vpf_size dst) {
+  vpf_rect r = {0u, 0u, 0u, 0u};
+  const uint64_t w = src.width, h = src.height, dw = dst.width, dh = dst.height;
+  if (!w || !h || !dw || !dh) return r;
+  uint64_t iw, ih;
+  if (w * dh >= h * dw) {  // width-limited
+    iw = dw;
+    ih = (2 * h * dw + w) / (2 * w);  // round half up
+    ih = ih < 1 ? 1 : (ih > dh ? dh : ih);
+  } else {
+    ih = dh;
+    iw = (2 * w * dh + h) / (2 * h);
+    iw = iw < 1 ? 1 : (iw > dw ? dw : iw);
+  }
+  r.x = (uint32_t)((dw - iw) / 2); r.y = (uint32_t)((dh - ih) / 2); r.width = (uint32_t)iw; r.height = (uint32_t)ih;
+  return r;
+}
+
+// Many rectangles of decoded frames, each resized into a rectangle of its own inside its destination planes, the rest padded (include/vpf_hip.h):
+// the ROI entry's checks and colour rules, kLetterboxBatch jobs per job table, each table at most two dispatches (k_convert_letterbox.hip).
+vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
+                                        const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts) {
+  const Mark mark("vpf_convert_letterbox_tensor");
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
+  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const vpf_rect &r = jobs[i].rect, &d = jobs[i].dst_rect;
+    if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
+    if (!d.width || !d.height || (uint64_t)d.x + d.width > ds.width || (uint64_t)d.y + d.height > ds.height) return VPF_ERR_BAD_ARG;  // ... on either side
+    if (!tensor_src_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(jobs[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their pad bytes here
+  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
+  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
+  if (opts)
+    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->pad[bgr ? 2 - k : k] << (8 * k);
+  LetterboxDesc table[kLetterboxBatch];
+  for (uint32_t base = 0; base < n; base += kLetterboxBatch) {
+    const uint32_t m = (n - base < (uint32_t)kLetterboxBatch) ? n - base : (uint32_t)kLetterboxBatch;
+    for (uint32_t i = 0; i < m; i++) {
+      const vpf_letterbox_io& io = jobs[base + i];
+      vpf_plane d[3];
+      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
+      LetterboxDesc& j = table[i];
+      fill_desc(j.r.f, io.src, num_planes(sf), d, nd);
+      j.r.x = io.rect.x; j.r.y = io.rect.y; j.r.w = io.rect.width; j.r.h = io.rect.height;
+      j.ix = io.dst_rect.x; j.iy = io.dst_rect.y; j.iw = io.dst_rect.width; j.ih = io.dst_rect.height;
+      j.r.scx = (float)j.r.w / (float)j.iw; j.r.scy = (float)j.r.h / (float)j.ih;
+    }
+    const hipError_t e = launch_convert_letterbox(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, nhwc);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
 // Many affine warps of decoded frames -> one batch of normalised planes (include/vpf_hip.h): per-job matrices, kWarpBatch jobs per job table,
 // each table at most two dispatches (k_convert_warp.hip).
 vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_warp_io* jobs,

@@ -131,6 +131,24 @@ struct RoiArgs {
 };
 static_assert(sizeof(RoiDesc) == 96 && sizeof(RoiArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the ROI job table must not outgrow the largest frame table");
 
+// The job table of a letterbox launch (vpf_convert_letterbox_tensor, k_convert_letterbox.hip): a RoiDesc — its scale factors are the rectangle's over
+// the PICTURE's size, (float)w / (float)iw — plus where the picture goes inside the destination plane.  The rectangle travels as four 32-bit fields:
+// 112 B per job, 82 jobs + the epilogue = 9 216 B, within the 9 248 B of BatchArgsTE<kMaxBatch>.  (Packed as 16-bit pairs — iw - 1, ih - 1: sizes
+// run to 65536 — it would keep 96 jobs per table at the price of an unpack per field in every wave; a call of 96 jobs then takes two tables
+// instead of one, which the job-table test crosses either way.)  The three pad bytes (kernel channel order R G B) travel in TensorEpi::pad:
+// pad = pad[0] | pad[1] << 8 | pad[2] << 16, bits 24 .. 31 zero.  The NHWC staging plan lives in TensorEpi::dtype (nhwc_stage_plan): no collision.
+constexpr int kLetterboxBatch = 82;
+struct LetterboxDesc {
+  RoiDesc r;
+  uint32_t ix, iy, iw, ih;
+};
+struct LetterboxArgs {
+  LetterboxDesc j[kLetterboxBatch];
+  TensorEpi e;
+};
+static_assert(sizeof(LetterboxDesc) == 112 && sizeof(LetterboxArgs) == 82 * 112 + 32 && sizeof(LetterboxArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
+              "the letterbox job table must not outgrow the largest frame table");
+
 // The job table of a multi-ROI affine warp (vpf_convert_warp_tensor, k_convert_warp.hip): per job the planes of the WHOLE source frame and of the
 // destination and the inverse matrix m = (m00 m01 m02; m10 m11 m12), destination pixel -> source coordinates in luma pixels.  96 B like RoiDesc,
 // so the same 96 jobs per table.  The three border bytes (kernel channel order R G B) and the border mode travel in TensorEpi::pad:
@@ -198,6 +216,10 @@ hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbC
 // carries border and mode (WarpArgs); k_convert_warp.hip
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
                                uint32_t dh, const TensorEpi& te, bool nhwc = false);
+// n <= kLetterboxBatch jobs on frames `W` pixels wide -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of dw x dh, the picture at each job's (ix, iy, iw, ih)
+// and `te.pad` everywhere else: at most two dispatches (staged jobs, gather jobs); k_convert_letterbox.hip
+hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
+                                    uint32_t dh, const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 

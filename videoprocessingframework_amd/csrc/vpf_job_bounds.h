@@ -3,6 +3,8 @@
 // through tests/c/job_bounds_capi.cpp) use the SAME code.  The sibling of vpf_plan_bounds.h, for the same reason: a bound that is one byte
 // or one row short is silent — k_roi_strip returns without writing, k_warp_strip blends from the wrong texels.
 //   ROI   roi_strip_need: the largest workgroup strip of a job, WALKED with the kernel's own fp32 tap arithmetic, and the policy's two limits
+//   letterbox  letterbox_strip_need: the same walk over tiles laid on the destination plane and clipped to the picture (k_convert_letterbox.hip;
+//         tests/test_letterbox_bounds_cpu.py through tests/c/letterbox_bounds_capi.cpp)
 //   warp  warp_xy / warp_window / warp_strip: what the kernel computes per tile; warp_need: the launcher's closed-form bound over all tiles
 #ifndef VPF_JOB_BOUNDS_H_
 #define VPF_JOB_BOUNDS_H_
@@ -49,6 +51,36 @@ static inline RoiStripNeed roi_strip_need(uint32_t x, uint32_t w, uint32_t h, fl
 // the policy: staged where the window fits a strip that leaves three workgroups per CU and converts at most kRoiConvMax source pixels per
 // destination pixel; everything else gathers
 static inline bool roi_job_staged(const RoiStripNeed& need) { return need.bytes <= kRoiStripMax && need.conv <= kRoiConvMax; }
+
+// ------------------------------------------------------------------------------------------
+// Letterbox (k_convert_letterbox.hip).  The ROI kernels' workgroup tile (16 rows x 256 columns), laid on the DESTINATION PLANE dw x dh; the picture
+// (rectangle -> iw x ih, scx = (float)w / (float)iw and scy likewise) sits at (ix, iy) of the plane.  A tile that meets the picture clips its column
+// and row range to it — xs' = max(xs, ix) - ix .. xe' = min(xe, ix + iw - 1) - ix, rows likewise — and its strip holds the taps of that range: a
+// clipped chunk does not start at a multiple of 256 picture columns, so this is a walk of its own, with the same fp32 tap arithmetic.  Tiles that
+// miss the picture have no strip.  `conv` counts against the picture pixels a tile can hold (min(iw, 256) x min(ih, 16)): with (ix, iy, iw, ih) =
+// (0, 0, dw, dh) both members equal roi_strip_need's, and the policy is the ROI one (roi_job_staged).
+// ------------------------------------------------------------------------------------------
+static inline RoiStripNeed letterbox_strip_need(uint32_t x, uint32_t w, uint32_t h, float scx, float scy, uint32_t ix, uint32_t iy, uint32_t iw,
+                                                uint32_t ih, uint32_t dw, uint32_t dh) {
+  uint32_t rowbytes = 0, rows = 0;
+  for (uint32_t xs = ix & ~255u; xs < dw && xs < ix + iw; xs += 256) {  // (the chunks left of ix & ~255 end before the picture)
+    const uint32_t xe = xs + 255 < dw - 1 ? xs + 255 : dw - 1;
+    const uint32_t cs = (xs > ix ? xs : ix) - ix, ce = (xe < ix + iw - 1 ? xe : ix + iw - 1) - ix;
+    const uint32_t i0 = vpf_lin_i0(ce, scx, w);
+    const uint32_t first = x + vpf_lin_i0(cs, scx, w), last = x + (i0 + 1 < w ? i0 + 1 : w - 1);
+    const uint32_t rb = 32u * (((last - (first & ~1u)) >> 3) + 1u) + 16u;
+    rowbytes = rb > rowbytes ? rb : rowbytes;
+  }
+  constexpr uint32_t kBand = 4 * kRoiBandRows;
+  for (uint32_t ya = iy - iy % kBand; ya < dh && ya < iy + ih; ya += kBand) {
+    const uint32_t yb = ya + kBand - 1 < dh - 1 ? ya + kBand - 1 : dh - 1;
+    const uint32_t cs = (ya > iy ? ya : iy) - iy, ce = (yb < iy + ih - 1 ? yb : iy + ih - 1) - iy;
+    const uint32_t lo = vpf_lin_i0(cs, scy, h), hi0 = vpf_lin_i0(ce, scy, h), hi = hi0 + 1 < h ? hi0 + 1 : h - 1;
+    rows = hi - lo + 1 > rows ? hi - lo + 1 : rows;
+  }
+  const uint32_t cols = iw < 256 ? iw : 256, brows = ih < kBand ? ih : kBand;
+  return RoiStripNeed{rows * rowbytes, (double)rows * (rowbytes / 4) / ((double)cols * brows)};
+}
 
 // ------------------------------------------------------------------------------------------
 // Warp (k_convert_warp.hip).
