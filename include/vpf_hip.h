@@ -297,6 +297,47 @@ VPF_API vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int src_
                                                   vpf_size dst_size, uint32_t n, const vpf_roi_io* rois, const vpf_tensor_norm* norm);
 
 /*
+ * The same with the rectangles in DEVICE memory: what stands behind a detector and its NMS that run on the GPU.  No sync, no copy of the boxes to the
+ * host, and a captured graph replays with the boxes and the count of REPLAY time.
+ * `frames` is a HOST array of the planes of n_frames (1 .. 128) WHOLE frames of src_size = (W, H), consumed before return.  table->boxes points to
+ * DEVICE memory: entry k = five int32 (frame, x, y, width, height) at byte k * box_stride (a row of a torch.int32 [K, 5] tensor: box_stride = 20;
+ * any multiple of 4 from 20 up: padded tables); table->count to ONE device int32, or NULL.  The kernel reads both WHEN IT RUNS on exec->stream; the
+ * host never dereferences them: the caller orders their producer before this call on that stream (or makes the stream wait for it).
+ *   c = clamp(*count, 0, max_n); count == NULL: c = max_n.  max_n (1 .. 65535) is the size of the dispatch.
+ *   job k < c with a VALID box — 0 <= frame < n_frames, width >= 1, height >= 1, x >= 0, y >= 0, x + width <= W, y + height <= H, evaluated without
+ *        overflow for any five ints —: every element of its planes is bit for bit what vpf_convert_resize_tensor_rois writes for (frames[frame],
+ *        rect = (x, y, width, height), planes dst[c].ptr + k * dst_job_stride with dst[c].pitch), for the same src_fmt (NV12, YUV420, P10, P12),
+ *        dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC (dst[0] = the one interleaved plane of job 0) and colour rules;
+ *   job k < c with an INVALID box: every element of its planes takes the epilogue of byte 0, round_to_dtype(fmaf(0, scale[c], bias[c])) —
+ *        vpf_convert_letterbox_tensor's default pad.  No clipping, and no byte of any frame is read;
+ *   job k >= c: NOTHING is written — a call costs c regions, not max_n; those rows of a fresh tensor stay undefined.
+ * Nothing outside the planes of jobs < c is ever written.  One dispatch; every workgroup decides for its own tile of 16 x 256 destination pixels
+ * whether its source window is converted once into LDS or sampled per tap (identical bits; the host-table entry decides per job).
+ * Checked on the host before any device access, with the ROI entry's answers: unsupported format / matrix / dtype / flag: VPF_ERR_UNSUPPORTED; null
+ * pointers (exec, frames, table, table->boxes, norm), bad sizes, short source pitches, misaligned source (P10 / P12) or destination planes, non-finite
+ * scale / bias, n_frames outside 1 .. 128, max_n outside 1 .. 65535, boxes or count not 4-byte aligned, box_stride < 20 or not a multiple of 4,
+ * dst_job_stride not a multiple of the element size: VPF_ERR_BAD_ARG.  Whatever the boxes hold, the call returns VPF_OK.
+ * Under stream capture the frame and destination pointers are baked into the graph, as in every entry; boxes and count are read at every replay.
+ */
+typedef struct vpf_roi_dev {
+  int32_t frame, x, y, width, height;
+} vpf_roi_dev; /* 20 bytes: a row of a torch.int32 [K, 5] tensor */
+typedef struct vpf_frame_src {
+  vpf_plane src[3]; /* the WHOLE frame's planes */
+} vpf_frame_src; /* 48 bytes */
+typedef struct vpf_rois_dev {
+  const vpf_roi_dev* boxes; /* DEVICE memory, 4-byte aligned */
+  const int32_t* count;     /* DEVICE memory, or NULL = max_n */
+  uint32_t box_stride;      /* bytes between entries: >= 20, multiple of 4 */
+  uint32_t max_n;           /* 1 .. 65535: grid z */
+  vpf_plane dst[3];         /* planes of job 0 (one plane with VPF_TENSOR_NHWC) */
+  uint64_t dst_job_stride;  /* bytes from job k's planes to job k + 1's: multiple of the element size */
+} vpf_rois_dev; /* 80 bytes, no implicit padding */
+VPF_API vpf_status vpf_convert_resize_tensor_rois_dev(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                      vpf_size dst_size, uint32_t n_frames, const vpf_frame_src* frames, const vpf_rois_dev* table,
+                                                      const vpf_tensor_norm* norm);
+
+/*
  * Letterbox into the tensor — fused multi-ROI crop + bilinear resize with PLACEMENT and PADDING: vpf_convert_resize_tensor_rois with a destination
  * rectangle per job.  What a detector-style network takes first (resize to fit, centre, pad the rest with a constant: YOLO's 114-grey letterbox),
  * and what ReID / face / OCR crops padded to the input aspect need behind it: `n` jobs of K different aspect ratios in one dispatch.

@@ -298,6 +298,103 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
     return out
 
 
+def boxes_to_rois(boxes_xyxy, frame_index, width, height) -> torch.Tensor:
+    """A detector's float boxes [K, 4] (x1, y1, x2, y2, in pixels of a width x height frame) and integer frame indices [K] -> the int32 [K, 5] table
+    (frame, x, y, w, h) device_rois_to_normalized_tensor takes.  Pure torch, on whatever device the boxes live on: no sync.  The rectangle is the
+    box rounded OUTWARDS and clipped to the frame: x = clamp(floor(x1), 0, W - 1), w = clamp(ceil(x2), x + 1, W) - x, y and h likewise — always at
+    least one pixel, always inside the frame.  A box with a NaN coordinate gets w = h = 0: an invalid box, whose output frame is normalised zeros."""
+    b = torch.as_tensor(boxes_xyxy)
+    if b.dim() != 2 or b.shape[1] != 4 or not b.dtype.is_floating_point:
+        raise ValueError(f"boxes_to_rois: boxes_xyxy must be a float tensor of shape [K, 4], got {b.dtype} {tuple(b.shape)}")
+    f = torch.as_tensor(frame_index, device=b.device)
+    if f.dim() != 1 or f.shape[0] != b.shape[0] or f.dtype.is_floating_point or f.dtype.is_complex or f.dtype == torch.bool:
+        raise ValueError(f"boxes_to_rois: frame_index must be an integer tensor of shape [{b.shape[0]}], got {f.dtype} {tuple(f.shape)}")
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError("boxes_to_rois: width and height must be at least 1")
+    b = b.to(torch.float64)  # exact for every float dtype; the clamps come before the conversion to integers
+    bad = torch.isnan(b).any(dim=1)
+    b = torch.nan_to_num(b, nan=0.0)
+    x = b[:, 0].floor().clamp(0, W - 1).to(torch.int64)
+    y = b[:, 1].floor().clamp(0, H - 1).to(torch.int64)
+    x2 = torch.minimum(torch.maximum(b[:, 2].ceil().clamp(0, W).to(torch.int64), x + 1), torch.full_like(x, W))
+    y2 = torch.minimum(torch.maximum(b[:, 3].ceil().clamp(0, H).to(torch.int64), y + 1), torch.full_like(y, H))
+    w = torch.where(bad, torch.zeros_like(x), x2 - x)
+    h = torch.where(bad, torch.zeros_like(y), y2 - y)
+    return torch.stack([f.to(torch.int64), x, y, w, h], dim=1).to(torch.int32)
+
+
+def device_rois_to_normalized_tensor(resizer, surfaces, boxes, mean, std, count=None, dtype=torch.float32, bgr=False, out=None, cc_ctx=None,
+                                     channels_last=False) -> torch.Tensor:
+    """rois_to_normalized_tensor for boxes that never leave the GPU (PySurfaceConvertResizer.ExecuteRoisDevToTensor, vpf_convert_resize_tensor_rois_dev):
+    no synchronisation, no copy of the boxes to the host, one dispatch, and the call can be captured in a graph that replays with the boxes and the
+    count of replay time.
+    `boxes`: a device torch.int32 tensor [K, 5] of (surface_index, x, y, w, h) rows (last stride 1, row stride >= 5: a slice of a wider table works),
+    e.g. boxes_to_rois(...) of a detector's output; `count`: a device torch.int32 tensor of ONE element (how many rows are valid: NMS's count), or
+    None for all K.  At most 128 surfaces, K at most 65535.  Returns [K, 3, dh, dw]:
+      rows below the count with a valid box    the bits rois_to_normalized_tensor gives for that rectangle;
+      rows below the count with an invalid box (empty, negative, leaving its surface, no such surface)   normalised zeros, round(-mean / std): nothing is
+                                               clipped and no surface is read;
+      rows at or behind the count              NOT WRITTEN: undefined in a fresh tensor (torch.empty), unchanged in `out`.
+    The kernel reads boxes and count when it runs; this function orders it behind torch's current stream, where their producer ran.  `out`,
+    channels_last, dtype, bgr, the returned tensor and the stream ordering: as rois_to_normalized_tensor.  ValueError for boxes or count on the host or on
+    another device than `out`, another dtype or shape."""
+    fn = "device_rois_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    surfaces = list(surfaces)
+    if not 1 <= len(surfaces) <= 128:
+        raise ValueError(f"{fn}: 1 .. 128 surfaces per call, got {len(surfaces)}")
+    if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda:
+        raise ValueError(f"{fn}: boxes must be a device tensor (for host boxes there is rois_to_normalized_tensor)")
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise ValueError(f"{fn}: boxes must be torch.int32 of shape [K, 5], got {boxes.dtype} {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if n > 65535:
+        raise ValueError(f"{fn}: at most 65535 boxes per call, got {n}")
+    if boxes.stride(1) != 1 or (n > 1 and boxes.stride(0) < 5):
+        raise ValueError(f"{fn}: boxes needs unit stride along its rows and a row stride of at least 5, got strides {boxes.stride()}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1:
+            raise ValueError(f"{fn}: count must be a device torch.int32 tensor of one element, or None")
+        if count.device != boxes.device:
+            raise ValueError(f"{fn}: count lives on {count.device}, boxes on {boxes.device}")
+    w, h = resizer.DstSize()
+    if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != boxes.device:
+        raise ValueError(f"{fn}: out lives on {out.device}, boxes on {boxes.device}")
+    if channels_last:
+        with torch.cuda.device(boxes.device):
+            out = _channels_last_out(fn, out, n, h, w, dtype)
+    elif out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=boxes.device)
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    if n == 0:
+        return out
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the producer of boxes / count and the allocation of `out` on torch's stream come first
+        ok = resizer.ExecuteRoisDevToTensor(surfaces, boxes.data_ptr(), n, count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype],
+                                            [float(m) for m in mean], [float(v) for v in std], cc_ctx, bool(bgr), s2 * elem, s1 * elem,
+                                            (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (boxes.stride(0) if n > 1 else 5))
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out
+
+
 _WARP_MODES = {"constant": 0, "replicate": 1}
 
 

@@ -31,7 +31,7 @@ EXPORTS = [
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
-    "vpf_convert_letterbox_tensor", "vpf_letterbox_fit",
+    "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -90,6 +90,22 @@ class LetterboxIO(C.Structure):
 class LetterboxOpts(C.Structure):
     """vpf_letterbox_opts: the pad bytes per output channel"""
     _fields_ = [("pad", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class RoiDev(C.Structure):
+    """vpf_roi_dev: one box of vpf_convert_resize_tensor_rois_dev as it lies in DEVICE memory — a row of a torch.int32 [K, 5] tensor"""
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class FrameSrc(C.Structure):
+    """vpf_frame_src: the planes of one WHOLE source frame"""
+    _fields_ = [("src", Plane * 3)]
+
+
+class RoisDev(C.Structure):
+    """vpf_rois_dev: where the boxes and their count lie (device pointers), how many jobs the dispatch holds, job 0's planes and the stride"""
+    _fields_ = [("boxes", C.c_void_p), ("count", C.c_void_p), ("box_stride", C.c_uint32), ("max_n", C.c_uint32), ("dst", Plane * 3),
+                ("dst_job_stride", C.c_uint64)]
 
 
 class TensorNorm(C.Structure):
@@ -184,6 +200,7 @@ def lib() -> C.CDLL:
         L.vpf_convert_warp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(WarpIO), PN, C.POINTER(WarpOpts)]
         L.vpf_convert_letterbox_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(LetterboxIO), PN,
                                                    C.POINTER(LetterboxOpts)]
+        L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
         L.vpf_letterbox_fit.argtypes = [Size, Size]
         L.vpf_letterbox_fit.restype = Rect
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
@@ -371,6 +388,38 @@ def convert_resize_tensor_rois(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, rois, 
                                               C.byref(norm) if norm is not None else None)
     if check:
         _check(st, "vpf_convert_resize_tensor_rois")
+    return st
+
+
+def make_frame_srcs(frames) -> "C.Array[FrameSrc]":
+    """frames: list of src_desc as in planes(): the planes of each WHOLE frame"""
+    arr = (FrameSrc * len(frames))()
+    for i, s in enumerate(frames):
+        s = planes(s)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+    return arr
+
+
+def make_rois_dev(boxes_ptr, max_n, dst, dst_job_stride, count_ptr=None, box_stride=20) -> RoisDev:
+    """vpf_rois_dev: boxes_ptr / count_ptr are DEVICE addresses (count_ptr None: max_n jobs), dst = job 0's planes as in planes(), dst_job_stride =
+    bytes from one job's planes to the next's"""
+    t = RoisDev()
+    t.boxes, t.count, t.box_stride, t.max_n, t.dst_job_stride = boxes_ptr or None, count_ptr or None, box_stride, max_n, dst_job_stride
+    d = planes(dst)
+    for k in range(3):
+        t.dst[k].ptr, t.dst[k].pitch = d[k].ptr, d[k].pitch
+    return t
+
+
+def convert_resize_tensor_rois_dev(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, frames, table: RoisDev, norm: TensorNorm, n_frames=None, check=True) -> int:
+    """frames: FrameSrc array from make_frame_srcs() (at most 128), table: make_rois_dev(); the kernel reads boxes and count when it runs on
+    ex.stream: no sync, no copy, capturable"""
+    st = lib().vpf_convert_resize_tensor_rois_dev(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                                  (len(frames) if frames is not None else 0) if n_frames is None else n_frames, frames,
+                                                  C.byref(table) if table is not None else None, C.byref(norm) if norm is not None else None)
+    if check:
+        _check(st, "vpf_convert_resize_tensor_rois_dev")
     return st
 
 

@@ -229,6 +229,22 @@ public:
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorRois(a.data(), (uint32_t)a.size(), index.data(), rects.data(), (uint32_t)rois.size(), planes.data(), norm, cc.get());
   }
+  // additive: up to max_n rectangles that lie in DEVICE memory -> a normalised planar tensor [max_n, 3, dh, dw] at device address `dst`
+  // (vpf_convert_resize_tensor_rois_dev): entry k = five int32 (surface index, x, y, w, h) at boxes + k box_stride, *count (device int32; 0: max_n)
+  // of them valid; read by the kernel when it runs on the task's stream.  At most 128 surfaces; tensor layout and mean / std as ExecuteToTensor
+  bool ExecuteRoisDevToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t boxes, uint32_t max_n, uint64_t count, uint64_t dst, uint32_t dtype,
+                              const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr,
+                              uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last, uint32_t box_stride) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || src.size() > 128 || !boxes || !max_n || !dst) return false;
+    std::vector<vpf_plane> planes;  // two jobs' planes: the second minus the first is the stride from job to job
+    if (!tensor_planes(dst, dtype, 2, task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    const uint64_t job_stride = (uint64_t)((uintptr_t)planes[channels_last ? 1 : 3].ptr - (uintptr_t)planes[0].ptr);
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    return TASK_EXEC_SUCCESS == task_->RunTensorRoisDev(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)boxes, box_stride, max_n,
+                                                        (const void*)(uintptr_t)count, planes.data(), job_stride, norm, cc.get());
+  }
   // additive: K affine warps of surfaces -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_warp_tensor):
   // warps[i] = (surface index, m00, m01, m02, m10, m11, m12), the inverse matrix (destination pixel -> source luma pixel coordinates);
   // border per output channel, border_mode 0 = constant, 1 = replicate; tensor layout and mean / std as ExecuteToTensor
@@ -794,6 +810,15 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
            "K rectangles (surface_index, x, y, w, h) of the surfaces, each resized to the task's destination size and normalised, into a planar tensor "
            "[K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one dispatch per 96 regions")
+      .def("ExecuteRoisDevToTensor", &PySurfaceConvertResizer::ExecuteRoisDevToTensor, py::arg("surfaces"), py::arg("boxes_ptr"), py::arg("max_n"),
+           py::arg("count_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("row_stride") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::arg("box_stride") = 20u,
+           py::call_guard<py::gil_scoped_release>(),
+           "Up to max_n rectangles that lie in DEVICE memory: entry k = five int32 (surface_index, x, y, w, h) at boxes_ptr + k box_stride, the first "
+           "*count_ptr (a device int32; 0 = max_n) of them resized to the task's destination size and normalised into frame k of a planar tensor "
+           "[max_n, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous).  The kernel reads boxes and count when it runs on the task's "
+           "stream: no sync, no copy to the host, capturable.  An invalid box gives a frame of normalised zeros; frames at or behind the count are "
+           "not written.  At most 128 surfaces; one dispatch")
       .def("ExecuteWarpsToTensor", &PySurfaceConvertResizer::ExecuteWarpsToTensor, py::arg("surfaces"), py::arg("surface_index"), py::arg("matrices"),
            py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
            py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,

@@ -61,6 +61,12 @@ public:
   // and size, every job the task's destination size.  The same colour-context rules as RunTensor.
   TaskExecStatus RunTensorRois(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, uint32_t n,
                                const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
+  // up to max_n rectangles that lie in DEVICE memory (vpf_convert_resize_tensor_rois_dev): entry k = five int32 (frame index, x, y, w, h) at
+  // boxes + k box_stride, *count (device; nullptr: max_n) of them valid; the kernel reads both when it runs on the task's stream — no sync, no
+  // copy, capturable.  dst = the planes of job 0 (three; one with VPF_TENSOR_NHWC), job k's lie k dst_job_stride bytes further.  At most 128
+  // frames, each of the task's source format and size.  The same colour-context rules as RunTensor.
+  TaskExecStatus RunTensorRoisDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride, uint32_t max_n, const void* count,
+                                  const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
   // n affine warps of surfaces -> n frames of a normalised planar tensor (vpf_convert_warp_tensor): job i samples frames[frame_index[i]] through
   // the inverse matrix matrices[6 i .. 6 i + 5] (m00 m01 m02 m10 m11 m12: destination pixel -> source coordinates in luma pixels) and writes
   // dst[3 i .. 3 i + 2]; every surface has the task's source format and size, every job the task's destination size; opts == nullptr:

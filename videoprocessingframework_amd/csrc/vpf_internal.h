@@ -131,6 +131,28 @@ struct RoiArgs {
 };
 static_assert(sizeof(RoiDesc) == 96 && sizeof(RoiArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the ROI job table must not outgrow the largest frame table");
 
+// The arguments of a multi-ROI launch whose rectangles live in DEVICE memory (vpf_convert_resize_tensor_rois_dev, k_convert_roi_dev.hip): no job
+// table — the source planes of up to 128 frames (40 B each), where the boxes and their count lie, and job 0's destination planes with the stride
+// from job to job.  The kernel reads (frame, x, y, w, h) of job blockIdx.z when it runs.  5 224 B, below the largest argument block.
+constexpr int kRoiDevFrames = 128;
+struct FrameSrcDesc {
+  const uint8_t* s[3];
+  uint32_t sp[3];
+  uint32_t pad;
+};
+struct RoiDevArgs {
+  FrameSrcDesc f[kRoiDevFrames];
+  const int32_t* boxes;  // device: five ints per job, box_stride bytes apart
+  const int32_t* count;  // device, or null: max_n
+  uint8_t* d[3];         // job 0's planes (kernel channel order); job k's lie k * job_stride bytes further
+  uint64_t job_stride;
+  uint32_t dp[3];
+  uint32_t box_stride, max_n, n_frames;
+  TensorEpi e;
+};
+static_assert(sizeof(FrameSrcDesc) == 40 && sizeof(RoiDevArgs) == 128 * 40 + 104 && sizeof(RoiDevArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
+              "the device-ROI arguments must not outgrow the largest frame table");
+
 // The job table of a letterbox launch (vpf_convert_letterbox_tensor, k_convert_letterbox.hip): a RoiDesc — its scale factors are the rectangle's over
 // the PICTURE's size, (float)w / (float)iw — plus where the picture goes inside the destination plane.  The rectangle travels as four 32-bit fields:
 // 112 B per job, 82 jobs + the epilogue = 9 216 B, within the 9 248 B of BatchArgsTE<kMaxBatch>.  (Packed as 16-bit pairs — iw - 1, ih - 1: sizes
@@ -220,6 +242,10 @@ hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c,
 // and `te.pad` everywhere else: at most two dispatches (staged jobs, gather jobs); k_convert_letterbox.hip
 hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
                                     uint32_t dh, const TensorEpi& te, bool nhwc = false);
+// up to a.max_n jobs whose rectangles the kernel reads from device memory, on frames of W x H pixels -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of
+// dw x dh: ONE dispatch, every tile staged or per tap by its own window; a.e is set here; k_convert_roi_dev.hip
+hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
+                                          const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 

@@ -15,8 +15,10 @@
 
 #ifdef __HIPCC__
 #define VPF_JB_HD __host__ __device__ __forceinline__
+#define VPF_JB_HDI __host__ __device__ __forceinline__
 #else
 #define VPF_JB_HD
+#define VPF_JB_HDI inline  // (functions a translation unit may leave unused: no warning under -Wall)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -51,6 +53,64 @@ static inline RoiStripNeed roi_strip_need(uint32_t x, uint32_t w, uint32_t h, fl
 // the policy: staged where the window fits a strip that leaves three workgroups per CU and converts at most kRoiConvMax source pixels per
 // destination pixel; everything else gathers
 static inline bool roi_job_staged(const RoiStripNeed& need) { return need.bytes <= kRoiStripMax && need.conv <= kRoiConvMax; }
+
+// ------------------------------------------------------------------------------------------
+// Device-resident boxes (k_convert_roi_dev.hip, vpf_convert_resize_tensor_rois_dev).  The rectangle is read from device memory by the kernel, so what
+// the host entry checks before the launch and what its launcher decides per job happen in the kernel: the guard, and staged or per tap PER TILE.
+// ------------------------------------------------------------------------------------------
+// The guard: the ONLY thing between five untrusted ints and a read outside the frame.  Unsigned compares, no sums: w <= W before W - w, so no
+// operation can wrap.  (frame < 0 is a large unsigned number; n_frames <= 128.)
+static VPF_JB_HDI bool roi_dev_box_ok(int32_t frame, int32_t x, int32_t y, int32_t w, int32_t h, uint32_t n_frames, uint32_t W, uint32_t H) {
+  return (uint32_t)frame < n_frames && w >= 1 && h >= 1 && x >= 0 && y >= 0 && (uint32_t)w <= W && (uint32_t)h <= H && (uint32_t)x <= W - (uint32_t)w &&
+         (uint32_t)y <= H - (uint32_t)h;
+}
+// vpf_lin_i0 (= make_tap<LINEAR>'s i0) for host and device
+static VPF_JB_HDI uint32_t roi_lin_i0(uint32_t d, float scale, uint32_t size) {
+  float s = fmaf((float)d + 0.5f, scale, -0.5f);
+  s = fmaxf(s, 0.f);
+  s = fminf(s, (float)(size - 1));
+  return (uint32_t)(int32_t)s;
+}
+// The source window of ONE tile (destination columns xs .. xe, rows Y0 .. Y1) of a job: frame pixels first .. last of every row, rectangle rows
+// lo .. hi, and the strip that holds them (whole conversion units from the even pixel at or below `first`: the layout of k_roi_strip) — the
+// arithmetic roi_strip_need walks per chunk and per band.
+struct RoiTileWin {
+  uint32_t first, last, lo, hi;  // frame pixels | rectangle rows
+  uint32_t base_px, ng, rowbytes, rows;
+};
+static VPF_JB_HDI RoiTileWin roi_tile_window(uint32_t x, uint32_t w, uint32_t h, float scx, float scy, uint32_t xs, uint32_t xe, uint32_t Y0, uint32_t Y1) {
+  RoiTileWin t;
+  const uint32_t i0 = roi_lin_i0(xe, scx, w), hi0 = roi_lin_i0(Y1, scy, h);
+  t.first = x + roi_lin_i0(xs, scx, w);
+  t.last = x + (i0 + 1 < w ? i0 + 1 : w - 1);
+  t.lo = roi_lin_i0(Y0, scy, h);
+  t.hi = hi0 + 1 < h ? hi0 + 1 : h - 1;
+  t.base_px = t.first & ~1u;
+  t.ng = ((t.last - t.base_px) >> 3) + 1u;
+  t.rowbytes = 32u * t.ng + 16u;
+  t.rows = t.hi - t.lo + 1u;
+  return t;
+}
+// ... and what the policy looks at.  `conv` counts against the pixels a full tile of the job holds (min(dw, 256) x min(dh, 16)), as roi_strip_need's
+// does: over all tiles of a job the largest `bytes` is roi_strip_need's bytes and the largest `conv` its conv (rows and row bytes vary independently
+// over the grid of tiles; tests/test_rois_dev_bounds_cpu.py).
+static VPF_JB_HDI RoiStripNeed roi_tile_need_of(const RoiTileWin& t, uint32_t dw, uint32_t dh) {
+  const uint32_t cols = dw < 256 ? dw : 256, brows = dh < 4 * kRoiBandRows ? dh : 4 * kRoiBandRows;
+  return RoiStripNeed{t.rows * t.rowbytes, (double)t.rows * (t.rowbytes / 4) / ((double)cols * brows)};
+}
+static VPF_JB_HDI RoiStripNeed roi_tile_need(uint32_t x, uint32_t w, uint32_t h, float scx, float scy, uint32_t xs, uint32_t xe, uint32_t Y0, uint32_t Y1,
+                                            uint32_t dw, uint32_t dh) {
+  return roi_tile_need_of(roi_tile_window(x, w, h, scx, scy, xs, xe, Y0, Y1), dw, dh);
+}
+// A tile is staged when its strip fits the dynamic LDS of the dispatch and converts at most kRoiConvMax source pixels per destination pixel.
+// conv <= kRoiConvMax bounds the strip by 12 B x the pixels of a full tile, so a dispatch never needs more LDS than that (roi_dev_lds_bytes): small
+// destinations keep their occupancy although no strip is known at the launch.
+static VPF_JB_HDI bool roi_tile_staged(const RoiStripNeed& need, uint32_t lds_bytes) { return need.bytes <= lds_bytes && need.conv <= kRoiConvMax; }
+static inline uint32_t roi_dev_lds_bytes(uint32_t dw, uint32_t dh) {
+  const uint32_t cols = dw < 256 ? dw : 256, brows = dh < 4 * kRoiBandRows ? dh : 4 * kRoiBandRows;
+  const uint32_t cap = ((uint32_t)(kRoiConvMax * 4.0) * cols * brows + 15u) & ~15u;
+  return cap < kRoiStripMax ? cap : kRoiStripMax;
+}
 
 // ------------------------------------------------------------------------------------------
 // Letterbox (k_convert_letterbox.hip).  The ROI kernels' workgroup tile (16 rows x 256 columns), laid on the DESTINATION PLANE dw x dh; the picture
