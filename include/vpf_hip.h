@@ -427,6 +427,53 @@ VPF_API vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int src_fmt, in
                                            uint32_t n, const vpf_warp_io* jobs, const vpf_tensor_norm* norm, const vpf_warp_opts* opts);
 
 /*
+ * The same with the matrices in DEVICE memory: what stands behind a landmark network (face alignment) or an oriented-box head that runs on the GPU.
+ * No sync, no copy of the matrices to the host, and a captured graph replays with the matrices, frame indices and count of REPLAY time.
+ * `frames` is a HOST array of the planes of n_frames (1 .. 128) WHOLE frames of src_size = (W, H) (vpf_frame_src), consumed before return.
+ * table->matrices points to DEVICE memory: job k = six floats m00 m01 m02 m10 m11 m12 at byte k * matrix_stride (a row of a float32 [K, 2, 3] or
+ * [K, 6] tensor: matrix_stride = 24; any multiple of 4 from 24 up: padded tables); table->frame_index to job k's frame, one int32 at byte
+ * k * frame_stride (a multiple of 4 from 4 up), or NULL: every job samples frames[0]; table->count to ONE device int32, or NULL.  The kernel reads
+ * all three WHEN IT RUNS on exec->stream; the host never dereferences them: the caller orders their producer before this call on that stream (or
+ * makes the stream wait for it).
+ *   c = clamp(*count, 0, max_n); count == NULL: c = max_n.  max_n (1 .. 65535) is the size of the dispatch.
+ *   job k < c with a VALID entry — 0 <= frame < n_frames and fabsf(m) <= 2^24 for each of the six coefficients (vpf_convert_warp_tensor's rule: NaN
+ *        and the infinities fail it) —: every element of its planes is bit for bit what vpf_convert_warp_tensor writes for (frames[frame], m, planes
+ *        dst[c].ptr + k * dst_job_stride with dst[c].pitch), for the same src_fmt (NV12, YUV420, P10, P12), dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC
+ *        (dst[0] = the one interleaved plane of job 0), border mode, border and colour rules;
+ *   job k < c with an INVALID entry: every element of its planes takes the epilogue of border[c], round_to_dtype(fmaf(border[c], scale[c], bias[c]))
+ *        (0 0 0 when opts == NULL) — in BOTH border modes: what a valid job wholly outside the frame writes under VPF_WARP_CONSTANT.  No byte of
+ *        any frame is read;
+ *   job k >= c: NOTHING is written, and neither its matrix nor its frame index is read — the tables may be shorter than max_n.
+ * Nothing outside the planes of jobs < c is ever written.  One dispatch over (32 x 32 destination tiles, max_n); every workgroup decides for its own
+ * tile whether its source window is converted once into LDS or sampled per tap (identical bits).
+ * max_step is the LDS hint.  The host cannot see the matrices, so the caller bounds them: max_step >= |m00| + |m01| and >= |m10| + |m11|, the source
+ * pixels per destination pixel step (a crop rotated by 45 degrees at scale s: sqrt(2) s).  The dispatch takes the LDS that covers every tile of every
+ * such matrix with |m02| <= W, |m12| <= H, at most 64 KiB; max_step == 0: no hint, 64 KiB.  The hint is never a correctness input: a tile whose window
+ * outgrows the LDS it was given is sampled per tap, with identical bits — a wrong hint costs time, not pixels.
+ * Checked on the host before any device access, with the warp entry's answers: unsupported format / matrix / dtype / flag / border mode:
+ * VPF_ERR_UNSUPPORTED; null pointers (exec, frames, table, table->matrices, norm), bad sizes, short source pitches, misaligned source (P10 / P12) or
+ * destination planes, non-finite scale / bias, non-zero reserved fields, n_frames outside 1 .. 128, max_n outside 1 .. 65535, matrices, frame_index or
+ * count not 4-byte aligned, matrix_stride < 24 or not a multiple of 4, frame_stride < 4 or not a multiple of 4 (with a frame_index), dst_job_stride
+ * not a multiple of the element size, max_step negative or not finite: VPF_ERR_BAD_ARG.  Whatever the device tables hold, the call returns VPF_OK.
+ * Under stream capture the frame and destination pointers are baked into the graph, as in every entry; matrices, frame indices and count are read at
+ * every replay.
+ */
+typedef struct vpf_warps_dev {
+  const float* matrices;      /* DEVICE: job k = six floats m00 m01 m02 m10 m11 m12 at byte k * matrix_stride */
+  const int32_t* frame_index; /* DEVICE: job k's frame at byte k * frame_stride; NULL = every job samples frames[0] */
+  const int32_t* count;       /* DEVICE: one int32, or NULL = max_n */
+  uint32_t matrix_stride;     /* >= 24, multiple of 4 (a row of a float32 [K, 2, 3] / [K, 6] tensor: 24) */
+  uint32_t frame_stride;      /* >= 4, multiple of 4; ignored when frame_index == NULL */
+  uint32_t max_n;             /* 1 .. 65535: grid z */
+  float max_step;             /* LDS hint, see above; 0 = none */
+  vpf_plane dst[3];           /* planes of job 0 (one plane with VPF_TENSOR_NHWC) */
+  uint64_t dst_job_stride;    /* bytes from job k's planes to job k + 1's: multiple of the element size */
+} vpf_warps_dev; /* 96 bytes, no implicit padding */
+VPF_API vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size, vpf_size dst_size,
+                                               uint32_t n_frames, const vpf_frame_src* frames, const vpf_warps_dev* table, const vpf_tensor_norm* norm,
+                                               const vpf_warp_opts* opts);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

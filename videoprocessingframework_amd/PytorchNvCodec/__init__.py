@@ -493,6 +493,126 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
     return out
 
 
+def rotated_boxes_to_warps(boxes_cxcywha, dw, dh) -> torch.Tensor:
+    """An oriented detector's boxes [K, 5] (cx, cy, w, h, angle in radians; frame pixels with pixel centres at index + 0.5) -> the float32 [K, 2, 3]
+    inverse matrices device_warps_to_normalized_tensor (and warps_to_normalized_tensor) take for a dw x dh destination.  Pure torch, on whatever
+    device the boxes live on: no sync.  The resize convention: destination pixel (dx, dy) samples
+      u = (dx + 0.5) w / dw - w / 2,  v = (dy + 0.5) h / dh - h / 2,  sx = cx + u cos a - v sin a - 0.5,  sy = cy + u sin a + v cos a - 0.5
+    so m00 = (w / dw) cos a, m01 = -(h / dh) sin a, m10 = (w / dw) sin a, m11 = (h / dh) cos a and m02, m12 the constants that remain.  A row with a
+    non-finite value gives a non-finite matrix: an invalid job, whose output frame is the normalised border."""
+    b = torch.as_tensor(boxes_cxcywha)
+    if b.dim() != 2 or b.shape[1] != 5 or not b.dtype.is_floating_point:
+        raise ValueError(f"rotated_boxes_to_warps: boxes must be a float tensor of shape [K, 5], got {b.dtype} {tuple(b.shape)}")
+    dw, dh = int(dw), int(dh)
+    if dw < 1 or dh < 1:
+        raise ValueError("rotated_boxes_to_warps: dw and dh must be at least 1")
+    b = b.to(torch.float32)
+    cx, cy, w, h, a = b.unbind(dim=1)
+    ax, ay = w / dw, h / dh                      # source pixels per destination pixel along the box's own axes
+    cos, sin = torch.cos(a), torch.sin(a)
+    m00, m01, m10, m11 = ax * cos, -(ay * sin), ax * sin, ay * cos
+    u0, v0 = 0.5 * ax - 0.5 * w, 0.5 * ay - 0.5 * h  # u, v of destination pixel (0, 0)
+    m02 = cx + u0 * cos - v0 * sin - 0.5
+    m12 = cy + u0 * sin + v0 * cos - 0.5
+    return torch.stack([m00, m01, m02, m10, m11, m12], dim=1).reshape(-1, 2, 3)
+
+
+def device_warps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, surface_index=None, count=None, max_step=None, dtype=torch.float32, bgr=False,
+                                      border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
+    """warps_to_normalized_tensor for matrices that never leave the GPU (PySurfaceConvertResizer.ExecuteWarpsDevToTensor, vpf_convert_warp_tensor_dev):
+    no synchronisation, no copy of the matrices to the host, one dispatch, and the call can be captured in a graph that replays with the matrices,
+    surface indices and count of replay time.
+    `matrices`: a device torch.float32 tensor [K, 2, 3] or [K, 6] whose six elements per job are contiguous (any row stride of at least 6: a slice of a
+    wider tensor works), e.g. rotated_boxes_to_warps(...) of a detector's output; `surface_index`: a device torch.int32 tensor [K] (any stride), or
+    None: every job samples surfaces[0]; `count`: a device torch.int32 tensor of ONE element (how many rows are valid), or None for all K.
+    `max_step`: a bound on |m00| + |m01| and |m10| + |m11| (source pixels per destination pixel step; sqrt(2) s for a 45 degree crop at scale s) that
+    sizes the kernel's LDS; None: the 64 KiB default.  It never changes a pixel.  At most 128 surfaces, K at most 65535.  Returns [K, 3, dh, dw]:
+      rows below the count with a valid job    the bits warps_to_normalized_tensor gives for that matrix;
+      rows below the count with an invalid job (a coefficient that is not finite or exceeds 2^24, no such surface)   the normalised border in both
+                                               modes: no surface is read;
+      rows at or behind the count              NOT WRITTEN: undefined in a fresh tensor (torch.empty), unchanged in `out`.
+    The kernel reads the tables when it runs; this function orders it behind torch's current stream, where their producer ran.  border, border_mode,
+    `out`, channels_last, dtype, bgr, the returned tensor and the stream ordering: as warps_to_normalized_tensor.  ValueError for matrices,
+    surface_index or count on the host or on another device than each other or `out`, another dtype or shape."""
+    fn = "device_warps_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    if border_mode not in _WARP_MODES:
+        raise ValueError(f"{fn}: border_mode must be one of {list(_WARP_MODES)}, got {border_mode!r}")
+    try:
+        border = [operator.index(v) for v in border]
+    except TypeError:
+        raise ValueError(f"{fn}: border must hold three integers, got {border!r}") from None
+    if len(border) != 3 or any(not 0 <= v <= 255 for v in border):
+        raise ValueError(f"{fn}: border must hold three values in 0..255, got {border}")
+    surfaces = list(surfaces)
+    if not 1 <= len(surfaces) <= 128:
+        raise ValueError(f"{fn}: 1 .. 128 surfaces per call, got {len(surfaces)}")
+    if not isinstance(matrices, torch.Tensor) or not matrices.is_cuda:
+        raise ValueError(f"{fn}: matrices must be a device tensor (for host matrices there is warps_to_normalized_tensor)")
+    if matrices.dtype != torch.float32 or not ((matrices.dim() == 3 and tuple(matrices.shape[1:]) == (2, 3)) or (matrices.dim() == 2 and matrices.shape[1] == 6)):
+        raise ValueError(f"{fn}: matrices must be torch.float32 of shape [K, 2, 3] or [K, 6], got {matrices.dtype} {tuple(matrices.shape)}")
+    n = matrices.shape[0]
+    if n > 65535:
+        raise ValueError(f"{fn}: at most 65535 matrices per call, got {n}")
+    inner = matrices.stride()[1:]
+    if inner != ((3, 1) if matrices.dim() == 3 else (1,)) or (n > 1 and matrices.stride(0) < 6):
+        raise ValueError(f"{fn}: the six elements of a matrix must be contiguous and the row stride at least 6, got strides {matrices.stride()}")
+    if surface_index is not None:
+        if not isinstance(surface_index, torch.Tensor) or not surface_index.is_cuda or surface_index.dtype != torch.int32 or tuple(surface_index.shape) != (n,):
+            raise ValueError(f"{fn}: surface_index must be a device torch.int32 tensor of shape [{n}], or None")
+        if surface_index.device != matrices.device:
+            raise ValueError(f"{fn}: surface_index lives on {surface_index.device}, matrices on {matrices.device}")
+        if n > 1 and surface_index.stride(0) < 1:
+            raise ValueError(f"{fn}: surface_index needs a positive stride, got {surface_index.stride()}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1:
+            raise ValueError(f"{fn}: count must be a device torch.int32 tensor of one element, or None")
+        if count.device != matrices.device:
+            raise ValueError(f"{fn}: count lives on {count.device}, matrices on {matrices.device}")
+    if max_step is None:
+        max_step = 0.0
+    max_step = float(max_step)
+    if not (max_step >= 0.0 and max_step < float("inf")):
+        raise ValueError(f"{fn}: max_step must be finite and not negative, got {max_step}")
+    w, h = resizer.DstSize()
+    if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != matrices.device:
+        raise ValueError(f"{fn}: out lives on {out.device}, matrices on {matrices.device}")
+    if channels_last:
+        with torch.cuda.device(matrices.device):
+            out = _channels_last_out(fn, out, n, h, w, dtype)
+    elif out is None:
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=matrices.device)
+    else:
+        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        s0, s1, s2, s3 = out.stride()
+        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
+            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    if n == 0:
+        return out
+    elem = out.element_size()
+    s0, s1, s2, _ = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
+    with torch.cuda.device(out.device):
+        cur = torch.cuda.current_stream()
+        rs = int(resizer.Stream())
+        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
+        if side is not None:
+            side.wait_stream(cur)  # the producer of the tables and the allocation of `out` on torch's stream come first
+        ok = resizer.ExecuteWarpsDevToTensor(surfaces, matrices.data_ptr(), n, surface_index.data_ptr() if surface_index is not None else 0,
+                                             count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean],
+                                             [float(v) for v in std], cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem,
+                                             (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (matrices.stride(0) if n > 1 else 6),
+                                             4 * (surface_index.stride(0) if surface_index is not None and n > 1 else 1), max_step)
+        if side is not None:
+            cur.wait_stream(side)
+    if not ok:
+        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+    return out
+
+
 def _dst_rects_list(dst_rects, n, w, h, fn):
     """dst_rects -> list of n 4-tuples of Python ints inside the w x h destination: ValueError for a device tensor, a non-integer dtype, another
     length than the rois', an empty rectangle or one that leaves the destination"""

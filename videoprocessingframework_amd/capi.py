@@ -31,7 +31,7 @@ EXPORTS = [
     "vpf_status_string", "vpf_version", "vpf_device_count", "vpf_set_tuning", "vpf_trace_push", "vpf_trace_pop",
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
-    "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev",
+    "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -106,6 +106,13 @@ class RoisDev(C.Structure):
     """vpf_rois_dev: where the boxes and their count lie (device pointers), how many jobs the dispatch holds, job 0's planes and the stride"""
     _fields_ = [("boxes", C.c_void_p), ("count", C.c_void_p), ("box_stride", C.c_uint32), ("max_n", C.c_uint32), ("dst", Plane * 3),
                 ("dst_job_stride", C.c_uint64)]
+
+
+class WarpsDev(C.Structure):
+    """vpf_warps_dev: where the matrices, their frame indices and the count lie (device pointers), how many jobs the dispatch holds, the LDS hint, job 0's
+    planes and the stride"""
+    _fields_ = [("matrices", C.c_void_p), ("frame_index", C.c_void_p), ("count", C.c_void_p), ("matrix_stride", C.c_uint32), ("frame_stride", C.c_uint32),
+                ("max_n", C.c_uint32), ("max_step", C.c_float), ("dst", Plane * 3), ("dst_job_stride", C.c_uint64)]
 
 
 class TensorNorm(C.Structure):
@@ -201,6 +208,8 @@ def lib() -> C.CDLL:
         L.vpf_convert_letterbox_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(LetterboxIO), PN,
                                                    C.POINTER(LetterboxOpts)]
         L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
+        L.vpf_convert_warp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(WarpsDev), PN,
+                                                  C.POINTER(WarpOpts)]
         L.vpf_letterbox_fit.argtypes = [Size, Size]
         L.vpf_letterbox_fit.restype = Rect
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
@@ -508,4 +517,28 @@ def tensor_convert_batch(ex: Exec, dst_fmt, cs, cr, w, h, batch, denorm: TensorN
     st = lib().vpf_tensor_convert_batch(C.byref(ex), dst_fmt, cs, cr, Size(w, h), len(batch) if n is None else n, batch, C.byref(denorm))
     if check:
         _check(st, "vpf_tensor_convert_batch")
+    return st
+
+
+def make_warps_dev(matrices_ptr, max_n, dst, dst_job_stride, frame_index_ptr=None, count_ptr=None, matrix_stride=24, frame_stride=4, max_step=0.0) -> WarpsDev:
+    """vpf_warps_dev: matrices_ptr / frame_index_ptr / count_ptr are DEVICE addresses (frame_index_ptr None: every job samples frame 0; count_ptr None:
+    max_n jobs), dst = job 0's planes as in planes(), dst_job_stride = bytes from one job's planes to the next's, max_step = the LDS hint (0: none)"""
+    t = WarpsDev()
+    t.matrices, t.frame_index, t.count = matrices_ptr or None, frame_index_ptr or None, count_ptr or None
+    t.matrix_stride, t.frame_stride, t.max_n, t.max_step, t.dst_job_stride = matrix_stride, frame_stride, max_n, max_step, dst_job_stride
+    d = planes(dst)
+    for k in range(3):
+        t.dst[k].ptr, t.dst[k].pitch = d[k].ptr, d[k].pitch
+    return t
+
+
+def convert_warp_tensor_dev(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, frames, table: WarpsDev, norm: TensorNorm, opts=None, n_frames=None, check=True) -> int:
+    """frames: FrameSrc array from make_frame_srcs() (at most 128), table: make_warps_dev(), opts: make_warp_opts() or None; the kernel reads matrices,
+    frame indices and count when it runs on ex.stream: no sync, no copy, capturable"""
+    st = lib().vpf_convert_warp_tensor_dev(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                           (len(frames) if frames is not None else 0) if n_frames is None else n_frames, frames,
+                                           C.byref(table) if table is not None else None, C.byref(norm) if norm is not None else None,
+                                           C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_warp_tensor_dev")
     return st

@@ -274,6 +274,32 @@ public:
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorWarps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
   }
+  // additive: up to max_n affine warps whose matrices lie in DEVICE memory -> a normalised planar tensor [max_n, 3, dh, dw] at device address `dst`
+  // (vpf_convert_warp_tensor_dev): job k = six float32 at matrices + k matrix_stride, its surface index one int32 at index + k index_stride (index 0:
+  // surface 0), *count (device int32; 0: max_n) of them valid; read by the kernel when it runs on the task's stream.  max_step: the LDS hint (0: none).
+  // At most 128 surfaces; border, border_mode, tensor layout and mean / std as ExecuteWarpsToTensor
+  bool ExecuteWarpsDevToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t matrices, uint32_t max_n, uint64_t index, uint64_t count, uint64_t dst,
+                               uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc,
+                               bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode, uint64_t row_pitch, uint64_t plane_stride,
+                               uint64_t frame_stride, bool channels_last, uint32_t matrix_stride, uint32_t index_stride, float max_step) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || src.size() > 128 || !matrices || !max_n || !dst) return false;
+    std::vector<vpf_plane> planes;  // two jobs' planes: the second minus the first is the stride from job to job
+    if (!tensor_planes(dst, dtype, 2, task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    const uint64_t job_stride = (uint64_t)((uintptr_t)planes[channels_last ? 1 : 3].ptr - (uintptr_t)planes[0].ptr);
+    vpf_warp_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    opts.border_mode = border_mode;
+    for (int c = 0; c < 3; c++) {
+      if (border[c] < 0 || border[c] > 255) return false;
+      opts.border[c] = (uint8_t)border[c];
+    }
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    return TASK_EXEC_SUCCESS == task_->RunTensorWarpsDev(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)matrices, matrix_stride, (const void*)(uintptr_t)index,
+                                                         index_stride, max_n, (const void*)(uintptr_t)count, max_step, planes.data(), job_stride, norm, &opts,
+                                                         cc.get());
+  }
   // additive: K letterbox jobs -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_letterbox_tensor): rois[i] as
   // ExecuteRoisToTensor, dst_rects[i] = (ix, iy, iw, ih) where that region's picture goes inside dw x dh, `pad` (per output channel) everywhere else;
   // std::invalid_argument (ValueError) for a pad value outside 0..255 and for rois / dst_rects of different lengths
@@ -819,6 +845,18 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "[max_n, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous).  The kernel reads boxes and count when it runs on the task's "
            "stream: no sync, no copy to the host, capturable.  An invalid box gives a frame of normalised zeros; frames at or behind the count are "
            "not written.  At most 128 surfaces; one dispatch")
+      .def("ExecuteWarpsDevToTensor", &PySurfaceConvertResizer::ExecuteWarpsDevToTensor, py::arg("surfaces"), py::arg("matrices_ptr"), py::arg("max_n"),
+           py::arg("index_ptr"), py::arg("count_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
+           py::arg("bgr") = false, py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0,
+           py::arg("plane_stride") = 0, py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::arg("matrix_stride") = 24u,
+           py::arg("index_stride") = 4u, py::arg("max_step") = 0.0f, py::call_guard<py::gil_scoped_release>(),
+           "Up to max_n affine warps whose matrices lie in DEVICE memory: job k = six float32 (m00 m01 m02 m10 m11 m12) at matrices_ptr + k matrix_stride, "
+           "its surface index one int32 at index_ptr + k index_stride (0 = every job samples surface 0), the first *count_ptr (a device int32; 0 = max_n) "
+           "of them warped to the task's destination size and normalised into frame k of a planar tensor [max_n, 3, dh, dw] at device address ptr (strides "
+           "in bytes, 0 = contiguous).  The kernel reads matrices, indices and count when it runs on the task's stream: no sync, no copy to the host, "
+           "capturable.  An invalid job (a coefficient that is not finite or exceeds 2^24, no such surface) gives a frame of the normalised border; frames "
+           "at or behind the count are not written.  max_step: the caller's bound on |m00| + |m01| and |m10| + |m11| that sizes the LDS (0 = none).  At "
+           "most 128 surfaces; one dispatch")
       .def("ExecuteWarpsToTensor", &PySurfaceConvertResizer::ExecuteWarpsToTensor, py::arg("surfaces"), py::arg("surface_index"), py::arg("matrices"),
            py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
            py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,

@@ -1,6 +1,7 @@
 // The body of k_warp_strip / k_warp_strip_nhwc (k_convert_warp.hip), included into both with DST = FC_TENSOR / FC_TENSOR_NHWC in scope: the text
 // stands in the kernel itself, so the planar kernel's code object is what it was before the second destination class existed.
-  const WarpDesc& J = args.j[blockIdx.z];
+// Also the body of k_warp_dev / k_warp_dev_nhwc (k_convert_warp_dev.hip) behind their prologue.  In scope: J (the job: a WarpDesc), args.e, c, W, H, dw,
+// dh, dmask, lds_bytes.
   const FrameDesc& f = J.f;
   const TensorEpi te = args.e;
   const bool rep = warp_rep(te);

@@ -576,6 +576,41 @@ TaskExecStatus ConvertResizeSurface::RunTensorRoisDev(Surface* const* frames, ui
   }
   return TASK_EXEC_SUCCESS;
 }
+TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride,
+                                                       const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count, float max_step,
+                                                       const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
+                                                       const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorWarpsDev");
+  if (!frames || !n_frames || n_frames > 128u || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  std::vector<vpf_frame_src> fr(n_frames);
+  for (uint32_t i = 0; i < n_frames; i++) {
+    Surface* s = frames[i];
+    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
+    std::memset(&fr[i], 0, sizeof(fr[i]));
+    fill_planes(s, fr[i].src);
+  }
+  vpf_warps_dev table;
+  std::memset(&table, 0, sizeof(table));
+  table.matrices = static_cast<const float*>(matrices);
+  table.frame_index = static_cast<const int32_t*>(frame_index);
+  table.count = static_cast<const int32_t*>(count);
+  table.matrix_stride = matrix_stride;
+  table.frame_stride = frame_stride;
+  table.max_n = max_n;
+  table.max_step = max_step;
+  for (int k = 0; k < ((norm.flags & VPF_TENSOR_NHWC) ? 1 : 3); k++) table.dst[k] = dst[k];
+  table.dst_job_stride = dst_job_stride;
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_warp_tensor_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames, fr.data(),
+                                                    &table, &norm, opts);
+  if (st != VPF_OK) {
+    std::cerr << "Failed to warp device-resident regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+    return TASK_EXEC_FAIL;
+  }
+  return TASK_EXEC_SUCCESS;
+}
 TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                                     const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
                                                     const ColorspaceConversionContext* cc) {

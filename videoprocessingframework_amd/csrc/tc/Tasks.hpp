@@ -67,6 +67,14 @@ public:
   // frames, each of the task's source format and size.  The same colour-context rules as RunTensor.
   TaskExecStatus RunTensorRoisDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride, uint32_t max_n, const void* count,
                                   const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const ColorspaceConversionContext* ctx);
+  // up to max_n affine warps whose matrices lie in DEVICE memory (vpf_convert_warp_tensor_dev): job k = six floats at matrices + k matrix_stride, its
+  // frame index one int32 at frame_index + k frame_stride (nullptr: frame 0), *count (device; nullptr: max_n) of them valid; the kernel reads all
+  // three when it runs on the task's stream — no sync, no copy, capturable.  max_step: the caller's bound on |m00| + |m01| and |m10| + |m11| that
+  // sizes the LDS (0: none).  dst = the planes of job 0 (three; one with VPF_TENSOR_NHWC), job k's lie k dst_job_stride bytes further.  At most 128
+  // frames, each of the task's source format and size; opts as RunTensorWarps.  The same colour-context rules as RunTensor.
+  TaskExecStatus RunTensorWarpsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride, const void* frame_index,
+                                   uint32_t frame_stride, uint32_t max_n, const void* count, float max_step, const vpf_plane* dst, uint64_t dst_job_stride,
+                                   const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
   // n affine warps of surfaces -> n frames of a normalised planar tensor (vpf_convert_warp_tensor): job i samples frames[frame_index[i]] through
   // the inverse matrix matrices[6 i .. 6 i + 5] (m00 m01 m02 m10 m11 m12: destination pixel -> source coordinates in luma pixels) and writes
   // dst[3 i .. 3 i + 2]; every surface has the task's source format and size, every job the task's destination size; opts == nullptr:

@@ -746,6 +746,62 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
   return VPF_OK;
 }
 
+// The same with the matrices, their frame indices and the count in DEVICE memory (include/vpf_hip.h): every check that needs no matrix happens here,
+// the matrix check in the kernel (k_convert_warp_dev.hip); one dispatch.
+vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames,
+                                       const vpf_warps_dev* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
+  const Mark mark("vpf_convert_warp_tensor_dev");
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
+  if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
+  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
+  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
+  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  if (!table->matrices || (((uintptr_t)table->matrices | (uintptr_t)table->frame_index | (uintptr_t)table->count) & 3u) || table->matrix_stride < 24u ||
+      (table->matrix_stride & 3u) || (table->frame_index && (table->frame_stride < 4u || (table->frame_stride & 3u))) ||
+      (table->dst_job_stride & (elem - 1)) || !(table->max_step >= 0.f) || !std::isfinite(table->max_step))
+    return VPF_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n_frames; i++) {
+    if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
+    for (int k = 0; k < num_planes(sf); k++)
+      if (frames[i].src[k].reserved) return VPF_ERR_BAD_ARG;
+  }
+  if (!tensor_planes_ok(table->dst, nhwc, ds.width, elem, true)) return VPF_ERR_BAD_ARG;
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their border bytes here
+  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
+  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
+  if (opts) {
+    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->border[bgr ? 2 - k : k] << (8 * k);
+    te.pad |= opts->border_mode << 24;
+  }
+  WarpDevArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (uint32_t i = 0; i < n_frames; i++)
+    for (int k = 0; k < num_planes(sf); k++) { a.f[i].s[k] = static_cast<const uint8_t*>(frames[i].src[k].ptr); a.f[i].sp[k] = frames[i].src[k].pitch; }
+  vpf_plane d[3];
+  const int nd = tensor_planes(table->dst, nhwc, bgr, d);
+  for (int k = 0; k < nd; k++) { a.d[k] = static_cast<uint8_t*>(d[k].ptr); a.dp[k] = d[k].pitch; }
+  a.matrices = table->matrices;
+  a.frame_index = table->frame_index;
+  a.count = table->count;
+  a.job_stride = table->dst_job_stride;
+  a.matrix_stride = table->matrix_stride; a.frame_stride = table->frame_index ? table->frame_stride : 0u; a.max_n = table->max_n; a.n_frames = n_frames;
+  return status_of(launch_convert_warp_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height,
+                                           table->max_step, te, nhwc));
+}
+
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
 int vpf_tensor_convert_supported(int df, int cs, int cr) {
   return (df == VPF_FMT_NV12 || df == VPF_FMT_YUV420) && classify(VPF_FMT_RGB_PLANAR, VPF_FMT_YUV420, cs, cr) == FAM_RGB2YUV;

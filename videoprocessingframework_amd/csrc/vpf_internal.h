@@ -186,6 +186,24 @@ struct WarpArgs {
 };
 static_assert(sizeof(WarpDesc) == 96 && sizeof(WarpArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the warp job table must not outgrow the largest frame table");
 
+// The arguments of a warp launch whose matrices live in DEVICE memory (vpf_convert_warp_tensor_dev, k_convert_warp_dev.hip): the shape of RoiDevArgs —
+// the source planes of up to 128 frames, where the matrices, the frame indices and the count lie, and job 0's destination planes with the stride
+// from job to job.  The kernel reads (frame, m[6]) of job blockIdx.z when it runs.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
+// 5 240 B, below the largest argument block.
+struct WarpDevArgs {
+  FrameSrcDesc f[kRoiDevFrames];
+  const float* matrices;       // device: six floats per job, matrix_stride bytes apart
+  const int32_t* frame_index;  // device: one int per job, frame_stride bytes apart; null: every job samples f[0]
+  const int32_t* count;        // device, or null: max_n
+  uint8_t* d[3];               // job 0's planes (kernel channel order); job k's lie k * job_stride bytes further
+  uint64_t job_stride;
+  uint32_t dp[3];
+  uint32_t matrix_stride, frame_stride, max_n, n_frames, pad;
+  TensorEpi e;
+};
+static_assert(sizeof(WarpDevArgs) == 128 * 40 + 120 && sizeof(WarpDevArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
+              "the device-warp arguments must not outgrow the largest frame table");
+
 // The prologue of a tensor -> NV12 / YUV420 launch (vpf_tensor_convert): q[c] = rint(clamp(x[c] * scale[c] + bias[c], 0, 255)) feeds the RGB -> YUV
 // arithmetic.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
 struct TensorPro {
@@ -246,6 +264,11 @@ hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoe
 // dw x dh: ONE dispatch, every tile staged or per tap by its own window; a.e is set here; k_convert_roi_dev.hip
 hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
                                           const TensorEpi& te, bool nhwc = false);
+// up to a.max_n jobs whose matrices the kernel reads from device memory, on frames of W x H pixels -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of
+// dw x dh: ONE dispatch, every tile staged or per tap by its own window; `max_step` sizes the dynamic LDS (warp_dev_lds_bytes, vpf_job_bounds.h);
+// `te.pad` carries border and mode; a.e is set here; k_convert_warp_dev.hip
+hipError_t launch_convert_warp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
+                                   float max_step, const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 

@@ -5,7 +5,9 @@
 //   ROI   roi_strip_need: the largest workgroup strip of a job, WALKED with the kernel's own fp32 tap arithmetic, and the policy's two limits
 //   letterbox  letterbox_strip_need: the same walk over tiles laid on the destination plane and clipped to the picture (k_convert_letterbox.hip;
 //         tests/test_letterbox_bounds_cpu.py through tests/c/letterbox_bounds_capi.cpp)
-//   warp  warp_xy / warp_window / warp_strip: what the kernel computes per tile; warp_need: the launcher's closed-form bound over all tiles
+//   warp  warp_xy / warp_window / warp_strip: what the kernel computes per tile; warp_need: the launcher's closed-form bound over all tiles;
+//         warp_dev_job_ok / warp_dev_lds_bytes: the guard and the LDS bound of the device-table form (k_convert_warp_dev.hip;
+//         tests/test_warps_dev_bounds_cpu.py through tests/c/warp_dev_bounds_capi.cpp)
 #ifndef VPF_JOB_BOUNDS_H_
 #define VPF_JOB_BOUNDS_H_
 #include <math.h>
@@ -232,6 +234,37 @@ static inline WarpNeed warp_need(const float m[6], uint32_t W, uint32_t H, uint3
   const uint32_t ng_max = ((W - 1) >> 3) + 1;
   ng = ng < ng_max ? ng : ng_max;
   return WarpNeed{rows * (32u * ng + 16u)};
+}
+
+// ------------------------------------------------------------------------------------------
+// Device-resident matrices (k_convert_warp_dev.hip, vpf_convert_warp_tensor_dev).  The kernel reads (frame, m[6]) of its job from device memory, so the
+// host entry's check of the matrix happens in the kernel, and the launcher sizes the LDS without a matrix.
+// ------------------------------------------------------------------------------------------
+// The guard: the ONLY thing between untrusted device memory and a read outside a frame.  One unsigned compare (frame < 0 is a large unsigned number;
+// n_frames <= 128) and the host entry's six: NaN and the infinities fail `<=`.  With every |m| <= 2^24 and dx, dy <= 65535, sx and sy are finite (at
+// most 2^41 in magnitude), the range test and the clamps work on ordinary numbers and every tap lies inside the frame (include/vpf_hip.h).
+static VPF_JB_HDI bool warp_dev_job_ok(int32_t frame, const float* m, uint32_t n_frames) {
+  bool ok = (uint32_t)frame < n_frames;
+  for (int k = 0; k < 6; k++) ok = ok && fabsf(m[k]) <= 0x1p24f;
+  return ok;
+}
+// The dynamic LDS of a dispatch whose matrices nobody has seen, from the caller's hint `max_step` >= |m00| + |m01|, |m10| + |m11| (source pixels per
+// destination pixel step) and |m02| <= W, |m12| <= H: warp_need's bound over every such matrix.  warp_need_count is convex in (|r0|, |r1|) before its
+// floor, so over the L1 ball of radius max_step it is largest at a vertex: the rows (max_step, 0) and (0, max_step).  Capped at kWarpStripMax, which
+// is also the answer without a hint (max_step == 0).  Never a correctness input: a tile whose strip exceeds the LDS it was given samples per tap
+// (k_convert_warp_strip_body.h), with identical bits.
+static inline uint32_t warp_dev_lds_bytes(float max_step, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  if (!(max_step > 0.f)) return kWarpStripMax;
+  const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
+  const float rx[2][3] = {{max_step, 0.f, (float)W}, {0.f, max_step, (float)W}}, ry[2][3] = {{max_step, 0.f, (float)H}, {0.f, max_step, (float)H}};
+  const uint32_t nx0 = warp_need_count(rx[0], W, tw, th, dw, dh), nx1 = warp_need_count(rx[1], W, tw, th, dw, dh);
+  const uint32_t ny0 = warp_need_count(ry[0], H, tw, th, dw, dh), ny1 = warp_need_count(ry[1], H, tw, th, dw, dh);
+  const uint32_t nx = nx0 > nx1 ? nx0 : nx1, rows = ny0 > ny1 ? ny0 : ny1;
+  uint32_t ng = (nx >> 3) + 1;
+  const uint32_t ng_max = ((W - 1) >> 3) + 1;
+  ng = ng < ng_max ? ng : ng_max;
+  const uint64_t bytes = (uint64_t)rows * (32u * ng + 16u);
+  return bytes < kWarpStripMax ? (uint32_t)bytes : kWarpStripMax;
 }
 
 #endif  // VPF_JOB_BOUNDS_H_
