@@ -13,6 +13,7 @@ torch is plumbing here (allocation, streams); no pixel arithmetic happens in thi
 from __future__ import annotations
 
 import operator
+import sys
 from typing import TYPE_CHECKING, overload
 
 import torch
@@ -151,14 +152,61 @@ def _channels_last_strides(fn, t, what):
     return (s0 if n > 1 else 0), (s2 if h > 1 else 0)
 
 
-def _channels_last_out(fn, out, n, h, w, dtype):
-    """the destination of a channels_last=True call: a new [n, 3, h, w] tensor in torch.channels_last memory format, or the checked `out`"""
-    if out is None:
-        return torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()), memory_format=torch.channels_last)
-    if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
+def _tensor_out(fn, out, n, h, w, dtype, channels_last, device=None):
+    """the destination of a *_to_normalized_tensor call and its (frame, plane, row) strides in elements: the checked `out`, or a new [n, 3, h, w] tensor
+    on `device` (None: torch's current device), in torch.channels_last memory format when channels_last says so (the plane stride is 0 then)"""
+    given = out is not None
+    if not given:
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        out = torch.empty((n, 3, h, w), dtype=dtype, device=device, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    elif out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
         raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    _channels_last_strides(fn, out, "out")
-    return out
+    s0, s1, s2, s3 = out.stride()
+    if channels_last:
+        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
+    elif given and (s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0):
+        raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    return out, s0, s1, s2
+
+
+class _on_task_stream:
+    """Context manager: under torch.cuda.device(device) the body runs between two waits.  The stream of `task` (a resizer / converter) waits for
+    torch's current stream — the allocation, the producers and the earlier users of the tensors come first —, and torch's current stream then waits
+    for what the body put on the task's (not after an exception).  `as` gives the task's stream, or None when it IS torch's current stream and there
+    is nothing to order.  (A class, not a contextlib generator: that costs a microsecond per call, 5 % of a device-table call.)"""
+    __slots__ = ("task", "guard", "cur", "side")
+
+    def __init__(self, task, device):
+        self.task, self.guard = task, torch.cuda.device(device)
+
+    def __enter__(self):
+        self.guard.__enter__()
+        try:
+            self.cur = torch.cuda.current_stream()
+            ts = int(self.task.Stream())
+            self.side = torch.cuda.ExternalStream(ts) if ts != self.cur.cuda_stream else None
+            if self.side is not None:
+                self.side.wait_stream(self.cur)
+        except BaseException:
+            self.guard.__exit__(*sys.exc_info())  # never leave the caller on another device
+            raise
+        return self.side
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            if exc_type is None and self.side is not None:
+                self.cur.wait_stream(self.side)
+        finally:
+            self.guard.__exit__(exc_type, exc, tb)
+        return False
+
+
+_RESIZER_REFUSED = "the surfaces do not match the resizer (format / size) or the colour context was refused"
+_CONVERTER_REFUSED = "the surfaces do not match the converter (format / size), the tensor layout was refused or the colour context was refused"
+
+
+def _refused(fn, why):
+    raise RuntimeError(f"{fn}: {why}")
 
 
 def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=False, out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
@@ -182,36 +230,15 @@ def to_normalized_tensor(resizer, surfaces, mean, std, dtype=torch.float32, bgr=
     surfaces = list(surfaces)
     n = len(surfaces)
     w, h = resizer.DstSize()
-    if channels_last:
-        out = _channels_last_out("to_normalized_tensor", out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"to_normalized_tensor: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} "
-                             f"{tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"to_normalized_tensor: out needs unit stride along W and non-overlapping rows, planes and frames, got strides "
-                             f"{out.stride()}")
+    out, s0, s1, s2 = _tensor_out("to_normalized_tensor", out, n, h, w, dtype, channels_last)
     if n == 0:
         return out
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides("to_normalized_tensor", out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteToTensor(surfaces, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
                                      bool(bgr), s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError("to_normalized_tensor: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused("to_normalized_tensor", _RESIZER_REFUSED)
     return out
 
 
@@ -267,34 +294,15 @@ def rois_to_normalized_tensor(resizer, surfaces, rois, mean, std, dtype=torch.fl
     jobs = _rois_list(rois, surfaces, fn)
     n = len(jobs)
     w, h = resizer.DstSize()
-    if channels_last:
-        out = _channels_last_out(fn, out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last)
     if n == 0:
         return out
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteRoisToTensor(surfaces, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
                                          bool(bgr), s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused(fn, _RESIZER_REFUSED)
     return out
 
 
@@ -362,36 +370,16 @@ def device_rois_to_normalized_tensor(resizer, surfaces, boxes, mean, std, count=
     w, h = resizer.DstSize()
     if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != boxes.device:
         raise ValueError(f"{fn}: out lives on {out.device}, boxes on {boxes.device}")
-    if channels_last:
-        with torch.cuda.device(boxes.device):
-            out = _channels_last_out(fn, out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=boxes.device)
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last, boxes.device)
     if n == 0:
         return out
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the producer of boxes / count and the allocation of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteRoisDevToTensor(surfaces, boxes.data_ptr(), n, count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype],
                                             [float(m) for m in mean], [float(v) for v in std], cc_ctx, bool(bgr), s2 * elem, s1 * elem,
                                             (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (boxes.stride(0) if n > 1 else 5))
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused(fn, _RESIZER_REFUSED)
     return out
 
 
@@ -462,34 +450,15 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
             raise ValueError(f"{fn}: surface_index[{i}] names surface {k}, there are {len(surfaces)}")
     n = len(jobs)
     w, h = resizer.DstSize()
-    if channels_last:
-        out = _channels_last_out(fn, out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last)
     if n == 0:
         return out
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteWarpsToTensor(surfaces, index, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
                                           cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused(fn, _RESIZER_REFUSED)
     return out
 
 
@@ -578,38 +547,18 @@ def device_warps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, su
     w, h = resizer.DstSize()
     if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != matrices.device:
         raise ValueError(f"{fn}: out lives on {out.device}, matrices on {matrices.device}")
-    if channels_last:
-        with torch.cuda.device(matrices.device):
-            out = _channels_last_out(fn, out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=matrices.device)
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last, matrices.device)
     if n == 0:
         return out
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the producer of the tables and the allocation of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteWarpsDevToTensor(surfaces, matrices.data_ptr(), n, surface_index.data_ptr() if surface_index is not None else 0,
                                              count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean],
                                              [float(v) for v in std], cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem,
                                              (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (matrices.stride(0) if n > 1 else 6),
                                              4 * (surface_index.stride(0) if surface_index is not None and n > 1 else 1), max_step)
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused(fn, _RESIZER_REFUSED)
     return out
 
 
@@ -686,34 +635,15 @@ def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_
     else:
         rects = _dst_rects_list(dst_rects, n, w, h, fn)
     placement = torch.tensor(rects, dtype=torch.int64).reshape(n, 4)
-    if channels_last:
-        out = _channels_last_out(fn, out, n, h, w, dtype)
-    elif out is None:
-        out = torch.empty((n, 3, h, w), dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-    else:
-        if out.dtype != dtype or not out.is_cuda or tuple(out.shape) != (n, 3, h, w):
-            raise ValueError(f"{fn}: out must be a {dtype} device tensor of shape {(n, 3, h, w)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        s0, s1, s2, s3 = out.stride()
-        if s3 != 1 or s2 < w or (h > 1 and s1 < h * s2) or (n > 1 and s0 < 3 * s1) or min(s0, s1, s2) <= 0:
-            raise ValueError(f"{fn}: out needs unit stride along W and non-overlapping rows, planes and frames, got strides {out.stride()}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last)
     if n == 0:
         return out, placement
     elem = out.element_size()
-    s0, s1, s2, _ = out.stride()
-    if channels_last:
-        (s0, s2), s1 = _channels_last_strides(fn, out, "out"), 0
-    with torch.cuda.device(out.device):
-        cur = torch.cuda.current_stream()
-        rs = int(resizer.Stream())
-        side = torch.cuda.ExternalStream(rs) if rs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # the allocation / earlier users of `out` on torch's stream come first
+    with _on_task_stream(resizer, out.device):
         ok = resizer.ExecuteLetterboxToTensor(surfaces, jobs, rects, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
                                               cc_ctx, bool(bgr), pad, s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
-        if side is not None:
-            cur.wait_stream(side)
     if not ok:
-        raise RuntimeError(f"{fn}: the surfaces do not match the resizer (format / size) or the colour context was refused")
+        _refused(fn, _RESIZER_REFUSED)
     return out, placement
 
 
@@ -769,20 +699,14 @@ def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None,
     if n == 0:
         return []
     elem = tensor.element_size()
-    with torch.cuda.device(tensor.device):
-        if out is None:
+    if out is None:
+        with torch.cuda.device(tensor.device):
             out = [nvc.Surface.Make(converter.Format(), w, h, dev if dev >= 0 else tensor.device.index) for _ in range(n)]
-        cur = torch.cuda.current_stream()
-        cs = int(converter.Stream())
-        side = torch.cuda.ExternalStream(cs) if cs != cur.cuda_stream else None
-        if side is not None:
-            side.wait_stream(cur)  # whatever produced `tensor` on torch's stream comes first
+    with _on_task_stream(converter, tensor.device) as side:
         ok = converter.ExecuteBatch(tensor.data_ptr(), out, _TENSOR_DTYPES[tensor.dtype], [float(m) for m in mean], [float(v) for v in std], cc_ctx,
                                     bool(bgr), s2 * elem, (0 if channels_last else s1) * elem, s0 * elem, bool(channels_last))
         if side is not None:
-            cur.wait_stream(side)
             tensor.record_stream(side)  # the caching allocator must not hand the tensor's memory out before the converter has read it
     if not ok:
-        raise RuntimeError("from_normalized_tensor: the surfaces do not match the converter (format / size), the tensor layout was refused or "
-                           "the colour context was refused")
+        _refused("from_normalized_tensor", _CONVERTER_REFUSED)
     return out

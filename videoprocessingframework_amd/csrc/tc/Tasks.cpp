@@ -191,6 +191,34 @@ void fill_planes(Surface* s, vpf_plane out[3]) {
   }
 }
 
+// The batch entries of the fused tensor path (ConvertResizeSurface::RunTensor*, TensorToSurface::RunTensorBatch) share these four.
+constexpr uint32_t kMaxDevFrames = 128;  // the frame table of the device-table entries (include/vpf_hip.h: n_frames 1 .. 128)
+// all n surfaces are there, hold memory and are what the task was built for
+static bool surfaces_match(Surface* const* s, uint32_t n, Pixel_Format fmt, uint32_t w, uint32_t h) {
+  for (uint32_t i = 0; i < n; i++)
+    if (!s[i] || s[i]->Empty() || s[i]->PixelFormat() != fmt || s[i]->Width() != w || s[i]->Height() != h) return false;
+  return true;
+}
+// the tensor planes of frame / job i in the caller's flat table: with VPF_TENSOR_NHWC one interleaved plane per job, else three
+static void tensor_job_planes(const vpf_plane* table, uint32_t i, const vpf_tensor_norm& norm, vpf_plane out[3]) {
+  if (norm.flags & VPF_TENSOR_NHWC) out[0] = table[i];
+  else for (int k = 0; k < 3; k++) out[k] = table[3 * i + k];
+}
+static std::vector<vpf_frame_src> frame_srcs(Surface* const* frames, uint32_t n) {
+  std::vector<vpf_frame_src> fr(n);
+  for (uint32_t i = 0; i < n; i++) {
+    std::memset(&fr[i], 0, sizeof(fr[i]));
+    fill_planes(frames[i], fr[i].src);
+  }
+  return fr;
+}
+// the library's answer as the task's: "Failed to <what>. Error code: ..." on stderr for anything but VPF_OK
+static TaskExecStatus exec_status(vpf_status st, const char* what) {
+  if (st == VPF_OK) return TASK_EXEC_SUCCESS;
+  std::cerr << "Failed to " << what << ". Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
+  return TASK_EXEC_FAIL;
+}
+
 // How each reference impl turns the optional ColorspaceConversionContext into a matrix, and what it rejects.
 enum CtxRule {
   RULE_NONE,         // context ignored (pure re-layout)
@@ -499,23 +527,17 @@ TaskExecStatus ConvertResizeSurface::RunTensor(Surface* const* ins, uint32_t n, 
   if (!ins || !dst || !n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(ins, n, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
   std::vector<vpf_frame_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
-    Surface* s = ins[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
-    fill_planes(s, io[i].src);
-    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
-    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    fill_planes(ins[i], io[i].src);
+    tensor_job_planes(dst, i, norm, io[i].dst);
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_resize_tensor_batch(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
                                                         io.data(), &norm);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to convert + resize surfaces into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "convert + resize surfaces into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, uint32_t n,
                                                    const vpf_plane* dst, const vpf_tensor_norm& norm, const ColorspaceConversionContext* cc) {
@@ -523,74 +545,52 @@ TaskExecStatus ConvertResizeSurface::RunTensorRois(Surface* const* frames, uint3
   if (!frames || !n_frames || !frame_index || !rects || !dst || !n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  for (uint32_t i = 0; i < n_frames; i++) {
-    Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
-  }
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
   std::vector<vpf_roi_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
     if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(frames[frame_index[i]], io[i].src);
-    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
-    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    tensor_job_planes(dst, i, norm, io[i].dst);
     io[i].rect = rects[i];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_resize_tensor_rois(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
                                                        io.data(), &norm);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to convert + resize regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "convert + resize regions into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorRoisDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride, uint32_t max_n,
                                                       const void* count, const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm,
                                                       const ColorspaceConversionContext* cc) {
   const HipMark tick("ConvertResizeSurface::RunTensorRoisDev");
-  if (!frames || !n_frames || n_frames > 128u || !boxes || !dst || !max_n) return TASK_EXEC_FAIL;
+  if (!frames || !n_frames || n_frames > kMaxDevFrames || !boxes || !dst || !max_n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  std::vector<vpf_frame_src> fr(n_frames);
-  for (uint32_t i = 0; i < n_frames; i++) {
-    Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
-    std::memset(&fr[i], 0, sizeof(fr[i]));
-    fill_planes(s, fr[i].src);
-  }
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
   vpf_rois_dev table;
   std::memset(&table, 0, sizeof(table));
   table.boxes = static_cast<const vpf_roi_dev*>(boxes);
   table.count = static_cast<const int32_t*>(count);
   table.box_stride = box_stride;
   table.max_n = max_n;
-  for (int k = 0; k < ((norm.flags & VPF_TENSOR_NHWC) ? 1 : 3); k++) table.dst[k] = dst[k];
+  tensor_job_planes(dst, 0, norm, table.dst);
   table.dst_job_stride = dst_job_stride;
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_resize_tensor_rois_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames,
                                                            fr.data(), &table, &norm);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to convert + resize device-resident regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "convert + resize device-resident regions into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride,
                                                        const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count, float max_step,
                                                        const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
                                                        const ColorspaceConversionContext* cc) {
   const HipMark tick("ConvertResizeSurface::RunTensorWarpsDev");
-  if (!frames || !n_frames || n_frames > 128u || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
+  if (!frames || !n_frames || n_frames > kMaxDevFrames || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  std::vector<vpf_frame_src> fr(n_frames);
-  for (uint32_t i = 0; i < n_frames; i++) {
-    Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
-    std::memset(&fr[i], 0, sizeof(fr[i]));
-    fill_planes(s, fr[i].src);
-  }
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
   vpf_warps_dev table;
   std::memset(&table, 0, sizeof(table));
   table.matrices = static_cast<const float*>(matrices);
@@ -600,16 +600,12 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, u
   table.frame_stride = frame_stride;
   table.max_n = max_n;
   table.max_step = max_step;
-  for (int k = 0; k < ((norm.flags & VPF_TENSOR_NHWC) ? 1 : 3); k++) table.dst[k] = dst[k];
+  tensor_job_planes(dst, 0, norm, table.dst);
   table.dst_job_stride = dst_job_stride;
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_warp_tensor_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames, fr.data(),
                                                     &table, &norm, opts);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to warp device-resident regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "warp device-resident regions into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                                     const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
@@ -618,27 +614,19 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
   if (!frames || !n_frames || !frame_index || !matrices || !dst || !n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  for (uint32_t i = 0; i < n_frames; i++) {
-    Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
-  }
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
   std::vector<vpf_warp_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
     if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(frames[frame_index[i]], io[i].src);
-    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
-    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    tensor_job_planes(dst, i, norm, io[i].dst);
     for (int k = 0; k < 6; k++) io[i].m[k] = matrices[6 * i + k];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_warp_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(),
                                                 &norm, opts);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to warp regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "warp regions into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects,
                                                         const vpf_rect* dst_rects, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm,
@@ -647,28 +635,20 @@ TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, 
   if (!frames || !n_frames || !frame_index || !rects || !dst_rects || !dst || !n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  for (uint32_t i = 0; i < n_frames; i++) {
-    Surface* s = frames[i];
-    if (!s || s->Empty() || s->PixelFormat() != pImpl->in || s->Width() != pImpl->sw || s->Height() != pImpl->sh) return TASK_EXEC_FAIL;
-  }
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
   std::vector<vpf_letterbox_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
     if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
     fill_planes(frames[frame_index[i]], io[i].src);
-    if (norm.flags & VPF_TENSOR_NHWC) io[i].dst[0] = dst[i];  // one interleaved plane per frame / job
-    else for (int k = 0; k < 3; k++) io[i].dst[k] = dst[3 * i + k];
+    tensor_job_planes(dst, i, norm, io[i].dst);
     io[i].rect = rects[i];
     io[i].dst_rect = dst_rects[i];
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_letterbox_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
                                                      io.data(), &norm, opts);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to letterbox regions into a tensor. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "letterbox regions into a tensor");
 }
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
@@ -722,22 +702,16 @@ TaskExecStatus TensorToSurface::RunTensorBatch(const vpf_plane* src, Surface* co
   if (!src || !outs || !n) return TASK_EXEC_FAIL;
   int cs, cr;
   if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(outs, n, pImpl->out_fmt, pImpl->w, pImpl->h)) return TASK_EXEC_FAIL;
   std::vector<vpf_frame_io> io(n);
   for (uint32_t i = 0; i < n; i++) {
-    Surface* d = outs[i];
-    if (!d || d->Empty() || d->PixelFormat() != pImpl->out_fmt || d->Width() != pImpl->w || d->Height() != pImpl->h) return TASK_EXEC_FAIL;
     std::memset(&io[i], 0, sizeof(io[i]));
-    if (denorm.flags & VPF_TENSOR_NHWC) io[i].src[0] = src[i];  // one interleaved plane per frame
-    else for (int k = 0; k < 3; k++) io[i].src[k] = src[3 * i + k];
-    fill_planes(d, io[i].dst);
+    tensor_job_planes(src, i, denorm, io[i].src);
+    fill_planes(outs[i], io[i].dst);
   }
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_tensor_convert_batch(&ex, pImpl->out_fmt, cs, cr, vpf_size{pImpl->w, pImpl->h}, n, io.data(), &denorm);
-  if (st != VPF_OK) {
-    std::cerr << "Failed to convert tensors into surfaces. Error code: " << st << " (" << vpf_status_string(st) << ")" << std::endl;
-    return TASK_EXEC_FAIL;
-  }
-  return TASK_EXEC_SUCCESS;
+  return exec_status(st, "convert tensors into surfaces");
 }
 
 // ------------------------------------------------------------------------------------------ ResizeSurface

@@ -164,9 +164,12 @@ static int tensor_src_class(int f) {
     default: return -1;
   }
 }
-// planes_ok, and for the 16-bit formats 2-B aligned pointers and pitches
-static bool tensor_src_ok(int f, uint32_t w, const vpf_plane* p) {
+// planes_ok, for the 16-bit formats 2-B aligned pointers and pitches, and where the entry says so (the warp entries) zero `reserved` fields
+static bool tensor_src_ok(int f, uint32_t w, const vpf_plane* p, bool reserved_zero = false) {
   if (!planes_ok(f, w, p)) return false;
+  if (reserved_zero)
+    for (int k = 0; k < num_planes(f); k++)
+      if (p[k].reserved) return false;
   if (f == VPF_FMT_P10 || f == VPF_FMT_P12)
     for (int k = 0; k < 2; k++)
       if (((uintptr_t)p[k].ptr | p[k].pitch) & 1) return false;
@@ -231,6 +234,85 @@ static vpf_status status_of(hipError_t e) {
   return VPF_ERR_LAUNCH;
 }
 
+// one frame's planes as the batch entries take them: the single-frame entries are their batch entry with n = 1
+static vpf_frame_io single_frame(const vpf_plane* src, int ns, const vpf_plane* dst, int nd) {
+  vpf_frame_io io;
+  std::memset(&io, 0, sizeof(io));
+  for (int k = 0; k < ns; k++) io.src[k] = src[k];
+  for (int k = 0; k < nd; k++) io.dst[k] = dst[k];
+  return io;
+}
+// a non-empty rectangle inside a picture of `size` (64-bit sums: x + width may pass 2^32); nothing is clipped silently
+static bool rect_inside(const vpf_rect& r, vpf_size size) {
+  return r.width && r.height && (uint64_t)r.x + r.width <= size.width && (uint64_t)r.y + r.height <= size.height;
+}
+
+// ------------------------------------------------------------------------------------------
+// the tensor entries' host path: what every entry asks of its vpf_tensor_norm, and what the kernels get of it
+// ------------------------------------------------------------------------------------------
+// The refusals that come between the source format's and the pointers', in the order the entries have always had: no norm, an unknown dtype or
+// flag, then what the entry's own options refuse (unsupported before bad), and only then a non-finite scale or bias — options BEFORE finiteness.
+static vpf_status norm_status(const vpf_tensor_norm* norm, bool opts_unsupported = false, bool opts_bad = false) {
+  if (!norm) return VPF_ERR_BAD_ARG;
+  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
+  if (opts_unsupported) return VPF_ERR_UNSUPPORTED;
+  if (opts_bad) return VPF_ERR_BAD_ARG;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  return VPF_OK;
+}
+struct TensorLayout {
+  uint32_t elem;  // bytes per element
+  bool nhwc, bgr;
+};
+static TensorLayout layout_of(const vpf_tensor_norm& norm) {
+  return TensorLayout{norm.dtype == VPF_TENSOR_F32 ? 4u : 2u, (norm.flags & VPF_TENSOR_NHWC) != 0, (norm.flags & VPF_TENSOR_BGR) != 0};
+}
+// the kernels give channel k (R G B) parameter k: B G R order swaps the parameters of channels 0 and 2 (and tensor_planes() their planes)
+static void kernel_scale_bias(const vpf_tensor_norm& norm, float scale[3], float bias[3]) {
+  const bool bgr = layout_of(norm).bgr;
+  for (int k = 0; k < 3; k++) { scale[k] = norm.scale[bgr ? 2 - k : k]; bias[k] = norm.bias[bgr ? 2 - k : k]; }
+}
+// The planes of a tensor frame or job: three of `width` elements per row, or with VPF_TENSOR_NHWC the ONE interleaved plane p[0] of 3 x width
+// elements per row (p[1], p[2] are not looked at).  Pointers and pitches are multiples of the element size.
+static bool tensor_planes_ok(const vpf_plane* p, const TensorLayout& l, uint32_t width, bool reserved_zero = false) {
+  for (int k = 0; k < (l.nhwc ? 1 : 3); k++) {
+    if (!p[k].ptr || (reserved_zero && p[k].reserved) || (uint64_t)p[k].pitch < (uint64_t)width * l.elem * (l.nhwc ? 3u : 1u) ||
+        (((uintptr_t)p[k].ptr | p[k].pitch) & (l.elem - 1)))
+      return false;
+  }
+  return true;
+}
+// the planes the kernels take: kernel channel k (R G B) -> plane k, B G R order swaps planes 0 and 2; NHWC: the one plane (the kernel swaps slots)
+static int tensor_planes(const vpf_plane* p, const TensorLayout& l, vpf_plane out[3]) {
+  if (l.nhwc) { out[0] = p[0]; return 1; }
+  for (int k = 0; k < 3; k++) out[k] = p[l.bgr ? 2 - k : k];
+  return 3;
+}
+// the device-table entries (vpf_*_dev): the whole frames the jobs sample, and job 0's destination planes in kernel channel order
+static void fill_frame_srcs(FrameSrcDesc* f, const vpf_frame_src* frames, uint32_t n_frames, int ns) {
+  for (uint32_t i = 0; i < n_frames; i++)
+    for (int k = 0; k < ns; k++) { f[i].s[k] = static_cast<const uint8_t*>(frames[i].src[k].ptr); f[i].sp[k] = frames[i].src[k].pitch; }
+}
+static void fill_job0_dst(uint8_t* d[3], uint32_t dp[3], const vpf_plane* dst, const TensorLayout& l) {
+  vpf_plane p[3];
+  const int nd = tensor_planes(dst, l, p);
+  for (int k = 0; k < nd; k++) { d[k] = static_cast<uint8_t*>(p[k].ptr); dp[k] = p[k].pitch; }
+}
+// The epilogue of a tensor launch.  `fill`: the three pad (letterbox) or border (warp) bytes per OUTPUT channel, swapped like the parameters, or
+// null for zeros; `mode`: the warp's border mode, bits 24 .. 31 of TensorEpi::pad.
+static TensorEpi make_epi(const vpf_tensor_norm& norm, const uint8_t* fill = nullptr, uint32_t mode = 0u) {
+  const TensorLayout l = layout_of(norm);
+  TensorEpi te;
+  std::memset(&te, 0, sizeof(te));
+  kernel_scale_bias(norm, te.scale, te.bias);
+  te.dtype = norm.dtype | (l.nhwc && l.bgr ? kEpiSwapRB : 0u);
+  if (fill)
+    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)fill[l.bgr ? 2 - k : k] << (8 * k);
+  te.pad |= mode << 24;
+  return te;
+}
+
 }  // namespace vpf
 
 using namespace vpf;
@@ -281,10 +363,7 @@ vpf_status vpf_convert(const vpf_exec* exec, int sf, int df, int cs, int cr, vpf
                        const vpf_plane dst[3]) {
   if (classify(sf, df, cs, cr) == FAM_NONE) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
-  vpf_frame_io io;
-  std::memset(&io, 0, sizeof(io));
-  for (int k = 0; k < num_planes(sf); k++) io.src[k] = src[k];
-  for (int k = 0; k < num_planes(df); k++) io.dst[k] = dst[k];
+  const vpf_frame_io io = single_frame(src, num_planes(sf), dst, num_planes(df));
   return vpf_convert_batch(exec, sf, df, cs, cr, size, 1, &io);
 }
 
@@ -357,9 +436,7 @@ vpf_status vpf_resize(const vpf_exec* exec, int fmt, int interp, vpf_size ss, co
   bool f32 = false;
   if (!resize_jobs(fmt, vpf_size{2, 2}, vpf_size{2, 2}, probe, &f32)) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
-  vpf_frame_io io;
-  std::memset(&io, 0, sizeof(io));
-  for (int k = 0; k < num_planes(fmt); k++) { io.src[k] = src[k]; io.dst[k] = dst[k]; }
+  const vpf_frame_io io = single_frame(src, num_planes(fmt), dst, num_planes(fmt));
   return vpf_resize_batch(exec, fmt, interp, ss, ds, 1, &io);
 }
 
@@ -452,28 +529,8 @@ vpf_status vpf_convert_resize(const vpf_exec* exec, int sf, int df, int cs, int 
                               vpf_size ds, const vpf_plane dst[3]) {
   if (!(sf == VPF_FMT_NV12 || sf == VPF_FMT_YUV420) || rgb_class(df) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
-  vpf_frame_io io;
-  std::memset(&io, 0, sizeof(io));
-  for (int k = 0; k < num_planes(sf); k++) io.src[k] = src[k];
-  for (int k = 0; k < num_planes(df); k++) io.dst[k] = dst[k];
+  const vpf_frame_io io = single_frame(src, num_planes(sf), dst, num_planes(df));
   return vpf_convert_resize_batch(exec, sf, df, cs, cr, ss, ds, 1, &io);
-}
-
-// The planes of a tensor frame or job: three of `width` elements per row, or with VPF_TENSOR_NHWC the ONE interleaved plane p[0] of 3 x width
-// elements per row (p[1], p[2] are not looked at).  Pointers and pitches are multiples of the element size.
-static bool tensor_planes_ok(const vpf_plane* p, bool nhwc, uint32_t width, uint32_t elem, bool reserved_zero = false) {
-  for (int k = 0; k < (nhwc ? 1 : 3); k++) {
-    if (!p[k].ptr || (reserved_zero && p[k].reserved) || (uint64_t)p[k].pitch < (uint64_t)width * elem * (nhwc ? 3u : 1u) ||
-        (((uintptr_t)p[k].ptr | p[k].pitch) & (elem - 1)))
-      return false;
-  }
-  return true;
-}
-// the planes the kernels take: kernel channel k (R G B) -> plane k, B G R order swaps planes 0 and 2; NHWC: the one plane (the kernel swaps slots)
-static int tensor_planes(const vpf_plane* p, bool nhwc, bool bgr, vpf_plane out[3]) {
-  if (nhwc) { out[0] = p[0]; return 1; }
-  for (int k = 0; k < 3; k++) out[k] = p[bgr ? 2 - k : k];
-  return 3;
 }
 
 // The planar-tensor form of the fused path (include/vpf_hip.h): the RGB_PLANAR bytes through one fp32 fma per channel, stored as f32 / f16 / bf16.
@@ -481,38 +538,29 @@ vpf_status vpf_convert_resize_tensor_batch(const vpf_exec* exec, int sf, int cs,
                                            const vpf_frame_io* frames, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_batch");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm)) return refused;
   if (!exec || !frames || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   for (uint32_t i = 0; i < n; i++) {
     if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
-    if (!tensor_planes_ok(frames[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(frames[i].dst, l, ds.width)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
-  const uint32_t per = frames_per_dispatch(frame_bytes(sf, ss) + 3ull * ds.width * ds.height * elem, true);  // the tensor's real bytes: 4x the 8-bit planes for f32
+  const TensorEpi te = make_epi(*norm);
+  const uint32_t per = frames_per_dispatch(frame_bytes(sf, ss) + 3ull * ds.width * ds.height * l.elem, true);  // the tensor's real bytes: 4x the 8-bit planes for f32
   for (uint32_t base = 0; base < n; base += per) {
     const uint32_t m = (n - base < per) ? n - base : per;
     BatchArgsL a;
     for (uint32_t i = 0; i < m; i++) {
       vpf_plane d[3];
-      const int nd = tensor_planes(frames[base + i].dst, nhwc, bgr, d);
+      const int nd = tensor_planes(frames[base + i].dst, l, d);
       fill_desc(a.f[i], frames[base + i].src, num_planes(sf), d, nd);
     }
     for (uint32_t i = m; i < ((m + 7u) & ~7u); i++) a.f[i] = a.f[0];
-    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), nhwc ? FC_TENSOR_NHWC : FC_TENSOR, c, ss.width, ss.height, m, a,
+    const hipError_t e = launch_convert_resize(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), l.nhwc ? FC_TENSOR_NHWC : FC_TENSOR, c, ss.width, ss.height, m, a,
                                                ds.width, ds.height, &te);
     if (e != hipSuccess) return status_of(e);
   }
@@ -523,10 +571,7 @@ vpf_status vpf_convert_resize_tensor(const vpf_exec* exec, int sf, int cs, int c
                                      const vpf_plane dst[3], const vpf_tensor_norm* norm) {
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
-  vpf_frame_io io;
-  std::memset(&io, 0, sizeof(io));
-  for (int k = 0; k < num_planes(sf); k++) io.src[k] = src[k];
-  for (int k = 0; k < 3; k++) io.dst[k] = dst[k];
+  const vpf_frame_io io = single_frame(src, num_planes(sf), dst, 3);
   return vpf_convert_resize_tensor_batch(exec, sf, cs, cr, ss, ds, 1, &io, norm);
 }
 
@@ -536,42 +581,32 @@ vpf_status vpf_convert_resize_tensor_rois(const vpf_exec* exec, int sf, int cs, 
                                           const vpf_roi_io* rois, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_rois");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm)) return refused;
   if (!exec || !rois || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   for (uint32_t i = 0; i < n; i++) {
-    const vpf_rect& r = rois[i].rect;
-    if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
+    if (!rect_inside(rois[i].rect, ss)) return VPF_ERR_BAD_ARG;
     if (!tensor_src_ok(sf, ss.width, rois[i].src)) return VPF_ERR_BAD_ARG;
-    if (!tensor_planes_ok(rois[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(rois[i].dst, l, ds.width)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
+  const TensorEpi te = make_epi(*norm);
   RoiDesc jobs[kRoiBatch];
   for (uint32_t base = 0; base < n; base += kRoiBatch) {
     const uint32_t m = (n - base < (uint32_t)kRoiBatch) ? n - base : (uint32_t)kRoiBatch;
     for (uint32_t i = 0; i < m; i++) {
       const vpf_roi_io& io = rois[base + i];
       vpf_plane d[3];
-      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
+      const int nd = tensor_planes(io.dst, l, d);
       RoiDesc& j = jobs[i];
       fill_desc(j.f, io.src, num_planes(sf), d, nd);
       j.x = io.rect.x; j.y = io.rect.y; j.w = io.rect.width; j.h = io.rect.height;
       j.scx = (float)j.w / (float)ds.width; j.scy = (float)j.h / (float)ds.height;
     }
-    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te, nhwc);
+    const hipError_t e = launch_convert_resize_rois(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, jobs, ds.width, ds.height, te, l.nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -583,42 +618,30 @@ vpf_status vpf_convert_resize_tensor_rois_dev(const vpf_exec* exec, int sf, int 
                                               const vpf_frame_src* frames, const vpf_rois_dev* table, const vpf_tensor_norm* norm) {
   const Mark mark("vpf_convert_resize_tensor_rois_dev");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm)) return refused;
   if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   if (!table->boxes || (((uintptr_t)table->boxes | (uintptr_t)table->count) & 3u) || table->box_stride < sizeof(vpf_roi_dev) || (table->box_stride & 3u) ||
-      (table->dst_job_stride & (elem - 1)))
+      (table->dst_job_stride & (l.elem - 1)))
     return VPF_ERR_BAD_ARG;
   for (uint32_t i = 0; i < n_frames; i++)
     if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
-  if (!tensor_planes_ok(table->dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
+  if (!tensor_planes_ok(table->dst, l, ds.width)) return VPF_ERR_BAD_ARG;
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
+  const TensorEpi te = make_epi(*norm);
   RoiDevArgs a;
   std::memset(&a, 0, sizeof(a));
-  for (uint32_t i = 0; i < n_frames; i++)
-    for (int k = 0; k < num_planes(sf); k++) { a.f[i].s[k] = static_cast<const uint8_t*>(frames[i].src[k].ptr); a.f[i].sp[k] = frames[i].src[k].pitch; }
-  vpf_plane d[3];
-  const int nd = tensor_planes(table->dst, nhwc, bgr, d);
-  for (int k = 0; k < nd; k++) { a.d[k] = static_cast<uint8_t*>(d[k].ptr); a.dp[k] = d[k].pitch; }
+  fill_frame_srcs(a.f, frames, n_frames, num_planes(sf));
+  fill_job0_dst(a.d, a.dp, table->dst, l);
   a.boxes = reinterpret_cast<const int32_t*>(table->boxes);
   a.count = table->count;
   a.job_stride = table->dst_job_stride;
   a.box_stride = table->box_stride; a.max_n = table->max_n; a.n_frames = n_frames;
-  return status_of(launch_convert_resize_rois_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height, te, nhwc));
+  return status_of(launch_convert_resize_rois_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height, te, l.nhwc));
 }
 
 // The aspect-preserving placement of a w x h picture inside dw x dh (include/vpf_hip.h): integers only, 64-bit products.
@@ -646,47 +669,33 @@ vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, in
                                         const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts) {
   const Mark mark("vpf_convert_letterbox_tensor");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm, false, opts && opts->reserved)) return refused;
   if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   for (uint32_t i = 0; i < n; i++) {
-    const vpf_rect &r = jobs[i].rect, &d = jobs[i].dst_rect;
-    if (!r.width || !r.height || (uint64_t)r.x + r.width > ss.width || (uint64_t)r.y + r.height > ss.height) return VPF_ERR_BAD_ARG;  // no silent clipping
-    if (!d.width || !d.height || (uint64_t)d.x + d.width > ds.width || (uint64_t)d.y + d.height > ds.height) return VPF_ERR_BAD_ARG;  // ... on either side
+    if (!rect_inside(jobs[i].rect, ss) || !rect_inside(jobs[i].dst_rect, ds)) return VPF_ERR_BAD_ARG;
     if (!tensor_src_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
-    if (!tensor_planes_ok(jobs[i].dst, nhwc, ds.width, elem)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(jobs[i].dst, l, ds.width)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their pad bytes here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
-  if (opts)
-    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->pad[bgr ? 2 - k : k] << (8 * k);
+  const TensorEpi te = make_epi(*norm, opts ? opts->pad : nullptr);
   LetterboxDesc table[kLetterboxBatch];
   for (uint32_t base = 0; base < n; base += kLetterboxBatch) {
     const uint32_t m = (n - base < (uint32_t)kLetterboxBatch) ? n - base : (uint32_t)kLetterboxBatch;
     for (uint32_t i = 0; i < m; i++) {
       const vpf_letterbox_io& io = jobs[base + i];
       vpf_plane d[3];
-      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
+      const int nd = tensor_planes(io.dst, l, d);
       LetterboxDesc& j = table[i];
       fill_desc(j.r.f, io.src, num_planes(sf), d, nd);
       j.r.x = io.rect.x; j.r.y = io.rect.y; j.r.w = io.rect.width; j.r.h = io.rect.height;
       j.ix = io.dst_rect.x; j.iy = io.dst_rect.y; j.iw = io.dst_rect.width; j.ih = io.dst_rect.height;
       j.r.scx = (float)j.r.w / (float)j.iw; j.r.scy = (float)j.r.h / (float)j.ih;
     }
-    const hipError_t e = launch_convert_letterbox(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, nhwc);
+    const hipError_t e = launch_convert_letterbox(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, l.nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -698,49 +707,32 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
                                    const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
   const Mark mark("vpf_convert_warp_tensor");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
-  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE, opts && opts->reserved)) return refused;
   if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   for (uint32_t i = 0; i < n; i++) {
     for (int k = 0; k < 6; k++)
       if (!(std::fabs(jobs[i].m[k]) <= 16777216.0f)) return VPF_ERR_BAD_ARG;  // NaN and infinities fail the comparison too
-    if (!tensor_src_ok(sf, ss.width, jobs[i].src)) return VPF_ERR_BAD_ARG;
-    for (int k = 0; k < num_planes(sf); k++)
-      if (jobs[i].src[k].reserved) return VPF_ERR_BAD_ARG;
-    if (!tensor_planes_ok(jobs[i].dst, nhwc, ds.width, elem, true)) return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, jobs[i].src, true)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(jobs[i].dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their border bytes here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
-  if (opts) {
-    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->border[bgr ? 2 - k : k] << (8 * k);
-    te.pad |= opts->border_mode << 24;
-  }
+  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
   WarpDesc table[kWarpBatch];
   for (uint32_t base = 0; base < n; base += kWarpBatch) {
     const uint32_t m = (n - base < (uint32_t)kWarpBatch) ? n - base : (uint32_t)kWarpBatch;
     for (uint32_t i = 0; i < m; i++) {
       const vpf_warp_io& io = jobs[base + i];
       vpf_plane d[3];
-      const int nd = tensor_planes(io.dst, nhwc, bgr, d);
+      const int nd = tensor_planes(io.dst, l, d);
       fill_desc(table[i].f, io.src, num_planes(sf), d, nd);
       for (int k = 0; k < 6; k++) table[i].m[k] = io.m[k];
     }
     const hipError_t e = launch_convert_warp(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
-                                             ds.height, te, nhwc);
+                                             ds.height, te, l.nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -752,54 +744,33 @@ vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int sf, int cs, int
                                        const vpf_warps_dev* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
   const Mark mark("vpf_convert_warp_tensor_dev");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!norm) return VPF_ERR_BAD_ARG;
-  if (norm->dtype > VPF_TENSOR_BF16 || (norm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  if (opts && opts->border_mode > VPF_WARP_REPLICATE) return VPF_ERR_UNSUPPORTED;
-  if (opts && opts->reserved) return VPF_ERR_BAD_ARG;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(norm->scale[c]) || !std::isfinite(norm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE, opts && opts->reserved)) return refused;
   if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
   if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = norm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (norm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*norm);
   if (!table->matrices || (((uintptr_t)table->matrices | (uintptr_t)table->frame_index | (uintptr_t)table->count) & 3u) || table->matrix_stride < 24u ||
       (table->matrix_stride & 3u) || (table->frame_index && (table->frame_stride < 4u || (table->frame_stride & 3u))) ||
-      (table->dst_job_stride & (elem - 1)) || !(table->max_step >= 0.f) || !std::isfinite(table->max_step))
+      (table->dst_job_stride & (l.elem - 1)) || !(table->max_step >= 0.f) || !std::isfinite(table->max_step))
     return VPF_ERR_BAD_ARG;
-  for (uint32_t i = 0; i < n_frames; i++) {
-    if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
-    for (int k = 0; k < num_planes(sf); k++)
-      if (frames[i].src[k].reserved) return VPF_ERR_BAD_ARG;
-  }
-  if (!tensor_planes_ok(table->dst, nhwc, ds.width, elem, true)) return VPF_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n_frames; i++)
+    if (!tensor_src_ok(sf, ss.width, frames[i].src, true)) return VPF_ERR_BAD_ARG;
+  if (!tensor_planes_ok(table->dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
-  // the kernels write channel k (R G B) to plane k with parameter k; B G R order swaps planes 0 and 2, their parameters and their border bytes here
-  const bool bgr = (norm->flags & VPF_TENSOR_BGR) != 0;
-  TensorEpi te;
-  std::memset(&te, 0, sizeof(te));
-  for (int k = 0; k < 3; k++) { te.scale[k] = norm->scale[bgr ? 2 - k : k]; te.bias[k] = norm->bias[bgr ? 2 - k : k]; }
-  te.dtype = norm->dtype | (nhwc && bgr ? kEpiSwapRB : 0u);
-  if (opts) {
-    for (int k = 0; k < 3; k++) te.pad |= (uint32_t)opts->border[bgr ? 2 - k : k] << (8 * k);
-    te.pad |= opts->border_mode << 24;
-  }
+  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
   WarpDevArgs a;
   std::memset(&a, 0, sizeof(a));
-  for (uint32_t i = 0; i < n_frames; i++)
-    for (int k = 0; k < num_planes(sf); k++) { a.f[i].s[k] = static_cast<const uint8_t*>(frames[i].src[k].ptr); a.f[i].sp[k] = frames[i].src[k].pitch; }
-  vpf_plane d[3];
-  const int nd = tensor_planes(table->dst, nhwc, bgr, d);
-  for (int k = 0; k < nd; k++) { a.d[k] = static_cast<uint8_t*>(d[k].ptr); a.dp[k] = d[k].pitch; }
+  fill_frame_srcs(a.f, frames, n_frames, num_planes(sf));
+  fill_job0_dst(a.d, a.dp, table->dst, l);
   a.matrices = table->matrices;
   a.frame_index = table->frame_index;
   a.count = table->count;
   a.job_stride = table->dst_job_stride;
   a.matrix_stride = table->matrix_stride; a.frame_stride = table->frame_index ? table->frame_stride : 0u; a.max_n = table->max_n; a.n_frames = n_frames;
   return status_of(launch_convert_warp_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height,
-                                           table->max_step, te, nhwc));
+                                           table->max_step, te, l.nhwc));
 }
 
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
@@ -811,15 +782,11 @@ vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int df, int cs, int cr
                                     const vpf_tensor_norm* denorm) {
   const Mark mark("vpf_tensor_convert_batch");
   if (!vpf_tensor_convert_supported(df, cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (!denorm) return VPF_ERR_BAD_ARG;
-  if (denorm->dtype > VPF_TENSOR_BF16 || (denorm->flags & ~(VPF_TENSOR_BGR | VPF_TENSOR_NHWC))) return VPF_ERR_UNSUPPORTED;
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(denorm->scale[c]) || !std::isfinite(denorm->bias[c])) return VPF_ERR_BAD_ARG;
+  if (const vpf_status refused = norm_status(denorm)) return refused;
   if (!exec || !frames || !n || !dims_ok(size)) return VPF_ERR_BAD_ARG;
-  const uint32_t elem = denorm->dtype == VPF_TENSOR_F32 ? 4u : 2u;
-  const bool nhwc = (denorm->flags & VPF_TENSOR_NHWC) != 0;
+  const TensorLayout l = layout_of(*denorm);
   for (uint32_t i = 0; i < n; i++) {
-    if (!tensor_planes_ok(frames[i].src, nhwc, size.width, elem)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(frames[i].src, l, size.width)) return VPF_ERR_BAD_ARG;
     if (!planes_ok(df, size.width, frames[i].dst)) return VPF_ERR_BAD_ARG;
   }
   DeviceGuard guard(exec->device);
@@ -827,23 +794,22 @@ vpf_status vpf_tensor_convert_batch(const vpf_exec* exec, int df, int cs, int cr
   Rgb2YuvCoef rc;
   make_rgb2yuv(cr, &rc);
   // the kernels read channel k (R G B) from plane k with parameter k; B G R order swaps planes 0 and 2 and their parameters here
-  const bool bgr = (denorm->flags & VPF_TENSOR_BGR) != 0;
   TensorPro tp;
   std::memset(&tp, 0, sizeof(tp));
-  for (int k = 0; k < 3; k++) { tp.scale[k] = denorm->scale[bgr ? 2 - k : k]; tp.bias[k] = denorm->bias[bgr ? 2 - k : k]; }
+  kernel_scale_bias(*denorm, tp.scale, tp.bias);
   tp.dtype = denorm->dtype;
-  tp.pad = nhwc && bgr ? 1u : 0u;
+  tp.pad = l.nhwc && l.bgr ? 1u : 0u;
   const int nd = num_planes(df);
   for (uint32_t base = 0; base < n; base += kSmallBatch) {
     const uint32_t m = (n - base < (uint32_t)kSmallBatch) ? n - base : (uint32_t)kSmallBatch;
     BatchArgs a;
     for (uint32_t i = 0; i < m; i++) {
       vpf_plane s[3];
-      const int ns = tensor_planes(frames[base + i].src, nhwc, bgr, s);
+      const int ns = tensor_planes(frames[base + i].src, l, s);
       fill_desc(a.f[i], s, ns, frames[base + i].dst, nd);
     }
     for (uint32_t i = m; i < (uint32_t)kSmallBatch; i++) a.f[i] = a.f[0];
-    const hipError_t e = launch_tensor_to_yuv(static_cast<hipStream_t>(exec->stream), df == VPF_FMT_NV12, rc, tp, size.width, size.height, m, a, nhwc);
+    const hipError_t e = launch_tensor_to_yuv(static_cast<hipStream_t>(exec->stream), df == VPF_FMT_NV12, rc, tp, size.width, size.height, m, a, l.nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
@@ -853,10 +819,7 @@ vpf_status vpf_tensor_convert(const vpf_exec* exec, int df, int cs, int cr, vpf_
                               const vpf_tensor_norm* denorm) {
   if (!vpf_tensor_convert_supported(df, cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (!src || !dst) return VPF_ERR_BAD_ARG;
-  vpf_frame_io io;
-  std::memset(&io, 0, sizeof(io));
-  for (int k = 0; k < 3; k++) io.src[k] = src[k];
-  for (int k = 0; k < num_planes(df); k++) io.dst[k] = dst[k];
+  const vpf_frame_io io = single_frame(src, 3, dst, num_planes(df));
   return vpf_tensor_convert_batch(exec, df, cs, cr, size, 1, &io, denorm);
 }
 
