@@ -1,0 +1,390 @@
+"""The case generator of the seeded differential fuzz of the fused tensor entries (tests/test_gpu_tensor_fuzz.py), importable without a GPU:
+tests/test_tensor_fuzz_cases_cpu.py checks, on the CPU, that it is deterministic, emits only calls the library accepts, reaches both kernel forms
+of every entry that has two, and that the composed FP32 ground truth stays within 2 codes of the same composition in the oracle's EXACT mode.
+
+One function per entry family.  Each takes np.random.default_rng(BASE[family] + seed) and returns the plain description of ONE call — a dict of
+ints, floats, strings and lists, printable in one line, reproducible from (seed, case index) alone: cases(family, seed) draws the
+CASES_PER_SEED[family] calls of a seed one after the other from the same generator.
+
+What is drawn PER JOB and not per call: the frame the job reads, its geometry, and the layout of its destination planes (LAYOUT_KINDS) — all jobs of
+a host-table call sit in one canary-filled buffer at differing row pitches and base alignments (job_geo / pack).  The device-table entries have one
+destination and a job stride, so their stride and base are drawn instead (dev_geo)."""
+import math
+
+import numpy as np
+
+from test_letterbox_tensor_cpu import fit_reference
+
+F = np.float32
+FAMILIES = ("whole", "rois", "rois_dev", "letterbox", "warp", "warp_dev", "encode")
+BASE = {"whole": 21000, "rois": 23000, "rois_dev": 25000, "letterbox": 27000, "warp": 29000, "warp_dev": 31000, "encode": 33000}
+CASES_PER_SEED = {"whole": 4, "rois": 5, "rois_dev": 5, "letterbox": 5, "warp": 5, "warp_dev": 5, "encode": 6}
+TABLE = {"rois": 96, "warp": 96, "letterbox": 82}  # jobs per job table (kRoiBatch, kWarpBatch, kLetterboxBatch of csrc/vpf_internal.h)
+OVER_TABLE = {"rois": (97, 110), "warp": (97, 110), "letterbox": (83, 90)}
+LIMIT = 16777216.0  # |matrix coefficient| limit of the warp entries (include/vpf_hip.h)
+SOURCES = ("NV12", "YUV420", "P10", "P12")
+PARAM_NAMES = ("imagenet", "unit", "symmetric")
+ELEM = {0: 4, 1: 2, 2: 2}
+LAYOUT_KINDS = ("contiguous", "off_by_one_element", "padded", "padded64")
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def cases(family, seed):
+    """the calls of one seed, in the order the GPU test runs them"""
+    rng = np.random.default_rng(BASE[family] + seed)
+    return [GENERATORS[family](rng) for _ in range(CASES_PER_SEED[family])]
+
+
+def describe(call):
+    """one line that names the whole call"""
+    return repr(call)
+
+
+def _i(rng, lo, hi):
+    """an int in lo .. hi, both included"""
+    return int(rng.integers(lo, hi + 1))
+
+
+def _pick(rng, seq):
+    return seq[int(rng.integers(len(seq)))]
+
+
+# ------------------------------------------------------------------------------------------------ what every decode-side call draws
+def draw_frame_size(rng):
+    """W x H: anything from 2 x 2 to 420 x 300; wide and flat (several 256-column chunks, a unit against the right edge at every W mod 8); narrow
+    and tall — every frame stays far below 1 MB"""
+    k = int(rng.integers(5))
+    if k == 0:
+        return _i(rng, 900, 2100), _i(rng, 2, 40)
+    if k == 1:
+        return _i(rng, 2, 24), _i(rng, 150, 500)
+    return _i(rng, 2, 420), _i(rng, 2, 300)
+
+
+def draw_dst_size(rng):
+    """dw x dh: small; a second and third 256-column chunk; multiples of 4 wide with band edges at 16 rows; scalar tails only"""
+    k = int(rng.integers(6))
+    if k == 0:
+        return _i(rng, 250, 530), _i(rng, 1, 24)
+    if k == 1:
+        return 4 * _i(rng, 1, 30), _i(rng, 15, 50)
+    if k == 2:
+        return _i(rng, 1, 5), _i(rng, 1, 70)
+    return _i(rng, 1, 90), _i(rng, 1, 70)
+
+
+def draw_common(rng, entry):
+    sf = _pick(rng, SOURCES)
+    W, H = draw_frame_size(rng)
+    call = dict(entry=entry, sf=sf, cs=_i(rng, 0, 1), cr=_i(rng, 0, 1), W=W, H=H, dtype=_i(rng, 0, 2), bgr=bool(rng.integers(2)), nhwc=bool(rng.integers(2)),
+                params=_pick(rng, PARAM_NAMES), tune=0 if rng.integers(5) else 9)
+    # source pitches: rows padded to 64 B plus an odd remainder (rows start at every alignment; 16-bit samples: 2-B aligned) or unpadded
+    call["frames"] = [dict(seed=_i(rng, 0, (1 << 30) - 1), align=64, extra=2 if sf in ("P10", "P12") else 3) if rng.integers(2) else
+                      dict(seed=_i(rng, 0, (1 << 30) - 1), align=1, extra=0) for _ in range(_i(rng, 2, 3))]
+    return call
+
+
+def settle_sources(call):
+    """once W x H is final: the planted 16-bit frames (tests/test_p16_tensor_cpu.py::plant) need seven luma samples and seven chroma pairs, so a
+    smaller frame takes the 8-bit format instead; padded 16-bit rows stay 2-B aligned"""
+    if call["sf"] in ("P10", "P12") and ((call["W"] + 1) // 2) * ((call["H"] + 1) // 2) < 7:
+        call["sf"] = {"P10": "NV12", "P12": "YUV420"}[call["sf"]]
+    for f in call["frames"]:
+        if f["align"] == 64:
+            f["extra"] = 2 if call["sf"] in ("P10", "P12") else 3
+    return call
+
+
+def job_geo(kind, dw, dh, e, nhwc):
+    """one job's planes inside a part of its own: TensorBuf / NhwcBuf keywords (n = 1) and the part's size in bytes, a multiple of 256 so that the
+    next part starts as aligned as the buffer"""
+    rb = (3 if nhwc else 1) * dw * e
+    if kind == "contiguous":
+        row, gap, lead = rb, 0, 256
+    elif kind == "off_by_one_element":
+        row, gap, lead = rb, 0, 256 + e
+    elif kind == "padded":          # rows padded by 16 B + 1 element: no row but the first is vector aligned
+        row, gap, lead = rb + 16 + e, 40 * e, 24 * e
+    else:                           # rows padded to the next 64 B and 64 B more
+        row, gap, lead = (rb + 63) // 64 * 64 + 64, 64, 512
+    body = lead + (dh - 1) * row + rb + (0 if nhwc else 2 * (dh * row + gap))
+    tail = 64 + (-(body + 64)) % 256
+    geo = dict(kind=kind, lead=lead, row=row, tail=tail, size=body + tail)
+    if not nhwc:
+        geo["plane"] = dh * row + gap
+    return geo
+
+
+def pack(call, kinds):
+    """lay the jobs' parts one after the other: job i's part starts at jobs[i]["layout"]["off"]"""
+    off = 0
+    for job, kind in zip(call["jobs"], kinds):
+        geo = job_geo(kind, call["dw"], call["dh"], ELEM[call["dtype"]], call["nhwc"])
+        geo["off"] = off
+        off += geo["size"]
+        job["layout"] = geo
+    call["size"] = off
+    return call
+
+
+def plane_offsets(call, job):
+    """[(byte offset from the buffer's base, pitch)] of the job's planes: what the alignment rules of include/vpf_hip.h speak about"""
+    g = job["layout"]
+    if call["nhwc"]:
+        return [(g["off"] + g["lead"], g["row"])]
+    return [(g["off"] + g["lead"] + c * g["plane"], g["row"]) for c in range(3)]
+
+
+def dev_geo(rng, n, dw, dh, e, nhwc):
+    """the ONE destination of a device-table call: TensorBuf / NhwcBuf keywords for n jobs, the job stride (`frame`) and the base (`lead`) drawn"""
+    geo = job_geo(_pick(rng, LAYOUT_KINDS), dw, dh, e, nhwc)
+    out = dict(kind=geo["kind"], lead=geo["lead"], row=geo["row"])
+    if nhwc:
+        out["frame"] = dh * geo["row"] + e * (_i(rng, 0, 40) if rng.integers(2) else 0)
+    else:
+        out["plane"] = geo["plane"]
+        out["frame"] = 3 * geo["plane"] + e * (_i(rng, 0, 40) if rng.integers(2) else 0)
+    return out
+
+
+def draw_job_count(rng, entry):
+    """mostly 1 .. 12; one call in eight crosses the job table"""
+    if rng.integers(8) == 0:
+        return _i(rng, *OVER_TABLE[entry]), True
+    return _i(rng, 1, 12), False
+
+
+# ------------------------------------------------------------------------------------------------ rectangles
+def draw_rect(rng, W, H, dw, dh):
+    """(x, y, w, h) inside W x H: the whole frame, 1 .. 4 px sides, touching the right / bottom edge, arbitrary at odd offsets, a large down-scale of
+    dw x dh (the per-tap job class), the identity scale"""
+    k = int(rng.integers(7))
+    if k == 0:
+        return (0, 0, W, H)
+    if k == 1:
+        w, h = _i(rng, 1, min(4, W)), _i(rng, 1, min(4, H))
+    elif k == 4 or k == 5:
+        w, h = _i(rng, min(W, 3 * dw), W), _i(rng, min(H, 2 * dh), H)
+    elif k == 6:
+        w, h = min(W, dw), min(H, dh)
+    else:
+        w, h = _i(rng, 1, W), _i(rng, 1, H)
+    x, y = _i(rng, 0, W - w), _i(rng, 0, H - h)
+    if k == 2:
+        edge = int(rng.integers(3))
+        x = W - w if edge != 1 else x
+        y = H - h if edge != 0 else y
+    elif k == 3:
+        x, y = min(x | 1, W - w), min(y | 1, H - h)
+    return (x, y, w, h)
+
+
+def draw_inner(rng, w, h, dw, dh):
+    """(ix, iy, iw, ih) inside dw x dh for a w x h rectangle: vpf_letterbox_fit's own answer, one pixel, the whole destination, an odd ix, anything"""
+    k = int(rng.integers(6))
+    if k <= 1:
+        return tuple(fit_reference(w, h, dw, dh))
+    if k == 2:
+        return (_i(rng, 0, dw - 1), _i(rng, 0, dh - 1), 1, 1)
+    if k == 3:
+        return (0, 0, dw, dh)
+    iw, ih = _i(rng, 1, dw), _i(rng, 1, dh)
+    ix, iy = _i(rng, 0, dw - iw), _i(rng, 0, dh - ih)
+    if k == 4:
+        ix = min(ix | 1, dw - iw)
+    return (ix, iy, iw, ih)
+
+
+def roi_case(rng, entry="rois"):
+    call = draw_common(rng, entry)
+    n, over = draw_job_count(rng, entry)
+    call["dw"], call["dh"] = (_i(rng, 1, 24), _i(rng, 1, 16)) if over else draw_dst_size(rng)
+    call["jobs"] = [dict(frame=_i(rng, 0, len(call["frames"]) - 1), rect=draw_rect(rng, call["W"], call["H"], call["dw"], call["dh"])) for _ in range(n)]
+    if entry == "letterbox":
+        call["pad"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+        for job in call["jobs"]:
+            job["dst_rect"] = draw_inner(rng, job["rect"][2], job["rect"][3], call["dw"], call["dh"])
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
+
+
+def letterbox_case(rng):
+    return roi_case(rng, "letterbox")
+
+
+def box_valid(f, x, y, w, h, n_frames, W, H):
+    """the header's rule for a device box, in Python's exact integers"""
+    return 0 <= f < n_frames and w >= 1 and h >= 1 and x >= 0 and y >= 0 and x + w <= W and y + h <= H
+
+
+def draw_count(rng, max_n):
+    """None (all of max_n), below, at and above max_n"""
+    k = int(rng.integers(5))
+    if k <= 1:
+        return None
+    return (_i(rng, 0, max_n - 1), max_n, max_n + _i(rng, 1, 5))[k - 2]
+
+
+def rois_dev_case(rng):
+    call = draw_common(rng, "rois_dev")
+    W, H = call["W"], call["H"]
+    n = _i(rng, 1, 14)
+    call["dw"], call["dh"] = draw_dst_size(rng)
+    nf = len(call["frames"])
+    boxes = [(_i(rng, 0, nf - 1),) + draw_rect(rng, W, H, call["dw"], call["dh"]) for _ in range(n)]
+    # a few entries the header defines as invalid (the spellings of tests/test_gpu_rois_dev.py::test_invalid_boxes_are_zero_filled): zero fill
+    bad = [(1, 3, 5, 0, 10), (0, 3, 5, 20, -3), (0, -1, 5, 2, 2), (1, W - 1, 0, 2, 1), (0, 0, H - 1, 1, 2), (-1, 0, 0, 1, 1), (nf, 0, 0, 1, 1),
+           (0, INT_MAX, 0, INT_MAX, 1), (0, 0, INT_MIN, 1, 1), (0, 1, 1, INT_MIN, 2), (0, 0, 0, W + 1, H)]
+    for _ in range(int(rng.integers(3)) if n > 1 else 0):
+        boxes[_i(rng, 0, n - 1)] = _pick(rng, bad)
+    call["boxes"] = boxes
+    call["valid"] = [box_valid(*b, nf, W, H) for b in boxes]
+    call["box_ints"] = _pick(rng, (5, 5, 6, 8, 9))  # the box stride in int32s; the padding holds a pattern the kernel must not read
+    call["max_n"] = n
+    call["count"] = draw_count(rng, n)
+    call["geo"] = dev_geo(rng, n, call["dw"], call["dh"], ELEM[call["dtype"]], call["nhwc"])
+    return settle_sources(call)
+
+
+# ------------------------------------------------------------------------------------------------ matrices
+def f32(v):
+    return float(F(v))
+
+
+def centred(a, b, c, d, W, H, dw, dh, tx=0.0, ty=0.0):
+    """the matrix with linear part (a b; c d) that takes the destination's centre to the frame's centre, moved by (tx, ty)"""
+    cx, cy, ex, ey = (W - 1) / 2.0, (H - 1) / 2.0, (dw - 1) / 2.0, (dh - 1) / 2.0
+    return tuple(f32(v) for v in (a, b, cx - (a * ex + b * ey) + tx, c, d, cy - (c * ex + d * ey) + ty))
+
+
+def draw_matrix(rng, W, H, dw, dh, steep=False):
+    """identity plus integer / half-integer translations, the four right angles, rotations at scales 0.3 .. 9, shear, a zero row, wholly outside, and
+    — `steep` — 5 .. 9 x down-scales (windows that outgrow the staged form); the interesting ones centred on the frame"""
+    k = 7 if steep and rng.integers(4) else int(rng.integers(8))
+    if k == 0:
+        return tuple(f32(v) for v in (1, 0, _i(rng, -3, max(W - dw + 3, -3)), 0, 1, _i(rng, -3, max(H - dh + 3, -3))))
+    if k == 1:
+        return tuple(f32(v) for v in (1, 0, _i(rng, -3, max(W - dw + 3, -3)) + 0.5, 0, 1, _i(rng, -3, max(H - dh + 3, -3)) + 0.5))
+    if k == 2:
+        a, b = ((1, 0), (0, -1), (-1, 0), (0, 1))[int(rng.integers(4))]
+        return centred(a, b, -b, a, W, H, dw, dh, _i(rng, -2, 2), _i(rng, -2, 2))
+    if k == 3:
+        t, s = rng.uniform(0, 2 * math.pi), math.exp(rng.uniform(math.log(0.3), math.log(9.0)))
+        return centred(s * math.cos(t), -s * math.sin(t), s * math.sin(t), s * math.cos(t), W, H, dw, dh, rng.uniform(-4, 4), rng.uniform(-4, 4))
+    if k == 4:
+        return centred(1, rng.uniform(-0.6, 0.6), rng.uniform(-0.6, 0.6), 1, W, H, dw, dh)
+    if k == 5:
+        z = int(rng.integers(3))
+        a, b, c, d = (0, 0, rng.uniform(-1, 1), 1) if z == 0 else (1, rng.uniform(-1, 1), 0, 0) if z == 1 else (0, 0, 0, 0)
+        m = centred(a, b, c, d, W, H, dw, dh)
+        return tuple(f32(v) for v in (m[0], m[1], rng.uniform(0, W - 1) if z != 1 else m[2], m[3], m[4], rng.uniform(0, H - 1) if z != 0 else m[5]))
+    if k == 6:
+        far = _pick(rng, (500.0 + W, -700.0 - dw, 3.0e6, -LIMIT))
+        return tuple(f32(v) for v in ((1, 0, far, 0, 1, 0) if rng.integers(2) else (1, 0, 0, 0, 1, far)))
+    sx, sy = rng.uniform(5, 9), rng.uniform(5, 9)
+    t = rng.uniform(-0.2, 0.2) if rng.integers(2) else 0.0
+    return centred(sx * math.cos(t), -sy * math.sin(t), sx * math.sin(t), sy * math.cos(t), W, H, dw, dh)
+
+
+def draw_warp_shape(rng, call):
+    """the destination of a warp call; one call in four is the steep family: a frame of at least 200 x 200 and a destination of whole 32 x 32
+    tiles, so that a 5 .. 9 x down-scale's tile window outgrows the staged form's 64 KiB (on smaller frames no window does)"""
+    steep = rng.integers(4) == 0
+    if steep:
+        call["W"], call["H"] = _i(rng, 200, 420), _i(rng, 200, 300)
+        call["dw"], call["dh"] = _i(rng, 32, 90), _i(rng, 32, 70)
+    else:
+        call["dw"], call["dh"] = draw_dst_size(rng)
+    return bool(steep)
+
+
+def warp_case(rng):
+    call = draw_common(rng, "warp")
+    steep = draw_warp_shape(rng, call)
+    n, over = draw_job_count(rng, "warp")
+    if over:
+        call["dw"], call["dh"] = (_i(rng, 32, 40), _i(rng, 32, 36)) if steep else (_i(rng, 1, 24), _i(rng, 1, 16))
+    call["mode"] = _i(rng, 0, 1)
+    call["border"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+    call["jobs"] = [dict(frame=_i(rng, 0, len(call["frames"]) - 1), m=draw_matrix(rng, call["W"], call["H"], call["dw"], call["dh"], steep)) for _ in range(n)]
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
+
+
+def matrix_valid(f, m, n_frames):
+    return 0 <= f < n_frames and all(abs(v) <= LIMIT for v in m)  # (NaN fails the comparison)
+
+
+def warp_dev_case(rng):
+    call = draw_common(rng, "warp_dev")
+    steep = draw_warp_shape(rng, call)
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    n = _i(rng, 1, 14)
+    nf = len(call["frames"])
+    call["mode"] = _i(rng, 0, 1)
+    call["border"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+    rows = [(_i(rng, 0, nf - 1), draw_matrix(rng, W, H, dw, dh, steep)) for _ in range(n)]
+    # a few entries the header defines as invalid (the spellings of tests/test_gpu_warps_dev.py::test_invalid_entries_take_the_border): the border
+    nan, inf, above = math.nan, math.inf, float(np.nextafter(F(LIMIT), F(np.inf)))
+    bad = [(1, (nan, 0, 33, 0, 1, 5)), (0, (1, inf, 33, 0, 1, 5)), (0, (1, 0, -inf, 0, 1, 5)), (1, (1, 0, 33, above, 1, 5)), (1, (1, 0, 33, 0, -above, 5)),
+           (-1, (1, 0, 3, 0, 1, 5)), (nf, (1, 0, 3, 0, 1, 5)), (1, (1, 0, 33, 0, 1, nan)), (INT_MIN, (1, 0, 3, 0, 1, 5)), (INT_MAX, (1, 0, 3, 0, 1, 5)), (0, (nan,) * 6)]
+    for _ in range(int(rng.integers(3)) if n > 1 else 0):
+        f, m = _pick(rng, bad)
+        rows[_i(rng, 0, n - 1)] = (f, tuple(float(v) for v in m))
+    call["index"] = [f for f, _ in rows]
+    call["mats"] = [m for _, m in rows]
+    call["valid"] = [matrix_valid(f, m, nf) for f, m in rows]
+    call["mat_floats"] = _pick(rng, (6, 6, 7, 8, 10))   # the matrix stride in floats; the padding holds NaNs the kernel must not read
+    call["index_ints"] = _pick(rng, (1, 1, 2, 5))       # the frame-index stride in int32s; the gaps name a frame that does not exist
+    call["max_n"] = n
+    call["count"] = draw_count(rng, n)
+    # the LDS hint: none, or a true bound of the valid matrices (never a correctness input, so it is never drawn short)
+    steps = [max(abs(m[0]) + abs(m[1]), abs(m[3]) + abs(m[4])) for m, ok in zip(call["mats"], call["valid"]) if ok]
+    call["max_step"] = 0.0 if rng.integers(2) or not steps else f32(max(steps) * rng.uniform(1.0, 1.5) + 1e-3)
+    call["geo"] = dev_geo(rng, n, dw, dh, ELEM[call["dtype"]], call["nhwc"])
+    return settle_sources(call)
+
+
+# ------------------------------------------------------------------------------------------------ whole frames and the way back
+def whole_case(rng):
+    """vpf_convert_resize_tensor(_batch): (W, H) -> (dw, dh) drawn like tests/test_gpu_parity.py::test_fuzz_resize_and_fused — a ratio of 0.15 .. 3
+    per axis, one call in four an exact integer ratio per axis (2 x and 3 x among them) — and n = 1 .. 40 frames, each with a layout of its own"""
+    call = draw_common(rng, "whole")
+    n = _i(rng, 1, 40) if rng.integers(3) == 0 else _i(rng, 1, 6)
+    W, H = call["W"], call["H"]
+    dw, dh = max(1, int(W * rng.uniform(0.15, 3.0))), max(1, int(H * rng.uniform(0.15, 3.0)))
+    dw, dh = min(dw, 600 if n <= 6 else 128), min(dh, 300 if n <= 6 else 64)
+    if rng.integers(4) == 0:
+        kx, ky = _i(rng, 1, 5), _i(rng, 1, 5)
+        dw, dh = max(2, min(dw, 300)), max(2, min(dh, 40))
+        W, H = dw * kx, dh * ky
+    call.update(W=W, H=H, dw=dw, dh=dh, batch=bool(n > 1 or rng.integers(2)))
+    call["jobs"] = [dict(frame=i % len(call["frames"])) for i in range(n)]
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
+
+
+def encode_case(rng):
+    """vpf_tensor_convert(_batch): w x h (odd sizes included; one call in three a multiple of 16 wide and even high: the fast kernel's shape),
+    NV12 or YUV420, dtype, channel order, layout of the source tensor and of the destination picture, 1 .. 4 frames"""
+    w, h = (16 * _i(rng, 1, 70), 2 * _i(rng, 1, 12)) if rng.integers(3) == 0 else (_i(rng, 1, 300), _i(rng, 1, 80))
+    dtype, nhwc = _i(rng, 0, 2), bool(rng.integers(2))
+    e = ELEM[dtype]
+    n = _i(rng, 1, 4)
+    call = dict(entry="encode", dst_fmt=_pick(rng, ("NV12", "YUV420")), cr=_i(rng, 0, 1), w=w, h=h, dtype=dtype, bgr=bool(rng.integers(2)), nhwc=nhwc,
+                params=_pick(rng, ("imagenet", "unit")), tune=0 if rng.integers(5) else 9, n=n, batch=bool(n > 1 or rng.integers(2)),
+                input=_pick(rng, ("planted", "special")), seed=_i(rng, 0, (1 << 30) - 1))
+    # the source tensor: TensorSrc / NhwcSrc keywords
+    rb = (3 if nhwc else 1) * w * e
+    kind = _pick(rng, LAYOUT_KINDS)
+    row = rb if kind in ("contiguous", "off_by_one_element") else rb + 16 + e if kind == "padded" else (rb + 63) // 64 * 64 + 64
+    src = dict(kind=kind, row=row, lead=e if kind == "off_by_one_element" else 0 if kind == "contiguous" else 24 * e if kind == "padded" else 512)
+    if nhwc:
+        src["frame"] = h * row + e * _i(rng, 0, 9)
+    else:
+        src["plane"] = h * row + e * _i(rng, 0, 9)
+        src["frame"] = 3 * src["plane"] + e * _i(rng, 0, 9)
+    call["src"] = src
+    call["dst"] = _pick(rng, (dict(align=256, extra=0, offset=0), dict(align=64, extra=3, offset=0), dict(align=1, extra=0, offset=0), dict(align=16, extra=0, offset=8)))
+    return call
+
+
+GENERATORS = {"whole": whole_case, "rois": roi_case, "rois_dev": rois_dev_case, "letterbox": letterbox_case, "warp": warp_case, "warp_dev": warp_dev_case,
+              "encode": encode_case}

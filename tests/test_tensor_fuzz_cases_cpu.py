@@ -1,0 +1,465 @@
+"""The generator of the fused-tensor fuzz (tests/cases_tensor_fuzz.py) and its ground truth, without a GPU.
+
+  - the same seed gives the same description; every rectangle lies inside its frame or destination, every matrix coefficient of a valid job is
+    at most 2^24 in magnitude, every destination layout satisfies the alignment rules of include/vpf_hip.h;
+  - every generated call passes the library's validation: the real entry is called with fake plane pointers on a device no machine has and
+    must answer VPF_ERR_NO_DEVICE (invoke() below is the one place that turns a description into the C call: the GPU test runs the same code);
+  - reach: over the default seeds each kernel form holds at least 10 % of the jobs of every entry that has two forms, decided by the kernels' own
+    policy functions behind tests/c/*_capi.cpp (csrc/vpf_job_bounds.h compiled with g++), counted over calls with the tuning knob at 0 only — the
+    knob's 9 forces the per-tap form and would make the condition empty; and every source format, dtype, channel order, layout, border mode, a
+    two-table call, a call whose jobs differ in alignment and a unit clamped at the right edge occur per entry;
+  - the independent link: the composed FP32 ground truth of the GPU test (roi_reference_u8, letterbox_reference_u8, warp_reference_u8) against the
+    same composition with every oracle call in EXACT mode, at most 2 codes apart (test_composed_fp32_reference_is_near_the_exact_chain)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cases_tensor_fuzz as cases
+from test_letterbox_tensor_cpu import letterbox_reference_u8
+from test_roi_tensor_cpu import roi_reference_u8
+from test_tensor_in_cpu import PARAM_SETS as DENORM_SETS
+from test_tensor_in_cpu import denorm_scale_bias_f32
+from test_tensor_out_cpu import PARAM_SETS
+from test_warp_tensor_cpu import warp_maps, warp_reference_u8
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "videoprocessingframework_amd", "libvpfhip.so")
+PARAMS = {name: (mean, std) for name, mean, std in PARAM_SETS}
+DENORM = {name: (mean, std) for name, mean, std in DENORM_SETS}
+SEEDS = range(64)        # the default seed set of the GPU test
+SOAK = range(500)        # the soak's seeds (VPF_FUZZ_SEEDS=500): validity and acceptance are checked for these too
+NO_GPU = 1 << 20         # a device index no machine has: a call that passes validation stops at the device switch
+FAKE_DST, FAKE_SRC, FAKE_TABLE = 0x40000000, 0x10000000, 0x70000000
+HOST_TABLE = ("rois", "letterbox", "warp")
+P16 = ("P10", "P12")
+
+
+def round_up(v, a):
+    return (v + a - 1) // a * a
+
+
+# ------------------------------------------------------------------------------------------------ description -> C call (shared with the GPU test)
+def source_pitches(call, k):
+    """the pitches DevPlanes gives frame k's planes"""
+    f = call["frames"][k]
+    e = 2 if call["sf"] in P16 else 1
+    W, cw = call["W"], (call["W"] + 1) // 2
+    rows = [W * e, 2 * cw * e] if call["sf"] != "YUV420" else [W, cw, cw]
+    return [round_up(rb, f["align"]) + f["extra"] for rb in rows]
+
+
+def dst_planes(call, job, base):
+    p = [(base + off, pitch) for off, pitch in cases.plane_offsets(call, job)]
+    return p + [(0, 0), (0, 0)] if call["nhwc"] else p
+
+
+def dev_dst(call, base):
+    """(planes of job 0, job stride) of a device-table call"""
+    g = call["geo"]
+    if call["nhwc"]:
+        return [(base + g["lead"], g["row"]), (0, 0), (0, 0)], g["frame"]
+    return [(base + g["lead"] + c * g["plane"], g["row"]) for c in range(3)], g["frame"]
+
+
+def invoke(capi, call, ex, srcs, base, tables=None, check=True):
+    """run the decode-side call a description names: srcs = the plane descriptors of its frames, base = the address of its destination buffer,
+    tables = the device addresses of a device-table call (boxes / mats, index, count)"""
+    entry, jobs = call["entry"], call.get("jobs")
+    norm = capi.make_tensor_norm(*PARAMS[call["params"]], dtype=call["dtype"], bgr=call["bgr"], nhwc=call["nhwc"])
+    head = (ex, getattr(capi, call["sf"]), call["cs"], call["cr"], call["W"], call["H"])
+    dw, dh = call["dw"], call["dh"]
+    if entry == "whole":
+        if call["batch"]:
+            return capi.convert_resize_tensor_batch(*head, dw, dh, capi.make_batch([(srcs[j["frame"]], dst_planes(call, j, base)) for j in jobs]), norm, check=check)
+        return capi.convert_resize_tensor(*head, srcs[jobs[0]["frame"]], dw, dh, dst_planes(call, jobs[0], base), norm, check=check)
+    if entry == "rois":
+        return capi.convert_resize_tensor_rois(*head, dw, dh, capi.make_rois([(srcs[j["frame"]], dst_planes(call, j, base), j["rect"]) for j in jobs]), norm, check=check)
+    if entry == "letterbox":
+        arr = capi.make_letterbox_jobs([(srcs[j["frame"]], dst_planes(call, j, base), j["rect"], j["dst_rect"]) for j in jobs])
+        return capi.convert_letterbox_tensor(*head, dw, dh, arr, norm, capi.make_letterbox_opts(call["pad"]), check=check)
+    if entry == "warp":
+        arr = capi.make_warps([(srcs[j["frame"]], dst_planes(call, j, base), j["m"]) for j in jobs])
+        return capi.convert_warp_tensor(*head, dw, dh, arr, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
+    planes0, stride = dev_dst(call, base)
+    if entry == "rois_dev":
+        table = capi.make_rois_dev(tables["boxes"], call["max_n"], planes0, stride, tables["count"], 4 * call["box_ints"])
+        return capi.convert_resize_tensor_rois_dev(*head, dw, dh, capi.make_frame_srcs(srcs), table, norm, check=check)
+    assert entry == "warp_dev"
+    table = capi.make_warps_dev(tables["mats"], call["max_n"], planes0, stride, tables["index"], tables["count"], 4 * call["mat_floats"], 4 * call["index_ints"],
+                                call["max_step"])
+    return capi.convert_warp_tensor_dev(*head, dw, dh, capi.make_frame_srcs(srcs), table, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
+
+
+def host_jobs(call):
+    """the host-table call on the jobs a device-table call defines as written and valid, into a buffer of the same layout: [(job index k, job)]"""
+    c = call["max_n"] if call["count"] is None else min(max(call["count"], 0), call["max_n"])
+    if call["entry"] == "rois_dev":
+        return [(k, dict(frame=b[0], rect=tuple(b[1:]))) for k, b in enumerate(call["boxes"][:c]) if call["valid"][k]], c
+    return [(k, dict(frame=f, m=m)) for k, (f, m) in enumerate(zip(call["index"][:c], call["mats"][:c])) if call["valid"][k]], c
+
+
+def invoke_host(capi, call, ex, srcs, base):
+    """the host-table entry on host_jobs(call), job k at the device-table call's planes of job k"""
+    planes0, stride = dev_dst(call, base)
+    norm = capi.make_tensor_norm(*PARAMS[call["params"]], dtype=call["dtype"], bgr=call["bgr"], nhwc=call["nhwc"])
+    head = (ex, getattr(capi, call["sf"]), call["cs"], call["cr"], call["W"], call["H"], call["dw"], call["dh"])
+    jobs, _ = host_jobs(call)
+    if not jobs:
+        return
+
+    def dst(k):
+        return [(p + k * stride if p else 0, pitch) for p, pitch in planes0]
+
+    if call["entry"] == "rois_dev":
+        capi.convert_resize_tensor_rois(*head, capi.make_rois([(srcs[j["frame"]], dst(k), j["rect"]) for k, j in jobs]), norm)
+    else:
+        capi.convert_warp_tensor(*head, capi.make_warps([(srcs[j["frame"]], dst(k), j["m"]) for k, j in jobs]), norm, capi.make_warp_opts(call["mode"], call["border"]))
+
+
+def encode_src_planes(call, i, base):
+    s = call["src"]
+    if call["nhwc"]:
+        return [(base + s["lead"] + i * s["frame"], s["row"]), (0, 0), (0, 0)]
+    return [(base + s["lead"] + i * s["frame"] + c * s["plane"], s["row"]) for c in range(3)]
+
+
+def invoke_encode(capi, call, ex, base, dsts, check=True):
+    """vpf_tensor_convert(_batch): base = the address of the source tensor buffer, dsts = the plane descriptors of the n destination pictures"""
+    scale, bias = denorm_scale_bias_f32(*DENORM[call["params"]])
+    dn = capi.make_tensor_denorm(dtype=call["dtype"], bgr=call["bgr"], scale=[float(s) for s in scale], bias=[float(b) for b in bias], nhwc=call["nhwc"])
+    head = (ex, getattr(capi, call["dst_fmt"]), 0, call["cr"], call["w"], call["h"])
+    if call["batch"]:
+        return [capi.tensor_convert_batch(*head, capi.make_batch([(encode_src_planes(call, i, base), d) for i, d in enumerate(dsts)]), dn, check=check)]
+    return [capi.tensor_convert(*head, encode_src_planes(call, i, base), d, dn, check=check) for i, d in enumerate(dsts)]
+
+
+# ------------------------------------------------------------------------------------------------ the ground truth of a call (shared with the GPU test)
+def host_frames(orc, call):
+    """the host planes of the call's frames; 16-bit ones are the planted frames of tests/test_gpu_p16_tensor.py"""
+    if call["sf"] in P16:
+        import test_gpu_p16_tensor as p16
+        return [p16.p16_frame(orc, call["sf"], call["W"], call["H"], f["seed"]) for f in call["frames"]]
+    return [orc.synth(getattr(orc, call["sf"]), call["W"], call["H"], f["seed"]) for f in call["frames"]]
+
+
+def forget_p16():
+    """tests/test_gpu_p16_tensor.py keeps every frame it made; a fuzz never asks for the same one twice"""
+    import test_gpu_p16_tensor as p16
+    p16._SRC.clear()
+    p16._NV12.clear()
+
+
+def eight_bit(orc, call, srcs, mode):
+    """(format, planes) per frame as the definition sees them: 16-bit sources narrowed by oracle.convert(P10 | P12 -> NV12) first"""
+    if call["sf"] not in P16:
+        return [(getattr(orc, call["sf"]), s) for s in srcs]
+    if mode == orc.FP32:
+        import test_gpu_p16_tensor as p16
+        return [(orc.NV12, p16.nv12_of(orc, call["sf"], call["W"], call["H"], f["seed"])) for f in call["frames"]]
+    out = []
+    for s in srcs:
+        st, nv = orc.convert(getattr(orc, call["sf"]), orc.NV12, 0, 0, call["W"], call["H"], s, mode)
+        assert st == 0
+        out.append((orc.NV12, nv))
+    return out
+
+
+def rgb_frames(orc, call, srcs, mode=None):
+    """the converted WHOLE frames the ROI, letterbox and warp references crop and sample"""
+    mode = orc.FP32 if mode is None else mode
+    out = []
+    for fmt, planes in eight_bit(orc, call, srcs, mode):
+        st, rgb = orc.convert(fmt, orc.RGB_PLANAR, call["cs"], call["cr"], call["W"], call["H"], planes, mode)
+        assert st == 0
+        out.append(rgb)
+    return out
+
+
+def rgb_order(call, triple):
+    """pad[c] / border[c] belong to OUTPUT channel c: in R G B order for the references"""
+    return tuple(triple[::-1]) if call["bgr"] else tuple(triple)
+
+
+def job_u8(orc, call, job, rgb):
+    """[3, dh, dw] R G B bytes of one job: the composed FP32 reference the GPU tests of the entry use"""
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    if "m" in job:
+        return warp_reference_u8(orc, None, call["cs"], call["cr"], W, H, job["m"], dw, dh, rgb_order(call, call["border"]), call["mode"], rgb=rgb)
+    if "dst_rect" in job:
+        return letterbox_reference_u8(orc, None, call["cs"], call["cr"], W, H, None, job["rect"], job["dst_rect"], dw, dh, rgb_order(call, call["pad"]), rgb=rgb)
+    return roi_reference_u8(orc, None, call["cs"], call["cr"], W, H, None, job["rect"], dw, dh, rgb=rgb)
+
+
+def job_u8_exact(orc, call, job, rgb):
+    """the same composition with every oracle call in EXACT mode (rgb: the EXACT conversion), on the same float32 maps"""
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    if "m" in job:
+        packed = np.ascontiguousarray(np.stack(rgb, axis=-1).reshape(H, 3 * W))
+        sx, sy = warp_maps(job["m"], dw, dh, W, H, call["mode"])
+        dst = np.ascontiguousarray(np.broadcast_to(np.asarray(rgb_order(call, call["border"]), np.uint8), (dh, dw, 3)).reshape(dh, 3 * dw))
+        st, out = orc.remap(orc.RGB, W, H, [packed], sx, sy, orc.EXACT, dst=[dst])
+        assert st == 0
+        return np.ascontiguousarray(out[0].reshape(dh, dw, 3).transpose(2, 0, 1))
+    x, y, w, h = job["rect"]
+    ix, iy, iw, ih = job.get("dst_rect", (0, 0, dw, dh))
+    out = np.empty((3, dh, dw), np.uint8)
+    for c, v in enumerate(rgb_order(call, call.get("pad", (0, 0, 0)))):
+        out[c] = v
+    st, _ = orc.resize(orc.RGB_PLANAR, orc.LINEAR, w, h, [p[y:y + h, x:x + w] for p in rgb], iw, ih, orc.EXACT, dst=[out[c, iy:iy + ih, ix:ix + iw] for c in range(3)])
+    assert st == 0
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ determinism and validity
+@pytest.mark.parametrize("family", cases.FAMILIES)
+def test_same_seed_same_description(family):
+    for seed in (0, 7, 63, 499):
+        a, b = cases.cases(family, seed), cases.cases(family, seed)
+        assert [cases.describe(c) for c in a] == [cases.describe(c) for c in b]  # (repr: a NaN coefficient is not equal to itself)
+        assert len(a) == cases.CASES_PER_SEED[family]
+    assert cases.describe(cases.cases(family, 0)[0]) != cases.describe(cases.cases(family, 1)[0])
+
+
+def all_cases(family, seeds=SEEDS):
+    return [(seed, k, c) for seed in seeds for k, c in enumerate(cases.cases(family, seed))]
+
+
+def every_job(call):
+    """(frame, job) of every job that names a frame and a geometry, device tables included (valid entries only)"""
+    if call["entry"] == "rois_dev":
+        return [dict(frame=b[0], rect=tuple(b[1:])) for b, ok in zip(call["boxes"], call["valid"]) if ok]
+    if call["entry"] == "warp_dev":
+        return [dict(frame=f, m=m) for f, m, ok in zip(call["index"], call["mats"], call["valid"]) if ok]
+    return call["jobs"]
+
+
+@pytest.mark.parametrize("family", [f for f in cases.FAMILIES if f != "encode"])
+def test_geometry_and_layouts_are_valid(family):
+    for seed, k, call in all_cases(family, SOAK):
+        what = f"seed {seed} case {k} {cases.describe(call)}"
+        W, H, dw, dh, e = call["W"], call["H"], call["dw"], call["dh"], cases.ELEM[call["dtype"]]
+        assert call["sf"] not in P16 or ((W + 1) // 2) * ((H + 1) // 2) >= 7, what   # what the planted 16-bit frames need
+        assert all(f["extra"] % 2 == 0 for f in call["frames"]) or call["sf"] not in P16, what
+        assert 2 <= W <= 2100 and 2 <= H <= 500 and W * H * (2 if call["sf"] in P16 else 1) * 3 // 2 < (1 << 20), what
+        assert 1 <= dw <= 600 and 1 <= dh <= 300, what
+        assert 2 <= len(call["frames"]) <= 3, what
+        for job in every_job(call):
+            assert 0 <= job["frame"] < len(call["frames"]), what
+            if "rect" in job:
+                x, y, w, h = job["rect"]
+                assert w >= 1 and h >= 1 and x >= 0 and y >= 0 and x + w <= W and y + h <= H, what
+            if "dst_rect" in job:
+                ix, iy, iw, ih = job["dst_rect"]
+                assert iw >= 1 and ih >= 1 and ix >= 0 and iy >= 0 and ix + iw <= dw and iy + ih <= dh, what
+            if "m" in job:
+                assert len(job["m"]) == 6 and all(abs(v) <= cases.LIMIT and float(np.float32(v)) == v for v in job["m"]), what
+        # include/vpf_hip.h: plane pointers and pitches are multiples of the element size, pitch >= width x element size (3 x: one interleaved plane)
+        rb = (3 if call["nhwc"] else 1) * dw * e
+        if "jobs" in call:
+            spans = []
+            for job in call["jobs"]:
+                g = job["layout"]
+                assert g["off"] % 256 == 0 and g["off"] + g["size"] <= call["size"], what
+                for off, pitch in cases.plane_offsets(call, job):
+                    assert off % e == 0 and pitch % e == 0 and pitch >= rb, what
+                    assert g["off"] + 16 <= off and off + (dh - 1) * pitch + rb + 16 <= g["off"] + g["size"], what   # canaries on both sides
+                    spans.append((off, off + (dh - 1) * pitch + rb))
+            spans.sort()
+            assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), what   # no two planes overlap
+        else:
+            g = call["geo"]
+            assert g["lead"] % e == 0 and g["row"] % e == 0 and g["row"] >= rb and g["frame"] % e == 0, what
+            assert g["frame"] >= (dh * g["row"] if call["nhwc"] else 3 * g["plane"]) and (call["nhwc"] or g["plane"] >= dh * g["row"]), what
+            assert call["max_n"] == len(call["valid"]) and 1 <= call["max_n"] <= 65535, what
+        if family == "warp_dev":
+            assert call["max_step"] >= 0 and np.isfinite(call["max_step"]), what
+            steps = [max(abs(m[0]) + abs(m[1]), abs(m[3]) + abs(m[4])) for m, ok in zip(call["mats"], call["valid"]) if ok]
+            assert call["max_step"] == 0 or call["max_step"] >= max(steps), what   # 0 or a TRUE bound
+
+
+def test_encode_cases_are_valid():
+    for seed, k, call in all_cases("encode", SOAK):
+        what = f"seed {seed} case {k} {cases.describe(call)}"
+        e, s = cases.ELEM[call["dtype"]], call["src"]
+        rb = (3 if call["nhwc"] else 1) * call["w"] * e
+        assert 1 <= call["w"] <= 1200 and 1 <= call["h"] <= 100 and 1 <= call["n"] <= 4, what
+        assert s["lead"] % e == 0 and s["row"] % e == 0 and s["row"] >= rb and s["frame"] % e == 0, what
+        assert s["frame"] >= (call["h"] * s["row"] if call["nhwc"] else 3 * s["plane"]) and (call["nhwc"] or s["plane"] >= call["h"] * s["row"]), what
+
+
+# ------------------------------------------------------------------------------------------------ acceptance
+def _lib_or_skip():
+    if not os.path.exists(LIB):
+        pytest.skip("libvpfhip.so not built")
+    from videoprocessingframework_amd import capi
+    capi.lib()
+    return capi
+
+
+def fake_sources(call):
+    """plane descriptors of the call's frames at fake addresses, with the pitches the GPU test's DevPlanes have"""
+    return [[(FAKE_SRC + 0x1000000 * k + 0x400000 * i, p) for i, p in enumerate(source_pitches(call, k))] for k in range(len(call["frames"]))]
+
+
+@pytest.mark.parametrize("family", cases.FAMILIES)
+def test_every_call_passes_validation(family):
+    """the real entry, fake pointers, a device that does not exist: VPF_ERR_NO_DEVICE — validation is over by then and nothing was launched"""
+    capi = _lib_or_skip()
+    ex = capi.make_exec(device=NO_GPU)
+    for seed, k, call in all_cases(family, SOAK):
+        what = f"seed {seed} case {k} {cases.describe(call)}"
+        if family == "encode":
+            cw, ch = (call["w"] + 1) // 2, (call["h"] + 1) // 2
+            rows = [call["w"], 2 * cw] if call["dst_fmt"] == "NV12" else [call["w"], cw, cw]
+            d = call["dst"]
+            dsts = [[(FAKE_DST + 0x1000000 * i + 0x400000 * p + d["offset"], round_up(rb, d["align"]) + d["extra"]) for p, rb in enumerate(rows)] for i in range(call["n"])]
+            sts = invoke_encode(capi, call, ex, FAKE_SRC, dsts, check=False)
+        else:
+            tables = dict(boxes=FAKE_TABLE, mats=FAKE_TABLE, index=FAKE_TABLE + 0x100000, count=None if call.get("count") is None else FAKE_TABLE + 0x200000)
+            sts = [invoke(capi, call, ex, fake_sources(call), FAKE_DST, tables, check=False)]
+        assert all(st == capi.ERR_NO_DEVICE for st in sts), (what, [capi.status_string(st) for st in sts])
+
+
+# ------------------------------------------------------------------------------------------------ reach
+@pytest.fixture(scope="module")
+def bounds(tmp_path_factory):
+    """the four harnesses over csrc/vpf_job_bounds.h in one library, compiled with g++ as they stand"""
+    from conftest import native_test_build
+    so = str(tmp_path_factory.mktemp("fuzz_bounds") / "libfuzzbounds.so")
+    srcs = [os.path.join(ROOT, "tests", "c", f) for f in ("job_bounds_capi.cpp", "letterbox_bounds_capi.cpp", "rois_dev_bounds_capi.cpp", "warp_dev_bounds_capi.cpp")]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Werror", "-Wno-unused-function", *native_test_build()[0],
+                           "-I" + os.path.join(ROOT, "videoprocessingframework_amd", "csrc"), *srcs, "-o", so, "-lm"])
+    L = C.CDLL(so)
+    u32, fp, dp, ip = C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
+    L.jb_warp_strip_max.argtypes, L.jb_warp_strip_max.restype = [], u32
+    L.jb_roi_strip_need.argtypes, L.jb_roi_strip_need.restype = [u32] * 5 + [dp, ip], u32
+    L.jb_warp_need.argtypes, L.jb_warp_need.restype = [fp] + [u32] * 4, u32
+    L.lb_strip_need.argtypes, L.lb_strip_need.restype = [u32] * 9 + [dp, ip], u32
+    L.rd_lds_bytes.argtypes, L.rd_lds_bytes.restype = [u32, u32], u32
+    L.rd_tiles.argtypes, L.rd_tiles.restype = [u32] * 6 + [C.POINTER(u32), dp, C.POINTER(C.c_uint8)], u32
+    L.rd_box_ok.argtypes, L.rd_box_ok.restype = [C.c_int32] * 5 + [u32] * 3, C.c_int
+    L.wd_lds_bytes.argtypes, L.wd_lds_bytes.restype = [C.c_float] + [u32] * 4, u32
+    L.wd_largest_tile.argtypes, L.wd_largest_tile.restype = [fp, C.c_int] + [u32] * 4, u32
+    return L
+
+
+def job_forms(L, call, job):
+    """the forms one job of a call runs under the default policy: a subset of {"staged", "per_tap"} (a device-table job decides per tile)"""
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    conv, staged = C.c_double(), C.c_int()
+    if call["entry"] == "rois":
+        x, _, w, h = job["rect"]
+        L.jb_roi_strip_need(x, w, h, dw, dh, C.byref(conv), C.byref(staged))
+        return {"staged" if staged.value else "per_tap"}
+    if call["entry"] == "letterbox":
+        (x, _, w, h), (ix, iy, iw, ih) = job["rect"], job["dst_rect"]
+        L.lb_strip_need(x, w, h, ix, iy, iw, ih, dw, dh, C.byref(conv), C.byref(staged))
+        return {"staged" if staged.value else "per_tap"}
+    if call["entry"] == "rois_dev":
+        x, _, w, h = job["rect"]
+        n_tiles = ((dh + 15) // 16) * ((dw + 255) // 256) + 8
+        nbytes, convs, flags = (C.c_uint32 * n_tiles)(), (C.c_double * n_tiles)(), (C.c_uint8 * n_tiles)()
+        n = L.rd_tiles(x, w, h, dw, dh, L.rd_lds_bytes(dw, dh), nbytes, convs, flags)
+        assert 1 <= n <= n_tiles - 8
+        return {"staged" if flags[t] else "per_tap" for t in range(n)}
+    m = (C.c_float * 6)(*job["m"])
+    if call["entry"] == "warp":
+        return {"staged" if L.jb_warp_need(m, W, H, dw, dh) <= L.jb_warp_strip_max() else "per_tap"}
+    largest, lds = L.wd_largest_tile(m, call["mode"], W, H, dw, dh), L.wd_lds_bytes(call["max_step"], W, H, dw, dh)
+    return {"staged" if largest <= lds else "per_tap"}
+
+
+def reaches_right_edge(call, job):
+    """a conversion unit next to the frame's right edge takes clamped loads: W is no multiple of 8 and the job samples column W - 1"""
+    W, H = call["W"], call["H"]
+    if W % 8 == 0:
+        return False
+    if "rect" in job:
+        return job["rect"][0] + job["rect"][2] == W
+    sx, sy = warp_maps(job["m"], call["dw"], call["dh"], W, H, call["mode"])
+    inside = (sx >= 0) & (sx <= np.float32(W - 1)) & (sy >= 0) & (sy <= np.float32(H - 1))
+    return bool((inside & (sx >= np.float32(W - 2))).any())
+
+
+@pytest.mark.parametrize("family", [f for f in cases.FAMILIES if f not in ("whole", "encode")])
+def test_reach(bounds, family):
+    """a condition, not a measurement: the fuzz of this entry is worth running only if it holds"""
+    share = {"staged": 0, "per_tap": 0}
+    seen = dict(sf=set(), dtype=set(), bgr=set(), nhwc=set(), mode=set(), tune=set())
+    two_tables = mixed_alignment = right_edge = both_in_one_call = n_jobs = 0
+    for seed, k, call in all_cases(family):
+        for key in seen:
+            if key in call:
+                seen[key].add(call[key])
+        jobs = every_job(call)
+        right_edge += any(reaches_right_edge(call, j) for j in jobs)
+        if family in HOST_TABLE:
+            two_tables += len(jobs) > cases.TABLE[family]
+            mixed_alignment += len({(cases.plane_offsets(call, j)[0][0] % 16, j["layout"]["row"] % 16) for j in jobs}) > 1
+        if family == "rois_dev":
+            assert call["valid"] == [bool(bounds.rd_box_ok(*b, len(call["frames"]), call["W"], call["H"])) for b in call["boxes"]], cases.describe(call)
+        if call["tune"] != 0:
+            continue
+        forms = [job_forms(bounds, call, j) for j in jobs]
+        n_jobs += len(forms)
+        for f in share:
+            share[f] += sum(f in s for s in forms)
+        both_in_one_call += len(set().union(*forms)) == 2 if forms else 0
+    print(family, "jobs under the default policy", n_jobs, share, "calls holding both forms", both_in_one_call, "two tables", two_tables,
+          "mixed alignment", mixed_alignment, "right edge", right_edge)
+    assert share["staged"] >= 0.1 * n_jobs and share["per_tap"] >= 0.1 * n_jobs, (share, n_jobs)
+    assert both_in_one_call >= 1
+    assert seen["sf"] == set(cases.SOURCES) and seen["dtype"] == {0, 1, 2} and seen["bgr"] == {False, True} and seen["nhwc"] == {False, True}, seen
+    assert seen["tune"] == {0, 9}, seen
+    assert right_edge >= 1
+    if family in ("warp", "warp_dev"):
+        assert seen["mode"] == {0, 1}, seen
+    if family in HOST_TABLE:
+        assert two_tables >= 1 and mixed_alignment >= 1
+    else:
+        calls = [c for _, _, c in all_cases(family)]
+        assert {c["count"] is None for c in calls} == {False, True}
+        assert any(c["count"] is not None and c["count"] < c["max_n"] for c in calls) and any(c["count"] == c["max_n"] for c in calls)
+        assert any(c["count"] is not None and c["count"] > c["max_n"] for c in calls) and any(not all(c["valid"]) for c in calls)
+
+
+@pytest.mark.parametrize("family", ["whole", "encode"])
+def test_reach_of_the_single_form_entries(family):
+    calls = [c for _, _, c in all_cases(family)]
+    for key, want in (("dtype", {0, 1, 2}), ("bgr", {False, True}), ("nhwc", {False, True}), ("tune", {0, 9}), ("batch", {False, True})):
+        assert {c[key] for c in calls} == want, key
+    if family == "whole":
+        assert {c["sf"] for c in calls} == set(cases.SOURCES)
+        assert any(len(c["jobs"]) > 32 for c in calls)                                                     # the large frame table
+        assert any(c["W"] == 2 * c["dw"] and c["H"] == 2 * c["dh"] for c in calls) and any(c["W"] == 3 * c["dw"] for c in calls)
+        assert any(c["W"] % 8 for c in calls)
+        assert any(len({(cases.plane_offsets(c, j)[0][0] % 16, j["layout"]["row"] % 16) for j in c["jobs"]}) > 1 for c in calls)
+    else:
+        assert {c["dst_fmt"] for c in calls} == {"NV12", "YUV420"} and {c["input"] for c in calls} == {"planted", "special"}
+        assert any(c["w"] % 2 and c["h"] % 2 for c in calls) and any(c["w"] % 16 == 0 and c["h"] % 2 == 0 and c["src"]["kind"] == "contiguous" for c in calls)
+
+
+# ------------------------------------------------------------------------------------------------ the independent link
+@pytest.mark.parametrize("family", HOST_TABLE)
+def test_composed_fp32_reference_is_near_the_exact_chain(oracle, family):
+    """every job of every case of the default seeds: the composed FP32 reference (what the GPU must equal bit for bit) against the same composition
+    in the oracle's EXACT mode — convert EXACT, crop, resize or remap EXACT with the same float32 maps — at most 2 codes apart: the conversions
+    differ by at most 1 (tests/test_oracle_kat.py), a bilinear blend is a convex combination and carries that 1 through unamplified, and the
+    fp32 blend against the exact blend of equal inputs adds at most 1.
+    Measured maximum over these cases: rois 1, letterbox 1, warp 1 (the bound stays 2)."""
+    oracle.set_threads(16)
+    worst = n = 0
+    for seed, k, call in all_cases(family):
+        srcs = host_frames(oracle, call)
+        fp32, exact = rgb_frames(oracle, call, srcs), rgb_frames(oracle, call, srcs, oracle.EXACT)
+        for i, job in enumerate(call["jobs"]):
+            a, b = job_u8(oracle, call, job, fp32[job["frame"]]), job_u8_exact(oracle, call, job, exact[job["frame"]])
+            d = int(np.abs(a.astype(np.int16) - b.astype(np.int16)).max())
+            worst, n = max(worst, d), n + 1
+            assert d <= 2, f"seed {seed} case {k} job {i}: {d} codes apart; {cases.describe(call)}"
+        if call["sf"] in P16:
+            forget_p16()
+    print(family, "jobs", n, "largest |FP32 chain - EXACT chain|", worst)
