@@ -474,6 +474,37 @@ VPF_API vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int src_fmt
                                                const vpf_warp_opts* opts);
 
 /*
+ * Fused multi-ROI perspective warp (3 x 3 homography) -> normalised tensor: vpf_convert_warp_tensor for crops seen at an angle — a document, plate,
+ * sign or screen rectified from its four corners, a bird's-eye view from a calibrated camera, ground-plane registration.  A job = (the planes of a
+ * WHOLE frame of src_size = (W, H), m[9] = (m00 m01 m02; m10 m11 m12; m20 m21 m22), the destination planes).  The matrix is the INVERSE map:
+ * destination pixel -> source luma pixel indices, vpf_remap's convention.  For destination pixel (dx, dy) — every operation a separately rounded
+ * fp32 operation in this order, no fma, the division IEEE round-to-nearest, denormals kept:
+ *   nx = (m00 * (float)dx + m01 * (float)dy) + m02,  ny = (m10 * (float)dx + m11 * (float)dy) + m12,  w = (m20 * (float)dx + m21 * (float)dy) + m22;
+ *   !(w > 0): the pixel takes u8[c] = border[c], unblended, in BOTH border modes (it lies behind the plane or on the horizon);
+ *   else sx = nx / w, sy = ny / w, then exactly vpf_convert_warp_tensor from its range test on: VPF_WARP_CONSTANT's range test (-0.0 in range, +inf
+ *        out of range), VPF_WARP_REPLICATE's max-then-min, the sampling with chroma at (x >> 1, y >> 1), the blend, the truncation, the epilogue,
+ *        dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC, the narrowing of P10 / P12.
+ * With w > 0 and finite coefficients neither 0 / 0 nor inf / inf arises: no NaN exists.  sx = +-inf is legal: the border under CONSTANT, the edge
+ * under REPLICATE.  With the last row (0, 0, 1) w is exactly 1 and every element is bit for bit what vpf_convert_warp_tensor writes for the first
+ * six coefficients.  Equivalently u8 is the byte vpf_remap(RGB) writes when its source is vpf_convert(frame -> RGB), its maps hold the sx, sy above
+ * with the !(w > 0) pixels set out of range (CONSTANT) or overwritten with the border afterwards (REPLICATE), and its destination was pre-filled
+ * with `border`.  A matrix whose w is <= 0 everywhere, the zero last row included, is legal and writes the border.
+ * `jobs` is a HOST array, consumed before return; 82 jobs travel per job table, each table in at most two dispatches (jobs whose tiles may convert
+ * their source windows once into LDS, and jobs that convert per tap: identical bits).  opts as in vpf_convert_warp_tensor.
+ * Unsupported format / matrix / dtype / flag or an unknown border mode: VPF_ERR_UNSUPPORTED.  Null pointers, n == 0, bad sizes, short pitches,
+ * misaligned planes, non-finite scale / bias, non-zero reserved fields (the job's included), one of the nine coefficients not finite or above 2^24
+ * in magnitude: VPF_ERR_BAD_ARG — all checked before any device access.
+ */
+typedef struct vpf_persp_io {
+  vpf_plane src[3]; /* the WHOLE frame's planes */
+  vpf_plane dst[3];
+  float m[9];        /* m00 m01 m02 m10 m11 m12 m20 m21 m22: destination pixel -> homogeneous source coordinates */
+  uint32_t reserved; /* must be 0 */
+} vpf_persp_io; /* 136 bytes, no implicit padding */
+VPF_API vpf_status vpf_convert_persp_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size, vpf_size dst_size,
+                                            uint32_t n, const vpf_persp_io* jobs, const vpf_tensor_norm* norm, const vpf_warp_opts* opts);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

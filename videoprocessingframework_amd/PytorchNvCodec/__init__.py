@@ -135,6 +135,10 @@ if TYPE_CHECKING:  # the two call forms of the four tensor functions: the planar
     @overload
     def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, *, channels_last: bool) -> torch.Tensor: ...
     @overload
+    def persps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None) -> torch.Tensor: ...
+    @overload
+    def persps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, *, channels_last: bool) -> torch.Tensor: ...
+    @overload
     def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None) -> list: ...
     @overload
     def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None, *, channels_last: bool) -> list: ...
@@ -386,9 +390,9 @@ def device_rois_to_normalized_tensor(resizer, surfaces, boxes, mean, std, count=
 _WARP_MODES = {"constant": 0, "replicate": 1}
 
 
-def _matrices_list(matrices, fn):
+def _matrices_list(matrices, fn, rows=2):
     """matrices -> list of six-float lists (rounded to float32 once): ValueError for a device tensor, a non-float dtype, a shape other than
-    [K, 2, 3], a coefficient that is not finite or exceeds 2^24 in magnitude"""
+    [K, 2, 3], a coefficient that is not finite or exceeds 2^24 in magnitude.  rows = 3: nine-float lists from [K, 3, 3] or [K, 9]"""
     import numpy as np
 
     if isinstance(matrices, torch.Tensor):
@@ -402,14 +406,16 @@ def _matrices_list(matrices, fn):
         if arr.size and arr.dtype.kind != "f" and not (arr.dtype.kind in "iu" and not hasattr(matrices, "dtype")):
             raise ValueError(f"{fn}: matrices must hold floats, got {arr.dtype}")
     if arr.size == 0 and arr.ndim <= 1:
-        arr = arr.reshape(0, 2, 3)
-    if arr.ndim != 3 or tuple(arr.shape[1:]) != (2, 3):
-        raise ValueError(f"{fn}: matrices must have shape [K, 2, 3], got {tuple(arr.shape)}")
+        arr = arr.reshape(0, rows, 3)
+    if rows == 3 and arr.ndim == 2 and arr.shape[1] == 9:
+        arr = arr.reshape(-1, 3, 3)
+    if arr.ndim != 3 or tuple(arr.shape[1:]) != (rows, 3):
+        raise ValueError(f"{fn}: matrices must have shape [K, {rows}, 3]{' or [K, 9]' if rows == 3 else ''}, got {tuple(arr.shape)}")
     with np.errstate(over="ignore", invalid="ignore"):
         arr = arr.astype(np.float32)
     if not bool((np.abs(arr) <= np.float32(2.0 ** 24)).all()):
         raise ValueError(f"{fn}: every matrix coefficient must be finite and at most 2^24 in magnitude")
-    return [[float(v) for v in m.reshape(6)] for m in arr]
+    return [[float(v) for v in m.reshape(3 * rows)] for m in arr]
 
 
 def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
@@ -460,6 +466,92 @@ def warps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean,
     if not ok:
         _refused(fn, _RESIZER_REFUSED)
     return out
+
+
+def persps_to_normalized_tensor(resizer, surfaces, surface_index, matrices, mean, std, dtype=torch.float32, bgr=False, border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
+    """K perspective warps (3 x 3 homographies) of NV12 / YUV420 (or P10 / P12) surfaces -> the normalised float tensor [K, 3, dh, dw]: documents, plates,
+    signs and screens seen at an angle, bird's-eye views, ground-plane registration, in one dispatch per 82 regions
+    (PySurfaceConvertResizer.ExecutePerspsToTensor, vpf_convert_persp_tensor).
+    `matrices`: a host [K, 3, 3] or [K, 9] float tensor, ndarray or nested sequence (float64 is rounded to float32 once), e.g. quads_to_homographies(...);
+    matrices[i] is the INVERSE map of job i: destination pixel (dx, dy) -> (nx, ny, w), source coordinates (nx / w, ny / w) in luma pixels of
+    surfaces[surface_index[i]].  A pixel with w <= 0 (behind the plane, on the horizon) takes `border` under BOTH border modes; everything else —
+    border, border_mode, normalisation, `out`, channels_last, the returned tensor and the stream ordering — exactly as warps_to_normalized_tensor, whose
+    bits this function gives for matrices with the last row (0, 0, 1).
+
+    ValueError for matrices on the device (pass .cpu()), a wrong shape, a non-float dtype, a coefficient that is not finite or exceeds 2^24, a
+    bad surface index, a border value outside 0..255, an unknown mode.  K == 0 returns an empty tensor without a launch."""
+    fn = "persps_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    if border_mode not in _WARP_MODES:
+        raise ValueError(f"{fn}: border_mode must be one of {list(_WARP_MODES)}, got {border_mode!r}")
+    try:
+        border = [operator.index(v) for v in border]
+    except TypeError:
+        raise ValueError(f"{fn}: border must hold three integers, got {border!r}") from None
+    if len(border) != 3 or any(not 0 <= v <= 255 for v in border):
+        raise ValueError(f"{fn}: border must hold three values in 0..255, got {border}")
+    surfaces = list(surfaces)
+    jobs = _matrices_list(matrices, fn, rows=3)
+    if isinstance(surface_index, torch.Tensor):
+        if surface_index.device.type != "cpu":
+            raise ValueError(f"{fn}: surface_index must live on the host: pass surface_index.cpu()")
+        surface_index = surface_index.tolist()
+    try:
+        index = [operator.index(v) for v in surface_index]
+    except TypeError:
+        raise ValueError(f"{fn}: surface_index must hold integers") from None
+    if len(index) != len(jobs):
+        raise ValueError(f"{fn}: {len(index)} surface indices for {len(jobs)} matrices")
+    for i, k in enumerate(index):
+        if not 0 <= k < len(surfaces):
+            raise ValueError(f"{fn}: surface_index[{i}] names surface {k}, there are {len(surfaces)}")
+    n = len(jobs)
+    w, h = resizer.DstSize()
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last)
+    if n == 0:
+        return out
+    elem = out.element_size()
+    with _on_task_stream(resizer, out.device):
+        ok = resizer.ExecutePerspsToTensor(surfaces, index, jobs, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
+                                           cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
+    if not ok:
+        _refused(fn, _RESIZER_REFUSED)
+    return out
+
+
+def quads_to_homographies(quads, size) -> torch.Tensor:
+    """Source quadrilaterals [K, 4, 2] (x, y in luma pixel indices; corners in the order top-left, top-right, bottom-right, bottom-left) -> the float32
+    [K, 3, 3] inverse matrices persps_to_normalized_tensor takes for a destination of size = (dw, dh): matrix k sends the destination corners (0, 0),
+    (dw - 1, 0), (dw - 1, dh - 1), (0, dh - 1) to quad k's corners.  Solved in float64 with m22 = 1 (destination (0, 0) maps to a finite point, so that
+    normalisation always exists), rounded to float32 once.  Pure torch, on whatever device the quads live on.  A degenerate quad (three corners on a
+    line) has no homography: its matrix holds non-finite values or torch.linalg.solve raises.  ValueError for another shape or dw, dh below 2."""
+    fn = "quads_to_homographies"
+    q = torch.as_tensor(quads)
+    if q.dim() != 3 or tuple(q.shape[1:]) != (4, 2):
+        raise ValueError(f"{fn}: quads must have shape [K, 4, 2], got {tuple(q.shape)}")
+    try:
+        dw, dh = (operator.index(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: size must be (dw, dh), two integers, got {size!r}") from None
+    if dw < 2 or dh < 2:
+        raise ValueError(f"{fn}: the destination corners must be four different points: dw and dh at least 2, got {(dw, dh)}")
+    q = q.to(torch.float64)
+    k = q.shape[0]
+    if k == 0:
+        return torch.zeros((0, 3, 3), dtype=torch.float32, device=q.device)
+    d = torch.tensor([[0, 0], [dw - 1, 0], [dw - 1, dh - 1], [0, dh - 1]], dtype=torch.float64, device=q.device)
+    # per corner two rows of A h = b, h = (m00 m01 m02 m10 m11 m12 m20 m21):  m00 dx + m01 dy + m02 - X (m20 dx + m21 dy) = X, likewise Y
+    a = torch.zeros((k, 8, 8), dtype=torch.float64, device=q.device)
+    a[:, 0::2, 0:2] = d
+    a[:, 0::2, 2] = 1.0
+    a[:, 1::2, 3:5] = d
+    a[:, 1::2, 5] = 1.0
+    a[:, 0::2, 6:8] = -q[:, :, 0:1] * d
+    a[:, 1::2, 6:8] = -q[:, :, 1:2] * d
+    b = q.reshape(k, 8, 1)
+    h = torch.linalg.solve(a, b).reshape(k, 8)
+    return torch.cat([h, torch.ones((k, 1), dtype=torch.float64, device=q.device)], dim=1).to(torch.float32).reshape(k, 3, 3)
 
 
 def rotated_boxes_to_warps(boxes_cxcywha, dw, dh) -> torch.Tensor:

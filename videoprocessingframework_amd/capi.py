@@ -32,6 +32,7 @@ EXPORTS = [
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
     "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
+    "vpf_convert_persp_tensor",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -71,6 +72,11 @@ class RoiIO(C.Structure):
 class WarpIO(C.Structure):
     """vpf_warp_io: one job of vpf_convert_warp_tensor — the WHOLE source frame's planes, the destination planes, the inverse 2 x 3 matrix"""
     _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("m", C.c_float * 6)]
+
+
+class PerspIO(C.Structure):
+    """vpf_persp_io: one job of vpf_convert_persp_tensor — the WHOLE source frame's planes, the destination planes, the inverse 3 x 3 matrix"""
+    _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("m", C.c_float * 9), ("reserved", C.c_uint32)]
 
 
 class WarpOpts(C.Structure):
@@ -205,6 +211,7 @@ def lib() -> C.CDLL:
         L.vpf_convert_resize_tensor_batch.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, PF, PN]
         L.vpf_convert_resize_tensor_rois.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(RoiIO), PN]
         L.vpf_convert_warp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(WarpIO), PN, C.POINTER(WarpOpts)]
+        L.vpf_convert_persp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(PerspIO), PN, C.POINTER(WarpOpts)]
         L.vpf_convert_letterbox_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(LetterboxIO), PN,
                                                    C.POINTER(LetterboxOpts)]
         L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
@@ -461,6 +468,30 @@ def convert_warp_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, warps, norm: 
                                        C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
     if check:
         _check(st, "vpf_convert_warp_tensor")
+    return st
+
+
+def make_persps(jobs) -> "C.Array[PerspIO]":
+    """jobs: list of (src_desc, dst_desc, m) with desc as in planes(); src_desc = the planes of the WHOLE frame, m = nine floats
+    (m00 m01 m02 m10 m11 m12 m20 m21 m22) or a 3 x 3 nested sequence: destination pixel -> homogeneous source coordinates"""
+    arr = (PerspIO * len(jobs))()
+    for i, (s, d, m) in enumerate(jobs):
+        s, d = planes(s), planes(d)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+            arr[i].dst[k].ptr, arr[i].dst[k].pitch = d[k].ptr, d[k].pitch
+        flat = [v for row in m for v in row] if len(m) == 3 else list(m)
+        for k in range(9):
+            arr[i].m[k] = flat[k]
+    return arr
+
+
+def convert_persp_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, persps, norm: TensorNorm, opts: WarpOpts = None, n=None, check=True) -> int:
+    """persps: PerspIO array from make_persps(); every job sampled through its 3 x 3 matrix into dw x dh and normalised, 82 jobs per job table"""
+    st = lib().vpf_convert_persp_tensor(C.byref(ex), src_fmt, cs, cr, Size(sw, sh), Size(dw, dh), len(persps) if n is None else n, persps,
+                                        C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_persp_tensor")
     return st
 
 

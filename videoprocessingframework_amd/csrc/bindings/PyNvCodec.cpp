@@ -274,6 +274,34 @@ public:
     }
     return TASK_EXEC_SUCCESS == task_->RunTensorWarps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
   }
+  // additive: K perspective warps of surfaces -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_persp_tensor):
+  // ExecuteWarpsToTensor with the inverse 3 x 3 matrix (nine floats, row-major) per job; a pixel with w <= 0 takes the border in both modes
+  bool ExecutePerspsToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<int64_t>& index, const std::vector<std::array<float, 9>>& matrices,
+                             uint64_t dst, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
+                             std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode,
+                             uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || index.empty() || index.size() != matrices.size() || !dst) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, index.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    vpf_warp_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    opts.border_mode = border_mode;
+    for (int c = 0; c < 3; c++) {
+      if (border[c] < 0 || border[c] > 255) return false;
+      opts.border[c] = (uint8_t)border[c];
+    }
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    std::vector<uint32_t> idx(index.size());
+    std::vector<float> m(9 * index.size());
+    for (size_t i = 0; i < index.size(); i++) {
+      if (index[i] < 0 || index[i] > 0xffffffffll) return false;
+      idx[i] = (uint32_t)index[i];
+      for (int k = 0; k < 9; k++) m[9 * i + k] = matrices[i][k];
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensorPersps(a.data(), (uint32_t)a.size(), idx.data(), m.data(), (uint32_t)index.size(), planes.data(), norm, &opts, cc.get());
+  }
   // additive: up to max_n affine warps whose matrices lie in DEVICE memory -> a normalised planar tensor [max_n, 3, dh, dw] at device address `dst`
   // (vpf_convert_warp_tensor_dev): job k = six float32 at matrices + k matrix_stride, its surface index one int32 at index + k index_stride (index 0:
   // surface 0), *count (device int32; 0: max_n) of them valid; read by the kernel when it runs on the task's stream.  max_step: the LDS hint (0: none).
@@ -864,6 +892,13 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "K affine warps of the surfaces: job i samples surfaces[surface_index[i]] through the inverse 2 x 3 matrix matrices[i] (six floats) into the "
            "task's destination size, normalised, into a planar tensor [K, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous); one "
            "dispatch per 96 regions")
+      .def("ExecutePerspsToTensor", &PySurfaceConvertResizer::ExecutePerspsToTensor, py::arg("surfaces"), py::arg("surface_index"), py::arg("matrices"),
+           py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
+           "K perspective warps of the surfaces: job i samples surfaces[surface_index[i]] through the inverse 3 x 3 matrix matrices[i] (nine floats, row-major: "
+           "destination pixel -> homogeneous source coordinates) into the task's destination size, normalised, into a planar tensor [K, 3, dh, dw] at device "
+           "address ptr (strides in bytes, 0 = contiguous); a pixel with w <= 0 takes the border in both modes; one dispatch per 82 regions")
       .def("ExecuteLetterboxToTensor", &PySurfaceConvertResizer::ExecuteLetterboxToTensor, py::arg("surfaces"), py::arg("rois"), py::arg("dst_rects"),
            py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
            py::arg("pad") = std::vector<int64_t>{0, 0, 0}, py::arg("row_stride") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0,

@@ -628,6 +628,27 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint
                                                 &norm, opts);
   return exec_status(st, "warp regions into a tensor");
 }
+TaskExecStatus ConvertResizeSurface::RunTensorPersps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
+                                                     const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
+                                                     const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorPersps");
+  if (!frames || !n_frames || !frame_index || !matrices || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  std::vector<vpf_persp_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(frames[frame_index[i]], io[i].src);
+    tensor_job_planes(dst, i, norm, io[i].dst);
+    for (int k = 0; k < 9; k++) io[i].m[k] = matrices[9 * i + k];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_persp_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(),
+                                                 &norm, opts);
+  return exec_status(st, "warp regions through homographies into a tensor");
+}
 TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects,
                                                         const vpf_rect* dst_rects, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm,
                                                         const vpf_letterbox_opts* opts, const ColorspaceConversionContext* cc) {

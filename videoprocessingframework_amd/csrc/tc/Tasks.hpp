@@ -81,6 +81,10 @@ public:
   // VPF_WARP_CONSTANT with border 0 0 0.  The same colour-context rules as RunTensor.
   TaskExecStatus RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                 const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
+  // n perspective warps of surfaces (vpf_convert_persp_tensor): RunTensorWarps with the inverse 3 x 3 matrix matrices[9 i .. 9 i + 8] (m00 m01 m02 m10
+  // m11 m12 m20 m21 m22: destination pixel -> homogeneous source coordinates); a pixel with w <= 0 takes the border in both modes.
+  TaskExecStatus RunTensorPersps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
+                                 const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
   // n letterbox jobs (vpf_convert_letterbox_tensor): job i resizes rects[i] of frames[frame_index[i]] into dst_rects[i] (destination pixels, inside
   // the task's destination size) of the planes dst[3 i .. 3 i + 2] and writes the pad everywhere else in them; opts == nullptr: pad 0 0 0.
   // RunTensorRois' colour-context rules; the entry cuts the jobs into job tables.

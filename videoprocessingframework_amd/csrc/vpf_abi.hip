@@ -738,7 +738,45 @@ vpf_status vpf_convert_warp_tensor(const vpf_exec* exec, int sf, int cs, int cr,
   return VPF_OK;
 }
 
-// The same with the matrices, their frame indices and the count in DEVICE memory (include/vpf_hip.h): every check that needs no matrix happens here,
+// Many perspective warps of decoded frames -> one batch of normalised planes (include/vpf_hip.h): the warp entry's checks on nine coefficients,
+// kPerspBatch jobs per job table, each table at most two dispatches (k_convert_persp.hip).
+vpf_status vpf_convert_persp_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_persp_io* jobs,
+                                    const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
+  const Mark mark("vpf_convert_persp_tensor");
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE, opts && opts->reserved)) return refused;
+  if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const TensorLayout l = layout_of(*norm);
+  for (uint32_t i = 0; i < n; i++) {
+    for (int k = 0; k < 9; k++)
+      if (!(std::fabs(jobs[i].m[k]) <= 16777216.0f)) return VPF_ERR_BAD_ARG;  // NaN and infinities fail the comparison too
+    if (jobs[i].reserved) return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, jobs[i].src, true)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(jobs[i].dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
+  PerspDesc table[kPerspBatch];
+  for (uint32_t base = 0; base < n; base += kPerspBatch) {
+    const uint32_t m = (n - base < (uint32_t)kPerspBatch) ? n - base : (uint32_t)kPerspBatch;
+    for (uint32_t i = 0; i < m; i++) {
+      const vpf_persp_io& io = jobs[base + i];
+      vpf_plane d[3];
+      const int nd = tensor_planes(io.dst, l, d);
+      fill_desc(table[i].f, io.src, num_planes(sf), d, nd);
+      for (int k = 0; k < 9; k++) table[i].m[k] = io.m[k];
+    }
+    const hipError_t e = launch_convert_persp(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, m, table, ds.width,
+                                              ds.height, te, l.nhwc);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
+// The affine warp with the matrices, their frame indices and the count in DEVICE memory (include/vpf_hip.h): every check that needs no matrix happens here,
 // the matrix check in the kernel (k_convert_warp_dev.hip); one dispatch.
 vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames,
                                        const vpf_warps_dev* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {

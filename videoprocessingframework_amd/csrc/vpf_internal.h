@@ -186,6 +186,21 @@ struct WarpArgs {
 };
 static_assert(sizeof(WarpDesc) == 96 && sizeof(WarpArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the warp job table must not outgrow the largest frame table");
 
+// The job table of a multi-ROI perspective warp (vpf_convert_persp_tensor, k_convert_persp.hip): WarpDesc with the inverse 3 x 3 matrix
+// m = (m00 m01 m02; m10 m11 m12; m20 m21 m22).  72 + 36 B, 112 with the tail padding of the pointers' alignment: 82 jobs per table, the letterbox
+// table's 9 216 B.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
+constexpr int kPerspBatch = 82;
+struct PerspDesc {
+  FrameDesc f;
+  float m[9];
+};
+struct PerspArgs {
+  PerspDesc j[kPerspBatch];
+  TensorEpi e;
+};
+static_assert(sizeof(PerspDesc) == 112 && sizeof(PerspArgs) == 82 * 112 + 32 && sizeof(PerspArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
+              "the perspective job table must not outgrow the largest frame table");
+
 // The arguments of a warp launch whose matrices live in DEVICE memory (vpf_convert_warp_tensor_dev, k_convert_warp_dev.hip): the shape of RoiDevArgs —
 // the source planes of up to 128 frames, where the matrices, the frame indices and the count lie, and job 0's destination planes with the stride
 // from job to job.  The kernel reads (frame, m[6]) of job blockIdx.z when it runs.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
@@ -256,6 +271,10 @@ hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbC
 // carries border and mode (WarpArgs); k_convert_warp.hip
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
                                uint32_t dh, const TensorEpi& te, bool nhwc = false);
+// n <= kPerspBatch jobs on frames of W x H pixels -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of dw x dh: at most two dispatches (jobs whose
+// tiles may stage, per-tap jobs); `te.pad` carries border and mode; k_convert_persp.hip
+hipError_t launch_convert_persp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const PerspDesc* jobs, uint32_t dw,
+                                uint32_t dh, const TensorEpi& te, bool nhwc = false);
 // n <= kLetterboxBatch jobs on frames `W` pixels wide -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of dw x dh, the picture at each job's (ix, iy, iw, ih)
 // and `te.pad` everywhere else: at most two dispatches (staged jobs, gather jobs); k_convert_letterbox.hip
 hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,

@@ -267,4 +267,131 @@ static inline uint32_t warp_dev_lds_bytes(float max_step, uint32_t W, uint32_t H
   return bytes < kWarpStripMax ? (uint32_t)bytes : kWarpStripMax;
 }
 
+// ------------------------------------------------------------------------------------------
+// Perspective warp (k_convert_persp.hip, vpf_convert_persp_tensor): m = (m00 m01 m02; m10 m11 m12; m20 m21 m22), the warp's tile and strip.
+// tests/test_persp_bounds_cpu.py through tests/c/persp_bounds_capi.cpp.
+// ------------------------------------------------------------------------------------------
+// Coordinates (include/vpf_hip.h): three rounded-affine values, two IEEE divisions, no fma.  `front`: w > 0; a pixel behind the plane or on the
+// horizon (!(w > 0)) has no coordinate (sx = sy = 0 here, never used) and takes the border in both modes.  With finite coefficients and w > 0 no
+// NaN arises; sx, sy = +-inf are legal: out of range under CONSTANT, the edge under REPLICATE (a max, then a min).
+struct PerspXY {
+  float sx, sy;
+  bool front;
+};
+static VPF_JB_HDI PerspXY persp_xy(const float* m, uint32_t dx, uint32_t dy, bool rep, float wmax, float hmax) {
+  const float fx = (float)dx, fy = (float)dy;
+  const float nx = (m[0] * fx + m[1] * fy) + m[2];
+  const float ny = (m[3] * fx + m[4] * fy) + m[5];
+  const float w = (m[6] * fx + m[7] * fy) + m[8];
+  if (!(w > 0.f)) return PerspXY{0.f, 0.f, false};
+  float sx = nx / w, sy = ny / w;
+  if (rep) {
+    sx = fminf(fmaxf(sx, 0.f), wmax);
+    sy = fminf(fmaxf(sy, 0.f), hmax);
+  }
+  return PerspXY{sx, sy, true};
+}
+// What a destination tile [xs, xe] x [ys, ye] does, from its four corners.  w is rounded-affine, hence monotone in dx for fixed dy and in dy for
+// fixed dx, so its sign over the tile is decided at the corners:
+//   kPerspTileBorder  no corner has w > 0: no pixel has, the tile is the border
+//   kPerspTileTap     some corner has, some has not: the horizon crosses or touches the tile, which samples per tap
+//   kPerspTileOut     w > 0 everywhere, the corners' bounding box misses the frame (CONSTANT only): nothing is staged
+//   kPerspTileStage   w > 0 everywhere: the window is the corners' bounding box, one pixel wider on every side, cut to the frame
+// With w > 0 over the tile its exact image is a convex quadrilateral whose bounding box lies at the corners — but fl(fl(nx) / fl(w)) is a quotient
+// of two monotone functions and not monotone itself: with cancellation in nx a pixel's coordinate can lie anywhere.  The window is therefore a guess
+// that is nearly always right (the extra pixel per side absorbs ordinary rounding), and persp_px_in_window is the per-pixel test that makes the
+// kernel correct for every matrix: an in-range pixel that fails it is sampled per tap (kPerspTileOut: every in-range pixel).
+enum { kPerspTileBorder = 0, kPerspTileTap = 1, kPerspTileOut = 2, kPerspTileStage = 3 };
+struct PerspWin {
+  WarpWin w;  // (w.empty: cls != kPerspTileStage)
+  uint32_t cls;
+};
+static VPF_JB_HDI PerspWin persp_window(const float* m, uint32_t xs, uint32_t xe, uint32_t ys, uint32_t ye, bool rep, uint32_t W, uint32_t H) {
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  const PerspXY a = persp_xy(m, xs, ys, rep, wmax, hmax), b = persp_xy(m, xe, ys, rep, wmax, hmax), c = persp_xy(m, xs, ye, rep, wmax, hmax),
+                d = persp_xy(m, xe, ye, rep, wmax, hmax);
+  PerspWin p{WarpWin{0u, 0u, 0u, 0u, true}, kPerspTileBorder};
+  const uint32_t nfront = (uint32_t)a.front + (uint32_t)b.front + (uint32_t)c.front + (uint32_t)d.front;
+  if (nfront == 0u) return p;
+  p.cls = kPerspTileTap;
+  if (nfront != 4u) return p;
+  const float xmin = fminf(fminf(a.sx, b.sx), fminf(c.sx, d.sx)), xmax = fmaxf(fmaxf(a.sx, b.sx), fmaxf(c.sx, d.sx));
+  const float ymin = fminf(fminf(a.sy, b.sy), fminf(c.sy, d.sy)), ymax = fmaxf(fmaxf(a.sy, b.sy), fmaxf(c.sy, d.sy));
+  p.cls = kPerspTileOut;
+  if (!(xmax >= 0.f && xmin <= wmax && ymax >= 0.f && ymin <= hmax)) return p;
+  p.cls = kPerspTileStage;
+  p.w.empty = false;
+  const uint32_t xl = (uint32_t)(int)fmaxf(xmin, 0.f), yl = (uint32_t)(int)fmaxf(ymin, 0.f);
+  const uint32_t xh = (uint32_t)(int)fminf(xmax, wmax), yh = (uint32_t)(int)fminf(ymax, hmax);
+  p.w.x_lo = xl ? xl - 1 : 0u;
+  p.w.y_lo = yl ? yl - 1 : 0u;
+  p.w.x_hi = xh + 2 < W ? xh + 2 : W - 1;
+  p.w.y_hi = yh + 2 < H ? yh + 2 : H - 1;
+  return p;
+}
+// The per-pixel test of the staged kernel, on the taps of an IN-RANGE pixel (xa = floor(sx), ya = floor(sy); the second taps are
+// min(xa + 1, W - 1), min(ya + 1, H - 1), the frame's clamp): all four lie in the window the tile staged.
+static VPF_JB_HDI bool persp_px_in_window(const WarpWin& w, uint32_t xa, uint32_t ya, uint32_t W, uint32_t H) {
+  const uint32_t xb = xa + 1 < W ? xa + 1 : W - 1, yb = ya + 1 < H ? ya + 1 : H - 1;
+  return xa >= w.x_lo && xb <= w.x_hi && ya >= w.y_lo && yb <= w.y_hi;
+}
+// The launcher's LDS bound of a job, O(1).  Jobs with w > 0 at the four DESTINATION corners have w > 0 everywhere (w is affine).
+// d sx / d dx = (m00 w - nx m20) / w^2, and the numerator does not depend on dx: it is A dy + B with A = m00 m21 - m20 m01, B = m00 m22 - m20 m02.
+// For a fixed dy the quotient is largest where w is smallest, at dx = 0 or dw - 1: along either of those two edges it is |B + A t| / (c + d t)^2 in
+// t = dy, whose maximum over [0, dh - 1] lies at an end or at its one stationary point (persp_ratio_max).  Likewise d sx / d dy =
+// (D - A dx) / w^2 with D = m01 m22 - m21 m02, along the edges dy = 0 and dh - 1.  A tile of tw x th pixels therefore spans at most
+// gx (tw - 1) + gy (th - 1) source pixels along x, gx and gy those two maxima over the whole destination (computed in double: the products of floats
+// are exact; every w less the rounding the kernel's fp32 w can carry).  The rounding of a coordinate that lies in the frame (nx's and w's three
+// roundings each, the division's; a window is cut to the frame, so only such coordinates bound it) and the window's extra pixel per side come on top.
+// Jobs the bound does not cover — some destination corner with !(w > 0) — get kWarpStripMax: their tiles decide for themselves.  No corner with
+// w > 0: no tile stages, 0 bytes.  As in the affine entry a tile whose strip exceeds the LDS it was given samples per tap: a short bound costs
+// time, never pixels.
+// max over t in [0, T] of |a + b t| / (c + d t)^2, c + d t > 0 on the interval
+static inline double persp_ratio_max(double a, double b, double c, double d, double T) {
+  double best = fmax(fabs(a) / (c * c), fabs(a + b * T) / ((c + d * T) * (c + d * T)));
+  if (b * d != 0.0) {
+    const double t = (b * c - 2.0 * d * a) / (b * d);  // b (c + d t) = 2 d (a + b t)
+    if (t > 0.0 && t < T) best = fmax(best, fabs(a + b * t) / ((c + d * t) * (c + d * t)));
+  }
+  return best;
+}
+// pixels of a tile's window along one axis, at most (r: the matrix row of that axis, r2: the last row, S: the frame's size along it, werr: what
+// is taken off every w, wmin: the smallest w of the destination less werr)
+static inline uint32_t persp_need_count(const float* r, const float* r2, uint32_t S, double tw, double th, uint32_t dw, uint32_t dh, double werr, double wmin) {
+  const double smax = (double)(S - 1), X = (double)(dw - 1), Y = (double)(dh - 1);
+  const double A = (double)r[0] * r2[1] - (double)r2[0] * r[1], B = (double)r[0] * r2[2] - (double)r2[0] * r[2], D = (double)r[1] * r2[2] - (double)r2[1] * r[2];
+  const double w00 = (double)r2[2] - werr;
+  const double gx = fmax(persp_ratio_max(B, A, w00, r2[1], Y), persp_ratio_max(B, A, w00 + (double)r2[0] * X, r2[1], Y));
+  const double gy = fmax(persp_ratio_max(D, -A, w00, r2[0], X), persp_ratio_max(D, -A, w00 + (double)r2[1] * Y, r2[0], X));
+  const double span = gx * (tw - 1) + gy * (th - 1);
+  const double nmag = fabs((double)r[0]) * dw + fabs((double)r[1]) * dh + fabs((double)r[2]);
+  const double wmag = fabs((double)r2[0]) * dw + fabs((double)r2[1]) * dh + fabs((double)r2[2]);
+  const double err = 4.0 * 0x1p-23 * ((nmag + smax * wmag) / wmin + smax);
+  const double n = floor(span + 2.0 * err) + 5.0;
+  return n < (double)S ? (uint32_t)n : S;
+}
+static inline WarpNeed persp_need(const float m[9], uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  const uint32_t cx[4] = {0u, dw - 1, 0u, dw - 1}, cy[4] = {0u, 0u, dh - 1, dh - 1};
+  uint32_t nfront = 0;
+  double wmin = 0.0;
+  for (int k = 0; k < 4; k++) {
+    const float w = (m[6] * (float)cx[k] + m[7] * (float)cy[k]) + m[8];
+    if (w > 0.f) {
+      wmin = !nfront || (double)w < wmin ? (double)w : wmin;
+      nfront++;
+    }
+  }
+  if (!nfront) return WarpNeed{0u};
+  const double werr = 4.0 * 0x1p-23 * (fabs((double)m[6]) * dw + fabs((double)m[7]) * dh + fabs((double)m[8]));
+  wmin -= 2.0 * werr;  // (the exact w of a corner may lie werr below the fp32 one, and werr is taken off every exact w below)
+  if (nfront != 4u || !(wmin > 0.0)) return WarpNeed{kWarpStripMax};
+  const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
+  const uint32_t nx = persp_need_count(m, m + 6, W, tw, th, dw, dh, werr, wmin), rows = persp_need_count(m + 3, m + 6, H, tw, th, dw, dh, werr, wmin);
+  uint32_t ng = (nx >> 3) + 1;  // the strip starts on the even pixel at or below x_lo
+  const uint32_t ng_max = ((W - 1) >> 3) + 1;
+  ng = ng < ng_max ? ng : ng_max;
+  const uint64_t bytes = (uint64_t)rows * (32u * ng + 16u);
+  return WarpNeed{bytes < 0xffffffffull ? (uint32_t)bytes : 0xffffffffu};
+}
+
 #endif  // VPF_JOB_BOUNDS_H_
