@@ -256,10 +256,11 @@ def test_every_roi_call_launches_both_forms(logs):
 
 
 def test_log_names_p16_nhwc_job_kernels(logs):
-    """the FC_P16 instantiations of the four channels-last per-job kernels are what the P10 calls of this file run"""
+    """the FC_P16 instantiations of the four channels-last per-job kernels are what the P10 calls of this file run (the log carries the template-ids
+    of the code object: FC_P16 = 7, FC_TENSOR_NHWC = 8)"""
     for name in ("p10_roi0", "p10_roi9", "p10_warp0", "p10_warp9"):
         print(name, logs[name])
-    assert len(logs["p10_roi0"]) == 2 and "k_roi_strip_nhwc<FC_P16" in logs["p10_roi0"][0] and "k_roi_gather_nhwc<FC_P16" in logs["p10_roi0"][1], logs["p10_roi0"]
-    assert len(logs["p10_roi9"]) == 1 and "k_roi_gather_nhwc<FC_P16" in logs["p10_roi9"][0], logs["p10_roi9"]
-    assert len(logs["p10_warp0"]) == 2 and "k_warp_strip_nhwc<FC_P16" in logs["p10_warp0"][0] and "k_warp_gather_nhwc<FC_P16" in logs["p10_warp0"][1], logs["p10_warp0"]
-    assert len(logs["p10_warp9"]) == 1 and "k_warp_gather_nhwc<FC_P16" in logs["p10_warp9"][0], logs["p10_warp9"]
+    assert len(logs["p10_roi0"]) == 2 and "k_roi_strip<7, 8>" in logs["p10_roi0"][0] and "k_roi_gather<7, 8>" in logs["p10_roi0"][1], logs["p10_roi0"]
+    assert len(logs["p10_roi9"]) == 1 and "k_roi_gather<7, 8>" in logs["p10_roi9"][0], logs["p10_roi9"]
+    assert len(logs["p10_warp0"]) == 2 and "k_warp_strip<7, 8>" in logs["p10_warp0"][0] and "k_warp_gather<7, 8>" in logs["p10_warp0"][1], logs["p10_warp0"]
+    assert len(logs["p10_warp9"]) == 1 and "k_warp_gather<7, 8>" in logs["p10_warp9"][0], logs["p10_warp9"]

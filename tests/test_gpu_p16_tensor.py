@@ -171,7 +171,7 @@ print("done")
         if "strip_r" in name:
             assert "k_convert_strip_wg<" in logs[name][0]
     assert "kMaxBatch" in logs["batch_33_large_table"][0] and "kMaxBatch" in logs["strip_r16_large_table"][0]
-    for name, kernel in (("roi0", "k_roi_strip<FC_P16>"), ("roi9", "k_roi_gather<FC_P16>"), ("warp0", "k_warp_strip<FC_P16>"), ("warp9", "k_warp_gather<FC_P16>")):
+    for name, kernel in (("roi0", "k_roi_strip<7, 6>"), ("roi9", "k_roi_gather<7, 6>"), ("warp0", "k_warp_strip<7, 6>"), ("warp9", "k_warp_gather<7, 6>")):  # FC_P16 = 7, FC_TENSOR = 6
         assert len(logs[name]) == 1 and kernel in logs[name][0], (name, logs[name])
 
 

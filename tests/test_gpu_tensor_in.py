@@ -156,16 +156,16 @@ def test_kernel_selection():
             for nv12 in (True, False):
                 name = f"fast_{w}x{h}_{dtype}_{int(nv12)}"
                 cases.append((name, w, h, dtype, nv12, 0, 0, 0))
-                want[name] = (FAST, f"k_tensor_yuv_r<{('VPF_TENSOR_F32', 'VPF_TENSOR_F16', 'VPF_TENSOR_BF16')[dtype]}, {'true' if nv12 else 'false'}>")
+                want[name] = (FAST, f"k_tensor_yuv_r<{dtype}, {'true' if nv12 else 'false'}, false>")  # <dtype, NV12, NHWC> as the code object has them
     for w, h in GENERIC_SIZES:
         for nv12 in (True, False):
             name = f"generic_{w}x{h}_{int(nv12)}"
             cases.append((name, w, h, (w + h) % 3, nv12, 0, 0, 0))
-            want[name] = (GENERIC, f"k_tensor_yuv_quad<{'true' if nv12 else 'false'}>")
+            want[name] = (GENERIC, f"k_tensor_yuv_quad<{'true' if nv12 else 'false'}, false>")
     cases += [("forced", 1280, 720, 0, True, 9, 0, 0), ("src_off", 1280, 720, 1, True, 0, 1, 0), ("dst_off", 1280, 720, 2, False, 0, 0, 8),
               ("yuv420_8B_chroma", 1296, 720, 0, False, 0, 0, 0)]
-    want.update(forced=(GENERIC, "k_tensor_yuv_quad<true>"), src_off=(GENERIC, "k_tensor_yuv_quad<true>"), dst_off=(GENERIC, "k_tensor_yuv_quad<false>"),
-                yuv420_8B_chroma=(FAST, "k_tensor_yuv_r<VPF_TENSOR_F32, false>"))  # 1296 / 2 = 648: chroma rows 8-B, not 16-B aligned
+    want.update(forced=(GENERIC, "k_tensor_yuv_quad<true, false>"), src_off=(GENERIC, "k_tensor_yuv_quad<true, false>"), dst_off=(GENERIC, "k_tensor_yuv_quad<false, false>"),
+                yuv420_8B_chroma=(FAST, "k_tensor_yuv_r<0, false, false>"))  # 1296 / 2 = 648: chroma rows 8-B, not 16-B aligned
     logs = selection_log(cases)
     for name, (family, exact) in want.items():
         lines = logs[name]

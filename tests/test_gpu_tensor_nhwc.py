@@ -198,14 +198,15 @@ print("done")
     assert seen == {"k_convert_half<", "k_convert_strip_wg<", "k_convert_resize_band<", "k_convert_resize_lds<", "k_convert_resize<"}, seen
     # 97 jobs = two job tables; each table of the ROI call holds staged and per-tap jobs (the whole frame is a 12 x 4 down-scale)
     print(logs["rois"], logs["warps"], logs["warps9"])
-    assert any("k_roi_strip_nhwc<" in l for l in logs["rois"]) and any("k_roi_gather_nhwc<" in l for l in logs["rois"]), logs["rois"]
-    assert all("_nhwc<" in l for l in logs["rois"] + logs["warps"] + logs["warps9"])
-    assert any("k_warp_strip_nhwc<" in l for l in logs["warps"]), logs["warps"]
-    assert logs["warps9"] and all("k_warp_gather_nhwc<" in l for l in logs["warps9"]), logs["warps9"]
+    # the log carries the kernels' template-ids as the code object has them: <source class, destination class>, FC_NV12 = 0, FC_TENSOR_NHWC = 8
+    assert any("k_roi_strip<0, 8>" in l for l in logs["rois"]) and any("k_roi_gather<0, 8>" in l for l in logs["rois"]), logs["rois"]
+    assert all(", 8>)" in l for l in logs["rois"] + logs["warps"] + logs["warps9"])
+    assert any("k_warp_strip<0, 8>" in l for l in logs["warps"]), logs["warps"]
+    assert logs["warps9"] and all("k_warp_gather<0, 8>" in l for l in logs["warps9"]), logs["warps9"]
     for name, w, h, dtype, nv12, soff in ENCODE_LOG_CASES:
         fast = soff == 0 and w % 16 == 0 and h % 2 == 0
-        exact = (f"k_tensor_yuv_r_nhwc<{('VPF_TENSOR_F32', 'VPF_TENSOR_F16', 'VPF_TENSOR_BF16')[dtype]}, {'true' if nv12 else 'false'}>" if fast
-                 else f"k_tensor_yuv_quad_nhwc<{'true' if nv12 else 'false'}>")
+        exact = (f"k_tensor_yuv_r<{dtype}, {'true' if nv12 else 'false'}, true>" if fast  # <dtype (VPF_TENSOR_F32 = 0, F16 = 1, BF16 = 2), NV12, NHWC>
+                 else f"k_tensor_yuv_quad<{'true' if nv12 else 'false'}, true>")
         assert len(logs[name]) == 1 and exact in logs[name][0], (name, exact, logs[name])
 
 

@@ -4,9 +4,9 @@ k_roi_strip returns without writing, k_warp_strip blends a pixel from the wrong 
 (tests/c/job_bounds_capi.cpp); the reference side is numpy float32 and never calls it.
 
 Restated here: make_tap<LINEAR> (k_bilinear_blend.h; fma in fp32: the product of two floats is exact in float64, the sum with -0.5 as well at
-these magnitudes, one rounding to float32), the strip geometry of k_convert_roi_strip_body.h, the coordinates of the warp definition
+these magnitudes, one rounding to float32), the strip geometry of k_roi_strip (k_convert_roi.hip), the coordinates of the warp definition
 (include/vpf_hip.h: sx = (m00 dx + m01 dy) + m02, every operation rounded on its own — numpy float32 arrays round every operation, and the
-library is built with -ffp-contract=off), vpf_remap's range test, and the unit index of VPF_STRIP_FILL_WINDOW (k_fused_common.h)."""
+library is built with -ffp-contract=off), vpf_remap's range test, and the unit index of strip_fill_window (k_fused_common.h)."""
 import ctypes as C
 import math
 import os
@@ -58,7 +58,7 @@ def lin_taps(d, S, D):
 
 
 def roi_strips(x, y, w, h, dw, dh):
-    """what k_convert_roi_strip_body.h computes per 256-column chunk (first, last, base_px, ng, rowbytes) and per 16-row band (R_hi - R_lo + 1)"""
+    """what k_roi_strip computes per 256-column chunk (first, last, base_px, ng, rowbytes) and per 16-row band (R_hi - R_lo + 1)"""
     xs = np.arange(0, dw, 256)
     xe = np.minimum(xs + 255, dw - 1)
     first, last = x + lin_taps(xs, w, dw)[0], x + lin_taps(xe, w, dw)[1]
@@ -195,7 +195,7 @@ def check_warp_job(jb, m, W, H, dw, dh, rep, rng, tiles_max=12):
     empty = win[..., 4] == 1
     need = jb.jb_warp_need(mp, W, H, dw, dh)
     what = (m.tolist(), W, H, dw, dh, rep)
-    # the strip of the window, restated (k_convert_warp_strip_body.h fills [base_px, base_px + 8 ng) x [y_lo, y_hi])
+    # the strip of the window, restated (warp_strip_tile, k_convert_warp_common.h, fills [base_px, base_px + 8 ng) x [y_lo, y_hi])
     base = win[..., 0] & ~1
     ng = ((win[..., 1] - base) >> 3) + 1
     assert ((win[..., 5] == base) & (win[..., 6] == ng) & (win[..., 7] == 32 * ng + 16) & (win[..., 8] == win[..., 3] - win[..., 2] + 1)
@@ -275,7 +275,7 @@ def test_warp_xy_is_the_definition(jb):
 
 
 def test_fill_stage_unit_index_is_integer_division():
-    """VPF_STRIP_FILL_WINDOW maps unit u to (u / ng, u % ng) through (uint32_t)(((float)u + 0.5f) * (1.0f / ng)): equal to integer division for
+    """strip_fill_window maps unit u to (u / ng, u % ng) through (uint32_t)(((float)u + 0.5f) * (1.0f / ng)): equal to integer division for
     every ng and every u < units of every strip within the larger of the two strip limits (64 KiB: rows x (32 ng + 16) bytes; `rows` rows
     lie under at most rows / 2 + 1 chroma rows, one unit per chroma row and group), enumerated exhaustively"""
     limit = 64 * 1024

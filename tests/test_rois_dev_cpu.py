@@ -246,12 +246,12 @@ def test_boxes_to_rois_is_its_integer_definition():
         pnc.boxes_to_rois(torch.zeros((3, 4)), [0, 0], W, H)
 
 
-_DEV_KERNEL = re.compile(r"k_roi_dev(_nhwc)?<[017]>")  # FC_NV12 = 0, FC_YUV420 = 1, FC_P16 = 7
+_DEV_KERNEL = re.compile(r"k_roi_dev<[017], [68]>")  # FC_NV12 = 0, FC_YUV420 = 1, FC_P16 = 7; FC_TENSOR = 6, FC_TENSOR_NHWC = 8
 
 
 @pytest.mark.timeout(900)
 def test_the_six_instantiations_use_no_scratch():
-    """resource metadata of the code object only (tools/isa_stats.spills): k_roi_dev and k_roi_dev_nhwc for NV12, YUV420 and P10 / P12 hold the staged
+    """resource metadata of the code object only (tools/isa_stats.spills): both layouts of k_roi_dev for NV12, YUV420 and P10 / P12 hold the staged
     AND the per-tap form in one kernel — no scratch, no spills, at most 128 VGPRs (two workgroups of 256 lanes per SIMD)"""
     import isa_stats
 

@@ -280,12 +280,12 @@ def test_rotated_boxes_to_warps_is_its_definition():
         pnc.rotated_boxes_to_warps(torch.zeros((3, 5)), 0, 8)
 
 
-_DEV_KERNEL = re.compile(r"k_warp_dev(_nhwc)?<[017]>")  # FC_NV12 = 0, FC_YUV420 = 1, FC_P16 = 7
+_DEV_KERNEL = re.compile(r"k_warp_dev<[017], [68]>")  # FC_NV12 = 0, FC_YUV420 = 1, FC_P16 = 7; FC_TENSOR = 6, FC_TENSOR_NHWC = 8
 
 
 @pytest.mark.timeout(900)
 def test_the_six_instantiations_use_no_scratch():
-    """resource metadata of the code object only (tools/isa_stats.spills): k_warp_dev and k_warp_dev_nhwc for NV12, YUV420 and P10 / P12 hold the staged
+    """resource metadata of the code object only (tools/isa_stats.spills): both layouts of k_warp_dev for NV12, YUV420 and P10 / P12 hold the staged
     AND the per-tap form in one kernel — no scratch, no spills, at most 128 VGPRs (two workgroups of 256 lanes per SIMD)"""
     import isa_stats
 

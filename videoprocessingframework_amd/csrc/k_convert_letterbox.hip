@@ -6,13 +6,14 @@
 //                 pixels start at a multiple of four columns of the plane, so an aligned tensor keeps its 16-B / 8-B stores whatever ix is.
 //                 A tile that misses the picture stores the pad and leaves (no load, no strip, no barrier); a tile that meets it clips its
 //                 column and row range to the picture, converts the taps' source window once into an LDS strip of four-byte RGB pixels
-//                 (VPF_STRIP_FILL_WINDOW, the fill stage of k_roi_strip) and blends from bytes, choosing per pixel between blend and pad
+//                 (strip_fill_window, the fill stage of k_roi_strip) and blends from bytes, choosing per pixel between blend and pad
 //   k_lb_gather   per-tap texel_rgb: jobs whose window does not pay or does not fit (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
 // Definition (include/vpf_hip.h): inside the picture the byte vpf_convert_resize_tensor_rois defines for rect -> (iw, ih) at (dx - ix, dy - iy) —
 // make_tap<LINEAR> on the rectangle with scale (float)w / (float)iw, frame texels at absolute coordinates, bilerp, truncation —, outside pad[c];
 // then the tensor epilogue.  Both kernels run exactly the ROI kernels' fp32 operations in their order on the picture: identical bits.
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "k_job_launch.h"
 #include "vpf_job_bounds.h"  // kRoiBandRows, letterbox_strip_need, the policy's limits: shared with the CPU property test
 
 namespace vpf {
@@ -84,10 +85,10 @@ __global__ __launch_bounds__(256) void k_lb_strip(const LetterboxArgs args, cons
   const uint32_t R_lo_rel = __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(cys, scy, rh).i0);
   const uint32_t R_lo = ry + R_lo_rel, R_hi = ry + __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(cye, scy, rh).i1);  // frame rows
   uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
-  const uint32_t c_lo = R_lo >> 1, ncr = (R_hi >> 1) - c_lo + 1, ng = ((last - base_px) >> 3) + 1, units = ncr * ng;
+  const uint32_t ng = ((last - base_px) >> 3) + 1;
   const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
   if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, letterbox_strip_need)
-  VPF_STRIP_FILL_WINDOW  // (k_fused_common.h: shared with k_roi_strip and k_warp_strip)
+  strip_fill_window<SRC>(f, c, W, strip, base_px, R_lo, R_hi, ng, rowbytes, tid);  // (k_fused_common.h: shared with k_roi_strip and k_warp_strip)
   __syncthreads();
   if (ya > Y1) return;
   const uint32_t ra = ya > iy ? ya : iy, rb = yb < iye ? yb : iye;  // the wave's rows inside the picture (none: ra > rb)
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void k_lb_strip(const LetterboxArgs args, cons
 // The gather form: k_roi_gather on the plane (four rows x 64 lanes x 4 pixels per workgroup, a wave = one row).  A lane whose four
 // columns miss the picture loads nothing; a wave whose row or columns miss it branches over the conversion as a whole.
 // ------------------------------------------------------------------------------------------
-template <int SRC, int DST>  // (FC_TENSOR_NHWC: four waves per SIMD asked for, as k_roi_gather_nhwc)
+template <int SRC, int DST>  // (FC_TENSOR_NHWC: four waves per SIMD asked for, as k_roi_gather)
 __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gather(const LetterboxArgs args, const Yuv2RgbCoef c, uint32_t dw,
                                                                                     uint32_t dh, uint32_t dmask) {
   const LetterboxDesc& L = args.j[blockIdx.z];
@@ -173,44 +174,27 @@ __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gat
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
                                     uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kLetterboxBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
-  const uint32_t dmask = nhwc || (te.dtype & kEpiDtypeMask) == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane (one interleaved plane: 16 B)
-  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
-  LetterboxArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
-  std::memset(&as, 0, sizeof(as));
-  std::memset(&ag, 0, sizeof(ag));
-  as.e = ag.e = te;
-  uint32_t ns = 0, ngat = 0, lds = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const LetterboxDesc& j = jobs[i];
-    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : letterbox_strip_need(j.r.x, j.r.w, j.r.h, j.r.scx, j.r.scy, j.ix, j.iy, j.iw, j.ih, dw, dh);
-    if (!all_gather && roi_job_staged(need)) {
-      as.j[ns++] = jobs[i];
-      lds = need.bytes > lds ? need.bytes : lds;
-    } else {
-      ag.j[ngat++] = jobs[i];
-    }
-  }
+  if (!n || n > (uint32_t)kLetterboxBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
+  const uint32_t dmask = job_dmask(te, nhwc);
+  LetterboxArgs as, ag;
+  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const LetterboxDesc& j) {
+    const RoiStripNeed need = letterbox_strip_need(j.r.x, j.r.w, j.r.h, j.r.scx, j.r.scy, j.ix, j.iy, j.iw, j.ih, dw, dh);
+    return roi_job_staged(need) ? need.bytes : kNotStaged;
+  });
+  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
+  hipError_t e = hipSuccess;
   if (ns) {
     const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
     const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &as.e) : lds;  // the strip, then the waves' staging area where both fit
-#define VPF_LBS(S) do { if (nhwc) VPF_LAUNCH((k_lb_strip<S, FC_TENSOR_NHWC>), grid, dim3(256), lds_all, st, as, c, W, dw, dh, dmask, lds); \
-                        else VPF_LAUNCH((k_lb_strip<S, FC_TENSOR>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds); } while (0)
-    if (src_fc == FC_NV12) VPF_LBS(FC_NV12); else if (src_fc == FC_P16) VPF_LBS(FC_P16); else VPF_LBS(FC_YUV420);
-#undef VPF_LBS
-    const hipError_t e = hipGetLastError();
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_lb_strip, (S, D), grid, lds_all, st, as, c, W, dw, dh, dmask, lds); e = hipGetLastError(); });
     if (e != hipSuccess) return e;
   }
   if (ngat) {
     const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
     const uint32_t lds_g = nhwc ? nhwc_stage_plan(te, 0u, 4, &ag.e) : 0u;
-#define VPF_LBG(S) do { if (nhwc) VPF_LAUNCH((k_lb_gather<S, FC_TENSOR_NHWC>), grid, dim3(256), lds_g, st, ag, c, dw, dh, dmask); \
-                        else VPF_LAUNCH((k_lb_gather<S, FC_TENSOR>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask); } while (0)
-    if (src_fc == FC_NV12) VPF_LBG(FC_NV12); else if (src_fc == FC_P16) VPF_LBG(FC_P16); else VPF_LBG(FC_YUV420);
-#undef VPF_LBG
-    return hipGetLastError();
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_lb_gather, (S, D), grid, lds_g, st, ag, c, dw, dh, dmask); e = hipGetLastError(); });
   }
-  return hipSuccess;
+  return e;
 }
 
 }  // namespace vpf

@@ -3,7 +3,7 @@
 // Grid = (destination tiles of 32 x 32, job); a lane owns four consecutive pixels of one row, a workgroup 8 lanes x 32 rows.
 //   k_persp_strip    the staged form.  A tile whose four corners have w > 0 (then every pixel has: w is rounded-affine, monotone along both axes)
 //                    converts the corners' bounding box, one pixel wider per side, into an LDS strip of four-byte RGB pixels
-//                    (VPF_STRIP_FILL_WINDOW), one barrier, and blends from bytes.  Every in-range pixel tests its taps against that window
+//                    (strip_fill_window), one barrier, and blends from bytes.  Every in-range pixel tests its taps against that window
 //                    (persp_px_in_window): fl(fl(nx) / fl(w)) is not monotone, so the corner box is a guess; a pixel outside it is sampled per tap.
 //                    A tile the horizon crosses or touches samples per tap; one wholly behind the plane writes the border; one whose strip exceeds
 //                    the LDS of the dispatch samples per tap.  All workgroup-uniform branches.
@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "k_convert_warp_common.h"
+#include "k_job_launch.h"
 
 namespace vpf {
 
@@ -57,39 +58,94 @@ VPF_DEV void persp_gather4(const PerspDesc& J, const Yuv2RgbCoef& c, const Tenso
 }
 
 // ------------------------------------------------------------------------------------------
-// The staged form (DST = FC_TENSOR: three planes per job, k_persp_strip; FC_TENSOR_NHWC: one interleaved plane, k_persp_strip_nhwc)
+// The staged form (DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane).  What differs from the affine kernel
+// (k_warp_strip): the tile's class (persp_window: border, per tap, nothing staged, staged), and the per-pixel test of an in-range pixel's taps against
+// the window the tile staged (persp_px_in_window) — the affine kernel's "an in-range coordinate lies inside the window" does not hold for a rounded
+// quotient, so a pixel that fails the test is sampled per tap instead of being pulled into the window.
 // ------------------------------------------------------------------------------------------
-template <int SRC>
+template <int SRC, int DST>
 __global__ __launch_bounds__(256) void k_persp_strip(const PerspArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
                                                      uint32_t dmask, uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR;
   const PerspDesc& J = args.j[blockIdx.z];
-#include "k_convert_persp_strip_body.h"
-}
-template <int SRC>
-__global__ __launch_bounds__(256) void k_persp_strip_nhwc(const PerspArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
-                                                          uint32_t dmask, uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR_NHWC;  // one interleaved plane per job
-  const PerspDesc& J = args.j[blockIdx.z];
-#include "k_convert_persp_strip_body.h"
+  const FrameDesc& f = J.f;
+  const TensorEpi te = args.e;
+  const bool rep = warp_rep(te);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t xs = blockIdx.x * kWarpTileW, ys = blockIdx.y * kWarpTileH;  // the grid covers the destination exactly: xs < dw, ys < dh
+  const uint32_t xe = (xs + kWarpTileW - 1 < dw - 1) ? xs + kWarpTileW - 1 : dw - 1, ye = (ys + kWarpTileH - 1 < dh - 1) ? ys + kWarpTileH - 1 : dh - 1;
+  const uint32_t x0 = xs + (tid % kWarpLanesX) * 4, y = ys + tid / kWarpLanesX;
+  const bool mine = x0 < dw && y < dh;
+  PerspWin pw = persp_window(J.m, xs, xe, ys, ye, rep, W, H);
+  pw.cls = __builtin_amdgcn_readfirstlane(pw.cls);
+  WarpWin& w = pw.w;
+  w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
+  w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  if (pw.cls == kPerspTileBorder) {  // behind the plane: both modes
+    if (!mine) return;
+    float u[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) u[ch][k] = warp_border(te, ch);
+    warp_store4<DST>(f, x0, y, u, te, vec, nv);
+    return;
+  }
+  const bool staged = pw.cls == kPerspTileStage;
+  const WarpStrip S = warp_strip(w);  // (not staged: the window is 0 .. 0, never read)
+  if (pw.cls == kPerspTileTap || (staged && S.bytes > lds_bytes)) {  // the horizon in the tile, or a strip the dispatch has no room for
+    if (mine) persp_gather4<SRC, DST>(J, c, te, W, H, dw, dmask, x0, y);
+    return;
+  }
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  if (staged) {
+    strip_fill_window<SRC>(f, c, W, strip, S.base_px, w.y_lo, w.y_hi, S.ng, S.rowbytes, tid);
+    __syncthreads();
+  }
+  if (!mine) return;
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  float u[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const PerspXY s = persp_xy(J.m, (x0 + k < dw) ? x0 + k : dw - 1, y, rep, wmax, hmax);  // (front: w > 0 on every pixel of this tile)
+    const bool in = s.front && s.sx >= 0.f && s.sx <= wmax && s.sy >= 0.f && s.sy <= hmax;
+    const float cx = __builtin_amdgcn_fmed3f(s.sx, 0.f, wmax), cy = __builtin_amdgcn_fmed3f(s.sy, 0.f, hmax);  // == sx, sy when in range
+    const uint32_t xa0 = (uint32_t)(int)cx, ya0 = (uint32_t)(int)cy;
+    const bool inwin = staged && persp_px_in_window(w, xa0, ya0, W, H);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (staged) {
+      // a pixel inside the window keeps its taps (xb = min(xa + 1, W - 1) <= x_hi was tested); every other one reads some pixel of the strip and is
+      // replaced below
+      const uint32_t xa = xa0 < w.x_lo ? w.x_lo : (xa0 < w.x_hi ? xa0 : w.x_hi), ya = ya0 < w.y_lo ? w.y_lo : (ya0 < w.y_hi ? ya0 : w.y_hi);
+      const uint32_t xb = xa + 1 < w.x_hi ? xa + 1 : w.x_hi, yb = ya + 1 < w.y_hi ? ya + 1 : w.y_hi;
+      const float fx = cx - (float)xa0, fy = cy - (float)ya0;
+      const uint8_t* const ra = strip + (ya - w.y_lo) * S.rowbytes, * const rb = strip + (yb - w.y_lo) * S.rowbytes;
+      const uint32_t oa = 4 * (xa - S.base_px), ob = 4 * (xb - S.base_px);
+      const uint32_t q00 = *reinterpret_cast<const uint32_t*>(ra + oa), q01 = *reinterpret_cast<const uint32_t*>(ra + ob);
+      const uint32_t q10 = *reinterpret_cast<const uint32_t*>(rb + oa), q11 = *reinterpret_cast<const uint32_t*>(rb + ob);
+      v[0] = __builtin_truncf(bilerp(ubyte<0>(q00), ubyte<0>(q01), ubyte<0>(q10), ubyte<0>(q11), fx, fy));
+      v[1] = __builtin_truncf(bilerp(ubyte<1>(q00), ubyte<1>(q01), ubyte<1>(q10), ubyte<1>(q11), fx, fy));
+      v[2] = __builtin_truncf(bilerp(ubyte<2>(q00), ubyte<2>(q01), ubyte<2>(q10), ubyte<2>(q11), fx, fy));
+    }
+    if (in && !inwin) persp_tap<SRC>(f, c, cx, cy, W, H, v);  // cold: the corner box missed this pixel (or nothing was staged)
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) u[ch][k] = in ? v[ch] : warp_border(te, ch);
+  }
+  warp_store4<DST>(f, x0, y, u, te, vec, nv);
 }
 
 // ------------------------------------------------------------------------------------------
 // The gather form: the same tile and lane assignment, four texel_rgb per pixel.
 // ------------------------------------------------------------------------------------------
-template <int SRC>
+template <int SRC, int DST>
 __global__ __launch_bounds__(256) void k_persp_gather(const PerspArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
                                                       uint32_t dmask) {
   const uint32_t x0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, y = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
   if (x0 >= dw || y >= dh) return;
-  persp_gather4<SRC, FC_TENSOR>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
-}
-template <int SRC>
-__global__ __launch_bounds__(256) void k_persp_gather_nhwc(const PerspArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
-                                                           uint32_t dmask) {
-  const uint32_t x0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, y = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
-  if (x0 >= dw || y >= dh) return;
-  persp_gather4<SRC, FC_TENSOR_NHWC>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
+  persp_gather4<SRC, DST>(args.j[blockIdx.z], c, args.e, W, H, dw, dmask, x0, y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -101,40 +157,23 @@ __global__ __launch_bounds__(256) void k_persp_gather_nhwc(const PerspArgs args,
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_persp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const PerspDesc* jobs, uint32_t dw,
                                 uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kPerspBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
-  const uint32_t dmask = nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B)
-  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
-  PerspArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
-  std::memset(&as, 0, sizeof(as));
-  std::memset(&ag, 0, sizeof(ag));
-  as.e = ag.e = te;
-  uint32_t ns = 0, ngat = 0, lds = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const WarpNeed need = all_gather ? WarpNeed{0u} : persp_need(jobs[i].m, W, H, dw, dh);
-    if (!all_gather && need.bytes <= kWarpStripMax) {
-      as.j[ns++] = jobs[i];
-      lds = need.bytes > lds ? need.bytes : lds;
-    } else {
-      ag.j[ngat++] = jobs[i];
-    }
-  }
+  if (!n || n > (uint32_t)kPerspBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
+  const uint32_t dmask = job_dmask(te, nhwc);
+  PerspArgs as, ag;
+  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const PerspDesc& j) {
+    const WarpNeed need = persp_need(j.m, W, H, dw, dh);
+    return need.bytes <= kWarpStripMax ? need.bytes : kNotStaged;
+  });
+  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
   const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
+  hipError_t e = hipSuccess;
   if (ns) {
-#define VPF_PERSPS(S) do { if (nhwc) VPF_LAUNCH((k_persp_strip_nhwc<S>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds); \
-                           else VPF_LAUNCH((k_persp_strip<S>), dim3(gx, gy, ns), dim3(256), lds, st, as, c, W, H, dw, dh, dmask, lds); } while (0)
-    if (src_fc == FC_NV12) VPF_PERSPS(FC_NV12); else if (src_fc == FC_P16) VPF_PERSPS(FC_P16); else VPF_PERSPS(FC_YUV420);
-#undef VPF_PERSPS
-    const hipError_t e = hipGetLastError();
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_strip, (S, D), dim3(gx, gy, ns), lds, st, as, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
     if (e != hipSuccess) return e;
   }
-  if (ngat) {
-#define VPF_PERSPG(S) do { if (nhwc) VPF_LAUNCH((k_persp_gather_nhwc<S>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask); \
-                           else VPF_LAUNCH((k_persp_gather<S>), dim3(gx, gy, ngat), dim3(256), 0, st, ag, c, W, H, dw, dh, dmask); } while (0)
-    if (src_fc == FC_NV12) VPF_PERSPG(FC_NV12); else if (src_fc == FC_P16) VPF_PERSPG(FC_P16); else VPF_PERSPG(FC_YUV420);
-#undef VPF_PERSPG
-    return hipGetLastError();
-  }
-  return hipSuccess;
+  if (ngat)
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_gather, (S, D), dim3(gx, gy, ngat), 0u, st, ag, c, W, H, dw, dh, dmask); e = hipGetLastError(); });
+  return e;
 }
 
 }  // namespace vpf

@@ -10,6 +10,7 @@
 // P10 / P12 frames (FC_P16) take the same two kernels: their 16-bit samples are narrowed to 8 bits at the load (k_fused_common.h).
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "k_job_launch.h"
 #include "vpf_job_bounds.h"  // kRoiBandRows, roi_strip_need, the policy's limits: shared with the CPU property test
 
 namespace vpf {
@@ -22,32 +23,83 @@ namespace vpf {
 // row's last sample instead of the 8-byte ones (its surplus pixels are converted and never blended): no byte outside the frame's own
 // rows is read.  Rows need no clamp: every row of the window lies in the rectangle, every chroma row under it in the frame.
 // ------------------------------------------------------------------------------------------
-// (DST = FC_TENSOR: three planes per job, k_roi_strip; FC_TENSOR_NHWC: one interleaved plane, k_roi_strip_nhwc)
-template <int SRC>
+template <int SRC, int DST>  // DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane
 __global__ __launch_bounds__(256) void k_roi_strip(const RoiArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t dw, uint32_t dh, uint32_t dmask,
                                                    uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR;
-#include "k_convert_roi_strip_body.h"
-}
-template <int SRC>
-__global__ __launch_bounds__(256) void k_roi_strip_nhwc(const RoiArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t dw, uint32_t dh, uint32_t dmask,
-                                                   uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR_NHWC;  // one interleaved plane per job
-#include "k_convert_roi_strip_body.h"
+  constexpr int R = kRoiBandRows;
+  const RoiDesc& J = args.j[blockIdx.z];
+  const FrameDesc& f = J.f;
+  const uint32_t rx = J.x, ry = J.y, rw = J.w, rh = J.h;
+  const float scx = J.scx, scy = J.scy;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
+  const uint32_t Y0 = blockIdx.y * (4 * R), xs = blockIdx.x * 256;  // the grid covers the destination exactly: Y0 < dh, xs < dw
+  const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
+  const uint32_t first = rx + make_tap<VPF_INTERP_LINEAR>(xs, scx, rw).i0, last = rx + make_tap<VPF_INTERP_LINEAR>(xe, scx, rw).i1;  // frame pixels
+  const uint32_t base_px = first & ~1u;
+  const uint32_t R_lo_rel = __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y0, scy, rh).i0);
+  const uint32_t R_lo = ry + R_lo_rel, R_hi = ry + __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y1, scy, rh).i1);  // frame rows
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  const uint32_t ng = ((last - base_px) >> 3) + 1;
+  const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
+  if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, launch_convert_resize_rois)
+  strip_fill_window<SRC>(f, c, W, strip, base_px, R_lo, R_hi, ng, rowbytes, tid);  // (k_fused_common.h: shared with k_warp_strip)
+  __syncthreads();
+  const uint32_t ya = Y0 + wv * R;
+  if (ya > Y1) return;
+  const uint32_t yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;
+  const Tap row_taps = band_row_taps(ya, yb, scy, rh);  // every lane of the wave still active here
+  const uint32_t x0 = xs + lane * 4;
+  if (x0 >= dw) return;
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const ColTapsX T = make_col_taps_x(base_px - rx, x0, dw, rw, scx);  // tap offsets from the strip's first pixel (frame pixel base_px = rectangle pixel base_px - x, modulo 2^32)
+  const TensorEpi te = args.e;
+  band_blend_rows<3, R>(strip, rowbytes, R_lo_rel, ya, yb, row_taps, T, [&](uint32_t y, const float* o) {  // o: pixel-major R G B, + 0.5 added
+    if constexpr (DST == FC_TENSOR_NHWC) {
+      tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, o, 1, 3, te, vec, nv, wv, lane);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec, nv);
+    }
+  });
 }
 
 // ------------------------------------------------------------------------------------------
 // The gather form: k_convert_resize with per-job geometry (four lanes-rows x 64 lanes x 4 pixels per workgroup).
 // ------------------------------------------------------------------------------------------
-template <int SRC>
-__global__ __launch_bounds__(256) void k_roi_gather(const RoiArgs args, const Yuv2RgbCoef c, uint32_t dw, uint32_t dh, uint32_t dmask) {
-  constexpr int DST = FC_TENSOR;
-#include "k_convert_roi_gather_body.h"
-}
-template <int SRC>  // (four waves per SIMD asked for: the YUV420 instantiation stays within 128 VGPRs — the planar one takes 136)
-__global__ __launch_bounds__(256, 4) void k_roi_gather_nhwc(const RoiArgs args, const Yuv2RgbCoef c, uint32_t dw, uint32_t dh, uint32_t dmask) {
-  constexpr int DST = FC_TENSOR_NHWC;
-#include "k_convert_roi_gather_body.h"
+template <int SRC, int DST>  // (FC_TENSOR_NHWC: four waves per SIMD asked for — the YUV420 instantiation stays within 128 VGPRs, the planar one takes 136)
+__global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_roi_gather(const RoiArgs args, const Yuv2RgbCoef c, uint32_t dw, uint32_t dh,
+                                                                                     uint32_t dmask) {
+  const RoiDesc& J = args.j[blockIdx.z];
+  const FrameDesc& f = J.f;
+  const uint32_t x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  const uint32_t y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x0 >= dw || y >= dh) return;
+  const Tap ty = make_tap<VPF_INTERP_LINEAR>(y, J.scy, J.h);
+  float o[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const Tap tx = make_tap<VPF_INTERP_LINEAR>((x0 + k < dw) ? x0 + k : dw - 1, J.scx, J.w);
+    float p00[3], p01[3], p10[3], p11[3];
+    texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i0, p00);
+    texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i0, p01);
+    texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i1, p10);
+    texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i1, p11);
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) o[ch][k] = bilerp(p00[ch], p01[ch], p10[ch], p11[ch], tx.f, ty.f);
+  }
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  if constexpr (DST == FC_TENSOR_NHWC) {
+    tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, &o[0][0], 4, 1, args.e, vec, nv,
+                                    __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+  } else {
+    for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, args.e, ch, vec, nv);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -57,46 +109,29 @@ __global__ __launch_bounds__(256, 4) void k_roi_gather_nhwc(const RoiArgs args, 
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
                                       uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kRoiBatch || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16)) return hipErrorInvalidValue;
-  const uint32_t dmask = nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B)
+  if (!n || n > (uint32_t)kRoiBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
+  const uint32_t dmask = job_dmask(te, nhwc);
   // staged: the window fits a strip that leaves three workgroups per CU and converts at most three source pixels per destination pixel
   // (the measured break-even of the strip against the per-tap kernels, launch_convert_resize); everything else gathers
-  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
-  RoiArgs as, ag;  // (entries beyond a table's jobs are never read: blockIdx.z runs over its jobs)
-  std::memset(&as, 0, sizeof(as));
-  std::memset(&ag, 0, sizeof(ag));
-  as.e = ag.e = te;  // (one interleaved plane: the staging plan of each dispatch follows below, nhwc_stage_plan)
-  uint32_t ns = 0, ngat = 0, lds = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const RoiDesc& j = jobs[i];
-    const RoiStripNeed need = all_gather ? RoiStripNeed{0u, 1e9} : roi_strip_need(j.x, j.w, j.h, j.scx, j.scy, dw, dh);
-    if (!all_gather && roi_job_staged(need)) {
-      as.j[ns++] = jobs[i];
-      lds = need.bytes > lds ? need.bytes : lds;
-    } else {
-      ag.j[ngat++] = jobs[i];
-    }
-  }
+  RoiArgs as, ag;  // (one interleaved plane: the staging plan of each dispatch follows below, nhwc_stage_plan)
+  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const RoiDesc& j) {
+    const RoiStripNeed need = roi_strip_need(j.x, j.w, j.h, j.scx, j.scy, dw, dh);
+    return roi_job_staged(need) ? need.bytes : kNotStaged;
+  });
+  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
+  hipError_t e = hipSuccess;
   if (ns) {
     const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
     const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &as.e) : lds;  // the strip, then the waves' staging area where both fit
-#define VPF_ROIS(S) do { if (nhwc) VPF_LAUNCH((k_roi_strip_nhwc<S>), grid, dim3(256), lds_all, st, as, c, W, dw, dh, dmask, lds); \
-                         else VPF_LAUNCH((k_roi_strip<S>), grid, dim3(256), lds, st, as, c, W, dw, dh, dmask, lds); } while (0)
-    if (src_fc == FC_NV12) VPF_ROIS(FC_NV12); else if (src_fc == FC_P16) VPF_ROIS(FC_P16); else VPF_ROIS(FC_YUV420);
-#undef VPF_ROIS
-    const hipError_t e = hipGetLastError();
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_strip, (S, D), grid, lds_all, st, as, c, W, dw, dh, dmask, lds); e = hipGetLastError(); });
     if (e != hipSuccess) return e;
   }
   if (ngat) {
     const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
     const uint32_t lds_g = nhwc ? nhwc_stage_plan(te, 0u, 4, &ag.e) : 0u;
-#define VPF_ROIG(S) do { if (nhwc) VPF_LAUNCH((k_roi_gather_nhwc<S>), grid, dim3(256), lds_g, st, ag, c, dw, dh, dmask); \
-                         else VPF_LAUNCH((k_roi_gather<S>), grid, dim3(256), 0, st, ag, c, dw, dh, dmask); } while (0)
-    if (src_fc == FC_NV12) VPF_ROIG(FC_NV12); else if (src_fc == FC_P16) VPF_ROIG(FC_P16); else VPF_ROIG(FC_YUV420);
-#undef VPF_ROIG
-    return hipGetLastError();
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_gather, (S, D), grid, lds_g, st, ag, c, dw, dh, dmask); e = hipGetLastError(); });
   }
-  return hipSuccess;
+  return e;
 }
 
 }  // namespace vpf

@@ -1,31 +1,125 @@
 // k_convert_roi_dev.hip — the multi-ROI crop + bilinear resize of k_convert_roi.hip with the rectangles in DEVICE memory (gfx950):
 // vpf_convert_resize_tensor_rois_dev.  A detector and its NMS leave their boxes on the GPU; this kernel reads (frame, x, y, w, h) of job blockIdx.z and
 // the job count WHEN IT RUNS, so the call needs no sync and no copy to the host, and a captured graph replays with the boxes of replay time.
-//   k_roi_dev / k_roi_dev_nhwc   ONE dispatch over (tiles of 16 destination rows x 256 columns, max_n jobs).  A workgroup loads the count (jobs at or
+//   k_roi_dev      ONE dispatch over (tiles of 16 destination rows x 256 columns, max_n jobs).  A workgroup loads the count (jobs at or
 //                  behind it write nothing), loads its box, runs the guard (roi_dev_box_ok: an invalid box reads no frame and writes the epilogue
 //                  of byte 0), computes the job's scale factors — the correctly rounded fp32 quotients the host entry computes: no fast-math, no
 //                  contraction in this translation unit — and then decides for ITS TILE (roi_tile_need, vpf_job_bounds.h): the staged form of
 //                  k_roi_strip where the tile's strip fits the dispatch's LDS and converts at most kRoiConvMax source pixels per destination
 //                  pixel, k_roi_gather's per-tap pixel otherwise.  A workgroup-uniform branch, as in k_warp_strip.
-// Both forms run k_convert_roi.hip's fp32 operations in its order (VPF_STRIP_FILL_WINDOW, band_blend_rows, texel_rgb, the tensor_store4* epilogues):
+// Both forms run k_convert_roi.hip's fp32 operations in its order (strip_fill_window, band_blend_rows, texel_rgb, the tensor_store4* epilogues):
 // identical bits to vpf_convert_resize_tensor_rois on the same rectangles, whichever form either entry picks.
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "k_job_launch.h"
 #include "vpf_job_bounds.h"  // roi_dev_box_ok, roi_tile_window, roi_tile_need_of, roi_tile_staged: shared with the CPU tests
 
 namespace vpf {
 
-template <int SRC>
+template <int SRC, int DST>  // DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane
 __global__ __launch_bounds__(256) void k_roi_dev(const RoiDevArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh, uint32_t dmask,
                                                  uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR;
-#include "k_convert_roi_dev_body.h"
-}
-template <int SRC>
-__global__ __launch_bounds__(256) void k_roi_dev_nhwc(const RoiDevArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
-                                                      uint32_t dmask, uint32_t lds_bytes) {
-  constexpr int DST = FC_TENSOR_NHWC;  // one interleaved plane per job
-#include "k_convert_roi_dev_body.h"
+  constexpr int R = kRoiBandRows;
+  const uint32_t job = blockIdx.z;
+  // 1. the count: jobs at or behind it write nothing
+  uint32_t cnt = args.max_n;
+  if (args.count) {
+    const int32_t v = __builtin_amdgcn_readfirstlane(*args.count);
+    cnt = v < 0 ? 0u : ((uint32_t)v < args.max_n ? (uint32_t)v : args.max_n);
+  }
+  if (job >= cnt) return;
+  // 2. the five ints of this job, wave-uniform
+  const int32_t* const bp = reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(args.boxes) + (size_t)job * args.box_stride);
+  const int32_t b_f = __builtin_amdgcn_readfirstlane(bp[0]), b_x = __builtin_amdgcn_readfirstlane(bp[1]), b_y = __builtin_amdgcn_readfirstlane(bp[2]),
+                b_w = __builtin_amdgcn_readfirstlane(bp[3]), b_h = __builtin_amdgcn_readfirstlane(bp[4]);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
+  const uint32_t Y0 = blockIdx.y * (4 * R), xs = blockIdx.x * 256;  // the grid covers the destination exactly: Y0 < dh, xs < dw
+  const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
+  const TensorEpi te = args.e;
+  FrameDesc f;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    f.d[ch] = (DST == FC_TENSOR_NHWC && ch) ? nullptr : args.d[ch] + (size_t)job * args.job_stride;
+    f.dp[ch] = args.dp[ch];
+  }
+  const uint32_t ya = Y0 + wv * R, yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;  // this wave's rows (none when ya > Y1)
+  const uint32_t x0 = xs + lane * 4;                                        // this lane's four columns (none when x0 >= dw)
+  const uint32_t nv = x0 < dw ? (dw - x0 < 4 ? dw - x0 : 4) : 0;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  // 3. the guard (vpf_job_bounds.h): an invalid box reads no frame; its tile takes the epilogue of byte 0
+  if (!roi_dev_box_ok(b_f, b_x, b_y, b_w, b_h, args.n_frames, W, H)) {
+    if (ya > Y1 || !nv) return;
+    for (uint32_t y = ya; y <= yb; y++) {
+      if constexpr (DST == FC_TENSOR_NHWC) {
+        const float u[3][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        tensor_store_nhwc<false, 4>(f.d[0] + (size_t)y * f.dp[0], x0, u, te, vec, nv, kNoStage, 0u);
+      } else {
+        const float u[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec, nv);
+      }
+    }
+    return;
+  }
+  const FrameSrcDesc& fs = args.f[b_f];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) { f.s[ch] = fs.s[ch]; f.sp[ch] = fs.sp[ch]; }
+  const uint32_t rx = (uint32_t)b_x, ry = (uint32_t)b_y, rw = (uint32_t)b_w, rh = (uint32_t)b_h;
+  // 4. the scale factors: the correctly rounded fp32 quotients the host entry computes
+  const float scx = (float)rw / (float)dw, scy = (float)rh / (float)dh;
+  // staged or per tap: this tile's own window
+  RoiTileWin win = roi_tile_window(rx, rw, rh, scx, scy, xs, xe, Y0, Y1);
+  win.first = __builtin_amdgcn_readfirstlane(win.first); win.last = __builtin_amdgcn_readfirstlane(win.last);
+  win.lo = __builtin_amdgcn_readfirstlane(win.lo); win.hi = __builtin_amdgcn_readfirstlane(win.hi);
+  win.base_px = win.first & ~1u; win.ng = ((win.last - win.base_px) >> 3) + 1u; win.rowbytes = 32u * win.ng + 16u; win.rows = win.hi - win.lo + 1u;
+  if (roi_tile_staged(roi_tile_need_of(win, dw, dh), lds_bytes)) {
+    // the staged form: k_roi_strip from its fill stage on
+    const uint32_t base_px = win.base_px, R_lo_rel = win.lo, R_lo = ry + win.lo, R_hi = ry + win.hi;  // frame rows
+    uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+    const uint32_t rowbytes = win.rowbytes;
+    strip_fill_window<SRC>(f, c, W, strip, base_px, R_lo, R_hi, win.ng, rowbytes, tid);  // (k_fused_common.h)
+    __syncthreads();
+    if (ya > Y1) return;
+    const Tap row_taps = band_row_taps(ya, yb, scy, rh);  // every lane of the wave still active here
+    if (!nv) return;
+    const ColTapsX T = make_col_taps_x(base_px - rx, x0, dw, rw, scx);
+    band_blend_rows<3, R>(strip, rowbytes, R_lo_rel, ya, yb, row_taps, T, [&](uint32_t y, const float* o) {  // o: pixel-major R G B, + 0.5 added
+      if constexpr (DST == FC_TENSOR_NHWC) {
+        tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, o, 1, 3, te, vec, nv, wv, lane);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec, nv);
+      }
+    });
+    return;
+  }
+  // per tap: k_roi_gather's pixel, this wave's rows one after the other
+  if (ya > Y1 || !nv) return;
+  Tap tx[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) tx[k] = make_tap<VPF_INTERP_LINEAR>((x0 + k < dw) ? x0 + k : dw - 1, scx, rw);
+  for (uint32_t y = ya; y <= yb; y++) {
+    const Tap ty = make_tap<VPF_INTERP_LINEAR>(y, scy, rh);
+    float o[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float p00[3], p01[3], p10[3], p11[3];
+      texel_rgb<SRC>(f, c, rx + tx[k].i0, ry + ty.i0, p00);
+      texel_rgb<SRC>(f, c, rx + tx[k].i1, ry + ty.i0, p01);
+      texel_rgb<SRC>(f, c, rx + tx[k].i0, ry + ty.i1, p10);
+      texel_rgb<SRC>(f, c, rx + tx[k].i1, ry + ty.i1, p11);
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) o[ch][k] = bilerp(p00[ch], p01[ch], p10[ch], p11[ch], tx[k].f, ty.f);
+    }
+    if constexpr (DST == FC_TENSOR_NHWC) {
+      tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, &o[0][0], 4, 1, te, vec, nv, wv, lane);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o[ch], 1, te, ch, vec, nv);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -34,18 +128,15 @@ __global__ __launch_bounds__(256) void k_roi_dev_nhwc(const RoiDevArgs args, con
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
                                           const TensorEpi& te, bool nhwc) {
-  if (!a.max_n || a.max_n > 65535u || !a.n_frames || a.n_frames > (uint32_t)kRoiDevFrames || (src_fc != FC_NV12 && src_fc != FC_YUV420 && src_fc != FC_P16))
-    return hipErrorInvalidValue;
-  const uint32_t dmask = nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u;  // 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B)
+  if (!a.max_n || a.max_n > 65535u || !a.n_frames || a.n_frames > (uint32_t)kRoiDevFrames || !job_src_ok(src_fc)) return hipErrorInvalidValue;
+  const uint32_t dmask = job_dmask(te, nhwc);
   const uint32_t lds = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 ? 0u : roi_dev_lds_bytes(dw, dh);
   a.e = te;
   const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &a.e) : lds;  // the strip, then the waves' staging area where both fit
   const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), a.max_n);
-#define VPF_ROID(S) do { if (nhwc) VPF_LAUNCH((k_roi_dev_nhwc<S>), grid, dim3(256), lds_all, st, a, c, W, H, dw, dh, dmask, lds); \
-                         else VPF_LAUNCH((k_roi_dev<S>), grid, dim3(256), lds_all, st, a, c, W, H, dw, dh, dmask, lds); } while (0)
-  if (src_fc == FC_NV12) VPF_ROID(FC_NV12); else if (src_fc == FC_P16) VPF_ROID(FC_P16); else VPF_ROID(FC_YUV420);
-#undef VPF_ROID
-  return hipGetLastError();
+  hipError_t e = hipSuccess;
+  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_dev, (S, D), grid, lds_all, st, a, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
+  return e;
 }
 
 }  // namespace vpf

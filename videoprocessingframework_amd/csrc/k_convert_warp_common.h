@@ -1,7 +1,7 @@
 // k_convert_warp_common.h — the device helpers the affine-warp translation units share (k_convert_warp.hip: the host-table kernels;
 // k_convert_warp_dev.hip: the device-table kernel): border mode and bytes out of TensorEpi::pad, the four-pixel store through the tensor epilogue,
-// and the per-tap form of a lane's four pixels.  Forced inline everywhere: the text moved here from k_convert_warp.hip unchanged, and the four
-// kernels of that file compile to the instructions they had before.
+// the per-tap form of a lane's four pixels and the staged form of a workgroup's tile (warp_strip_tile: the whole of k_warp_strip, the tail of
+// k_warp_dev).  Forced inline everywhere.
 #ifndef VPF_K_CONVERT_WARP_COMMON_H_
 #define VPF_K_CONVERT_WARP_COMMON_H_
 #include "k_bilinear_blend.h"
@@ -55,6 +55,83 @@ VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorE
 #pragma unroll
   for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
   warp_store4<DST>(f, x0, y, u, te, vec, nv);
+}
+
+// ------------------------------------------------------------------------------------------
+// The staged form of a workgroup's tile (k_warp_strip on the job of its table, k_warp_dev on the job it assembled from the device tables).  The
+// window is wave-uniform (block indices and kernel arguments only).  A tile whose window is empty writes the border; a tile whose strip would not
+// fit the LDS it was given — never in k_warp_strip: the launcher's bound covers every tile (warp_need) — takes the per-tap form instead of
+// writing from a short strip.  Every lane of the workgroup calls this (one barrier inside).
+// ------------------------------------------------------------------------------------------
+template <int SRC, int DST>
+VPF_DEV void warp_strip_tile(const WarpDesc& J, const TensorEpi& te, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh, uint32_t dmask,
+                             uint32_t lds_bytes) {
+  const FrameDesc& f = J.f;
+  const bool rep = warp_rep(te);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t xs = blockIdx.x * kWarpTileW, ys = blockIdx.y * kWarpTileH;  // the grid covers the destination exactly: xs < dw, ys < dh
+  const uint32_t xe = (xs + kWarpTileW - 1 < dw - 1) ? xs + kWarpTileW - 1 : dw - 1, ye = (ys + kWarpTileH - 1 < dh - 1) ? ys + kWarpTileH - 1 : dh - 1;
+  const uint32_t x0 = xs + (tid % kWarpLanesX) * 4, y = ys + tid / kWarpLanesX;
+  const bool mine = x0 < dw && y < dh;
+  WarpWin w = warp_window(J.m, xs, xe, ys, ye, rep, W, H);
+  w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
+  w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  if (w.empty) {  // (CONSTANT only: a clamped coordinate is always in range)
+    if (!mine) return;
+    if constexpr (DST == FC_TENSOR_NHWC) {
+      float u[3][4];
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) u[ch][k] = warp_border(te, ch);
+      warp_store4<DST>(f, x0, y, u, te, vec, nv);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        const float b = warp_border(te, ch), u[4] = {b, b, b, b};
+        tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u, te, ch, vec, nv);
+      }
+    }
+    return;
+  }
+  const WarpStrip S = warp_strip(w);
+  if (S.bytes > lds_bytes) {
+    if (mine) warp_gather4<SRC, DST>(J, c, te, W, H, dw, dmask, x0, y);
+    return;
+  }
+  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
+  strip_fill_window<SRC>(f, c, W, strip, S.base_px, w.y_lo, w.y_hi, S.ng, S.rowbytes, tid);
+  __syncthreads();
+  if (!mine) return;
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  const float xlf = (float)w.x_lo, xhf = (float)w.x_hi, ylf = (float)w.y_lo, yhf = (float)w.y_hi;
+  float u[3][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const WarpXY s = warp_xy(J.m, (x0 + k < dw) ? x0 + k : dw - 1, y, rep, wmax, hmax);
+    const bool in = s.sx >= 0.f && s.sx <= wmax && s.sy >= 0.f && s.sy <= hmax;
+    // an in-range coordinate lies inside the window, so pulling it to the window leaves it unchanged; every other one reads some pixel of
+    // the strip and is replaced by the border.  x1 = min(x0 + 1, x_hi) is min(x0 + 1, W - 1) for an in-range pixel (x_hi = min(floor + 1, W - 1)).
+    const float cx = __builtin_amdgcn_fmed3f(s.sx, xlf, xhf), cy = __builtin_amdgcn_fmed3f(s.sy, ylf, yhf);
+    const uint32_t xa = (uint32_t)(int)cx, ya = (uint32_t)(int)cy;
+    const uint32_t xb = xa + 1 < w.x_hi ? xa + 1 : w.x_hi, yb = ya + 1 < w.y_hi ? ya + 1 : w.y_hi;
+    const float fx = cx - (float)xa, fy = cy - (float)ya;
+    const uint8_t* const ra = strip + (ya - w.y_lo) * S.rowbytes, * const rb = strip + (yb - w.y_lo) * S.rowbytes;
+    const uint32_t oa = 4 * (xa - S.base_px), ob = 4 * (xb - S.base_px);
+    const uint32_t q00 = *reinterpret_cast<const uint32_t*>(ra + oa), q01 = *reinterpret_cast<const uint32_t*>(ra + ob);
+    const uint32_t q10 = *reinterpret_cast<const uint32_t*>(rb + oa), q11 = *reinterpret_cast<const uint32_t*>(rb + ob);
+    const float v[3] = {__builtin_truncf(bilerp(ubyte<0>(q00), ubyte<0>(q01), ubyte<0>(q10), ubyte<0>(q11), fx, fy)),
+                        __builtin_truncf(bilerp(ubyte<1>(q00), ubyte<1>(q01), ubyte<1>(q10), ubyte<1>(q11), fx, fy)),
+                        __builtin_truncf(bilerp(ubyte<2>(q00), ubyte<2>(q01), ubyte<2>(q10), ubyte<2>(q11), fx, fy))};
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) u[ch][k] = in ? v[ch] : warp_border(te, ch);
+  }
+  if constexpr (DST == FC_TENSOR_NHWC) warp_store4<DST>(f, x0, y, u, te, vec, nv);
+  else for (int ch = 0; ch < 3; ch++) tensor_store4<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, u[ch], te, ch, vec, nv);
 }
 
 }  // namespace vpf

@@ -1,5 +1,5 @@
 // k_fused_common.h — what the fused translation units (k_convert_resize.hip, k_convert_roi.hip, k_convert_warp.hip) share: the per-texel conversion,
-// the planar-tensor store epilogue, the 8-pixel conversion unit of the workgroup-shared RGB strips and the fill stage of the per-job strips.
+// the planar-tensor store epilogue, the 8-pixel conversion unit of the workgroup-shared RGB strips and the fill stage of the per-job strips (strip_fill_window).
 #ifndef VPF_K_FUSED_COMMON_H_
 #define VPF_K_FUSED_COMMON_H_
 #include "k_bilinear_blend.h"
@@ -264,94 +264,96 @@ VPF_DEV void convert_unit8(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t cr
 // 4 (px0 / 2)), loaded at any 2-B alignment and narrowed to the two dwords the 8-bit unit takes.  The whole-unit loads run under the same
 // condition px0 + 8 <= W: luma bytes [2 px0, 2 px0 + 16) end at or before 2 W, chroma bytes at 4 (px0 / 2 + 4) <= 4 ceil(W / 2) — inside the
 // rows' own samples.  The right-edge unit takes 2-B sample loads with indices clamped to the row's last sample (pair), as the 8-bit code does.
-// A statement macro, not a function: its text is k_roi_strip's original fill stage, so that kernel's code object is unchanged.  It expands in
-// a template <int SRC> kernel and uses these names of the enclosing scope: f (FrameDesc), c (Yuv2RgbCoef), W (frame width), strip (uint8_t*),
-// base_px (even), R_lo, R_hi (frame rows), c_lo = R_lo >> 1, ng (units per row), units = chroma rows x ng, rowbytes, tid.
-#define VPF_STRIP_FILL_WINDOW \
-  const uint32_t cw = (W + 1) >> 1;                                                                                                                      \
-  const float rng = 1.0f / (float)ng;                                                                                                                    \
-  /* unit u -> (chroma row ci = u / ng, group g): (u + 0.5) / ng is at least 0.5 / ng from an integer, far more than the fp32 error for u < 2^14 */      \
-  struct Unit { bool act = false, ra = false, rb = false; uint8_t* w = nullptr; u32x2 ya = {0u, 0u}, yb = {0u, 0u}, cq = {0u, 0u}; uint32_t vq = 0; };   \
-  auto bytes8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  /* samples i0 .. i0 + 7 of a row of n, indices clamped to n - 1 */                   \
-    uint32_t d[2] = {0u, 0u};                                                                                                                            \
-  _Pragma("unroll")                                                                                                                                      \
-    for (int k = 0; k < 8; k++) {                                                                                                                        \
-      const uint32_t i = i0 + k < n ? i0 + k : n - 1;                                                                                                    \
-      d[k >> 2] |= (uint32_t)row[i] << (8 * (k & 3));                                                                                                    \
-    }                                                                                                                                                    \
-    return u32x2{d[0], d[1]};                                                                                                                            \
-  };                                                                                                                                                     \
-  auto fetch = [&](uint32_t u, Unit& q) {                                                                                                                \
-    q.act = u < units;                                                                                                                                   \
-    if (!q.act) return;                                                                                                                                  \
-    const uint32_t ci = (uint32_t)(((float)u + 0.5f) * rng), g = u - ci * ng;                                                                            \
-    const uint32_t crow = c_lo + ci, px0 = base_px + 8 * g, r0 = 2 * crow;                                                                               \
-    q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  /* (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window) */                             \
-    const uint8_t* const y0p = f.s[0] + (size_t)r0 * f.sp[0];                                                                                            \
-    const uint8_t* const c1p = f.s[1] + (size_t)crow * f.sp[1];                                                                                          \
-    if constexpr (SRC == FC_P16) {                                                                                                                       \
-      (void)bytes8;                                                                                                                                      \
-      auto words8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  /* 16-bit samples i0 .. i0 + 7 of a row of n, clamped to n - 1, narrowed */      \
-        uint32_t d[2] = {0u, 0u};                                                                                                                        \
-  _Pragma("unroll")                                                                                                                                      \
-        for (int k = 0; k < 8; k++) {                                                                                                                    \
-          const uint32_t i = i0 + k < n ? i0 + k : n - 1;                                                                                                \
-          d[k >> 2] |= (uint32_t)p16_to_8(reinterpret_cast<const uint16_t*>(row)[i]) << (8 * (k & 3));                                                   \
-        }                                                                                                                                                \
-        return u32x2{d[0], d[1]};                                                                                                                        \
-      };                                                                                                                                                 \
-      if (px0 + 8 <= W) {                                                                                                                                \
-        q.cq = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(c1p + 2 * (size_t)px0));                                                                   \
-        if (q.ra) q.ya = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + 2 * (size_t)px0));                                                         \
-        if (q.rb) q.yb = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + f.sp[0] + 2 * (size_t)px0));                                               \
-      } else {  /* the unit that holds the frame's right edge */                                                                                         \
-        uint32_t d[2] = {0u, 0u};  /* U V pairs of chroma samples (px0 >> 1) .. + 3 */                                                                   \
-  _Pragma("unroll")                                                                                                                                      \
-        for (int k = 0; k < 4; k++) {                                                                                                                    \
-          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;                                                                              \
-          const uint16_t* const pc = reinterpret_cast<const uint16_t*>(c1p);                                                                             \
-          d[k >> 1] |= ((uint32_t)p16_to_8(pc[2 * i]) | (uint32_t)p16_to_8(pc[2 * i + 1]) << 8) << (16 * (k & 1));                                       \
-        }                                                                                                                                                \
-        q.cq = u32x2{d[0], d[1]};                                                                                                                        \
-        if (q.ra) q.ya = words8(y0p, px0, W);                                                                                                            \
-        if (q.rb) q.yb = words8(y0p + f.sp[0], px0, W);                                                                                                  \
-      }                                                                                                                                                  \
-    } else if (px0 + 8 <= W) {                                                                                                                           \
-      if constexpr (SRC == FC_NV12) {                                                                                                                    \
-        q.cq = *reinterpret_cast<const u32x2_any*>(c1p + px0);                                                                                           \
-      } else {                                                                                                                                           \
-        q.cq = u32x2{*reinterpret_cast<const u32_any*>(c1p + (px0 >> 1)), 0u};                                                                           \
-        q.vq = *reinterpret_cast<const u32_any*>(f.s[2] + (size_t)crow * f.sp[2] + (px0 >> 1));                                                          \
-      }                                                                                                                                                  \
-      if (q.ra) q.ya = *reinterpret_cast<const u32x2_any*>(y0p + px0);                                                                                   \
-      if (q.rb) q.yb = *reinterpret_cast<const u32x2_any*>(y0p + f.sp[0] + px0);                                                                         \
-    } else {  /* the unit that holds the frame's right edge */                                                                                           \
-      if constexpr (SRC == FC_NV12) {                                                                                                                    \
-        uint32_t d[2] = {0u, 0u};  /* U V pairs of chroma samples (px0 >> 1) .. + 3 */                                                                   \
-  _Pragma("unroll")                                                                                                                                      \
-        for (int k = 0; k < 4; k++) {                                                                                                                    \
-          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;                                                                              \
-          d[k >> 1] |= ((uint32_t)c1p[2 * i] | (uint32_t)c1p[2 * i + 1] << 8) << (16 * (k & 1));                                                         \
-        }                                                                                                                                                \
-        q.cq = u32x2{d[0], d[1]};                                                                                                                        \
-      } else {                                                                                                                                           \
-        q.cq = u32x2{bytes8(c1p, px0 >> 1, cw)[0], 0u};                                                                                                  \
-        q.vq = bytes8(f.s[2] + (size_t)crow * f.sp[2], px0 >> 1, cw)[0];                                                                                 \
-      }                                                                                                                                                  \
-      if (q.ra) q.ya = bytes8(y0p, px0, W);                                                                                                              \
-      if (q.rb) q.yb = bytes8(y0p + f.sp[0], px0, W);                                                                                                    \
-    }                                                                                                                                                    \
-    /* strip byte of (row r0, px0); r0 may be R_lo - 1 (that row is not written then: only row r0 + 1 is) — a signed offset */                           \
-    q.w = strip + ((int32_t)(r0 - R_lo) * (int32_t)rowbytes + (int32_t)(4 * (px0 - base_px)));                                                           \
-  };                                                                                                                                                     \
-  for (uint32_t u0 = tid; u0 < units; u0 += 512) {  /* two units per lane in flight */                                                                   \
-    Unit q0, q1;                                                                                                                                         \
-    fetch(u0, q0);                                                                                                                                       \
-    fetch(u0 + 256, q1);                                                                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);  /* both units' loads are requested before the first conversion */                                                \
-    if (q0.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);             \
-    if (q1.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);             \
-  }                                                                                                                                                     
+// `base_px` is even; ng = units per row; the window holds the chroma rows (R_lo >> 1) .. (R_hi >> 1); tid = the lane's index in the workgroup.
+template <int SRC>
+VPF_DEV void strip_fill_window(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t W, uint8_t* strip, uint32_t base_px, uint32_t R_lo, uint32_t R_hi, uint32_t ng,
+                               uint32_t rowbytes, uint32_t tid) {
+  const uint32_t c_lo = R_lo >> 1, units = ((R_hi >> 1) - c_lo + 1) * ng;
+  const uint32_t cw = (W + 1) >> 1;
+  const float rng = 1.0f / (float)ng;
+  // unit u -> (chroma row ci = u / ng, group g): (u + 0.5) / ng is at least 0.5 / ng from an integer, far more than the fp32 error for u < 2^14
+  struct Unit { bool act = false, ra = false, rb = false; uint8_t* w = nullptr; u32x2 ya = {0u, 0u}, yb = {0u, 0u}, cq = {0u, 0u}; uint32_t vq = 0; };
+  auto bytes8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  // samples i0 .. i0 + 7 of a row of n, indices clamped to n - 1
+    uint32_t d[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t i = i0 + k < n ? i0 + k : n - 1;
+      d[k >> 2] |= (uint32_t)row[i] << (8 * (k & 3));
+    }
+    return u32x2{d[0], d[1]};
+  };
+  auto fetch = [&](uint32_t u, Unit& q) {
+    q.act = u < units;
+    if (!q.act) return;
+    const uint32_t ci = (uint32_t)(((float)u + 0.5f) * rng), g = u - ci * ng;
+    const uint32_t crow = c_lo + ci, px0 = base_px + 8 * g, r0 = 2 * crow;
+    q.ra = r0 >= R_lo; q.rb = r0 + 1 <= R_hi;  // (r0 <= R_hi and r0 + 1 >= R_lo hold for every chroma row of the window)
+    const uint8_t* const y0p = f.s[0] + (size_t)r0 * f.sp[0];
+    const uint8_t* const c1p = f.s[1] + (size_t)crow * f.sp[1];
+    if constexpr (SRC == FC_P16) {
+      (void)bytes8;
+      auto words8 = [&](const uint8_t* row, uint32_t i0, uint32_t n) {  // 16-bit samples i0 .. i0 + 7 of a row of n, clamped to n - 1, narrowed
+        uint32_t d[2] = {0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const uint32_t i = i0 + k < n ? i0 + k : n - 1;
+          d[k >> 2] |= (uint32_t)p16_to_8(reinterpret_cast<const uint16_t*>(row)[i]) << (8 * (k & 3));
+        }
+        return u32x2{d[0], d[1]};
+      };
+      if (px0 + 8 <= W) {
+        q.cq = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(c1p + 2 * (size_t)px0));
+        if (q.ra) q.ya = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + 2 * (size_t)px0));
+        if (q.rb) q.yb = p16x8_to_8(*reinterpret_cast<const u32x4_any*>(y0p + f.sp[0] + 2 * (size_t)px0));
+      } else {  // the unit that holds the frame's right edge
+        uint32_t d[2] = {0u, 0u};  // U V pairs of chroma samples (px0 >> 1) .. + 3
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;
+          const uint16_t* const pc = reinterpret_cast<const uint16_t*>(c1p);
+          d[k >> 1] |= ((uint32_t)p16_to_8(pc[2 * i]) | (uint32_t)p16_to_8(pc[2 * i + 1]) << 8) << (16 * (k & 1));
+        }
+        q.cq = u32x2{d[0], d[1]};
+        if (q.ra) q.ya = words8(y0p, px0, W);
+        if (q.rb) q.yb = words8(y0p + f.sp[0], px0, W);
+      }
+    } else if (px0 + 8 <= W) {
+      if constexpr (SRC == FC_NV12) {
+        q.cq = *reinterpret_cast<const u32x2_any*>(c1p + px0);
+      } else {
+        q.cq = u32x2{*reinterpret_cast<const u32_any*>(c1p + (px0 >> 1)), 0u};
+        q.vq = *reinterpret_cast<const u32_any*>(f.s[2] + (size_t)crow * f.sp[2] + (px0 >> 1));
+      }
+      if (q.ra) q.ya = *reinterpret_cast<const u32x2_any*>(y0p + px0);
+      if (q.rb) q.yb = *reinterpret_cast<const u32x2_any*>(y0p + f.sp[0] + px0);
+    } else {  // the unit that holds the frame's right edge
+      if constexpr (SRC == FC_NV12) {
+        uint32_t d[2] = {0u, 0u};  // U V pairs of chroma samples (px0 >> 1) .. + 3
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const uint32_t i = (px0 >> 1) + k < cw ? (px0 >> 1) + k : cw - 1;
+          d[k >> 1] |= ((uint32_t)c1p[2 * i] | (uint32_t)c1p[2 * i + 1] << 8) << (16 * (k & 1));
+        }
+        q.cq = u32x2{d[0], d[1]};
+      } else {
+        q.cq = u32x2{bytes8(c1p, px0 >> 1, cw)[0], 0u};
+        q.vq = bytes8(f.s[2] + (size_t)crow * f.sp[2], px0 >> 1, cw)[0];
+      }
+      if (q.ra) q.ya = bytes8(y0p, px0, W);
+      if (q.rb) q.yb = bytes8(y0p + f.sp[0], px0, W);
+    }
+    // strip byte of (row r0, px0); r0 may be R_lo - 1 (that row is not written then: only row r0 + 1 is) — a signed offset
+    q.w = strip + ((int32_t)(r0 - R_lo) * (int32_t)rowbytes + (int32_t)(4 * (px0 - base_px)));
+  };
+  for (uint32_t u0 = tid; u0 < units; u0 += 512) {  // two units per lane in flight
+    Unit q0, q1;
+    fetch(u0, q0);
+    fetch(u0 + 256, q1);
+    __builtin_amdgcn_sched_barrier(0);  // both units' loads are requested before the first conversion
+    if (q0.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q0.ra, q0.rb, q0.w, rowbytes, q0.ya, q0.yb, q0.cq, q0.vq);
+    if (q1.act) convert_unit8<(SRC == FC_P16 ? (int)FC_NV12 : SRC)>(f, c, 0u, 0u, q1.ra, q1.rb, q1.w, rowbytes, q1.ya, q1.yb, q1.cq, q1.vq);
+  }
+}
 
 }  // namespace vpf
 #endif  // VPF_K_FUSED_COMMON_H_

@@ -1,0 +1,98 @@
+// k_job_launch.h — the host side the fused tensor launchers share (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip,
+// their device-table forms and launch_tensor_to_yuv): the argument check, the destination alignment mask, the run-time -> template-argument
+// dispatch, the launch of the instantiation it picked and the split of a host job table into its staged and its per-tap dispatch.  Inline functions, function templates over
+// callables and one launch macro: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
+#ifndef VPF_K_JOB_LAUNCH_H_
+#define VPF_K_JOB_LAUNCH_H_
+#include <cstdio>
+#include <cstring>
+#include <type_traits>
+
+#include "vpf_internal.h"
+
+namespace vpf {
+
+inline bool job_src_ok(int src_fc) { return src_fc == FC_NV12 || src_fc == FC_YUV420 || src_fc == FC_P16; }
+
+// 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B).  (`dtype` is compared whole: kEpiSwapRB is only
+// ever set for a channels-last destination, where the mask is 15 whatever the dtype — masking with kEpiDtypeMask first gives the same result.)
+inline uint32_t job_dmask(const TensorEpi& te, bool nhwc) { return nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u; }
+
+// f(SRC, DST): the source class and the destination layout as std::integral_constant<int, ...>, usable as template arguments
+template <class F>
+inline void with_src_dst(int src_fc, bool nhwc, F&& f) {
+  auto layout = [&](auto src) {
+    if (nhwc) f(src, std::integral_constant<int, FC_TENSOR_NHWC>{});
+    else f(src, std::integral_constant<int, FC_TENSOR>{});
+  };
+  if (src_fc == FC_NV12) layout(std::integral_constant<int, FC_NV12>{});
+  else if (src_fc == FC_P16) layout(std::integral_constant<int, FC_P16>{});
+  else layout(std::integral_constant<int, FC_YUV420>{});
+}
+// f(std::true_type / std::false_type)
+template <class F>
+inline void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// f(DT): the tensor dtype as std::integral_constant<int, VPF_TENSOR_*>; false, and f not called, for any other value
+template <class F>
+inline bool with_tensor_dtype(uint32_t dtype, F&& f) {
+  switch (dtype) {
+    case VPF_TENSOR_F32: f(std::integral_constant<int, VPF_TENSOR_F32>{}); return true;
+    case VPF_TENSOR_F16: f(std::integral_constant<int, VPF_TENSOR_F16>{}); return true;
+    case VPF_TENSOR_BF16: f(std::integral_constant<int, VPF_TENSOR_BF16>{}); return true;
+    default: return false;
+  }
+}
+
+// VPF_LAUNCH for the 256-lane instantiation K<TARGS> a dispatcher above picked: VPF_LAUNCH_T(k_roi_strip, (S, D), grid, lds, st, args...).  The
+// selection log (VPF_HIP_LOG=2, roctx markers) gets the template-id the code object and a profiler show — "(k_roi_strip<7, 8>)": FC_NV12 = 0,
+// FC_YUV420 = 1, FC_P16 = 7, FC_TENSOR = 6, FC_TENSOR_NHWC = 8; bools as true / false — written from the same K and TARGS tokens the launch is.
+inline int put_targ(char* p, size_t n, int v) { return std::snprintf(p, n, "%d, ", v); }
+inline int put_targ(char* p, size_t n, bool v) { return std::snprintf(p, n, "%s, ", v ? "true" : "false"); }
+template <class... T>  // T: std::integral_constant<int or bool, ...>
+inline void note_instantiation(const char* family, T... targs) {
+  char label[96];
+  size_t o = (size_t)std::snprintf(label, sizeof(label), "(%s<", family);
+  ((o += (size_t)put_targ(label + o, sizeof(label) - o, (typename T::value_type)targs)), ...);
+  std::snprintf(label + o - 2, sizeof(label) - o + 2, ">)");  // (over the last ", ")
+  note_kernel(label);
+}
+#define VPF_TARGS(...) __VA_ARGS__
+#define VPF_LAUNCH_T(K, TARGS, GRID, LDS, ST, ...)                                                         \
+  do {                                                                                                     \
+    if (vpf::log_level() >= 2 || vpf::trace_on()) vpf::note_instantiation(#K, VPF_TARGS TARGS);            \
+    (void)hipGetLastError(); /* (sticky per thread: see VPF_LAUNCH) */                                     \
+    hipLaunchKernelGGL((K<VPF_TARGS TARGS>), GRID, dim3(256), LDS, ST, __VA_ARGS__);                       \
+  } while (0)
+
+// The split of a host job table: `staged_bytes(job)` returns the dynamic LDS the job's strip needs, or kNotStaged for a job that samples per tap
+// (every job under VPF_TUNE_NV12_RGB_VARIANT = 9).  Fills the two zeroed tables — entries beyond a table's jobs are never read: blockIdx.z runs
+// over its jobs — and returns their job counts and the largest strip of the staged one.
+constexpr uint32_t kNotStaged = ~0u;
+struct JobSplit {
+  uint32_t ns, ngat, lds;
+};
+template <class Args, class Desc, class Need>
+inline JobSplit split_jobs(const Desc* jobs, uint32_t n, const TensorEpi& te, Args& as, Args& ag, Need&& staged_bytes) {
+  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
+  std::memset(&as, 0, sizeof(as));
+  std::memset(&ag, 0, sizeof(ag));
+  as.e = ag.e = te;
+  JobSplit s{0u, 0u, 0u};
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t bytes = all_gather ? kNotStaged : staged_bytes(jobs[i]);
+    if (bytes != kNotStaged) {
+      as.j[s.ns++] = jobs[i];
+      s.lds = bytes > s.lds ? bytes : s.lds;
+    } else {
+      ag.j[s.ngat++] = jobs[i];
+    }
+  }
+  return s;
+}
+
+}  // namespace vpf
+#endif  // VPF_K_JOB_LAUNCH_H_

@@ -7,6 +7,7 @@
 // One lane owns a 2x2 pixel quad: four luma samples, and either four chroma pairs (4:4:4) or one
 // (4:2:0, mean of the quad: matrix row applied to 0.25 * the exact integer channel sums).
 // 4.5-6 B/px of streaming traffic; the quad shape keeps the 4:2:0 decimation in registers.
+#include "k_job_launch.h"
 #include "vpf_device.h"
 
 namespace vpf {
@@ -315,17 +316,43 @@ VPF_DEV float tin_widen16(uint32_t d, int hi) {
 
 // generic path: one lane = one 2x2 quad, element accesses; any size, any alignment (of whole elements), odd edges.  The quad form of
 // k_rgb_yuv_quad<FC_PLANAR, true>; the dtype is a wave-uniform argument (two instantiations: NV12 / YUV420).
-// NHWC (VPF_TENSOR_NHWC, k_tensor_yuv_quad_nhwc): the three channels of pixel x are elements 3 x .. 3 x + 2 of the ONE plane s[0]; kernel channel
-// k sits in slot k, or 2 - k in B G R order (t.pad, wave-uniform).
-template <bool NV12>
+// NHWC (VPF_TENSOR_NHWC): the three channels of pixel x are elements 3 x .. 3 x + 2 of the ONE plane s[0]; kernel channel k sits in slot k, or
+// 2 - k in B G R order (t.pad, wave-uniform).
+template <bool NV12, bool NHWC>
 __global__ __launch_bounds__(256) void k_tensor_yuv_quad(const BatchArgs args, const Rgb2YuvCoef c, const TensorPro t, uint32_t w, uint32_t h) {
-  constexpr bool NHWC = false;
-#include "k_tensor_yuv_quad_body.h"
-}
-template <bool NV12>
-__global__ __launch_bounds__(256) void k_tensor_yuv_quad_nhwc(const BatchArgs args, const Rgb2YuvCoef c, const TensorPro t, uint32_t w, uint32_t h) {
-  constexpr bool NHWC = true;
-#include "k_tensor_yuv_quad_body.h"
+  const FrameDesc f = args.f[blockIdx.z];
+  const uint32_t qx = blockIdx.x * 64 + (threadIdx.x & 63), qy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const uint32_t x0 = 2 * qx, y0 = 2 * qy;
+  if (x0 >= w || y0 >= h) return;
+  const uint32_t x1 = (x0 + 1 < w) ? x0 + 1 : x0, y1 = (y0 + 1 < h) ? y0 + 1 : y0;  // edge quads replicate
+  const uint32_t xs[4] = {x0, x1, x0, x1}, ys[4] = {y0, y0, y1, y1};
+  const uint32_t dtype = t.dtype;
+  auto load = [&](int k, uint32_t y, uint32_t x) -> float {
+    const uint8_t* row = f.s[NHWC ? 0 : k] + (size_t)y * f.sp[NHWC ? 0 : k];
+    if constexpr (NHWC) x = 3 * x + (t.pad ? 2 - k : k);
+    if (dtype == VPF_TENSOR_F32) return reinterpret_cast<const float*>(row)[x];
+    const uint32_t d = reinterpret_cast<const uint16_t*>(row)[x];
+    return dtype == VPF_TENSOR_F16 ? tin_widen16<VPF_TENSOR_F16>(d, 0) : tin_widen16<VPF_TENSOR_BF16>(d, 0);
+  };
+  float rs = 0.f, gs = 0.f, bs = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint32_t x = xs[i], y = ys[i];
+    const float r = tin_quant(load(0, y, x), t.scale[0], t.bias[0]), g = tin_quant(load(1, y, x), t.scale[1], t.bias[1]),
+                b = tin_quant(load(2, y, x), t.scale[2], t.bias[2]);
+    rs += r; gs += g; bs += b;  // exact: small integers
+    const bool dup = (i == 1 && x1 == x0) || (i == 2 && y1 == y0) || (i == 3 && (x1 == x0 || y1 == y0));
+    if (!dup) f.d[0][(size_t)y * f.dp[0] + x] = (uint8_t)sat_trunc(mrow(c, 0, r, g, b));
+  }
+  rs *= 0.25f; gs *= 0.25f; bs *= 0.25f;  // exact in fp32
+  const uint8_t u = (uint8_t)sat_trunc(mrow(c, 1, rs, gs, bs)), v = (uint8_t)sat_trunc(mrow(c, 2, rs, gs, bs));
+  if constexpr (NV12) {
+    uint8_t* p = f.d[1] + (size_t)qy * f.dp[1] + 2 * (size_t)qx;
+    p[0] = u; p[1] = v;
+  } else {
+    f.d[1][(size_t)qy * f.dp[1] + qx] = u;
+    f.d[2][(size_t)qy * f.dp[2] + qx] = v;
+  }
 }
 
 // fast path: a wave = one row pair x 64 lanes x PX pixels; PX = 8 (f32) or 16 (f16 / bf16): two 16-B loads per lane, row and plane either way,
@@ -341,21 +368,93 @@ VPF_DEV void tin_store(uint8_t* p, const uint32_t* d) {
   else if constexpr (N == 2) stg<true, u32x2>(p, u32x2{d[0], d[1]});
   else stg<true, uint32_t>(p, d[0]);
 }
-// NHWC (k_tensor_yuv_r_nhwc): a lane's PX pixels x 3 channels are 96 contiguous bytes of a row of the ONE plane s[0]: six 16-B loads per row —
+// NHWC: a lane's PX pixels x 3 channels are 96 contiguous bytes of a row of the ONE plane s[0]: six 16-B loads per row —
 // the same twelve loads and 48 load registers, with dense addresses (every load instruction of a wave still covers every sixth 16 B of its
 // span, and the six together all of it); element 3 i + slot of the lane's run is channel `slot` of pixel i: compile-time register indexing,
 // and a wave-uniform select between slots 0 and 2 for B G R order (t.pad).
-template <int DT, bool NV12>
+template <int DT, bool NV12, bool NHWC>
 __global__ __launch_bounds__(256) void k_tensor_yuv_r(const BatchArgs args, const Rgb2YuvCoef c, const TensorPro t, uint32_t w, uint32_t h, uint32_t chunks_x,
                                                       uint32_t n_tasks) {
-  constexpr bool NHWC = false;
-#include "k_tensor_yuv_r_body.h"
-}
-template <int DT, bool NV12>
-__global__ __launch_bounds__(256) void k_tensor_yuv_r_nhwc(const BatchArgs args, const Rgb2YuvCoef c, const TensorPro t, uint32_t w, uint32_t h, uint32_t chunks_x,
-                                                      uint32_t n_tasks) {
-  constexpr bool NHWC = true;
-#include "k_tensor_yuv_r_body.h"
+  constexpr int EL = (DT == VPF_TENSOR_F32) ? 4 : 2, PX = 32 / EL, NG = PX / 4;
+  const FrameDesc f = args.f[blockIdx.y];
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const uint32_t wt = blockIdx.x * 4 + wv;
+  if (wt >= n_tasks) return;
+  const uint32_t rg = wt / chunks_x, chunk = wt - rg * chunks_x;
+  const uint32_t y0 = 2 * rg, x = (chunk * 64 + lane) * PX;
+  if (x >= w) return;  // (w % 16 == 0 and PX divides 16: a lane's pixels are all inside or all outside)
+  u32x4 in[2][3][2];  // NHWC: in[r][0..2][0..1] = the six 16-B units of row r in order
+#pragma unroll
+  for (int r = 0; r < 2; r++)
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        if constexpr (NHWC) in[r][k][j] = ldg<false, u32x4>(f.s[0] + (size_t)(y0 + r) * f.sp[0] + (size_t)x * 3 * EL + 16 * (2 * k + j));
+        else in[r][k][j] = ldg<false, u32x4>(f.s[k] + (size_t)(y0 + r) * f.sp[k] + (size_t)x * EL + 16 * j);
+      }
+  const bool swap_rb = NHWC && t.pad != 0;
+  uint32_t yo[2][NG], uv[NG], uo[NG / 2], vo[NG / 2];
+#pragma unroll
+  for (int g = 0; g < NG / 2; g++) uo[g] = vo[g] = 0;
+#pragma unroll
+  for (int g = 0; g < NG; g++) {
+    float q[2][3][4];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      if constexpr (NHWC) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          float e[3];  // slots 0 1 2 of pixel 4 g + i
+#pragma unroll
+          for (int sl = 0; sl < 3; sl++) {
+            const int el = 3 * (4 * g + i) + sl;  // element of the lane's run
+            if constexpr (DT == VPF_TENSOR_F32) e[sl] = __uint_as_float(in[r][el / 8][(el / 4) & 1][el & 3]);
+            else e[sl] = tin_widen16<DT>(in[r][el / 16][(el / 8) & 1][(el / 2) & 3], el & 1);
+          }
+          q[r][0][i] = tin_quant(swap_rb ? e[2] : e[0], t.scale[0], t.bias[0]);
+          q[r][1][i] = tin_quant(e[1], t.scale[1], t.bias[1]);
+          q[r][2][i] = tin_quant(swap_rb ? e[0] : e[2], t.scale[2], t.bias[2]);
+        }
+      } else {
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          float e;
+          if constexpr (DT == VPF_TENSOR_F32) e = __uint_as_float(in[r][k][g][i]);
+          else e = tin_widen16<DT>(in[r][k][g >> 1][2 * (g & 1) + (i >> 1)], i & 1);
+          q[r][k][i] = tin_quant(e, t.scale[k], t.bias[k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+      yo[r][g] = pack4_trunc(mrow(c, 0, q[r][0][0], q[r][1][0], q[r][2][0]), mrow(c, 0, q[r][0][1], q[r][1][1], q[r][2][1]),
+                             mrow(c, 0, q[r][0][2], q[r][1][2], q[r][2][2]), mrow(c, 0, q[r][0][3], q[r][1][3], q[r][2][3]));
+    // two quads: px {0,1} and {2,3} of both rows; sums of small integers are exact in fp32, as is the 0.25 scale
+    uint32_t cu[2], cv[2];
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+      const float qr = 0.25f * (q[0][0][2 * p] + q[0][0][2 * p + 1] + q[1][0][2 * p] + q[1][0][2 * p + 1]);
+      const float qg = 0.25f * (q[0][1][2 * p] + q[0][1][2 * p + 1] + q[1][1][2 * p] + q[1][1][2 * p + 1]);
+      const float qb = 0.25f * (q[0][2][2 * p] + q[0][2][2 * p + 1] + q[1][2][2 * p] + q[1][2][2 * p + 1]);
+      cu[p] = sat_trunc(mrow(c, 1, qr, qg, qb));
+      cv[p] = sat_trunc(mrow(c, 2, qr, qg, qb));
+    }
+    if constexpr (NV12) uv[g] = cu[0] | (cv[0] << 8) | (cu[1] << 16) | (cv[1] << 24);
+    else {
+      uo[g >> 1] |= (cu[0] | (cu[1] << 8)) << (16 * (g & 1));
+      vo[g >> 1] |= (cv[0] | (cv[1] << 8)) << (16 * (g & 1));
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 2; r++) tin_store<NG>(f.d[0] + (size_t)(y0 + r) * f.dp[0] + x, yo[r]);
+  if constexpr (NV12) tin_store<NG>(f.d[1] + (size_t)rg * f.dp[1] + x, uv);
+  else {
+    tin_store<NG / 2>(f.d[1] + (size_t)rg * f.dp[1] + (x >> 1), uo);
+    tin_store<NG / 2>(f.d[2] + (size_t)rg * f.dp[2] + (x >> 1), vo);
+  }
 }
 
 static bool tensor2yuv_r_ok(const BatchArgs& a, uint32_t n, bool nv12, uint32_t w, uint32_t h, bool nhwc) {
@@ -372,30 +471,23 @@ static bool tensor2yuv_r_ok(const BatchArgs& a, uint32_t n, bool nv12, uint32_t 
 
 hipError_t launch_tensor_to_yuv(hipStream_t st, bool nv12, const Rgb2YuvCoef& c, const TensorPro& t, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a,
                                 bool nhwc) {
+  hipError_t e = hipErrorInvalidValue;  // (stays for a dtype that is none of the three)
   if (tensor2yuv_r_ok(a, n, nv12, w, h, nhwc)) {
     const uint32_t px = t.dtype == VPF_TENSOR_F32 ? 8 : 16;
     const uint32_t chunks = (w + 64 * px - 1) / (64 * px), tasks = chunks * (h / 2);
     dim3 rgrid((tasks + 3) / 4, n);
-#define VPF_TIN(D)                                                                                                        \
-  if (nhwc && nv12) VPF_LAUNCH((k_tensor_yuv_r_nhwc<D, true>), rgrid, dim3(256), 0, st, a, c, t, w, h, chunks, tasks);    \
-  else if (nhwc) VPF_LAUNCH((k_tensor_yuv_r_nhwc<D, false>), rgrid, dim3(256), 0, st, a, c, t, w, h, chunks, tasks);      \
-  else if (nv12) VPF_LAUNCH((k_tensor_yuv_r<D, true>), rgrid, dim3(256), 0, st, a, c, t, w, h, chunks, tasks);            \
-  else VPF_LAUNCH((k_tensor_yuv_r<D, false>), rgrid, dim3(256), 0, st, a, c, t, w, h, chunks, tasks);                     \
-  return hipGetLastError();
-    switch (t.dtype) {
-      case VPF_TENSOR_F32: VPF_TIN(VPF_TENSOR_F32)
-      case VPF_TENSOR_F16: VPF_TIN(VPF_TENSOR_F16)
-      case VPF_TENSOR_BF16: VPF_TIN(VPF_TENSOR_BF16)
-      default: return hipErrorInvalidValue;
-    }
-#undef VPF_TIN
+    with_tensor_dtype(t.dtype, [&](auto DT) { with_bool(nv12, [&](auto NV12) { with_bool(nhwc, [&](auto NHWC) {
+      VPF_LAUNCH_T(k_tensor_yuv_r, (DT, NV12, NHWC), rgrid, 0, st, a, c, t, w, h, chunks, tasks);
+      e = hipGetLastError();
+    }); }); });
+    return e;
   }
   dim3 grid(((w + 1) / 2 + 63) / 64, ((h + 1) / 2 + 3) / 4, n);
-  if (nhwc && nv12) VPF_LAUNCH((k_tensor_yuv_quad_nhwc<true>), grid, dim3(256), 0, st, a, c, t, w, h);
-  else if (nhwc) VPF_LAUNCH((k_tensor_yuv_quad_nhwc<false>), grid, dim3(256), 0, st, a, c, t, w, h);
-  else if (nv12) VPF_LAUNCH((k_tensor_yuv_quad<true>), grid, dim3(256), 0, st, a, c, t, w, h);
-  else VPF_LAUNCH((k_tensor_yuv_quad<false>), grid, dim3(256), 0, st, a, c, t, w, h);
-  return hipGetLastError();
+  with_bool(nv12, [&](auto NV12) { with_bool(nhwc, [&](auto NHWC) {
+    VPF_LAUNCH_T(k_tensor_yuv_quad, (NV12, NHWC), grid, 0, st, a, c, t, w, h);
+    e = hipGetLastError();
+  }); });
+  return e;
 }
 
 }  // namespace vpf

@@ -252,7 +252,7 @@ static VPF_JB_HDI bool warp_dev_job_ok(int32_t frame, const float* m, uint32_t n
 // destination pixel step) and |m02| <= W, |m12| <= H: warp_need's bound over every such matrix.  warp_need_count is convex in (|r0|, |r1|) before its
 // floor, so over the L1 ball of radius max_step it is largest at a vertex: the rows (max_step, 0) and (0, max_step).  Capped at kWarpStripMax, which
 // is also the answer without a hint (max_step == 0).  Never a correctness input: a tile whose strip exceeds the LDS it was given samples per tap
-// (k_convert_warp_strip_body.h), with identical bits.
+// (warp_strip_tile, k_convert_warp_common.h), with identical bits.
 static inline uint32_t warp_dev_lds_bytes(float max_step, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
   if (!(max_step > 0.f)) return kWarpStripMax;
   const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
