@@ -166,10 +166,10 @@ def test_optional_libav_feeder_compiles_against_stub_headers():
 
 def test_batch_sizes_in_the_docs_are_the_ones_in_the_code():
     """VERDICT r5 weak 2 / ADVICE r5: the header said "one dispatch per 128 frames" for entries that loop on kSmallBatch = 32.  The constants
-    are read from vpf_internal.h / vpf_abi.hip, the comments of include/vpf_hip.h and INTEGRATION.md must name them per entry point."""
+    are read from vpf_classes.h / vpf_abi.hip, the comments of include/vpf_hip.h and INTEGRATION.md must name them per entry point."""
     import re
 
-    internal = open(os.path.join(ROOT, "videoprocessingframework_amd", "csrc", "vpf_internal.h")).read()
+    internal = open(os.path.join(ROOT, "videoprocessingframework_amd", "csrc", "vpf_classes.h")).read()  # (included by vpf_internal.h)
     abi = open(os.path.join(ROOT, "videoprocessingframework_amd", "csrc", "vpf_abi.hip")).read()
     small = int(re.search(r"constexpr int kSmallBatch = (\d+);", internal).group(1))
     large = int(re.search(r"constexpr int kMaxBatch = (\d+);", internal).group(1))

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from cases_fused_families import P16_WHOLE_CASES
 from gpu_util import DevPlanes, stream_handle
 from test_gpu_tensor_out import ELEM, MATRICES, PARAMS, TensorBuf, assert_bits, reference_bits
 from test_gpu_warp_tensor import BORDER, geometry_jobs
@@ -27,21 +28,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FRAME_SIZES = [(131, 79), (130, 78)]
 
-# whole frames: (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, (row alignment, extra pitch bytes), kernel the selection log must name)
-WHOLE_CASES = [
-    ("half_across_chunks", 1056, 36, 528, 18, 1, 0, (256, 0), "k_convert_half<"),       # exact 2x, a wave's 1024-px chunk boundary inside the row
-    ("strip_down_1_25", 160, 96, 128, 80, 1, 0, (256, 0), "k_convert_strip_wg<"),
-    ("strip_up_2", 64, 40, 128, 80, 1, 0, (256, 0), "k_convert_strip_wg<"),
-    ("odd_3x", 192, 96, 64, 32, 1, 0, (256, 0), "k_convert_resize<"),                    # odd integer factor: no strip; no 16-bit per-tap LDS form: gather
-    ("odd_sizes_pitch_plus_2", 131, 79, 61, 35, 1, 0, (64, 2), "k_convert_resize<"),     # rows start at addresses that are only 2-B aligned
-    ("gather_forced", 160, 96, 128, 80, 1, 9, (256, 0), "k_convert_resize<"),
-    ("batch_3", 64, 40, 128, 80, 3, 0, (256, 0), "k_convert_strip_wg<"),
-    ("batch_33_large_table", 64, 40, 32, 20, 33, 0, (256, 0), "k_convert_half<"),        # > 32 frames: the BatchArgsTE<128> instantiation
-    # the 4-, 8- and 16-row bands of the workgroup strip need 512 / 2048 workgroups in the launch: tall, narrow pictures reach them with few bytes
-    ("strip_r4", 8, 2560, 16, 2048, 8, 0, (256, 0), "FC_TENSOR, 4)"),
-    ("strip_r8", 8, 2560, 16, 2048, 32, 0, (256, 0), "FC_TENSOR, 8)"),
-    ("strip_r16_large_table", 8, 1024, 16, 2048, 64, 0, (256, 0), "FC_TENSOR, 16)"),
-]
+# whole frames: (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, (row alignment, extra pitch bytes), the label the selection log must carry)
+WHOLE_CASES = P16_WHOLE_CASES
 CASE = {c[0]: c for c in WHOLE_CASES}
 
 
@@ -123,8 +111,9 @@ def whole_case(capi, orc, name, fmt="P10", cs=1, cr=0, dtype=0, bgr=False, param
 
 
 def test_every_form_is_selected():
-    """the kernel-selection log (VPF_HIP_LOG=2, child process) names the form each whole-frame case, the ROI call and the warp call take, in the
-    default policy and with VPF_TUNE_NV12_RGB_VARIANT = 9, every one of them an FC_P16 instantiation"""
+    """the kernel-selection log (VPF_HIP_LOG=2, child process) carries exactly the label of the instantiation each whole-frame case takes
+    (tests/cases_fused_families.py: family, FC_P16 -> FC_TENSOR, band height, the table of 32 or of 128 frames with the epilogue) and names the
+    form the ROI call and the warp call take, in the default policy and with VPF_TUNE_NV12_RGB_VARIANT = 9, every one of them an FC_P16 instantiation"""
     code = f"""
 import sys
 sys.path.insert(0, {ROOT!r})
@@ -166,11 +155,9 @@ print("done")
         name, rest = chunk.split("\n", 1)
         logs[name.strip()] = [l for l in rest.split("\n") if "libvpfhip: launch" in l]
     print(logs)
-    for name, *_, family in WHOLE_CASES:
-        assert len(logs[name]) == 1 and family in logs[name][0] and "FC_P16" in logs[name][0] and "BatchArgsTE" in logs[name][0], (name, logs[name])
-        if "strip_r" in name:
-            assert "k_convert_strip_wg<" in logs[name][0]
-    assert "kMaxBatch" in logs["batch_33_large_table"][0] and "kMaxBatch" in logs["strip_r16_large_table"][0]
+    for name, *_, label in WHOLE_CASES:
+        assert len(logs[name]) == 1 and logs[name][0].split("launch ", 1)[1].strip() == label, (name, label, logs[name])
+    assert "BatchArgsTE<128>" in logs["batch_33_large_table"][0] and "BatchArgsTE<128>" in logs["strip_r16_large_table"][0]
     for name, kernel in (("roi0", "k_roi_strip<7, 6>"), ("roi9", "k_roi_gather<7, 6>"), ("warp0", "k_warp_strip<7, 6>"), ("warp9", "k_warp_gather<7, 6>")):  # FC_P16 = 7, FC_TENSOR = 6
         assert len(logs[name]) == 1 and kernel in logs[name][0], (name, logs[name])
 

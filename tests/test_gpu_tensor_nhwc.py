@@ -23,6 +23,7 @@ import test_gpu_p16_tensor as p16
 import test_gpu_roi_tensor as roi
 import test_gpu_tensor_in as tin
 import test_gpu_warp_tensor as warp
+from cases_fused_families import FAMILIES, NV12, P16, TENSOR_NHWC, TENSOR_NHWC_CASES, label
 from gpu_util import DevPlanes, stream_handle
 from test_gpu_tensor_out import ELEM, MATRICES, PARAMS, TensorBuf, assert_bits, picture, reference_bits
 from test_tensor_in_cpu import denorm_scale_bias_f32, special_values_f32
@@ -33,22 +34,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CANARY = 0xCD
 TDT = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}
 
-# (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, source offset in samples, what the selection log must name, 16-bit instantiation too)
-FAMILY_CASES = [
-    # two full 512-pixel wave chunks and a third with ONE active lane: the LDS hand-off with inactive lanes
-    ("half", 2080, 8, 1040, 4, 1, 0, 0, ("k_convert_half<",), True),
-    ("strip_r2_down", 192, 48, 128, 32, 1, 0, 0, ("k_convert_strip_wg<", "FC_TENSOR_NHWC, 2)"), True),   # 3 : 2 down
-    ("strip_r2_up", 128, 32, 192, 48, 1, 0, 0, ("k_convert_strip_wg<", "FC_TENSOR_NHWC, 2)"), True),     # 3 : 2 up
-    # the 4-, 8- and 16-row bands need 512 / 2048 workgroups in the launch: the tall narrow pictures of tests/test_gpu_p16_tensor.py
-    ("strip_r4", 8, 2560, 16, 2048, 8, 0, 0, ("k_convert_strip_wg<", "FC_TENSOR_NHWC, 4)"), True),
-    ("strip_r8", 8, 2560, 16, 2048, 32, 0, 0, ("k_convert_strip_wg<", "FC_TENSOR_NHWC, 8)"), True),
-    ("strip_r16", 8, 1024, 16, 2048, 64, 0, 0, ("k_convert_strip_wg<", "FC_TENSOR_NHWC, 16)"), True),
-    ("odd3x", 768, 48, 256, 16, 1, 0, 0, ("k_convert_resize_lds<",), False),
-    ("lds_forced", 192, 48, 128, 32, 1, 40, 0, ("k_convert_resize_lds<",), False),
-    ("band_forced", 640, 90, 256, 36, 3, 49, 0, ("k_convert_resize_band<",), False),
-    ("gather", 61, 35, 13, 9, 1, 0, 1, ("k_convert_resize<",), True),           # dw % 4 != 0: the nv < 4 tail; source base one sample off
-    ("gather_forced", 128, 32, 192, 48, 1, 9, 0, ("k_convert_resize<",), True),
-]
+# (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, source offset in samples, (family, band height or strip passes), 16-bit instantiation too)
+FAMILY_CASES = TENSOR_NHWC_CASES
 CASE = {c[0]: c for c in FAMILY_CASES}
 
 ROI_W, ROI_H, ROI_D = 192, 64, 16
@@ -131,8 +118,9 @@ def _child(code):
 
 
 def test_every_family_is_selected():
-    """the kernel-selection log (VPF_HIP_LOG=2, child process) names, for a channels-last destination, the family each case of FAMILY_CASES takes
-    — the same one as for planar planes — with the FC_TENSOR_NHWC class; the ROI and warp calls of this file run their staged AND their gather
+    """the kernel-selection log (VPF_HIP_LOG=2, child process) carries, for a channels-last destination, exactly the label of the instantiation each
+    case of FAMILY_CASES takes — the family and band height of the planar planes, with the FC_TENSOR_NHWC class, from NV12 and from P10
+    (tests/cases_fused_families.py); the ROI and warp calls of this file run their staged AND their gather
     kernels; the way back takes the fast kernel at the aligned shapes and the quad kernel otherwise"""
     code = f"""
 import sys
@@ -186,16 +174,13 @@ print("done")
 """
     logs = _child(code)
     seen = set()
-    for name, *_, want, p10 in FAMILY_CASES:
-        for key in (name,) + ((name + "_p10",) if p10 else ()):
-            lines = logs[key]
+    for name, _, _, _, _, n, _, _, (family, r), p10 in FAMILY_CASES:
+        for key, src in ((name, NV12),) + (((name + "_p10", P16),) if p10 else ()):
+            lines, want = logs[key], label(family, r, src, TENSOR_NHWC, n)
             print(key, lines)
-            assert lines and all("FC_TENSOR_NHWC" in l and "BatchArgsTE" in l for l in lines), (key, lines)
-            assert all(w in l for w in want for l in lines), (key, want, lines)
-            if key.endswith("_p10"):
-                assert all("FC_P16" in l for l in lines), (key, lines)
-        seen.add(want[0])
-    assert seen == {"k_convert_half<", "k_convert_strip_wg<", "k_convert_resize_band<", "k_convert_resize_lds<", "k_convert_resize<"}, seen
+            assert lines and all(l.split("launch ", 1)[1].strip() == want for l in lines), (key, want, lines)
+        seen.add(family)
+    assert seen == set(FAMILIES), seen
     # 97 jobs = two job tables; each table of the ROI call holds staged and per-tap jobs (the whole frame is a 12 x 4 down-scale)
     print(logs["rois"], logs["warps"], logs["warps9"])
     # the log carries the kernels' template-ids as the code object has them: <source class, destination class>, FC_NV12 = 0, FC_TENSOR_NHWC = 8

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from cases_fused_families import FAMILIES, TENSOR_OUT_CASES
 from gpu_util import DevPlanes, stream_handle
 from test_tensor_out_cpu import PARAM_SETS, scale_bias_f32
 
@@ -26,19 +27,8 @@ ELEM = {0: 4, 1: 2, 2: 2}
 MATRICES = [(0, 0), (0, 1), (1, 0), (1, 1)]  # (colour space, range): BT.601 / BT.709 x MPEG / JPEG
 PARAMS = {name: (mean, std) for name, mean, std in PARAM_SETS}
 
-# the fused families: (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, source offset, kernel the selection log must name)
-FAMILY_CASES = [
-    ("half", 3840, 2160, 1920, 1080, 1, 0, 0, "k_convert_half<"),
-    ("strip_down", 1920, 1080, 1280, 720, 1, 0, 0, "k_convert_strip_wg<"),
-    ("strip_up", 1280, 720, 1920, 1080, 1, 0, 0, "k_convert_strip_wg<"),
-    ("band", 3840, 2160, 1600, 900, 32, 0, 0, "k_convert_resize_band<"),
-    ("odd3x", 1920, 1080, 640, 360, 1, 0, 0, "k_convert_resize_lds<"),
-    ("resnet", 1920, 1080, 224, 224, 1, 0, 0, None),                        # whatever the policy takes for the network input
-    ("gather", 1917, 1079, 223, 225, 1, 0, 1, "k_convert_resize<"),          # source base 1 byte off: no LDS path
-    ("lds_forced", 1920, 1080, 1280, 720, 2, 40, 0, "k_convert_resize_lds<"),
-    ("band_forced", 1920, 1080, 800, 450, 3, 49, 0, "k_convert_resize_band<"),  # (1080p -> 224 x 224 spans too many source columns for LDS)
-    ("gather_forced", 1280, 720, 1920, 1080, 1, 9, 0, "k_convert_resize<"),
-]
+# the fused families: (name, sw, sh, dw, dh, frames, VPF_TUNE_NV12_RGB_VARIANT, source offset, the label the selection log must carry)
+FAMILY_CASES = TENSOR_OUT_CASES
 
 
 @pytest.fixture(scope="module")
@@ -124,7 +114,8 @@ def run_capi(capi, sf, cs, cr, sw, sh, dw, dh, srcs, dtype, bgr, params, buf, ba
 
 
 def test_every_family_is_selected():
-    """the kernel-selection log (VPF_HIP_LOG=2, child process) names the fused family each case of FAMILY_CASES takes for a tensor destination"""
+    """the kernel-selection log (VPF_HIP_LOG=2, child process) carries, for every case of FAMILY_CASES, exactly the label of its instantiation: family,
+    NV12 -> planar tensor, band height, frame table with the epilogue (tests/cases_fused_families.py)"""
     code = f"""
 import sys
 sys.path.insert(0, {ROOT!r})
@@ -151,16 +142,12 @@ print("done")
         name, rest = chunk.split("\n", 1)
         logs[name.strip()] = [l for l in rest.split("\n") if "libvpfhip: launch" in l]
     seen = set()
-    for name, *_, family in FAMILY_CASES:
+    for name, *_, label in FAMILY_CASES:
         lines = logs[name]
         print(name, lines)
-        assert lines and all("FC_TENSOR" in l and "BatchArgsTE" in l for l in lines), (name, lines)
-        if family:
-            assert all(family in l for l in lines), (name, family, lines)
-        for f in ("k_convert_half<", "k_convert_strip_wg<", "k_convert_resize_band<", "k_convert_resize_lds<", "k_convert_resize<"):
-            if any(f in l for l in lines):
-                seen.add(f)
-    assert len(seen) == 5, seen
+        assert lines and all(l.split("launch ", 1)[1].strip() == label for l in lines), (name, label, lines)
+        seen.add(label[1:label.index("<")])
+    assert seen == set(FAMILIES), seen
 
 
 @pytest.mark.parametrize("case", FAMILY_CASES, ids=[c[0] for c in FAMILY_CASES])

@@ -171,7 +171,7 @@ def test_task_layer_construction_and_refusals(capfd):
         nvc._UseHostAllocator(False)
 
 
-_P16_KERNEL = re.compile(r"k_convert_half<6, 7,|k_convert_strip_wg<7, 6,|k_convert_resize<7, 6,|k_roi_(strip|gather)<7, 6>|k_warp_(strip|gather)<7, 6>")  # FC_P16 = 7, FC_TENSOR = 6
+_P16_KERNEL = re.compile(r"k_convert_half<7, 6,|k_convert_strip_wg<7, 6,|k_convert_resize<7, 6,|k_roi_(strip|gather)<7, 6>|k_warp_(strip|gather)<7, 6>")  # FC_P16 = 7, FC_TENSOR = 6
 
 
 @pytest.mark.timeout(900)

@@ -63,7 +63,7 @@ def test_every_kernel_family_in_the_library_is_launched_by_the_product_sources()
     code = "\n".join(l.split("//")[0] for l in src.split("\n"))
     for lab in ("k_planes_mp_persist", "LanczosPairTask", "launch_planes_mp_persist", "k_convert_strip,", "vpf_persist.h"):
         assert lab not in code, lab  # (comments may mention them; code the product compiles may not)
-    launches = set(re.findall(r"\b(k_[a-z0-9_]+)\b", " ".join(re.findall(r"(?:hipLaunchKernelGGL|VPF_LAUNCH(?:_BA)?|VPF_LAUNCH_[A-Z0-9_]+)\s*\((.*)", code))))
+    launches = set(re.findall(r"\b(k_[a-z0-9_]+)\b", " ".join(re.findall(r"(?:hipLaunchKernelGGL|VPF_LAUNCH|VPF_LAUNCH_[A-Z0-9_]+)\s*\((.*)", code))))
     families = sorted({re.match(r"(k_[a-z0-9_]+)", n).group(1) for n in stubs()})
     assert len(families) > 40
     missing = [f for f in families if f not in launches and not re.search(r"\b" + f + r"\b\s*<", code.replace("void " + f, ""))]

@@ -201,7 +201,7 @@ def test_binding_arguments_without_gpu():
 
 
 # FC_TENSOR_NHWC = 8 (FC_TENSOR = 6, FC_P16 = 7): the channels-last instantiations of the fused families, of the ROI / warp kernels and of the way back
-_NHWC_KERNEL = re.compile(r"k_convert_half<8, |k_convert_(strip_wg|resize_band|resize_lds|resize)<\d, 8, |k_(roi|warp)_(strip|gather)<\d, 8>|k_tensor_yuv_r<\d, (true|false), true>|k_tensor_yuv_quad<(true|false), true>")
+_NHWC_KERNEL = re.compile(r"k_convert_(half|strip_wg|resize_band|resize_lds|resize)<\d, 8, |k_(roi|warp)_(strip|gather)<\d, 8>|k_tensor_yuv_r<\d, (true|false), true>|k_tensor_yuv_quad<(true|false), true>")
 
 
 @pytest.mark.timeout(900)

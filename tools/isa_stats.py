@@ -81,6 +81,9 @@ def old_name(new):
     m = re.match(r"(k_tensor_yuv_(?:quad|r))<(.*), (true|false)>$", new)
     if m:
         return f"{m.group(1)}{'_nhwc' if m.group(3) == 'true' else ''}<{m.group(2)}>"
+    m = re.match(r"(k_convert_half(?:_one)?)<(\d+), (\d+)(.*)>$", new)  # <SRC, DST, ...> was <DST, SRC, ...>
+    if m:
+        return f"{m.group(1)}<{m.group(3)}, {m.group(2)}{m.group(4)}>"
     return new
 
 

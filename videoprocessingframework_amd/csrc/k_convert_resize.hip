@@ -8,7 +8,9 @@
 
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
+#include "k_job_launch.h"
 #include "k_resize_common.h"
+#include "vpf_fused_plan.h"
 
 namespace vpf {
 
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(256) void k_convert_resize(const BA args, const Yuv
 // This kernel is VALU-bound, not HBM-bound: four full conversions (incl. the u8 rounding that keeps it bit-identical to
 // convert-then-resize) per destination pixel is ~500 VALU instructions per wave of 256 px, i.e. ~2.9 us per 4K->720p
 // frame of pure issue time on 1024 SIMDs; measured 3.2 us batched.
-constexpr uint32_t kFusedRowBytes = 2048;  // cap; the launch sizes the strips for its own scale factor (dyn_strip)
+// (kFusedRowBytes, the cap of a strip row; the launch sizes the strips for its own scale factor, dyn_strip: vpf_fused_plan.h)
 
 template <int SRC, int DST, int IT>
 VPF_DEV void convert_resize_lds_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, float scx,
@@ -459,7 +461,7 @@ __global__ __launch_bounds__(256) void k_convert_resize_band(const BA args, cons
 // narrowed to the dwordx4 the body works on.  Requires sw == 2 dw, sh == 2 dh, sw % 16 == 0, 16-B aligned luma and chroma planes and pitches
 // (an active lane has xs + 16 <= sw: its loads end inside the rows' own samples), 16-B aligned destination rows.
 // ------------------------------------------------------------------------------------------
-template <int DST, int SRC>
+template <int SRC, int DST>
 VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks, const TensorEpi& te) {
   __shared__ u32x4 tile[DST == FC_PLANAR || DST == FC_TENSOR_NHWC ? 1 : DST == FC_TENSOR ? 4 * 128 : 4 * 96];  // 1.5 KiB per wave: 64 lanes x 24 packed bytes (f32 tensor rows: 2 KiB)
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -570,15 +572,15 @@ VPF_DEV void convert_half_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_
     }
   }
 }
-template <int DST, int SRC, class BA = BatchArgs>
+template <int SRC, int DST, class BA = BatchArgs>
 __global__ __launch_bounds__(256) void k_convert_half(const BA args, const Yuv2RgbCoef c, uint32_t sw, uint32_t dh,
                                                       uint32_t chunks_x, uint32_t n_tasks) {
-  convert_half_task<DST, SRC>(args.f[blockIdx.y], c, sw, dh, chunks_x, n_tasks, epi_of(args));
+  convert_half_task<SRC, DST>(args.f[blockIdx.y], c, sw, dh, chunks_x, n_tasks, epi_of(args));
 }
-template <int DST, int SRC>  // single-frame entry: scalar arguments
+template <int SRC, int DST>  // single-frame entry: scalar arguments
 __global__ __launch_bounds__(256) void k_convert_half_one(VPF_ONE_SRC_PARAMS, uint32_t sw, uint32_t dh, uint32_t chunks_x, uint32_t n_tasks,
                                                           VPF_ONE_DST_PARAMS, const Yuv2RgbCoef c) {
-  convert_half_task<DST, SRC>(VPF_ONE_FRAME, c, sw, dh, chunks_x, n_tasks, TensorEpi{});
+  convert_half_task<SRC, DST>(VPF_ONE_FRAME, c, sw, dh, chunks_x, n_tasks, TensorEpi{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -593,7 +595,7 @@ __global__ __launch_bounds__(256) void k_convert_half_one(VPF_ONE_SRC_PARAMS, ui
 // Requires 8-B aligned source planes, sw % 8 == 0, and a window that fits 8 LDS rows; odd-integer factors keep k_convert_resize_lds
 // (whose centre-sample shortcut is HBM-bound already), exact 2x keeps k_convert_half.
 // ------------------------------------------------------------------------------------------
-constexpr int kStripRows = 8;  // source rows a wave's strip can hold
+// (kStripRows = 8, the source rows a wave's strip can hold: vpf_fused_plan.h)
 #ifdef VPF_LAB_FORMS  // superseded by k_convert_strip_wg (round 5): built into tools/lab/libvpfhip_forms.so only (VPF_TUNE_NV12_RGB_VARIANT = 47)
 template <int SRC, int DST, int R>
 VPF_DEV void convert_strip_task(const FrameDesc& f, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, float scx, float scy,
@@ -822,253 +824,72 @@ __global__ __launch_bounds__(256) void k_convert_strip_wg(const BA args, const Y
   convert_strip_wg_task<SRC, DST, R>(args.f[b.z], c, sw, sh, dw, dh, scx, scy, vec_ok, rowq, b.x, b.y, epi_of(args));
 }
 
+// The launch: reduce the frames' alignment, ask the policy (fused_plan, vpf_fused_plan.h: families, limits and their measured reasons), turn the
+// plan's run-time choices into template arguments and launch (k_job_launch.h).  Which instantiations the code object holds is decided here: FC_P16
+// has no per-tap LDS form, the single-frame scalar-argument entries exist for the 8-bit destinations only, the table follows from the destination.
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw, uint32_t sh,
                                  uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te) {
-  const float scx = (float)sw / (float)dw, scy = (float)sh / (float)dh;
-  int vec_ok = 1;
-  // up to 32 frames travel in the small frame table, more in the large one: two instantiations of every batch kernel (vpf_internal.h)
-  const bool small = n <= (uint32_t)kSmallBatch;
-  const BatchArgs as = small_batch(a, small ? n : 0u);
-#define VPF_UNPAREN(...) __VA_ARGS__
-#define VPF_LAUNCH_BA(K, TARGS, GRID, BLK, LDS, ST, ...) do { \
-    if (small) VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgs>), GRID, BLK, LDS, ST, as, __VA_ARGS__); \
-    else VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsL>), GRID, BLK, LDS, ST, a, __VA_ARGS__); } while (0)
-  // FC_TENSOR: the same frame table with the epilogue behind it (BatchArgsTE); entries up to the next multiple of 8 are defined (vpf_abi.hip)
-  // FC_TENSOR_NHWC: the same launches with the other destination class (VPF_TDST): the family is picked exactly as for FC_TENSOR, only the
-  // destination alignment test differs — one plane, whose vector stores are 16-B ones whatever the dtype
-  const bool nhwc = dst_fc == FC_TENSOR_NHWC, tens = dst_fc == FC_TENSOR || nhwc;
-  if (tens && (!te || n > (uint32_t)kMaxBatch)) return hipErrorInvalidValue;
-#define VPF_TDST(M, ...) do { if (nhwc) M(FC_TENSOR_NHWC, __VA_ARGS__); else M(FC_TENSOR, __VA_ARGS__); } while (0)
-  const uint32_t ncopy = ((n + 7u) & ~7u) < (uint32_t)kMaxBatch ? ((n + 7u) & ~7u) : (uint32_t)kMaxBatch;
-  // FC_TENSOR_NHWC: where the launch has room, a staging area for the waves' interleaved rows behind the kernel's own dynamic LDS, named in the
-  // epilogue (nhwc_stage_plan, vpf_internal.h); stage_npx = pixels per lane of the kernel about to be launched
-  uint32_t stage_npx = 4;
-#define VPF_LAUNCH_BAT(K, TARGS, GRID, BLK, LDS, ST, ...) do { \
-    TensorEpi e_ = *te; \
-    const uint32_t l_ = nhwc ? nhwc_stage_plan(*te, (uint32_t)(LDS), stage_npx, &e_) : (uint32_t)(LDS); \
-    if (small) { BatchArgsTE<kSmallBatch> t_; std::memcpy(t_.f, a.f, (ncopy < (uint32_t)kSmallBatch ? ncopy : (uint32_t)kSmallBatch) * sizeof(FrameDesc)); t_.e = e_; \
-                 VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kSmallBatch>>), GRID, BLK, l_, ST, t_, __VA_ARGS__); } \
-    else { BatchArgsTE<kMaxBatch> t_; std::memcpy(t_.f, a.f, ncopy * sizeof(FrameDesc)); t_.e = e_; \
-           VPF_LAUNCH((K<VPF_UNPAREN TARGS, BatchArgsTE<kMaxBatch>>), GRID, BLK, l_, ST, t_, __VA_ARGS__); } } while (0)
-  // destination alignment the vector stores need: 4 px x element size per lane and plane (1-B elements: the 8-bit classes)
-  const uint32_t dmask = nhwc ? 15u : dst_fc == FC_TENSOR ? (te->dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
-  const int ndp = dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 3 : 1;
-  const uint32_t rowb = lds_strip_bytes(1, sw, dw, a.f[0].s[0], a.f[0].sp[0], kFusedRowBytes);
-  bool lds_ok = rowb != 0;
+  FusedShape q{src_fc, dst_fc, te != nullptr, te ? te->dtype : 0u, sw, sh, dw, dh, n, tuning(VPF_TUNE_NV12_RGB_VARIANT), 0, 0};
+  const int nsp = src_fc == FC_YUV420 ? 3 : 2, ndp = dst_fc == FC_PLANAR || dst_fc == FC_TENSOR ? 3 : 1;
   for (uint32_t i = 0; i < n; i++) {
     const FrameDesc& f = a.f[i];
-    for (int k = 0; k < ndp; k++) vec_ok &= ((((uintptr_t)f.d[k] | f.dp[k]) & dmask) == 0);
-    for (int k = 0; k < (src_fc == FC_NV12 ? 2 : 3); k++) lds_ok = lds_ok && !(((uintptr_t)f.s[k] | f.sp[k]) & 15);
+    for (int k = 0; k < nsp; k++) q.src_bits |= (uintptr_t)f.s[k] | f.sp[k];
+    for (int k = 0; k < ndp; k++) q.dst_bits |= (uintptr_t)f.d[k] | f.dp[k];
   }
-  // 16-bit sources (FC_P16: P10 / P12, into FC_TENSOR only).  Policy: exact 2x -> k_convert_half; the workgroup strip under the wconv rule of
-  // the 8-bit sources below; everything else -> the gather form.  The per-tap LDS kernels stage raw bytes and have no 16-bit instantiation
-  // (DESIGN 4.10, 8).  VPF_TUNE_NV12_RGB_VARIANT = 9 / 40 / 49 keep the gather form.
-  const int p16_v = tuning(VPF_TUNE_NV12_RGB_VARIANT);
-  const bool p16_general = p16_v == 9 || p16_v == 40 || p16_v == 49;
-  bool p16_a16 = src_fc == FC_P16;  // 16-B aligned source planes and pitches: what the aligned 16-B loads of the half and strip kernels need
-  if (src_fc == FC_P16) {
-    if (!tens) return hipErrorInvalidValue;
-    for (uint32_t i = 0; i < n; i++)
-      for (int k = 0; k < 2; k++) p16_a16 = p16_a16 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 15);
-    if (sw == 2 * dw && sh == 2 * dh && sw % 16 == 0 && p16_a16 && !p16_general) {
-      bool ok16 = true;
-      for (uint32_t i = 0; i < n; i++)
-        for (int k = 0; k < ndp; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & 15u);
-      if (ok16) {
-        const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
-        dim3 hgrid((tasks + 3) / 4, n);
-#define VPF_HALFP(D, S) VPF_LAUNCH_BAT(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
-        stage_npx = 8;
-        VPF_TDST(VPF_HALFP, FC_P16);
-#undef VPF_HALFP
-        return hipGetLastError();
-      }
-    }
-  }
-  // exact 2x from NV12: the quad-structured kernel (no taps, no gathers); tuning 40 / 9 keep the general kernels
-  // (packed rows leave as 16-B stores: 3 * dw must be a multiple of 16)
-  if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && sw == 2 * dw && sh == 2 * dh && sw % (dst_fc == FC_PLANAR || tens ? 16 : 32) == 0 && lds_ok && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40) {
-    bool ok16 = true;
-    for (uint32_t i = 0; i < n; i++)
-      for (int k = 0; k < ndp; k++) ok16 = ok16 && !(((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (dst_fc == FC_PLANAR ? 7u : 15u));  // (FC_TENSOR: 16-B stores whatever the dtype)
-    if (ok16) {
-      const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
-      dim3 hgrid((tasks + 3) / 4, n);
-#define VPF_HALF1(D, S) do { if (n == 1) VPF_LAUNCH((k_convert_half_one<D, S>), hgrid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), sw, dh, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c); \
-                            else VPF_LAUNCH_BA(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks); } while (0)
-#define VPF_HALFT(D, S) VPF_LAUNCH_BAT(k_convert_half, (D, S), hgrid, dim3(256), 0, st, c, sw, dh, chunks, tasks)
-#define VPF_HALF(S) do { if (dst_fc == FC_RGB) VPF_HALF1(FC_RGB, S); else if (dst_fc == FC_BGR) VPF_HALF1(FC_BGR, S); else if (tens) VPF_TDST(VPF_HALFT, S); else VPF_HALF1(FC_PLANAR, S); } while (0)
-      stage_npx = 8;
-      if (src_fc == FC_NV12) VPF_HALF(FC_NV12); else VPF_HALF(FC_YUV420);
-#undef VPF_HALF
-#undef VPF_HALFT
-#undef VPF_HALF1
-      return hipGetLastError();
-    }
-  }
-  // general factors: convert the window once into an LDS RGB strip, blend from bytes (k_convert_strip); odd integer factors on either
-  // axis keep the kernels below (their zero-weight shortcuts skip whole rows / taps)
-  {
-    const bool odd_x = sw % dw == 0 && ((sw / dw) & 1), odd_y = sh % dh == 0 && ((sh / dh) & 1);
-    bool ok8 = (src_fc == FC_NV12 || src_fc == FC_YUV420 || (src_fc == FC_P16 && p16_a16)) && sw % 8 == 0 && !odd_x && !odd_y && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 &&
-               tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9 && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 49 && sw < (1u << 22) && sh < (1u << 22);
-    for (uint32_t i = 0; i < n && ok8; i++)
-      for (int k = 0; k < (src_fc == FC_YUV420 ? 3 : 2); k++) ok8 = ok8 && !(((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 7);
-    if (ok8) {
-#ifdef VPF_LAB_FORMS  // the per-wave strips of rounds 2-4 (k_convert_strip): variant 47, and where the workgroup strips do not apply
-      const uint32_t rowbytes = vpf_bound_fused_rowbytes(scx);  // a wave's source span + alignment + tap-window slack (vpf_plan_bounds.h)
-      int r = 0;
-      if (vpf_bound_fused_rows_fit(8, scy, kStripRows)) r = 8;  // rows a wave's R destination rows can touch: <= (R - 1) scy + 3 (+ fp32 slack)
-      else if (vpf_bound_fused_rows_fit(4, scy, kStripRows)) r = 4;
-      else if (vpf_bound_fused_rows_fit(2, scy, kStripRows)) r = 2;
-      if (dh < 64) r = r ? 2 : 0;  // short pictures: more, smaller tasks
-      if (r == 8 && (uint64_t)((dw + 255) / 256) * ((dh + 31) / 32) * n < 2048) r = 4;  // keep the chip covered
-      // strip rows per wave: what the bands of this shape really touch (a walk with the kernel's tap arithmetic, vpf_plan_bounds.h), not
-      // the kStripRows the band height was chosen against — 1080p -> 720p: 6 rows, five workgroups per CU instead of four
-      static thread_local struct { int r; uint32_t sh, dh, rows; } seen = {0, 0, 0, 0};
-      if (r && !(seen.r == r && seen.sh == sh && seen.dh == dh)) { seen.r = r; seen.sh = sh; seen.dh = dh; seen.rows = vpf_band_rows_exact(r, sh, dh, scy); }
-      const uint32_t srows = r ? (seen.rows < (uint32_t)kStripRows ? seen.rows : (uint32_t)kStripRows) : (uint32_t)kStripRows;
-      const uint32_t lds1 = 4u * srows * rowbytes;
-      // conversions per destination pixel: scx x ((r - 1) scy + 2) / r source pixels against the four taps of the per-tap kernel —
-      // measured break-even near 2x (4K -> 1600x900, 2.4x: 9.5 us here vs 5.2 us per-tap; 1080p -> 720p: 2.36 vs 3.21; 1080p -> 4K: 15.0 vs 23.6)
-      const double conv_per_px = r ? (double)scx * ((r - 1) * (double)scy + 2.0) / r : 1e9;
-#endif  // VPF_LAB_FORMS
-      // Round 5: the strip shared by the workgroup (k_convert_strip_wg: the source window of 4 R destination rows converted once, dealt
-      // out over all 256 lanes).  Band height: the largest of 16 (up-scales) / 8 / 4 / 2 whose strip leaves four workgroups per CU
-      // (<= 40 KiB of the CU's 160: round 6's four-byte pixels make 1080p -> 720p at R = 4 a 39.5-KiB strip) and whose launch still covers the chip.  (Lab builds: VPF_TUNE_NV12_RGB_VARIANT = 47 keeps the per-wave strips.)
-#ifdef VPF_LAB_FORMS
-      if (tuning(VPF_TUNE_NV12_RGB_VARIANT) != 47)
-#endif
-      {
-        static thread_local struct { uint32_t sh, dh, rows[4]; } wseen = {0, 0, {0, 0, 0, 0}};
-        if (!(wseen.sh == sh && wseen.dh == dh)) {
-          wseen.sh = sh; wseen.dh = dh;
-          for (int k = 0; k < 4; k++) wseen.rows[k] = vpf_band_rows_exact(4 * (2 << k), sh, dh, scy);  // the workgroup's 4 R rows: R = 2, 4, 8, 16
-        }
-        int rw = 0;
-        uint32_t wrows = 0;
-        const uint32_t rowbytes4 = vpf_bound_fused_rowbytes4(scx);  // the workgroup's strip holds four bytes per pixel (R G B x)
-        for (int k = 3; k >= 0; k--) {
-          const int cand = 2 << k;
-          if (cand == 16 && scy > 1.0f) continue;
-          if ((uint64_t)wseen.rows[k] * rowbytes4 > 40u * 1024u) continue;
-          if (cand > 2 && (uint64_t)((dw + 255) / 256) * ((dh + 4 * cand - 1) / (4 * cand)) * n < (cand >= 8 ? 2048u : 512u)) continue;  // keep the chip covered
-          rw = cand; wrows = wseen.rows[k];
-          break;
-        }
-        // source pixels converted per destination pixel: rows of the strip x its width / (4 R x 256); the per-tap kernel converts four
-        auto wconv_of = [&](int cand, uint32_t rows) { return cand ? (double)rows * ((double)scx * 255.0 + 18.0) / (4.0 * cand * 256.0) : 1e9; };
-        const double wmax = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 48 ? 8.0 : 3.0;
-        // Second pass (round 6: the four-byte pixels pushed factors of 1.55-1.9 and small single frames out of the first): 4- or 2-row bands
-        // with a strip of up to 53 KiB (three workgroups per CU) however few workgroups the launch has — the shapes the per-wave strips of
-        // rounds 2-4 (lab builds: k_convert_strip) used to take, with the rows neighbouring bands share converted once.
-        if (!rw || wconv_of(rw, wrows) > wmax) {
-          rw = 0;
-          for (int k = 1; k >= 0; k--) {
-            const int cand = 2 << k;
-            if ((uint64_t)wseen.rows[k] * rowbytes4 > 53u * 1024u || (dh < 64 && cand > 2)) continue;
-            if (wconv_of(cand, wseen.rows[k]) <= wmax) { rw = cand; wrows = wseen.rows[k]; break; }
+  const FusedPlan p = fused_plan(q);
+  if (p.family == FUSED_REFUSED) return hipErrorInvalidValue;
+  const dim3 grid(p.gx, p.gy, p.gz);
+  const bool small = p.table == FUSED_SMALL;
+  const FrameDesc& f0 = a.f[0];
+  with_fused_src_dst(src_fc, dst_fc, [&](auto S, auto D) {
+    constexpr bool y8 = S != FC_P16, d8 = D != FC_TENSOR && D != FC_TENSOR_NHWC;  // an 8-bit source / destination class
+    auto table = [&](auto&& launch) { with_frame_table<D>(a, n, small, te, p.lds, p.stage_npx, launch); };
+    switch (p.family) {
+      case FUSED_HALF:
+        if constexpr (d8) {
+          if (p.table == FUSED_ONE) {
+            VPF_LAUNCH_T(k_convert_half_one, (S, D), grid, 0, st, VPF_ONE_SRC_ARGS(f0), sw, dh, p.chunks, p.tasks, VPF_ONE_DST_ARGS(f0), c);
+            break;
           }
         }
-        const double wconv = wconv_of(rw, wrows);
-        if (rw && wconv <= wmax) {
-          const uint32_t ldsw = wrows * rowbytes4;
-          dim3 wgrid((dw + 255) / 256, (dh + 4 * rw - 1) / (4 * rw), n);
-#define VPF_WG1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip_wg, (S, D, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
-#define VPF_WG(S, D) do { if (rw == 16) VPF_WG1(S, D, 16); else if (rw == 8) VPF_WG1(S, D, 8); else if (rw == 4) VPF_WG1(S, D, 4); else VPF_WG1(S, D, 2); } while (0)
-#define VPF_WGT1(D, S, RR) VPF_LAUNCH_BAT(k_convert_strip_wg, (S, D, RR), wgrid, dim3(256), ldsw, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowbytes4 / 16)
-#define VPF_WGT2(D, S) do { if (rw == 16) VPF_WGT1(D, S, 16); else if (rw == 8) VPF_WGT1(D, S, 8); else if (rw == 4) VPF_WGT1(D, S, 4); else VPF_WGT1(D, S, 2); } while (0)
-#define VPF_WGT(S) VPF_TDST(VPF_WGT2, S)
-#define VPF_WGD(S) do { if (dst_fc == FC_RGB) VPF_WG(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_WG(S, FC_BGR); else if (tens) VPF_WGT(S); else VPF_WG(S, FC_PLANAR); } while (0)
-          if (src_fc == FC_NV12) VPF_WGD(FC_NV12); else if (src_fc == FC_P16) VPF_WGT(FC_P16); else VPF_WGD(FC_YUV420);
-#undef VPF_WGD
-#undef VPF_WGT
-#undef VPF_WGT2
-#undef VPF_WGT1
-#undef VPF_WG
-#undef VPF_WG1
-          return hipGetLastError();
-        }
-      }
+        table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_half, (S, D), t, grid, lds, st, c, sw, dh, p.chunks, p.tasks); });
+        break;
+      case FUSED_STRIP_WG:
+        with_rows<16, 8, 4, 2>(p.r, [&](auto R) {
+          table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_strip_wg, (S, D, R), t, grid, lds, st, c, sw, sh, dw, dh, p.scx, p.scy, p.vec_ok, p.rowq); });
+        });
+        break;
 #ifdef VPF_LAB_FORMS
-      if (r && lds1 <= 64u * 1024u && conv_per_px <= 3.0 && !tens) {  // (8-bit destinations only)
-        dim3 sgrid((dw + 255) / 256, (dh + 4 * r - 1) / (4 * r), n);
-#define VPF_STRIP1(S, D, RR) VPF_LAUNCH_BA(k_convert_strip, (S, D, RR), sgrid, dim3(256), lds1, st, c, sw, sh, dw, dh, scx, scy, vec_ok, (rowbytes / 16) | (srows << 16))
-#define VPF_STRIP(S, D) do { if (r == 8) VPF_STRIP1(S, D, 8); else if (r == 4) VPF_STRIP1(S, D, 4); else VPF_STRIP1(S, D, 2); } while (0)
-#define VPF_STRIPD(S) do { if (dst_fc == FC_RGB) VPF_STRIP(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_STRIP(S, FC_BGR); else VPF_STRIP(S, FC_PLANAR); } while (0)
-        if (src_fc == FC_NV12) VPF_STRIPD(FC_NV12); else VPF_STRIPD(FC_YUV420);
-#undef VPF_STRIPD
-#undef VPF_STRIP
-#undef VPF_STRIP1
-        return hipGetLastError();
-      }
-#endif  // VPF_LAB_FORMS
+      case FUSED_STRIP_WAVE:
+        if constexpr (y8 && d8)
+          with_rows<8, 4, 2>(p.r, [&](auto R) {
+            table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_strip, (S, D, R), t, grid, lds, st, c, sw, sh, dw, dh, p.scx, p.scy, p.vec_ok, p.rowq); });
+          });
+        break;
+#endif
+      case FUSED_BAND:
+        if constexpr (y8)
+          with_rows<1, 2>(p.r, [&](auto IT) {
+            table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_resize_band, (S, D, IT, 4), t, grid, lds, st, c, sw, sh, dw, dh, p.scx, p.scy, p.vec_ok, p.rowq); });
+          });
+        break;
+      case FUSED_LDS:
+        if constexpr (y8)
+          with_rows<1, 2>(p.r, [&](auto IT) {
+            if constexpr (d8) {
+              if (p.table == FUSED_ONE) {
+                VPF_LAUNCH_T(k_convert_resize_lds_one, (S, D, IT), grid, p.lds, st, f0.s[0], f0.s[1], f0.sp[0], f0.sp[1], sw, sh, dw, dh, p.scx, p.scy, p.rowq, p.vec_ok,
+                             f0.s[2], f0.sp[2], VPF_ONE_DST_ARGS(f0), c);
+                return;
+              }
+            }
+            table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_resize_lds, (S, D, IT), t, grid, lds, st, c, sw, sh, dw, dh, p.scx, p.scy, p.vec_ok, p.rowq); });
+          });
+        break;
+      default:  // FUSED_GATHER
+        table([&](const auto& t, uint32_t lds) { VPF_LAUNCH_TB(k_convert_resize, (S, D), t, grid, lds, st, c, sw, sh, dw, dh, p.scx, p.scy, p.vec_ok); });
     }
-  }
-  if (src_fc == FC_P16) {  // everything else from 16-bit sources: the gather form
-    dim3 ggrid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
-#define VPF_GATP(D, S) VPF_LAUNCH_BAT(k_convert_resize, (S, D), ggrid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
-    VPF_TDST(VPF_GATP, FC_P16);
-#undef VPF_GATP
-    return hipGetLastError();
-  }
-  const uint32_t lds = 4 * (src_fc == FC_NV12 ? 4 : 6) * rowb;
-  // factors beyond ~2x on a launch that covers the chip with four rows per wave: the per-tap kernel as a row band (k_convert_resize_band);
-  // odd integer factors keep the row-at-a-time kernel below and its zero-weight shortcuts.  VPF_TUNE_NV12_RGB_VARIANT = 40 / 9 keep it too.
-  {
-    const bool odd_x = sw % dw == 0 && ((sw / dw) & 1), odd_y = sh % dh == 0 && ((sh / dh) & 1);
-    const int v = tuning(VPF_TUNE_NV12_RGB_VARIANT);
-    if ((src_fc == FC_NV12 || src_fc == FC_YUV420) && lds_ok && !odd_x && !odd_y && v != 40 && v != 9 && sw < (1u << 22) && sh < (1u << 22) &&
-        ((uint64_t)((dw + 255) / 256) * ((dh + 15) / 16) * n >= 2048u || v == 49)) {  // 49: whatever the launch size (tests, A/B runs)
-      dim3 bgrid((dw + 255) / 256, (dh + 15) / 16, n);
-#define VPF_BAND1(S, D, I) VPF_LAUNCH_BA(k_convert_resize_band, (S, D, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
-#define VPF_BAND(S, D) do { if (rowb <= 1024) VPF_BAND1(S, D, 1); else VPF_BAND1(S, D, 2); } while (0)
-#define VPF_BANDT1(D, S, I) VPF_LAUNCH_BAT(k_convert_resize_band, (S, D, I, 4), bgrid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16)
-#define VPF_BANDT2(D, S) do { if (rowb <= 1024) VPF_BANDT1(D, S, 1); else VPF_BANDT1(D, S, 2); } while (0)
-#define VPF_BANDT(S) VPF_TDST(VPF_BANDT2, S)
-#define VPF_BANDD(S) do { if (dst_fc == FC_RGB) VPF_BAND(S, FC_RGB); else if (dst_fc == FC_BGR) VPF_BAND(S, FC_BGR); else if (tens) VPF_BANDT(S); else VPF_BAND(S, FC_PLANAR); } while (0)
-      if (src_fc == FC_NV12) VPF_BANDD(FC_NV12); else VPF_BANDD(FC_YUV420);
-#undef VPF_BANDD
-#undef VPF_BANDT
-#undef VPF_BANDT2
-#undef VPF_BANDT1
-#undef VPF_BAND
-#undef VPF_BAND1
-      return hipGetLastError();
-    }
-  }
-  dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
-#define VPF_GOL1(S, D, I) do { if (n == 1) VPF_LAUNCH((k_convert_resize_lds_one<S, D, I>), grid, dim3(256), lds, st, a.f[0].s[0], a.f[0].s[1], a.f[0].sp[0], a.f[0].sp[1], \
-                                                      sw, sh, dw, dh, scx, scy, rowb / 16, vec_ok, a.f[0].s[2], a.f[0].sp[2], VPF_ONE_DST_ARGS(a.f[0]), c); \
-                               else VPF_LAUNCH_BA(k_convert_resize_lds, (S, D, I), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); } while (0)
-#define VPF_GOL(S, D) do { if (rowb <= 1024) VPF_GOL1(S, D, 1); else VPF_GOL1(S, D, 2); } while (0)
-#define VPF_GO(S, D) VPF_LAUNCH_BA(k_convert_resize, (S, D), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
-#define VPF_PICK(S, D) do { if (lds_ok) VPF_GOL(S, D); else VPF_GO(S, D); } while (0)
-  // FC_TENSOR: the frame-table kernels for one frame too (no scalar-argument entry: the epilogue rides behind the table)
-#define VPF_GOLT(D, S) do { if (rowb <= 1024) VPF_LAUNCH_BAT(k_convert_resize_lds, (S, D, 1), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); \
-                            else VPF_LAUNCH_BAT(k_convert_resize_lds, (S, D, 2), grid, dim3(256), lds, st, c, sw, sh, dw, dh, scx, scy, vec_ok, rowb / 16); } while (0)
-#define VPF_GATT(D, S) VPF_LAUNCH_BAT(k_convert_resize, (S, D), grid, dim3(256), 0, st, c, sw, sh, dw, dh, scx, scy, vec_ok)
-#define VPF_PICKT(S) do { if (lds_ok) VPF_TDST(VPF_GOLT, S); else VPF_TDST(VPF_GATT, S); } while (0)
-  if (tens) {
-    if (src_fc == FC_NV12) VPF_PICKT(FC_NV12); else if (src_fc == FC_YUV420) VPF_PICKT(FC_YUV420); else return hipErrorInvalidValue;
-  } else if (src_fc == FC_NV12) {
-    if (dst_fc == FC_RGB) VPF_PICK(FC_NV12, FC_RGB); else if (dst_fc == FC_BGR) VPF_PICK(FC_NV12, FC_BGR); else VPF_PICK(FC_NV12, FC_PLANAR);
-  } else if (src_fc == FC_YUV420) {
-    if (dst_fc == FC_RGB) VPF_PICK(FC_YUV420, FC_RGB); else if (dst_fc == FC_BGR) VPF_PICK(FC_YUV420, FC_BGR); else VPF_PICK(FC_YUV420, FC_PLANAR);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef VPF_PICKT
-#undef VPF_GATT
-#undef VPF_GOLT
-#undef VPF_PICK
-#undef VPF_GO
-#undef VPF_GOL
-#undef VPF_GOL1
-#undef VPF_TDST
-#undef VPF_LAUNCH_BAT
-#undef VPF_LAUNCH_BA
-#undef VPF_UNPAREN
+  });
   return hipGetLastError();
 }
 

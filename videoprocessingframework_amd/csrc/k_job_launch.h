@@ -1,7 +1,7 @@
 // k_job_launch.h — the host side the fused tensor launchers share (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip,
-// their device-table forms and launch_tensor_to_yuv): the argument check, the destination alignment mask, the run-time -> template-argument
+// their device-table forms, launch_tensor_to_yuv and the whole-frame launch_convert_resize): the argument check, the destination alignment mask, the run-time -> template-argument
 // dispatch, the launch of the instantiation it picked and the split of a host job table into its staged and its per-tap dispatch.  Inline functions, function templates over
-// callables and one launch macro: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
+// callables and two launch macros: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
 #ifndef VPF_K_JOB_LAUNCH_H_
 #define VPF_K_JOB_LAUNCH_H_
 #include <cstdio>
@@ -52,11 +52,15 @@ inline bool with_tensor_dtype(uint32_t dtype, F&& f) {
 // FC_YUV420 = 1, FC_P16 = 7, FC_TENSOR = 6, FC_TENSOR_NHWC = 8; bools as true / false — written from the same K and TARGS tokens the launch is.
 inline int put_targ(char* p, size_t n, int v) { return std::snprintf(p, n, "%d, ", v); }
 inline int put_targ(char* p, size_t n, bool v) { return std::snprintf(p, n, "%s, ", v ? "true" : "false"); }
-template <class... T>  // T: std::integral_constant<int or bool, ...>
+template <class T> struct TableName {};  // a frame table as a template argument: "BatchArgsT<32>", "BatchArgsTE<128>"
+template <int CAP> inline int put_targ(char* p, size_t n, TableName<BatchArgsT<CAP>>) { return std::snprintf(p, n, "BatchArgsT<%d>, ", CAP); }
+template <int CAP> inline int put_targ(char* p, size_t n, TableName<BatchArgsTE<CAP>>) { return std::snprintf(p, n, "BatchArgsTE<%d>, ", CAP); }
+template <class T, T V> inline int put_targ(char* p, size_t n, std::integral_constant<T, V>) { return put_targ(p, n, V); }
+template <class... T>  // T: std::integral_constant<int or bool, ...>, TableName<...>
 inline void note_instantiation(const char* family, T... targs) {
   char label[96];
   size_t o = (size_t)std::snprintf(label, sizeof(label), "(%s<", family);
-  ((o += (size_t)put_targ(label + o, sizeof(label) - o, (typename T::value_type)targs)), ...);
+  ((o += (size_t)put_targ(label + o, sizeof(label) - o, targs)), ...);
   std::snprintf(label + o - 2, sizeof(label) - o + 2, ">)");  // (over the last ", ")
   note_kernel(label);
 }
@@ -67,6 +71,63 @@ inline void note_instantiation(const char* family, T... targs) {
     (void)hipGetLastError(); /* (sticky per thread: see VPF_LAUNCH) */                                     \
     hipLaunchKernelGGL((K<VPF_TARGS TARGS>), GRID, dim3(256), LDS, ST, __VA_ARGS__);                       \
   } while (0)
+// ... for the kernels whose LAST template argument is the type of their first argument, the frame table (with_frame_table below):
+// VPF_LAUNCH_TB(k_convert_strip_wg, (S, D, R), table, grid, lds, st, c, ...) launches and logs "(k_convert_strip_wg<0, 8, 2, BatchArgsTE<32>>)"
+#define VPF_LAUNCH_TB(K, TARGS, TABLE, GRID, LDS, ST, ...)                                                                             \
+  do {                                                                                                                                 \
+    using Table_ = std::decay_t<decltype(TABLE)>;                                                                                      \
+    if (vpf::log_level() >= 2 || vpf::trace_on()) vpf::note_instantiation(#K, VPF_TARGS TARGS, vpf::TableName<Table_>{});              \
+    (void)hipGetLastError();                                                                                                           \
+    hipLaunchKernelGGL((K<VPF_TARGS TARGS, Table_>), GRID, dim3(256), LDS, ST, TABLE, __VA_ARGS__);                                     \
+  } while (0)
+
+// ---- the whole-frame fused launch (k_convert_resize.hip)
+// f(SRC, DST) for the legal pairs: FC_NV12 / FC_YUV420 into the five destination classes (any class but the four named ones counts as
+// FC_PLANAR), FC_P16 into the two tensor classes; f is not called for anything else
+template <class F>
+inline void with_fused_src_dst(int src_fc, int dst_fc, F&& f) {
+  auto dst = [&](auto src) {
+    if (dst_fc == FC_TENSOR_NHWC) f(src, std::integral_constant<int, FC_TENSOR_NHWC>{});
+    else if (dst_fc == FC_TENSOR) f(src, std::integral_constant<int, FC_TENSOR>{});
+    else if constexpr (decltype(src)::value != FC_P16) {
+      if (dst_fc == FC_RGB) f(src, std::integral_constant<int, FC_RGB>{});
+      else if (dst_fc == FC_BGR) f(src, std::integral_constant<int, FC_BGR>{});
+      else f(src, std::integral_constant<int, FC_PLANAR>{});
+    }
+  };
+  if (src_fc == FC_NV12) dst(std::integral_constant<int, FC_NV12>{});
+  else if (src_fc == FC_YUV420) dst(std::integral_constant<int, FC_YUV420>{});
+  else if (src_fc == FC_P16) dst(std::integral_constant<int, FC_P16>{});
+}
+// f(R): a band height out of the descending list RS..., the last one for any other value — with_rows<16, 8, 4, 2>(r, f), with_rows<1, 2>(it, f)
+template <int R0, int... RS, class F>
+inline void with_rows(int r, F&& f) {
+  if constexpr (sizeof...(RS) == 0) f(std::integral_constant<int, R0>{});
+  else if (r == R0) f(std::integral_constant<int, R0>{});
+  else with_rows<RS...>(r, f);
+}
+// f(table, lds): the frame table a batch kernel of destination class DST takes for the first n frames of `a` — BatchArgs / BatchArgsL for the
+// 8-bit classes, for the tensor classes BatchArgsTE<32> / <128> (entries up to the next multiple of 8 are defined, vpf_abi.hip) with the
+// epilogue behind it — and the dynamic LDS to ask for: the kernel's own `lds`, plus where an FC_TENSOR_NHWC launch has room the staging area
+// of the waves' interleaved rows, named in the epilogue (nhwc_stage_plan, vpf_internal.h; npx = pixels per lane of the kernel)
+template <int DST, class F>
+inline void with_frame_table(const BatchArgsL& a, uint32_t n, bool small, const TensorEpi* te, uint32_t lds, uint32_t npx, F&& f) {
+  if constexpr (DST == FC_TENSOR || DST == FC_TENSOR_NHWC) {
+    const uint32_t ncopy = ((n + 7u) & ~7u) < (uint32_t)kMaxBatch ? ((n + 7u) & ~7u) : (uint32_t)kMaxBatch;
+    auto fill = [&](auto& t, uint32_t cap) {
+      std::memcpy(t.f, a.f, (ncopy < cap ? ncopy : cap) * sizeof(FrameDesc));
+      const uint32_t l = DST == FC_TENSOR_NHWC ? nhwc_stage_plan(*te, lds, npx, &t.e) : (t.e = *te, lds);
+      f(t, l);
+    };
+    if (small) { BatchArgsTE<kSmallBatch> t; fill(t, (uint32_t)kSmallBatch); }
+    else { BatchArgsTE<kMaxBatch> t; fill(t, (uint32_t)kMaxBatch); }
+  } else if (small) {
+    const BatchArgs t = small_batch(a, n);
+    f(t, lds);
+  } else {
+    f(a, lds);
+  }
+}
 
 // The split of a host job table: `staged_bytes(job)` returns the dynamic LDS the job's strip needs, or kNotStaged for a job that samples per tap
 // (every job under VPF_TUNE_NV12_RGB_VARIANT = 9).  Fills the two zeroed tables — entries beyond a table's jobs are never read: blockIdx.z runs

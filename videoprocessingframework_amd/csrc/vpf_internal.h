@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vpf_classes.h"
 #include "vpf_hip.h"
 
 namespace vpf {
@@ -35,8 +36,7 @@ bool make_rgb2yuv(int color_range, Rgb2YuvCoef* out);
 // The kernarg segment is write-combined host memory: a launch pays ~0.2 us of HOST time per KiB of argument (9 KiB: + 1.3-2 us per call,
 // profiles/r05_abi_launch_rate_9k_kernarg.txt) — nothing against a 128-frame dispatch, 40-70 % of a single frame's issue time.  Hence
 // two instantiations of the resize / fused batch kernels (template parameter BA) instead of one large table for everybody.
-constexpr int kSmallBatch = 32;
-constexpr int kMaxBatch = 128;
+// (kSmallBatch = 32, kMaxBatch = 128: vpf_classes.h)
 struct FrameDesc {
   const uint8_t* s[3];
   uint8_t* d[3];
@@ -65,18 +65,7 @@ inline BatchArgs small_batch(const BatchArgsL& a, uint32_t n) {
 #define VPF_ONE_SRC_ARGS(f) (f).s[0], (f).s[1], (f).s[2], (f).sp[0], (f).sp[1], (f).sp[2]
 #define VPF_ONE_DST_ARGS(f) (f).d[0], (f).d[1], (f).d[2], (f).dp[0], (f).dp[1], (f).dp[2]
 
-enum FmtClass : int {
-  FC_NV12 = 0,    // Y + interleaved UV, 4:2:0
-  FC_YUV420 = 1,  // Y + U + V planes, 4:2:0
-  FC_YUV444 = 2,  // three full planes
-  FC_RGB = 3,     // packed R,G,B
-  FC_BGR = 4,     // packed B,G,R
-  FC_PLANAR = 5,  // three full planes R,G,B
-  FC_TENSOR = 6,  // three full planes of f32 / f16 / bf16: the FC_PLANAR bytes through one fma each (vpf_convert_resize_tensor)
-  FC_P16 = 7,     // P10 / P12: Y + interleaved UV of 16-bit MSB-aligned samples, 4:2:0 — a SOURCE class of the fused tensor entries only: every
-                  // sample is narrowed to 8 bits at the load (p16_to_8, vpf_device.h), from there the code is FC_NV12's
-  FC_TENSOR_NHWC = 8,  // FC_TENSOR's elements in ONE interleaved plane per frame (VPF_TENSOR_NHWC): element (y, x, c) at d[0] + y dp[0] + (3 x + c) elem
-};
+// (FmtClass — FC_NV12 ... FC_TENSOR_NHWC: vpf_classes.h)
 // The epilogue of an FC_TENSOR launch: out[c] = to_dtype(fma(u8[c], scale[c], bias[c])).  It travels behind the frame table (BatchArgsTE), so
 // the 8-bit instantiations keep their kernarg layout.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
 // FC_TENSOR_NHWC has one plane, so B G R order cannot be a swap of planes there: the host still swaps the parameters (scale / bias / border stay
