@@ -14,13 +14,15 @@ import math
 import numpy as np
 
 from test_letterbox_tensor_cpu import fit_reference
+from test_persp_tensor_cpu import NAMED
 
 F = np.float32
-FAMILIES = ("whole", "rois", "rois_dev", "letterbox", "warp", "warp_dev", "encode")
-BASE = {"whole": 21000, "rois": 23000, "rois_dev": 25000, "letterbox": 27000, "warp": 29000, "warp_dev": 31000, "encode": 33000}
-CASES_PER_SEED = {"whole": 4, "rois": 5, "rois_dev": 5, "letterbox": 5, "warp": 5, "warp_dev": 5, "encode": 6}
-TABLE = {"rois": 96, "warp": 96, "letterbox": 82}  # jobs per job table (kRoiBatch, kWarpBatch, kLetterboxBatch of csrc/vpf_internal.h)
-OVER_TABLE = {"rois": (97, 110), "warp": (97, 110), "letterbox": (83, 90)}
+FAMILIES = ("whole", "rois", "rois_dev", "letterbox", "warp", "warp_dev", "encode", "persp")
+BASE = {"whole": 21000, "rois": 23000, "rois_dev": 25000, "letterbox": 27000, "warp": 29000, "warp_dev": 31000, "encode": 33000, "persp": 35000}
+CASES_PER_SEED = {"whole": 4, "rois": 5, "rois_dev": 5, "letterbox": 5, "warp": 5, "warp_dev": 5, "encode": 6, "persp": 5}
+# jobs per job table (kRoiBatch, kWarpBatch, kLetterboxBatch, kPerspBatch of csrc/vpf_internal.h)
+TABLE = {"rois": 96, "warp": 96, "letterbox": 82, "persp": 82}
+OVER_TABLE = {"rois": (97, 110), "warp": (97, 110), "letterbox": (83, 90), "persp": (83, 90)}
 LIMIT = 16777216.0  # |matrix coefficient| limit of the warp entries (include/vpf_hip.h)
 SOURCES = ("NV12", "YUV420", "P10", "P12")
 PARAM_NAMES = ("imagenet", "unit", "symmetric")
@@ -343,6 +345,158 @@ def warp_dev_case(rng):
     return settle_sources(call)
 
 
+# ------------------------------------------------------------------------------------------------ homographies
+# the classes draw_homography draws from, with their weights in a mixed call.  "behind" (no pixel has w > 0: a job whose strip need is 0 bytes)
+# and "degenerate" (w > 0 but tiny, or a signed zero) are apart so that a call of ONE class can be a table whose staged dispatch gets no LDS.
+PERSP_CLASSES = ("lifted", "moderate", "steep", "horizon", "behind", "degenerate", "outside", "cancelling", "sawtooth")
+PERSP_WEIGHTS = (3, 4, 1, 3, 1, 1, 2, 3, 1)
+# what a call of one class picks from: the two classes that make a dispatch no mixed call has (0 bytes of LDS; per-tap jobs only) come up more often
+PERSP_ONLY = ("behind", "behind", "behind", "steep", "steep", "lifted", "moderate", "horizon", "degenerate", "outside", "cancelling", "sawtooth")
+PERSP_MIX = tuple(c for c, w in zip(PERSP_CLASSES, PERSP_WEIGHTS) for _ in range(w))
+SAWTOOTH, SAWTOOTH_SHAPE = NAMED["sawtooth"][0], (131, 79, 33, 33)  # the named matrix and the shape it was found for (W, H, dw, dh)
+
+
+def nine(m):
+    """nine float32 values within the entry's limit"""
+    return tuple(f32(min(max(float(v), -LIMIT), LIMIT)) for v in m)
+
+
+def _sign(rng):
+    return 1 - 2 * int(rng.integers(2))
+
+
+def _log_uniform(rng, lo, hi):
+    return math.exp(rng.uniform(math.log(lo), math.log(hi)))
+
+
+def moderate_homography(rng, W, H, dw, dh):
+    """tests/test_persp_bounds_cpu.py::moderate on the call's own sizes: rotation x scale 0.3 .. 3 x shear about a point of the frame, a perspective
+    row that keeps w within [0.4, 1.6] x m22 over the destination, the whole matrix times 0.25 .. 4"""
+    th, s = rng.uniform(0, 2 * math.pi), _log_uniform(rng, 0.3, 3.0)
+    a, b, c, d = s * math.cos(th), -s * math.sin(th) + rng.uniform(-0.2, 0.2), s * math.sin(th), s * math.cos(th) * rng.uniform(0.8, 1.25)
+    cx, cy = rng.uniform(-0.1 * W, 1.1 * W), rng.uniform(-0.1 * H, 1.1 * H)
+    tx, ty = cx - a * (dw - 1) / 2 - b * (dh - 1) / 2, cy - c * (dw - 1) / 2 - d * (dh - 1) / 2
+    budget, split = rng.uniform(0, 0.6), rng.uniform(0, 1)
+    p, q = _sign(rng) * budget * split / max(dw - 1, 1), _sign(rng) * budget * (1 - split) / max(dh - 1, 1)
+    g = _log_uniform(rng, 0.25, 4.0)
+    return [g * v for v in (a, b, tx, c, d, ty, p, q, 1.0)]
+
+
+def cancelling_homography(rng, W, H, dw, dh):
+    """classes 0 .. 5 of tests/test_persp_bounds_cpu.py::adversarial: coefficients up to 2^24 whose offsets cancel them somewhere inside the
+    destination, in the numerators, the denominator or all three"""
+    def big():
+        return _sign(rng) * _log_uniform(rng, 1e3, 2.0 ** 24)
+
+    cls = int(rng.integers(6))
+    x0, y0 = rng.uniform(0, dw), rng.uniform(0, dh)
+    m = [1.0, 0.0, rng.uniform(0, W), 0.0, 1.0, rng.uniform(0, H), 0.0, 0.0, 1.0]
+    if cls in (0, 3, 5):
+        g = big()
+        m[0], m[2] = g, -g * x0 + rng.uniform(0, W)
+    if cls in (1, 3, 5):
+        g = big()
+        m[4], m[5] = g, -g * y0 + rng.uniform(0, H)
+    if cls in (2, 5):
+        g = big()
+        m[6], m[8] = g, -g * x0 + rng.uniform(0.5, 2)
+    if cls == 4:
+        g, q = abs(big()), abs(big())
+        m = [g * rng.uniform(0.5, 2), g * rng.uniform(-0.2, 0.2), g * rng.uniform(0, W), g * rng.uniform(-0.2, 0.2), g * rng.uniform(0.5, 2), g * rng.uniform(0, H),
+             q * rng.uniform(0, 0.01), q * rng.uniform(0, 0.01), q]
+        s = max(abs(v) for v in m) / 2.0 ** 24
+        if s > 1:
+            m = [v / s for v in m]
+    return m
+
+
+def draw_homography(rng, W, H, dw, dh, steep=False, cls=None):
+    """nine coefficients of the class `cls` (drawn by PERSP_WEIGHTS when None):
+    lifted      the affine family's matrices with the last row (0, 0, 1)
+    moderate    moderate_homography
+    steep       5 .. 9 x down-scales with a small perspective row (on a frame of 200 x 200 and more the tile window outgrows the staged form)
+    horizon     w changes sign inside the destination, along dx, dy or both; one in three in powers of two, w exactly 0 on a column, row or diagonal
+    behind      no pixel has w > 0: w < 0 everywhere, the last row all zero, m22 = -0.0
+    degenerate  w > 0 but denormal (coordinates of +-inf) or 1e-30 (finite coordinates above 1e29); w = m20 dx - 0.0: exactly 0 on column 0
+    outside     w > 0 everywhere, the footprint wholly beside the frame
+    cancelling  cancelling_homography
+    sawtooth    class 6 of adversarial: nx cancels on the destination's last row and sx is a sawtooth along it (the kernel's per-pixel fallback)"""
+    if cls is None:
+        cls = _pick(rng, PERSP_MIX)
+    if cls == "lifted":
+        return nine(draw_matrix(rng, W, H, dw, dh, steep) + (0.0, 0.0, 1.0))
+    if cls == "moderate":
+        return nine(moderate_homography(rng, W, H, dw, dh))
+    if cls == "steep":
+        sx, sy, t = rng.uniform(5, 9), rng.uniform(5, 9), rng.uniform(-0.2, 0.2) if rng.integers(2) else 0.0
+        p, q = _sign(rng) * rng.uniform(0, 0.05) / max(dw - 1, 1), _sign(rng) * rng.uniform(0, 0.05) / max(dh - 1, 1)
+        return nine(centred(sx * math.cos(t), -sy * math.sin(t), sx * math.sin(t), sy * math.cos(t), W, H, dw, dh) + (p, q, 1.0))
+    if cls == "horizon":
+        ux, uy = ((1, 0), (0, 1), (1, 1))[int(rng.integers(3))]
+        T, sg = ux * (dw - 1) + uy * (dh - 1), _sign(rng)
+        if rng.integers(3) == 0:   # exact: w = +-2^-k (t - t0) with t = ux dx + uy dy and t0 a whole number
+            s, t0 = 2.0 ** -_i(rng, 3, 7), float(_i(rng, 0, T))
+        else:
+            s, t0 = rng.uniform(0.5, 2.0) / max(T, 1), rng.uniform(0, T)
+        return nine(draw_matrix(rng, W, H, dw, dh, steep) + (sg * s * ux, sg * s * uy, -sg * s * t0))
+    if cls == "behind":
+        k = int(rng.integers(3))
+        row = (-rng.uniform(0, 0.01), -rng.uniform(0, 0.01), -rng.uniform(0.5, 2)) if k == 0 else (0.0, 0.0, 0.0) if k == 1 else (0.0, 0.0, -0.0)
+        return nine(draw_matrix(rng, W, H, dw, dh) + row)
+    if cls == "degenerate":
+        k = int(rng.integers(4))
+        if k == 0:   # denormal w: +-inf by the sign of the numerators
+            return nine(draw_matrix(rng, W, H, dw, dh) + (0.0, 0.0, 1e-40))
+        if k == 1:   # denormal w that grows along dx from the smallest denormal
+            return nine((1.0, 0.0, _i(rng, -3, 3), 0.0, _sign(rng), _i(rng, -3, 3), 1e-45, 0.0, 1e-45))
+        if k == 2:   # `huge`: finite coordinates above 1e29
+            return nine((1.0, 0.0, _i(rng, 1, 50), 0.0, 1.0, _i(rng, 1, 50), 0.0, 0.0, 1e-30))
+        return nine(draw_matrix(rng, W, H, dw, dh) + (rng.uniform(0.01, 0.1), 0.0, -0.0))
+    if cls == "outside":
+        m = moderate_homography(rng, W, H, dw, dh)
+        axis = int(rng.integers(2))
+        far = _sign(rng) * ((2 * (W, H)[axis] + 10 * (dw + dh) + 500) if rng.integers(3) else 3.0e6)   # sx (sy) moves by `far`: nx += far w
+        for k in range(3):
+            m[3 * axis + k] += far * m[6 + k]
+        return nine(m)
+    if cls == "cancelling":
+        return nine(cancelling_homography(rng, W, H, dw, dh))
+    assert cls == "sawtooth"
+    g = _sign(rng) * _log_uniform(rng, 1e4, 2.0 ** 24 / max(dh, 2))
+    return nine((rng.uniform(0.05, 0.9), g, -g * (dh - 1) + rng.uniform(2, 80), 0.0, 0.0, rng.uniform(1, 3), rng.uniform(1e-4, 3e-3), 0.0, rng.uniform(0.04, 0.1)))
+
+
+def persp_case(rng):
+    """vpf_convert_persp_tensor: warp_case with nine-coefficient matrices.  One call in sixteen draws all of its jobs from ONE class (a call of steep
+    jobs takes the steep shape); one in ten of the others is a sawtooth call: the shape the named sawtooth matrix was found for, or a destination of
+    33 / 65 rows, with that matrix and fresh draws of its class among jobs of every class"""
+    call = draw_common(rng, "persp")
+    only = _pick(rng, PERSP_ONLY) if rng.integers(16) == 0 else None
+    steep = draw_warp_shape(rng, call)
+    if only == "steep" and not steep:
+        steep = True
+        call["W"], call["H"], call["dw"], call["dh"] = _i(rng, 200, 420), _i(rng, 200, 300), _i(rng, 32, 90), _i(rng, 32, 70)
+    n, over = draw_job_count(rng, "persp")
+    if over:
+        call["dw"], call["dh"] = (_i(rng, 32, 40), _i(rng, 32, 36)) if steep else (_i(rng, 1, 24), _i(rng, 1, 16))
+    saw = not over and (only == "sawtooth" or (only is None and rng.integers(10) == 0))
+    named = saw and bool(rng.integers(3))
+    if named:
+        call["W"], call["H"], call["dw"], call["dh"] = SAWTOOTH_SHAPE
+    elif saw:
+        call["W"], call["H"], call["dw"], call["dh"] = _i(rng, 100, 420), _i(rng, 80, 300), _i(rng, 20, 90), _pick(rng, (33, 65))
+    call["mode"] = _i(rng, 0, 1)
+    call["border"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    call["jobs"] = []
+    for _ in range(n):
+        cls = only if only is not None else "sawtooth" if saw and rng.integers(3) == 0 else "steep" if steep and rng.integers(3) == 0 else None
+        call["jobs"].append(dict(frame=_i(rng, 0, len(call["frames"]) - 1), m=draw_homography(rng, W, H, dw, dh, steep, cls)))
+    if named:
+        call["jobs"][_i(rng, 0, n - 1)]["m"] = nine(SAWTOOTH)
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
+
+
 # ------------------------------------------------------------------------------------------------ whole frames and the way back
 def whole_case(rng):
     """vpf_convert_resize_tensor(_batch): (W, H) -> (dw, dh) drawn like tests/test_gpu_parity.py::test_fuzz_resize_and_fused — a ratio of 0.15 .. 3
@@ -387,4 +541,4 @@ def encode_case(rng):
 
 
 GENERATORS = {"whole": whole_case, "rois": roi_case, "rois_dev": rois_dev_case, "letterbox": letterbox_case, "warp": warp_case, "warp_dev": warp_dev_case,
-              "encode": encode_case}
+              "encode": encode_case, "persp": persp_case}

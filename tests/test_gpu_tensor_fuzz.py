@@ -1,5 +1,5 @@
 """Seeded differential fuzz of the fused tensor entries on the MI355X: vpf_convert_resize_tensor(_batch), vpf_convert_resize_tensor_rois(_dev),
-vpf_convert_letterbox_tensor, vpf_convert_warp_tensor(_dev) and vpf_tensor_convert(_batch).
+vpf_convert_letterbox_tensor, vpf_convert_warp_tensor(_dev), vpf_convert_persp_tensor and vpf_tensor_convert(_batch).
 
 The calls come from tests/cases_tensor_fuzz.py (one description per call, reproducible from the seed and the case index; tests/
 test_tensor_fuzz_cases_cpu.py checks the generator, that the library accepts every call, that both kernel forms of every entry are reached and
@@ -9,15 +9,19 @@ alignments (JobsBuf: TensorBuf / NhwcBuf parts laid over one allocation), so tha
 holds both kernel forms, and the staged dispatch's LDS is the largest of unlike needs.
 
 Ground truth, as in the entries' own tests: the CPU oracle composed as the definition says (roi_reference_u8, letterbox_reference_u8,
-warp_reference_u8, oracle.convert_resize; 16-bit sources narrowed by oracle.convert(P10 | P12 -> NV12) first), then reference_bits; the way back:
+warp_reference_u8, persp_reference_u8, oracle.convert_resize; 16-bit sources narrowed by oracle.convert(P10 | P12 -> NV12) first), then reference_bits; the way back:
 quantise_numpy, then oracle.convert(RGB_PLANAR -> YUV420 -> NV12).  Every written element must be bit-identical (assert_bits: no tolerance), every
 other byte of the buffer must still be the canary, jobs behind a device count must not be written, invalid device entries take the zero / border
-fill, and a device-table call must equal the host-table call on the same jobs.
+fill, and a device-table call must equal the host-table call on the same jobs.  The perspective entry runs every call twice more on the same
+uploads: in its other kernel form (the tuning knob at the other of 0 and 9: the two buffers byte-identical) and, for the jobs whose last row is
+(0, 0, 1), through vpf_convert_warp_tensor at the same planes (the header promises the affine entry's bits).
 
 Seeds: VPF_FUZZ_FIRST / VPF_FUZZ_SEEDS as in tests/test_gpu_parity.py (64 by default; VPF_FUZZ_SEEDS=500 is the soak, profiles/).
 Wall time of the default 64 seeds per function on one MI355X (the sum of pytest --durations over its 64 tests, references on 16 CPU threads
 included; the whole module: 448 passed in 8.6 s; the 500-seed soak: 3500 passed in 47.6 s, profiles/r15_tensor_fuzz_soak.txt):
-  whole_frame_tensor 0.9 s   rois 1.1 s   rois_dev 0.7 s   letterbox 1.1 s   warp 1.5 s   warp_dev 0.7 s   encode 0.6 s"""
+  whole_frame_tensor 0.9 s   rois 1.1 s   rois_dev 0.7 s   letterbox 1.1 s   warp 1.5 s   warp_dev 0.7 s   encode 0.6 s
+With the perspective family (its three calls per case included): persp 1.8 s, the whole module: 512 passed in 10.1 s; the 500-seed soak of
+test_fuzz_persp alone: 500 passed in 19.6 s (profiles/r19_persp_fuzz_soak.txt)."""
 import os
 
 import numpy as np
@@ -107,13 +111,15 @@ def want_of(call, u8):
     return hwc(bits) if call["nhwc"] else bits
 
 
-def host_table_family(capi, orc, family, seed):
-    """whole, rois, letterbox, warp: one call per case into a JobsBuf, every job against its reference"""
+def host_table_family(capi, orc, family, seed, also=None):
+    """whole, rois, letterbox, warp, persp: one call per case into a JobsBuf, every job against its reference; also(call, descs, buf, got, what):
+    further checks of a family on the same uploads"""
     for k, call in enumerate(cases.cases(family, seed)):
         what = f"{family} seed {seed} case {k}"
         srcs, devs = upload_frames(orc, call)
         buf = JobsBuf(call)
-        tuned(capi, call, lambda: invoke(capi, call, capi.make_exec(stream_handle()), [d.desc() for d in devs], buf.buf.data_ptr()))
+        descs = [d.desc() for d in devs]
+        tuned(capi, call, lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, buf.buf.data_ptr()))
         got, intact = buf.frames()
         if family == "whole":
             refs = []
@@ -127,6 +133,8 @@ def host_table_family(capi, orc, family, seed):
             want = refs[job["frame"]] if family == "whole" else want_of(call, job_u8(orc, call, job, rgb[job["frame"]]))
             assert_bits(got[i], want, f"{what} job {i} {job}: {cases.describe(call)}")
         assert intact, f"{what}: bytes outside the jobs' elements were written: {cases.describe(call)}"
+        if also is not None:
+            also(call, descs, buf, got, what)
     forget_p16()
 
 
@@ -212,6 +220,32 @@ def test_fuzz_warp_dev(capi, orc, seed):
     """vpf_convert_warp_tensor_dev: padded matrix tables with NaNs in the padding, a strided frame index, a count, invalid entries (the border in both
     modes), max_step 0 or a true bound"""
     device_table_family(capi, orc, "warp_dev", seed)
+
+
+def persp_other_form_and_affine_entry(capi):
+    def also(call, descs, buf, got, what):
+        other = JobsBuf(call)
+        tuned(capi, dict(call, tune=9 - call["tune"]), lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, other.buf.data_ptr()))
+        assert torch.equal(buf.buf, other.buf), f"{what}: the two kernel forms (tuning knob 0 and 9) differ: {cases.describe(call)}"
+        lifted = [i for i, j in enumerate(call["jobs"]) if tuple(j["m"][6:]) == (0.0, 0.0, 1.0)]
+        if not lifted:
+            return
+        affine = dict(call, entry="warp", jobs=[dict(call["jobs"][i], m=call["jobs"][i]["m"][:6]) for i in lifted])
+        third = JobsBuf(affine)   # the same layout: every job at its own planes, the other jobs' parts stay canary
+        tuned(capi, affine, lambda: invoke(capi, affine, capi.make_exec(stream_handle()), descs, third.buf.data_ptr()))
+        frames, intact = third.frames()
+        for i, f in zip(lifted, frames):
+            assert_bits(got[i], f, f"{what} job {i}: last row (0, 0, 1), vpf_convert_warp_tensor gives other bits: {cases.describe(call)}")
+        assert intact, f"{what}: vpf_convert_warp_tensor on the lifted jobs wrote outside their elements: {cases.describe(call)}"
+    return also
+
+
+@pytest.mark.parametrize("seed", _FUZZ_SEEDS)
+def test_fuzz_persp(capi, orc, seed):
+    """vpf_convert_persp_tensor: lifted affine, moderate and steep homographies, the horizon inside the destination (w exactly 0 on pixels), behind the
+    plane, denormal and tiny w (coordinates of +-inf and above 1e29), footprints wholly outside, cancelling coefficients up to 2^24 and the sawtooth
+    that takes the per-pixel fallback; both border modes; both kernel forms byte-identical; lifted jobs equal to the affine entry"""
+    host_table_family(capi, orc, "persp", seed, persp_other_form_and_affine_entry(capi))
 
 
 def encode_inputs(call):

@@ -7,9 +7,11 @@
   - reach: over the default seeds each kernel form holds at least 10 % of the jobs of every entry that has two forms, decided by the kernels' own
     policy functions behind tests/c/*_capi.cpp (csrc/vpf_job_bounds.h compiled with g++), counted over calls with the tuning knob at 0 only — the
     knob's 9 forces the per-tap form and would make the condition empty; and every source format, dtype, channel order, layout, border mode, a
-    two-table call, a call whose jobs differ in alignment and a unit clamped at the right edge occur per entry;
-  - the independent link: the composed FP32 ground truth of the GPU test (roi_reference_u8, letterbox_reference_u8, warp_reference_u8) against the
-    same composition with every oracle call in EXACT mode, at most 2 codes apart (test_composed_fp32_reference_is_near_the_exact_chain)."""
+    two-table call, a call whose jobs differ in alignment and a unit clamped at the right edge occur per entry; the perspective entry's tile
+    classes, its per-pixel fallback and its dispatches without LDS or without staged jobs besides (persp_reach);
+  - the independent link: the composed FP32 ground truth of the GPU test (roi_reference_u8, letterbox_reference_u8, warp_reference_u8,
+    persp_reference_u8) against the same composition with every oracle call in EXACT mode, at most 2 codes apart
+    (test_composed_fp32_reference_is_near_the_exact_chain)."""
 import ctypes as C
 import os
 import subprocess
@@ -19,6 +21,7 @@ import pytest
 
 import cases_tensor_fuzz as cases
 from test_letterbox_tensor_cpu import letterbox_reference_u8
+from test_persp_tensor_cpu import persp_maps, persp_reference_u8
 from test_roi_tensor_cpu import roi_reference_u8
 from test_tensor_in_cpu import PARAM_SETS as DENORM_SETS
 from test_tensor_in_cpu import denorm_scale_bias_f32
@@ -33,7 +36,7 @@ SEEDS = range(64)        # the default seed set of the GPU test
 SOAK = range(500)        # the soak's seeds (VPF_FUZZ_SEEDS=500): validity and acceptance are checked for these too
 NO_GPU = 1 << 20         # a device index no machine has: a call that passes validation stops at the device switch
 FAKE_DST, FAKE_SRC, FAKE_TABLE = 0x40000000, 0x10000000, 0x70000000
-HOST_TABLE = ("rois", "letterbox", "warp")
+HOST_TABLE = ("rois", "letterbox", "warp", "persp")
 P16 = ("P10", "P12")
 
 
@@ -83,6 +86,9 @@ def invoke(capi, call, ex, srcs, base, tables=None, check=True):
     if entry == "warp":
         arr = capi.make_warps([(srcs[j["frame"]], dst_planes(call, j, base), j["m"]) for j in jobs])
         return capi.convert_warp_tensor(*head, dw, dh, arr, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
+    if entry == "persp":
+        arr = capi.make_persps([(srcs[j["frame"]], dst_planes(call, j, base), j["m"]) for j in jobs])
+        return capi.convert_persp_tensor(*head, dw, dh, arr, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
     planes0, stride = dev_dst(call, base)
     if entry == "rois_dev":
         table = capi.make_rois_dev(tables["boxes"], call["max_n"], planes0, stride, tables["count"], 4 * call["box_ints"])
@@ -186,6 +192,8 @@ def rgb_order(call, triple):
 def job_u8(orc, call, job, rgb):
     """[3, dh, dw] R G B bytes of one job: the composed FP32 reference the GPU tests of the entry use"""
     W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    if "m" in job and len(job["m"]) == 9:
+        return persp_reference_u8(orc, None, call["cs"], call["cr"], W, H, job["m"], dw, dh, rgb_order(call, call["border"]), call["mode"], rgb=rgb)
     if "m" in job:
         return warp_reference_u8(orc, None, call["cs"], call["cr"], W, H, job["m"], dw, dh, rgb_order(call, call["border"]), call["mode"], rgb=rgb)
     if "dst_rect" in job:
@@ -198,11 +206,21 @@ def job_u8_exact(orc, call, job, rgb):
     W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
     if "m" in job:
         packed = np.ascontiguousarray(np.stack(rgb, axis=-1).reshape(H, 3 * W))
-        sx, sy = warp_maps(job["m"], dw, dh, W, H, call["mode"])
-        dst = np.ascontiguousarray(np.broadcast_to(np.asarray(rgb_order(call, call["border"]), np.uint8), (dh, dw, 3)).reshape(dh, 3 * dw))
+        border = rgb_order(call, call["border"])
+        if len(job["m"]) == 9:   # as persp_reference_u8: pixels with !front are out of range (CONSTANT) or any pixel (REPLICATE), the border afterwards
+            sx, sy, front = persp_maps(job["m"], dw, dh, W, H, call["mode"])
+            fill = np.float32(-1 if call["mode"] == 0 else 0)
+            sx, sy = np.ascontiguousarray(np.where(front, sx, fill)), np.ascontiguousarray(np.where(front, sy, fill))
+        else:
+            sx, sy = warp_maps(job["m"], dw, dh, W, H, call["mode"])
+            front = np.ones((dh, dw), bool)
+        dst = np.ascontiguousarray(np.broadcast_to(np.asarray(border, np.uint8), (dh, dw, 3)).reshape(dh, 3 * dw))
         st, out = orc.remap(orc.RGB, W, H, [packed], sx, sy, orc.EXACT, dst=[dst])
         assert st == 0
-        return np.ascontiguousarray(out[0].reshape(dh, dw, 3).transpose(2, 0, 1))
+        out = np.array(out[0].reshape(dh, dw, 3).transpose(2, 0, 1), order="C")
+        for c in range(3):
+            out[c][~front] = border[c]
+        return out
     x, y, w, h = job["rect"]
     ix, iy, iw, ih = job.get("dst_rect", (0, 0, dw, dh))
     out = np.empty((3, dh, dw), np.uint8)
@@ -255,7 +273,7 @@ def test_geometry_and_layouts_are_valid(family):
                 ix, iy, iw, ih = job["dst_rect"]
                 assert iw >= 1 and ih >= 1 and ix >= 0 and iy >= 0 and ix + iw <= dw and iy + ih <= dh, what
             if "m" in job:
-                assert len(job["m"]) == 6 and all(abs(v) <= cases.LIMIT and float(np.float32(v)) == v for v in job["m"]), what
+                assert len(job["m"]) == (9 if family == "persp" else 6) and all(abs(v) <= cases.LIMIT and float(np.float32(v)) == v for v in job["m"]), what
         # include/vpf_hip.h: plane pointers and pitches are multiples of the element size, pitch >= width x element size (3 x: one interleaved plane)
         rb = (3 if call["nhwc"] else 1) * dw * e
         if "jobs" in call:
@@ -326,10 +344,11 @@ def test_every_call_passes_validation(family):
 # ------------------------------------------------------------------------------------------------ reach
 @pytest.fixture(scope="module")
 def bounds(tmp_path_factory):
-    """the four harnesses over csrc/vpf_job_bounds.h in one library, compiled with g++ as they stand"""
+    """the five harnesses over csrc/vpf_job_bounds.h in one library, compiled with g++ as they stand"""
     from conftest import native_test_build
     so = str(tmp_path_factory.mktemp("fuzz_bounds") / "libfuzzbounds.so")
-    srcs = [os.path.join(ROOT, "tests", "c", f) for f in ("job_bounds_capi.cpp", "letterbox_bounds_capi.cpp", "rois_dev_bounds_capi.cpp", "warp_dev_bounds_capi.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "c", f) for f in ("job_bounds_capi.cpp", "letterbox_bounds_capi.cpp", "rois_dev_bounds_capi.cpp", "warp_dev_bounds_capi.cpp",
+                                                            "persp_bounds_capi.cpp")]
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Werror", "-Wno-unused-function", *native_test_build()[0],
                            "-I" + os.path.join(ROOT, "videoprocessingframework_amd", "csrc"), *srcs, "-o", so, "-lm"])
     L = C.CDLL(so)
@@ -343,6 +362,10 @@ def bounds(tmp_path_factory):
     L.rd_box_ok.argtypes, L.rd_box_ok.restype = [C.c_int32] * 5 + [u32] * 3, C.c_int
     L.wd_lds_bytes.argtypes, L.wd_lds_bytes.restype = [C.c_float] + [u32] * 4, u32
     L.wd_largest_tile.argtypes, L.wd_largest_tile.restype = [fp, C.c_int] + [u32] * 4, u32
+    L.pb_strip_max.argtypes, L.pb_strip_max.restype = [], u32
+    L.pb_need.argtypes, L.pb_need.restype = [fp] + [u32] * 4, u32
+    L.pb_tiles.argtypes, L.pb_tiles.restype = [fp, C.c_int] + [u32] * 4 + [C.c_void_p, u32], u32
+    L.pb_px_in_window.argtypes, L.pb_px_in_window.restype = [u32] * 4 + [C.c_void_p] * 2 + [u32] * 3 + [C.c_void_p], None
     return L
 
 
@@ -365,6 +388,8 @@ def job_forms(L, call, job):
         n = L.rd_tiles(x, w, h, dw, dh, L.rd_lds_bytes(dw, dh), nbytes, convs, flags)
         assert 1 <= n <= n_tiles - 8
         return {"staged" if flags[t] else "per_tap" for t in range(n)}
+    if call["entry"] == "persp":
+        return {"staged" if L.pb_need((C.c_float * 9)(*job["m"]), W, H, dw, dh) <= L.pb_strip_max() else "per_tap"}
     m = (C.c_float * 6)(*job["m"])
     if call["entry"] == "warp":
         return {"staged" if L.jb_warp_need(m, W, H, dw, dh) <= L.jb_warp_strip_max() else "per_tap"}
@@ -379,9 +404,82 @@ def reaches_right_edge(call, job):
         return False
     if "rect" in job:
         return job["rect"][0] + job["rect"][2] == W
-    sx, sy = warp_maps(job["m"], call["dw"], call["dh"], W, H, call["mode"])
-    inside = (sx >= 0) & (sx <= np.float32(W - 1)) & (sy >= 0) & (sy <= np.float32(H - 1))
+    if len(job["m"]) == 9:
+        sx, sy, front = persp_maps(job["m"], call["dw"], call["dh"], W, H, call["mode"])
+    else:
+        (sx, sy), front = warp_maps(job["m"], call["dw"], call["dh"], W, H, call["mode"]), True
+    inside = front & (sx >= 0) & (sx <= np.float32(W - 1)) & (sy >= 0) & (sy <= np.float32(H - 1))
     return bool((inside & (sx >= np.float32(W - 2))).any())
+
+
+PERSP_BORDER, PERSP_TAP, PERSP_OUT, PERSP_STAGE = 0, 1, 2, 3   # kPerspTile* of csrc/vpf_job_bounds.h
+
+
+def persp_tables(L, call):
+    """the launcher's split restated (vpf_convert_persp_tensor's chunks, split_jobs of csrc/k_job_launch.h, launch_convert_persp): jobs in chunks of
+    82; per chunk the staged jobs are those with pb_need <= pb_strip_max() and the dispatch's LDS is the largest such need
+    -> [(staged jobs, LDS bytes, per-tap jobs)] under the default policy"""
+    W, H, dw, dh, cap = call["W"], call["H"], call["dw"], call["dh"], L.pb_strip_max()
+    out = []
+    for at in range(0, len(call["jobs"]), cases.TABLE["persp"]):
+        chunk = call["jobs"][at:at + cases.TABLE["persp"]]
+        needs = [L.pb_need((C.c_float * 9)(*j["m"]), W, H, dw, dh) for j in chunk]
+        out.append(([j for j, n in zip(chunk, needs) if n <= cap], max([n for n in needs if n <= cap], default=0), [j for j, n in zip(chunk, needs) if n > cap]))
+    return out
+
+
+def persp_reach(L):
+    """what the perspective family must reach beyond the two dispatches: every tile class of the staged kernel, a staged tile whose strip exceeds the
+    LDS of its dispatch, the per-pixel fallback on a truly staged tile, a staged dispatch without LDS, a table of per-tap jobs only, w exactly 0 and
+    an infinite coordinate — decided by the kernel's own functions (tests/c/persp_bounds_capi.cpp), on the calls with the tuning knob at 0"""
+    calls_with = {c: 0 for c in (PERSP_BORDER, PERSP_TAP, PERSP_OUT, PERSP_STAGE)}
+    out_under_constant = over_lds = fallback_calls = fallback_px = no_lds = per_tap_only = zero_w = infinite = 0
+    for seed, k, call in all_cases("persp"):
+        W, H, dw, dh, mode = call["W"], call["H"], call["dw"], call["dh"], call["mode"]
+        for job in call["jobs"]:
+            m = np.asarray(job["m"], np.float32)
+            dx, dy = np.arange(dw, dtype=np.float32)[None, :], np.arange(dh, dtype=np.float32)[:, None]
+            zero_w += bool((((m[6] * dx + m[7] * dy) + m[8]) == 0).any())
+            sx, sy, _ = persp_maps(job["m"], dw, dh, W, H, 0)
+            infinite += bool(np.isinf(sx).any() or np.isinf(sy).any())
+        if call["tune"] != 0:
+            continue
+        classes, over, flagged = set(), False, 0
+        for staged, lds, per_tap in persp_tables(L, call):
+            no_lds += bool(staged) and lds == 0
+            per_tap_only += bool(per_tap) and not staged
+            for job in staged:
+                m = (C.c_float * 9)(*job["m"])
+                tiles = np.zeros((((dw + 31) // 32) * ((dh + 31) // 32), 10), np.uint32)
+                assert L.pb_tiles(m, mode, W, H, dw, dh, tiles.ctypes.data, len(tiles)) == len(tiles)
+                sx, sy, front = persp_maps(job["m"], dw, dh, W, H, mode)
+                inr = front & (sx >= 0) & (sx <= np.float32(W - 1)) & (sy >= 0) & (sy <= np.float32(H - 1))
+                for xs, ys, xe, ye, cls, x_lo, x_hi, y_lo, y_hi, nbytes in tiles.tolist():
+                    classes.add(cls)
+                    if cls != PERSP_STAGE:
+                        continue
+                    if nbytes > lds:   # the kernel's `S.bytes > lds_bytes`: this tile samples per tap
+                        over = True
+                        continue
+                    ii = inr[ys:ye + 1, xs:xe + 1]
+                    xa = np.ascontiguousarray(sx[ys:ye + 1, xs:xe + 1][ii].astype(np.uint32))
+                    ya = np.ascontiguousarray(sy[ys:ye + 1, xs:xe + 1][ii].astype(np.uint32))
+                    ok = np.empty(len(xa), np.uint8)
+                    L.pb_px_in_window(x_lo, x_hi, y_lo, y_hi, xa.ctypes.data, ya.ctypes.data, len(xa), W, H, ok.ctypes.data)
+                    flagged += int((ok == 0).sum())
+        for c in classes:
+            calls_with[c] += 1
+        out_under_constant += PERSP_OUT in classes and mode == 0
+        over_lds += over
+        fallback_calls += flagged > 0
+        fallback_px += flagged
+    print("persp calls whose staged dispatches hold a tile of class border / tap / out / stage", [calls_with[c] for c in (0, 1, 2, 3)], "out under CONSTANT",
+          out_under_constant, "a staged tile over the dispatch's LDS", over_lds, "the per-pixel fallback on a staged tile: calls", fallback_calls, "pixels", fallback_px,
+          "tables: a staged dispatch with 0 bytes of LDS", no_lds, "per-tap jobs only", per_tap_only, "jobs with w == 0 on a pixel", zero_w,
+          "with an infinite coordinate", infinite)
+    assert all(n >= 5 for n in calls_with.values()) and out_under_constant >= 1, (calls_with, out_under_constant)
+    assert over_lds >= 3 and fallback_calls >= 3 and fallback_px >= 20, (over_lds, fallback_calls, fallback_px)
+    assert no_lds >= 1 and per_tap_only >= 1 and zero_w >= 1 and infinite >= 1, (no_lds, per_tap_only, zero_w, infinite)
 
 
 @pytest.mark.parametrize("family", [f for f in cases.FAMILIES if f not in ("whole", "encode")])
@@ -415,8 +513,10 @@ def test_reach(bounds, family):
     assert seen["sf"] == set(cases.SOURCES) and seen["dtype"] == {0, 1, 2} and seen["bgr"] == {False, True} and seen["nhwc"] == {False, True}, seen
     assert seen["tune"] == {0, 9}, seen
     assert right_edge >= 1
-    if family in ("warp", "warp_dev"):
+    if family in ("warp", "warp_dev", "persp"):
         assert seen["mode"] == {0, 1}, seen
+    if family == "persp":
+        persp_reach(bounds)
     if family in HOST_TABLE:
         assert two_tables >= 1 and mixed_alignment >= 1
     else:
@@ -449,7 +549,7 @@ def test_composed_fp32_reference_is_near_the_exact_chain(oracle, family):
     in the oracle's EXACT mode — convert EXACT, crop, resize or remap EXACT with the same float32 maps — at most 2 codes apart: the conversions
     differ by at most 1 (tests/test_oracle_kat.py), a bilinear blend is a convex combination and carries that 1 through unamplified, and the
     fp32 blend against the exact blend of equal inputs adds at most 1.
-    Measured maximum over these cases: rois 1, letterbox 1, warp 1 (the bound stays 2)."""
+    Measured maximum over these cases: rois 1, letterbox 1, warp 1, persp 1 (the bound stays 2)."""
     oracle.set_threads(16)
     worst = n = 0
     for seed, k, call in all_cases(family):
