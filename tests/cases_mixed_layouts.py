@@ -244,8 +244,8 @@ def odd_turns(planes, shapes, frames, ladder_of):
 
 
 def _resize_flag_only(fmt, interp, shape, side, n):
-    """a destination plane decides the kernel only where the kernel's stores need it: the exact-2x kernels (planes_aligned(.., 7, 3 | 7) and
-    (.., 15, 15) of launch_resize_jobs) and the matrix-core Lanczos kernel (16-B rows on both sides; one frame per dispatch takes the tile
+    """a destination plane decides the kernel only where the kernel's stores need it: the exact-2x kernels (the `aligned(p, 7, 3 | 7)` and
+    `aligned(p, 15, 15)` tests of `resize_plan`, csrc/vpf_resize_plan.h) and the matrix-core Lanczos kernel (16-B rows on both sides; one frame per dispatch takes the tile
     kernel, whose stores do not).  Everywhere else the gate of a destination plane sets the runtime flag vec_ok of the same kernel, so the
     reach test asserts no change of kernel there."""
     if side == "src":
@@ -272,7 +272,7 @@ def _resize_directed(key):
         shape = ("2x", "down")[turn % 2]
         out.append(one_odd(call(shape, n), side, pos, k, min_rung(e)[-1], flag_only=_resize_flag_only(fmt, interp, shape, side, n)))
     if len(planes) > 2:
-        # the per-plane fallbacks of launch_resize_jobs: only the last SOURCE plane odd, in a batch of two
+        # the per-plane fallbacks of launch_resize_planned: only the last SOURCE plane odd, in a batch of two
         out.append(one_odd(call("down", 2), "src", 1, len(planes) // 2 - 1, "A1"))
         for (ww, hh, dw, dh) in ((227, 227, 113, 113), (225, 15, 150, 10)):
             out.append(stacked(_call("resize", "batch", 2, FMT[fmt], FMT[fmt], ww, hh, dw, dh, interp=interp, shape="odd", seed=200)))

@@ -219,7 +219,7 @@ def test_reach_of_the_cases():
       itself: the log of the uniform call under the forced-generic tuning value 9;
     - per entry and format family (resize: per filter) some (O) case leaves the uniform call's kernel, wherever there is one to leave;
     - Lanczos NV12 with only the UV source plane odd: the matrix-core kernel AND a gather launch (the per-plane fallback of
-      launch_resize_jobs); bilinear YUV420 with one odd chroma plane: more than one launch where the uniform call makes one."""
+      launch_resize_planned); bilinear YUV420 with one odd chroma plane: more than one launch where the uniform call makes one."""
     code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, VPF_HIP_LOG="2"), timeout=600)
     assert r.returncode == 0 and "done" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

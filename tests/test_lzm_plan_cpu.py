@@ -203,7 +203,7 @@ def test_planner_on_one_down_scaled_frame_per_dispatch(lzp):
     regrets = []
     for (fmt, sw, sh, dw, dh), res in lone_sweep_lines("r06_p_lone_downscales.txt").items():
         if fmt == "Y" and dw == 1920:
-            continue   # (one such plane per dispatch goes to the tile kernel by policy: launch_resize, not this planner)
+            continue   # (one such plane per dispatch goes to the tile kernel by policy: resize_plan, not this planner)
         p = plan(lzp, planes_of(fmt, sw, sh, dw, dh), 1)
         regrets.append(res[(p["nt"], p["r"])] / min(res.values()) - 1.0)   # (the pick itself was measured)
         assert regrets[-1] <= 0.13, (fmt, sw, dw, p)

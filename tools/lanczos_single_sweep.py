@@ -1,6 +1,6 @@
 """One Lanczos resize dispatch per frame (what an unmodified PySurfaceResizer.Execute loop issues): the matrix-core kernel (VPF_TUNE_RESIZE_MFMA
 0x800 / 0x400 forced) against the tile kernel (1 = matrix-core kernel off) and the policy (0), over source sizes and scale factors, RGB and Y.
-Rings past the Infinity Cache, medians of three passes.  The launch policy's single-frame rule (k_resize.hip: launch_resize) is fitted to this
+Rings past the Infinity Cache, medians of three passes.  The launch policy's single-frame rule (vpf_resize_plan.h: lanczos_single_prefers_tile) is fitted to this
 table.  python tools/lanczos_single_sweep.py"""
 import os, sys
 import torch

@@ -39,7 +39,7 @@ VPF_DEV float bilerp(float p00, float p01, float p10, float p11, float fx, float
   return __builtin_fmaf(fy, bot - top, top) + 0.5f;
 }
 
-constexpr uint32_t kResizeRowBytes = 4096;  // largest strip (IT = 4 dense 1-KiB loads per source row)
+// (kResizeRowBytes = 4096, the largest strip — IT = 4 dense 1-KiB loads per source row: vpf_classes.h)
 // The strips live in dynamic LDS sized for THIS launch's scale factor (strip bytes = span rounded up to 256):
 // a 3x down-scale of packed RGB needs 2.5 KiB per row instead of the 4 KiB worst case, so 8 workgroups fit a CU
 // instead of 5 and the load latency of one wave hides behind the arithmetic of more neighbours.
@@ -249,7 +249,7 @@ VPF_DEV void store_blend4(uint8_t* out, const float* o, bool vec4, uint32_t nv /
   }
 }
 
-constexpr int kBandSlots = 8;  // source rows a wave's strips can hold (twice as many when a strip is a single 1-KiB staging pass: IT = 1)
+// (kBandSlots = 8 source rows a wave's strips can hold, twice as many when a strip is a single 1-KiB staging pass, IT = 1: vpf_classes.h)
 // Horizontal lerps of one strip row for a lane's PX pixels, kept as PIXEL PAIRS: H[j * CH + c] = {pixel 2j, pixel 2j + 1} of channel c — the
 // operand layout of v_pk_fma_f32, so the vertical blend consumes the pairs as they are (a pixel-major array in between cost 8 v_mov per
 // row and lane and turned the vertical subtractions into scalar ones).
@@ -406,13 +406,8 @@ VPF_DEV void band_blend_rows(const uint8_t* strips, uint32_t rowbytes, uint32_t 
   band_blend_rows<CH, R, PX>(strips, rowbytes, r_lo, ya, yb, rows, T, w, static_cast<Put&&>(put));
 }
 
-// strip bytes a wave needs for the source span of its `cols` destination columns (vpf_bound_strip_bytes, checked on the CPU);
-// 0 when the LDS path does not apply (forced generic, unaligned source, span above the cap)
-static inline uint32_t lds_strip_bytes(int ch, uint32_t sw, uint32_t dw, const void* src, uint32_t sp, uint32_t row_bytes_cap, uint32_t cols = 256) {
-  if (tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9) return 0;  // forced generic
-  if (((uintptr_t)src | sp) & 15) return 0;
-  return vpf_bound_strip_bytes(ch, sw, dw, row_bytes_cap, cols);
-}
+// (strip bytes a wave needs for the source span of its destination columns, and where the LDS path does not apply — forced generic, unaligned
+// source, span above the cap: vpf_bound_strip_bytes under the alignment tests of vpf_resize_plan.h and vpf_fused_plan.h)
 
 }  // namespace vpf
 #endif  // VPF_K_BILINEAR_BLEND_H_

@@ -1,5 +1,5 @@
 // k_job_launch.h — the host side the fused tensor launchers share (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip,
-// their device-table forms, launch_tensor_to_yuv and the whole-frame launch_convert_resize): the argument check, the destination alignment mask, the run-time -> template-argument
+// their device-table forms, launch_tensor_to_yuv, the whole-frame launch_convert_resize and the plain launch_resize_planned): the argument check, the destination alignment mask, the run-time -> template-argument
 // dispatch, the launch of the instantiation it picked and the split of a host job table into its staged and its per-tap dispatch.  Inline functions, function templates over
 // callables and two launch macros: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
 #ifndef VPF_K_JOB_LAUNCH_H_
@@ -56,20 +56,26 @@ template <class T> struct TableName {};  // a frame table as a template argument
 template <int CAP> inline int put_targ(char* p, size_t n, TableName<BatchArgsT<CAP>>) { return std::snprintf(p, n, "BatchArgsT<%d>, ", CAP); }
 template <int CAP> inline int put_targ(char* p, size_t n, TableName<BatchArgsTE<CAP>>) { return std::snprintf(p, n, "BatchArgsTE<%d>, ", CAP); }
 template <class T, T V> inline int put_targ(char* p, size_t n, std::integral_constant<T, V>) { return put_targ(p, n, V); }
+// (`family` may open a template-id of its own, the task a generic kernel runs — "k_plane_batch<TileTaskF32": every bracket it opens is closed behind the arguments)
 template <class... T>  // T: std::integral_constant<int or bool, ...>, TableName<...>
 inline void note_instantiation(const char* family, T... targs) {
   char label[96];
   size_t o = (size_t)std::snprintf(label, sizeof(label), "(%s<", family);
   ((o += (size_t)put_targ(label + o, sizeof(label) - o, targs)), ...);
-  std::snprintf(label + o - 2, sizeof(label) - o + 2, ">)");  // (over the last ", ")
+  o -= 2;  // (over the last ", ")
+  for (const char* c = family; *c && o + 3 < sizeof(label); c++)
+    if (*c == '<') label[o++] = '>';
+  std::snprintf(label + o, sizeof(label) - o, ">)");
   note_kernel(label);
 }
 #define VPF_TARGS(...) __VA_ARGS__
-#define VPF_LAUNCH_T(K, TARGS, GRID, LDS, ST, ...)                                                         \
+#define VPF_LAUNCH_T(K, TARGS, GRID, LDS, ST, ...) VPF_LAUNCH_TN(K, TARGS, GRID, dim3(256), LDS, ST, __VA_ARGS__)
+// ... with the workgroup size as an argument (the tiled resize kernels: 64 lanes x waves per workgroup)
+#define VPF_LAUNCH_TN(K, TARGS, GRID, BLOCK, LDS, ST, ...)                                                 \
   do {                                                                                                     \
     if (vpf::log_level() >= 2 || vpf::trace_on()) vpf::note_instantiation(#K, VPF_TARGS TARGS);            \
     (void)hipGetLastError(); /* (sticky per thread: see VPF_LAUNCH) */                                     \
-    hipLaunchKernelGGL((K<VPF_TARGS TARGS>), GRID, dim3(256), LDS, ST, __VA_ARGS__);                       \
+    hipLaunchKernelGGL((K<VPF_TARGS TARGS>), GRID, BLOCK, LDS, ST, __VA_ARGS__);                           \
   } while (0)
 // ... for the kernels whose LAST template argument is the type of their first argument, the frame table (with_frame_table below):
 // VPF_LAUNCH_TB(k_convert_strip_wg, (S, D, R), table, grid, lds, st, c, ...) launches and logs "(k_convert_strip_wg<0, 8, 2, BatchArgsTE<32>>)"
@@ -106,6 +112,10 @@ inline void with_rows(int r, F&& f) {
   else if (r == R0) f(std::integral_constant<int, R0>{});
   else with_rows<RS...>(r, f);
 }
+// ... under a neutral name for values that are no band heights: the plain resize dispatch (k_resize.hip) picks channel counts, staging passes,
+// waves per workgroup and filters with it — with_value<1, 2, 3>(ch, f), with_value<8, 4>(wpb, f); f(V), the last one for any other value
+template <int... VS, class F>
+inline void with_value(int v, F&& f) { with_rows<VS...>(v, f); }
 // f(table, lds): the frame table a batch kernel of destination class DST takes for the first n frames of `a` — BatchArgs / BatchArgsL for the
 // 8-bit classes, for the tensor classes BatchArgsTE<32> / <128> (entries up to the next multiple of 8 are defined, vpf_abi.hip) with the
 // epilogue behind it — and the dynamic LDS to ask for: the kernel's own `lds`, plus where an FC_TENSOR_NHWC launch has room the staging area

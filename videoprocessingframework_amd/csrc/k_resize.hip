@@ -5,7 +5,8 @@
 // src/TC/src/Tasks.cpp:1162-1203,1217-1261) and nppiResize_32f_C3R / _C1R (:1334-1445).  The reference resizer asks NPP for
 // Lanczos (:1190), which is the Task layer's default here too (north_star benchmarks bilinear: VPF_INTERP_LINEAR).
 //
-// Kernel families; within a filter all are bit-identical to one another (launch_resize / launch_resize_jobs pick):
+// Kernel families; within a filter all are bit-identical to one another (resize_plan, vpf_resize_plan.h, picks; launch_resize_planned at the
+// end of this file dispatches on its answer):
 //   GatherTask, LanczosGatherTask, FloatGatherTask   gather forms: any size / alignment
 //   RowPairTask (k_resize_lds)    a wave stages the two source rows it needs in wave-private LDS strips (dynamic LDS sized per scale
 //                                 factor) and picks taps from LDS; taps with weight exactly 0 are skipped
@@ -24,8 +25,11 @@
 #include <cstring>
 
 #include <type_traits>
+#include <utility>
 
+#include "k_job_launch.h"
 #include "k_resize_common.h"
+#include "vpf_resize_plan.h"
 #ifdef VPF_LAB_FORMS
 #include "vpf_persist.h"
 #endif
@@ -289,7 +293,7 @@ VPF_DEV void RowPairTask<CH, IT>::run(const uint8_t* __restrict__ src, uint32_t 
 // ------------------------------------------------------------------------------------------
 // destination pixels per lane: 4, or 8 = 512 columns per wave on 1-channel planes in the `P1 = 8` instantiations (a wave's per-row fixed
 // work is the same whatever the channel count; the launcher picks them when 512-column chunks fill the planes' rows well)
-constexpr int band_px(int ch, int p1) { return ch == 1 ? p1 : 4; }
+// (band_px: vpf_classes.h)
 template <int CH, int R, int IT = 2 /* 1-KiB staging passes per strip */, int P1 = 4 /* pixels per lane on 1-channel planes */, bool MULTI = false /* several bands per wave */>
 struct RowBandTask {
   static constexpr int kThreads = 256;
@@ -505,9 +509,7 @@ VPF_DEV void RowBandTask<CH, R, IT, P1, MULTI>::run_chunks(BandChunk& c, Stream&
 // the duration of a single-frame launch (one round of workgroups, each a chain of dependent steps) is made of.
 // TileTaskF32 below is the same tiling for float surfaces (bilinear and Lanczos-3).
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kLzStripQ = 128;  // at most 2 KiB of source bytes per row of a tile
-
-constexpr int kTileStagePasses = 6;  // staging loads a thread may have in flight (the launcher sizes tiles accordingly)
+// (kLzStripQ = 128: at most 2 KiB of source bytes per row of a tile; kTileStagePasses = 6 staging loads a thread may have in flight: vpf_classes.h)
 
 template <int CH, int WPB>
 struct TileTask {
@@ -791,7 +793,7 @@ __global__ __launch_bounds__(64 * WPB) void k_resize_tile(const uint8_t* __restr
 // ------------------------------------------------------------------------------------------
 // Tiled, separable 8-bit LANCZOS-3 for what the matrix-core kernel (k_lanczos_mfma.hip) does not take: packed RGB beyond ~6 x and any plane
 // beyond ~10 x across / ~6 x down (its tap windows and its four-tile ring end there), and ONE small frame per dispatch, where this kernel's
-// short waves finish sooner than that kernel's latency chain (lanczos_single_prefers_tile, launch_resize_jobs).
+// short waves finish sooner than that kernel's latency chain (lanczos_single_prefers_tile and the 1-MB rule of resize_plan, vpf_resize_plan.h).
 // Same integer filter definition as that kernel, the gather kernel and the oracle: exact Q14 horizontal sums,
 // Hr = (H + 128) >> 8, vertical taps on byte-wide partial products with clamped taps merged per source row.  A workgroup of WPB waves owns
 // a tile of 64 columns x TY rows:
@@ -1108,165 +1110,6 @@ VPF_DEV void Half3R16Task::run(const uint8_t* __restrict__ src, uint32_t sp, uin
   }
 }
 
-// Shape of a tiled launch: destination rows per tile (ty) and waves per workgroup (wpb).  A taller tile computes fewer horizontal dots per
-// destination pixel ((ty - 1) scy + taps + 2 source rows for ty destination rows) but there are fewer of them to fill the chip with.
-// Rule read off rocprofv3 kernel durations over (ty, wpb) for six size pairs (profiles/r02_tile_shape_sweep.txt): 8 waves per workgroup
-// always (each wave walks fewer source rows one after the other), and the TALLEST tile that fits LDS and still leaves >= ~900 workgroups
-// (about one full round of the chip at 4 workgroups per CU) — e.g. 1080p -> 720p: ty 16 (900 workgroups, 7.5 us; ty 32: 7.7, ty 8: 9.7),
-// 720p -> 1080p: ty 32 (7.2 us; ty 64: 9.4), 1080p -> 4K: ty 64 (15.5 us; ty 32: 18.9), batches: the tallest that fits.
-// VPF_TUNE_RESIZE_TILE overrides the choice for such sweeps (ty | wpb << 8) — every shape writes the same pixels.
-struct TileShape { bool ok; uint32_t ty, nr, lds, rowq, lshift; int wpb; };
-static TileShape plan_tile(bool lz, int np, const int* ch, const uint32_t* dw, const uint32_t* dh, const float* scxs, const float* scys, uint32_t frames,
-                           int elem = 1 /* bytes per sample: 1, or 4 for float surfaces */) {
-  TileShape best{false, 0, 0, 0, 0, 0, 4};
-  int ch_max = 0;
-  uint32_t rowq = 0;  // 16-B units a tile row can span (+ alignment slack), the widest plane decides
-  float scy = 0.f;
-  for (int p = 0; p < np; p++) {
-    ch_max = ch[p] > ch_max ? ch[p] : ch_max;
-    const uint32_t q = vpf_bound_tile_rowq(scxs[p], lz ? 6 : 2, ch[p], elem);  // (8-bit Lanczos: + pad unit + right margin; vpf_plan_bounds.h)
-    rowq = q > rowq ? q : rowq;
-    scy = scys[p] > scy ? scys[p] : scy;
-  }
-  if (rowq > kLzStripQ * (uint32_t)elem || scy > 48.0f) return best;
-  uint32_t lshift = 0;
-  while ((1u << lshift) < rowq) lshift++;
-  const int forced = tuning(VPF_TUNE_RESIZE_TILE);
-  uint32_t best_wgs = 0;
-  for (int wpb = forced ? 4 : 8; wpb <= 8; wpb += 4)
-    for (uint32_t ty = forced ? 4 : 8; ty <= 64; ty += 4) {
-      if (forced && ((uint32_t)(forced & 0xff) != ty || (forced >> 8) != wpb)) continue;
-      const uint32_t nr = vpf_bound_tile_rows(ty, scy, lz ? 6 : 2);
-      const uint32_t lds = nr * rowq * 16 + nr * ch_max * 64 * 4 + ty * 8 * 4 + (lz ? (elem == 4 ? 7 : 4) * 64 * 4 : 0);  // RAW | H | WY | WX (Lanczos)
-      if (lds > 64u * 1024u) continue;
-      const uint32_t srows = (64u * wpb) >> lshift;  // source rows staged per pass
-      if (!srows || (elem == 1 && (nr + srows - 1) / srows > (uint32_t)kTileStagePasses)) continue;  // (the float task stages in rounds)
-      double wgs = 0;
-      for (int p = 0; p < np; p++) wgs += (double)((dw[p] + 63) / 64) * ((dh[p] + ty - 1) / ty);
-      wgs *= frames;
-      const uint32_t w = wgs > 4e9 ? 0xffffffffu : (uint32_t)wgs;
-      // candidates come in order of growing ty: take a taller tile while it still leaves >= 900 workgroups; below that, the most workgroups win
-      if (!best.ok || w >= 900u || w > best_wgs) { best = TileShape{true, ty, nr, lds, rowq, lshift, wpb}; best_wgs = w; }
-    }
-  return best;
-}
-
-// tiled separable launch of ONE plane of ONE frame (bilinear up-scales, where the horizontal lerp is shared by several destination
-// rows): needs 16-B aligned source rows and a 64-column span that fits the 2-KiB strip.  Returns false when it does not apply.
-static bool launch_resize_tile(hipStream_t st, int ch, uint32_t sw, uint32_t sh, const uint8_t* src, uint32_t sp,
-                               uint32_t dw, uint32_t dh, uint8_t* dst, uint32_t dp, float scx, float scy) {
-  if (tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 || (((uintptr_t)src | sp) & 15)) return false;
-  const TileShape t = plan_tile(false, 1, &ch, &dw, &dh, &scx, &scy, 1);
-  if (!t.ok) return false;
-  dim3 tgrid((dw + 63) / 64, (dh + t.ty - 1) / t.ty);
-  const int vec_ok = ((((uintptr_t)dst | dp) & 3) == 0) && (ch != 2 || (((uintptr_t)dst | dp) & 7) == 0);
-#define VPF_TILE3(C, W) VPF_LAUNCH((k_resize_tile<C, W>), tgrid, dim3(64 * W), t.lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, t.ty, t.nr, t.rowq, t.lshift, vec_ok)
-#define VPF_TILE(C) do { if (t.wpb == 8) VPF_TILE3(C, 8); else VPF_TILE3(C, 4); } while (0)
-  if (ch == 1) VPF_TILE(1); else if (ch == 2) VPF_TILE(2); else VPF_TILE(3);
-#undef VPF_TILE
-#undef VPF_TILE3
-  return true;
-}
-
-// ONE plane of ONE frame per dispatch (what an unmodified PySurfaceResizer.Execute loop issues): the matrix-core Lanczos kernel's waves are
-// few and long — operand tables, a ring to fill, two passes — and a lone launch of them is one latency chain of 5-6 us whatever the picture;
-// the tile kernel's waves are short and many, so a small single frame leaves it sooner although its throughput is 2.5x lower.  The tile
-// kernel's time grows with the DESTINATION (taps per output sample), the matrix-core kernel's with the source: over 63 measured shapes
-// (tools/lanczos_single_sweep.py, profiles/r04_lanczos_single_sweep.txt: RGB 1080p -> 720p 6.9 against 8.9 us, Y 4.7 against 6.9) the rule
-// "source bytes / 2 + 3 x destination bytes below 25.5 MB (3 channels) / 14 MB (1 channel)" picks the faster kernel but for 1 us summed over
-// all of them.  Same bytes either way (both kernels are the integer definition of the filter).  VPF_TUNE_RESIZE_MFMA | 0x40000, or a forced
-// launch shape: always the matrix-core kernel.
-static bool lanczos_single_prefers_tile(int ch, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh) {
-  if (tuning(VPF_TUNE_RESIZE_MFMA) & 0xfffff) return false;
-  const uint64_t src_b = (uint64_t)sw * sh * (uint32_t)ch, dst_b = (uint64_t)dw * dh * (uint32_t)ch;
-  return src_b + 6u * dst_b <= (ch == 1 ? 28000000ull : ch == 2 ? 40000000ull : 51000000ull);
-}
-
-hipError_t launch_resize(hipStream_t st, int ch, int interp, uint32_t sw, uint32_t sh, const uint8_t* src,
-                         uint32_t sp, uint32_t dw, uint32_t dh, uint8_t* dst, uint32_t dp) {
-  const float scx = (float)sw / (float)dw, scy = (float)sh / (float)dh;
-  const int vec_ok = ((((uintptr_t)dst | dp) & 3) == 0) && (ch != 2 || (((uintptr_t)dst | dp) & 7) == 0);
-  // Odd integer scale factors on both axes: s = (d + 0.5) k - 0.5 = k d + (k - 1) / 2 exactly, every destination centre is
-  // a source pixel centre, so the bilinear fractions are 0 and the Lanczos weights are (0, 0, 1, 0, 0, 0): both filters return
-  // that source pixel unchanged, which is also what NEAREST picks (floor((d + 0.5) k) = k d + (k - 1) / 2).  Identical
-  // bytes from the cheapest kernel (the tiled kernels were tried with per-tap zero-weight skipping instead: 10 us for
-  // Lanczos 4K -> 720p but 30-45 % slower on every other ratio).  Bilinear keeps its row-pair LDS kernel, whose own
-  // zero-weight shortcuts make it as fast there (kernel durations 5.1 vs 5.5 us at 4K -> 720p).
-  if (interp == VPF_INTERP_LANCZOS3 && sw % dw == 0 && sh % dh == 0 && ((sw / dw) & 1) && ((sh / dh) & 1) && sw < (1u << 22) && sh < (1u << 22) &&
-      tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9)
-    interp = VPF_INTERP_NEAREST;
-  // exact 2x bilinear: the quad-structured streaming kernel
-  if (interp == VPF_INTERP_LINEAR && sw == 2 * dw && sh == 2 * dh && dw % 4 == 0 && !(((uintptr_t)src | sp) & 7) &&
-      !(((uintptr_t)dst | dp) & (ch == 2 ? 7 : 3)) && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9) {
-    if (ch == 3 && sw % 32 == 0 && !(((uintptr_t)src | sp | (uintptr_t)dst | dp) & 15)) {
-      const uint32_t chunks = (sw + 1023) / 1024, tasks = chunks * dh;
-      VPF_LAUNCH(k_resize_half3_r16, dim3((tasks + 3) / 4), dim3(256), 0, st, src, sp, dst, dp, sw, chunks, tasks);
-      return hipGetLastError();
-    }
-    dim3 hgrid((dw / 4 + 63) / 64, (dh + 3) / 4);
-    if (ch == 1) VPF_LAUNCH((k_resize_half<1>), hgrid, dim3(256), 0, st, src, sp, dst, dp, dw, dh);
-    else if (ch == 2) VPF_LAUNCH((k_resize_half<2>), hgrid, dim3(256), 0, st, src, sp, dst, dp, dw, dh);
-    else VPF_LAUNCH((k_resize_half<3>), hgrid, dim3(256), 0, st, src, sp, dst, dp, dw, dh);
-    return hipGetLastError();
-  }
-  if (interp == VPF_INTERP_LANCZOS3) {
-    // the matrix-core kernel (k_lanczos_mfma.hip) wherever its windows fit; the tiled separable form for strong down-scales (beyond those
-    // windows) — and, tried FIRST, for one small plane per dispatch (lanczos_single_prefers_tile below); the gather form for what is left
-    auto mfma = [&]() -> bool {
-      BatchArgsL a;  // (host side only: one frame is launched with the small table)
-      std::memset(&a.f[0], 0, sizeof(a.f[0]));
-      a.f[0].s[0] = src; a.f[0].sp[0] = sp; a.f[0].d[0] = dst; a.f[0].dp[0] = dp;
-      const ResizeJob j{ch, 0, sw, sh, dw, dh};
-      return launch_lanczos_mfma(st, 1, &j, 1, a);
-    };
-    auto tile = [&]() -> bool {
-      if (tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 || tuning(VPF_TUNE_NV12_RGB_VARIANT) == 40 || (((uintptr_t)src | sp) & 15)) return false;
-      const TileShape t = plan_tile(true, 1, &ch, &dw, &dh, &scx, &scy, 1);
-      if (!t.ok) return false;
-      const dim3 tgrid((dw + 63) / 64, (dh + t.ty - 1) / t.ty);
-#define VPF_LZT3(C, W) VPF_LAUNCH((k_resize_lztile<C, W>), tgrid, dim3(64 * W), t.lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, t.ty, t.nr, t.rowq, t.lshift, vec_ok)
-#define VPF_LZT(C) do { if (t.wpb == 8) VPF_LZT3(C, 8); else VPF_LZT3(C, 4); } while (0)
-      if (ch == 1) VPF_LZT(1); else if (ch == 2) VPF_LZT(2); else VPF_LZT(3);
-#undef VPF_LZT
-#undef VPF_LZT3
-      return true;
-    };
-    if (lanczos_single_prefers_tile(ch, sw, sh, dw, dh) ? (tile() || mfma()) : (mfma() || tile())) return hipGetLastError();
-    dim3 lgrid((dw + 63) / 64, (dh + 3) / 4);
-    if (ch == 1) VPF_LAUNCH((k_resize_lanczos<1>), lgrid, dim3(256), 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy);
-    else if (ch == 2) VPF_LAUNCH((k_resize_lanczos<2>), lgrid, dim3(256), 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy);
-    else VPF_LAUNCH((k_resize_lanczos<3>), lgrid, dim3(256), 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy);
-    return hipGetLastError();
-  }
-  dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4);
-  // up-scaling: several destination rows sit between the same two source rows -> tiled kernel (horizontal lerp once per
-  // source row).  Kernel durations (rocprofv3), tiled vs row-pair: 1080p->4K 16.6 vs 20.6 us, 720p->1080p 8.2 vs 9.0;
-  // for mild down-scales the row-pair kernel is as fast or faster (1080p->720p 5.9 vs 5.8, 4K->1440p 16.2 vs 12.4,
-  // 4K->3000x1688 21.2 vs 14.9), so the tiled kernel is used below 1.0 only
-  if (interp == VPF_INTERP_LINEAR && (scy < 1.0f || tuning(VPF_TUNE_NV12_RGB_VARIANT) == 43) && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 &&
-      launch_resize_tile(st, ch, sw, sh, src, sp, dw, dh, dst, dp, scx, scy))
-    return hipGetLastError();
-  const uint32_t rowb = (interp == VPF_INTERP_LINEAR) ? lds_strip_bytes(ch, sw, dw, src, sp, kResizeRowBytes) : 0;
-  if (rowb) {
-    // (capping residency at 4 / 2 / 1 workgroups per CU to stagger the waves was measured: 8.5 / 8.7 / 11.3 us vs 8.4)
-    const uint32_t it = (rowb + 1023) / 1024, lds = 4 * 2 * rowb + 16;  // + 16: a tap window may start in a strip's last dword
-#define VPF_RL(C, I) VPF_LAUNCH((k_resize_lds<C, I>), grid, dim3(256), lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, vec_ok, rowb / 16)
-#define VPF_RLI(C) do { if (it == 1) VPF_RL(C, 1); else if (it == 2) VPF_RL(C, 2); else if (it == 3) VPF_RL(C, 3); else VPF_RL(C, 4); } while (0)
-    if (ch == 1) VPF_RLI(1); else if (ch == 2) VPF_RLI(2); else VPF_RLI(3);
-#undef VPF_RLI
-#undef VPF_RL
-    return hipGetLastError();
-  }
-#define VPF_GO(C, I) VPF_LAUNCH((k_resize<C, I>), grid, dim3(256), 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, vec_ok)
-  if (interp == VPF_INTERP_LINEAR) {
-    if (ch == 1) VPF_GO(1, VPF_INTERP_LINEAR); else if (ch == 2) VPF_GO(2, VPF_INTERP_LINEAR); else VPF_GO(3, VPF_INTERP_LINEAR);
-  } else {
-    if (ch == 1) VPF_GO(1, VPF_INTERP_NEAREST); else if (ch == 2) VPF_GO(2, VPF_INTERP_NEAREST); else VPF_GO(3, VPF_INTERP_NEAREST);
-  }
-#undef VPF_GO
-  return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------
 // 32-bit float surfaces (RGB_32F: CH = 3 interleaved, RGB_32F_PLANAR: CH = 1 per plane; reference
 // NppResizeSurfacePacked32F3C_Impl / NppResizeSurface32FPlanar_Impl, Tasks.cpp:1334-1445): the same taps and operation
@@ -1352,56 +1195,44 @@ VPF_DEV void FloatGatherTask<CH, INTERP>::run(const uint8_t* __restrict__ src, u
   }
 }
 
-hipError_t launch_resize_f32(hipStream_t st, int ch, int interp, uint32_t sw, uint32_t sh, const uint8_t* src, uint32_t sp,
-                             uint32_t dw, uint32_t dh, uint8_t* dst, uint32_t dp) {
-  const float scx = (float)sw / (float)dw, scy = (float)sh / (float)dh;
-  dim3 grid((dw + 63) / 64, (dh + 3) / 4);
-  if (interp != VPF_INTERP_NEAREST && sw % dw == 0 && sh % dh == 0 && ((sw / dw) & 1) && ((sh / dh) & 1) && sw < (1u << 22) && sh < (1u << 22) &&
-      tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9)
-    interp = VPF_INTERP_NEAREST;  // odd integer factors: every filter returns the centre sample (see launch_resize)
-  // Lanczos: the tiled separable form (16-B aligned source rows; 1080p -> 720p 22.7 -> 15.7 us, 720p -> 1080p 42.7 -> 19.5 us); the
-  // gather form below otherwise.  Bilinear stays on the gather form: tiled, a 720p -> 1080p up-scale took 17.0 us against 10.1 (four
-  // times the bytes of an 8-bit surface go through LDS for little reuse); the bilinear branch of TileTaskF32 is reachable with tuning 43.
-  if ((interp == VPF_INTERP_LANCZOS3 || (interp == VPF_INTERP_LINEAR && scy < 1.0f && tuning(VPF_TUNE_NV12_RGB_VARIANT) == 43)) && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 9 &&
-      tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && !(((uintptr_t)src | sp) & 15)) {
-    const bool lz = interp == VPF_INTERP_LANCZOS3;
-    const TileShape t = plan_tile(lz, 1, &ch, &dw, &dh, &scx, &scy, 1, 4);
-    if (t.ok) {
-      const PlaneGeom g{sw, sh, dw, dh, scx, scy, (int)((((uintptr_t)dst | dp) & 15) == 0), t.ty, t.nr, t.rowq, t.lshift};
-      const dim3 tgrid((dw + 63) / 64, (dh + t.ty - 1) / t.ty);
-      BatchArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.f[0].s[0] = src; a.f[0].sp[0] = sp; a.f[0].d[0] = dst; a.f[0].dp[0] = dp;
-#define VPF_TF(C, L, W) VPF_LAUNCH((k_plane_batch<TileTaskF32<C, L, W>>), tgrid, dim3(64 * W), t.lds, st, a, 0, g)
-#define VPF_TFW(C, L) do { if (t.wpb == 8) VPF_TF(C, L, 8); else VPF_TF(C, L, 4); } while (0)
-      if (ch == 3) { if (lz) VPF_TFW(3, true); else VPF_TFW(3, false); } else { if (lz) VPF_TFW(1, true); else VPF_TFW(1, false); }
-#undef VPF_TFW
-#undef VPF_TF
-      return hipGetLastError();
-    }
-  }
-#define VPF_F32(C, I) VPF_LAUNCH((k_resize_f32<C, I>), grid, dim3(256), 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy)
-  if (ch == 3) {
-    if (interp == VPF_INTERP_LANCZOS3) VPF_F32(3, VPF_INTERP_LANCZOS3); else if (interp == VPF_INTERP_LINEAR) VPF_F32(3, VPF_INTERP_LINEAR); else VPF_F32(3, VPF_INTERP_NEAREST);
-  } else {
-    if (interp == VPF_INTERP_LANCZOS3) VPF_F32(1, VPF_INTERP_LANCZOS3); else if (interp == VPF_INTERP_LINEAR) VPF_F32(1, VPF_INTERP_LINEAR); else VPF_F32(1, VPF_INTERP_NEAREST);
-  }
-#undef VPF_F32
-  return hipGetLastError();
-}
+// ------------------------------------------------------------------------------------------
+// The host side.  WHICH kernels a call takes is resize_plan (vpf_resize_plan.h: a pure function of the shapes, the alignment of the planes
+// and the four knobs, tested on the CPU); launch_resize_planned below reduces the alignment bits, asks it once and dispatches on the answer.
+// A run-time value becomes a template argument through with_value / with_bool (k_job_launch.h) or through a FORM: one of the named multi-plane
+// tasks above (TileBl8, RowPair2, RowBand4wm ...).  k_planes_mp takes the name itself, a plane launched on its own the task the name derives
+// from (k_plane_batch<RowBandTask<CH, 4, 1, 8, true>>): the instantiations are the ones there always were.
+// ------------------------------------------------------------------------------------------
+template <template <int> class MP> struct Form {};
+template <int CH, int IT> RowPairTask<CH, IT> form_base(const RowPairTask<CH, IT>&);
+template <int CH, int R, int IT, int P1, bool M> RowBandTask<CH, R, IT, P1, M> form_base(const RowBandTask<CH, R, IT, P1, M>&);
+template <int CH, int W> TileTask<CH, W> form_base(const TileTask<CH, W>&);
+template <int CH, int W> LanczosTileTask<CH, W> form_base(const LanczosTileTask<CH, W>&);
+template <template <int> class MP, int CH> using PlaneTaskOf = decltype(form_base(std::declval<MP<CH>>()));
 
-// ------------------------------------------------------------------------------------------
-// vpf_resize_batch: every plane of a frame and up to 32 same-shape frames in as few dispatches as possible.  A 720p plane is 2-3 us
-// of work, the same order as a kernel boundary, and an NV12 / YUV420 frame is two or three such planes: one launch per plane per
-// frame leaves the chip idle most of the time.  The plane geometry decides the kernel family exactly as in launch_resize; when every
-// plane of the format lands in the same (tiled or row-pair) family they all go into ONE launch (k_planes_mp), otherwise each plane
-// gets one launch over all frames (k_plane_batch).  Same task bodies as the single-frame kernels -> identical pixels.
-// ------------------------------------------------------------------------------------------
-static bool planes_aligned(const BatchArgsL& a, uint32_t n, int k, uintptr_t src_mask, uintptr_t dst_mask) {
-  for (uint32_t i = 0; i < n; i++)
-    if ((((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & src_mask) || (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & dst_mask)) return false;
-  return true;
+// f(Form<...>): the eight row-band instantiations — the ONE ladder over them, for the launch of all planes, of one plane and (lab builds) the persistent launch
+template <class F>
+static void with_band_form(const ResizeLaunch& l, F&& f) {
+  if (l.multi) f(Form<RowBand4wm>{});
+  else if (l.p1 == 8) { if (l.rows == 16) f(Form<RowBand16w>{}); else f(Form<RowBand8w>{}); }
+  else if (l.rows == 16) f(Form<RowBand16n>{});
+  else if (l.rows == 8) { if (l.narrow) f(Form<RowBand8n>{}); else f(Form<RowBand8>{}); }
+  else if (l.rows == 4) f(Form<RowBand4>{});
+  else f(Form<RowBand2>{});
 }
+// f(Form<...>) for a launch of family `fam`: RESIZE_TILE, RESIZE_LZ_TILE, RESIZE_ROWPAIR or RESIZE_BAND
+template <class F>
+static void with_form(int fam, const ResizeLaunch& l, F&& f) {
+  if (fam == RESIZE_TILE) { if (l.wpb == 8) f(Form<TileBl8>{}); else f(Form<TileBl4>{}); }
+  else if (fam == RESIZE_LZ_TILE) { if (l.wpb == 8) f(Form<TileLz8>{}); else f(Form<TileLz4>{}); }
+  else if (fam == RESIZE_BAND) with_band_form(l, f);
+  else if (l.it == 1) f(Form<RowPair1>{});
+  else if (l.it == 2) f(Form<RowPair2>{});
+  else if (l.it == 3) f(Form<RowPair3>{});
+  else f(Form<RowPair4>{});
+}
+template <class F> static void with_ch(int ch, F&& f) { with_value<1, 2, 3>(ch, f); }     // f(CH): 1, 2, else 3 interleaved channels
+template <class F> static void with_ch_f32(int ch, F&& f) { with_value<3, 1>(ch, f); }    // float surfaces: packed (3), else planar (1)
+
 // (the selection log / roctx mark carries __PRETTY_FUNCTION__: it names the task the generic entry was instantiated with)
 // (grid.z = the frames of the launch: up to 32 take the small frame table, more the large one — two instantiations of the same kernel)
 template <class Task>
@@ -1488,412 +1319,151 @@ static bool launch_planes_mp_persist(hipStream_t st, uint32_t lds, const BatchAr
   else hipLaunchKernelGGL((k_planes_mp_persist<TaskCH, BatchArgsL>), dim3(groups), dim3(TaskCH<3>::kThreads), lds, st, a, t, P);
   return true;
 }
+template <template <int> class MP>
+static bool launch_form_persist(Form<MP>, hipStream_t st, uint32_t lds, const BatchArgsL& a, const PlaneTable& t, uint32_t n, const uint32_t* nbx, const uint32_t* nbands, uint32_t chunk, uint32_t hops) {
+  return launch_planes_mp_persist<MP>(st, lds, a, t, n, nbx, nbands, chunk, hops);
+}
 #endif  // VPF_LAB_FORMS
-template <template <int, int> class T2, int I>
-static void launch_gather_ch(hipStream_t st, dim3 grid, const BatchArgsL& a, const ResizeJob& j, const PlaneGeom& g) {
-  if (j.ch == 1) launch_plane_batch<T2<1, I>>(st, grid, 0, a, j.k, g);
-  else if (j.ch == 2) launch_plane_batch<T2<2, I>>(st, grid, 0, a, j.k, g);
-  else launch_plane_batch<T2<3, I>>(st, grid, 0, a, j.k, g);
+template <template <int> class MP>
+static void launch_form_all(Form<MP>, hipStream_t st, dim3 grid, uint32_t lds, const BatchArgsL& a, const PlaneTable& t) { launch_planes_mp<MP>(st, grid, lds, a, t); }
+template <template <int> class MP>
+static void launch_form_plane(Form<MP>, hipStream_t st, dim3 grid, uint32_t lds, const BatchArgsL& a, const ResizeJob& j, const PlaneGeom& g) {
+  with_ch(j.ch, [&](auto C) { launch_plane_batch<PlaneTaskOf<MP, decltype(C)::value>>(st, grid, lds, a, j.k, g); });
 }
 
-// Destination rows per wave for a row-pair launch (RowBandTask) and the strips per wave its LDS is sized for: the largest of 16 / 8 / 4 / 2
-// whose bands fit the strip slots (8; 16 when a strip is at most 1 KiB = one staging pass, the 1- and 2-channel planes and the up-scales)
-// and 64 KB of LDS (`rb` bytes per strip, at most two 1-KiB staging passes) while the launch keeps at least kBandMinGroups workgroups (a
-// single small frame stays at one row per wave: it needs the parallelism more than the shared work).  Vertical factors above 2 skip
-// source rows (a contiguous band would read rows nobody blends) and odd integer factors on both axes move bytes (RowPairTask's
-// centre-sample shortcut): both keep one row per wave.  VPF_TUNE_RESIZE_BAND forces a value where it applies.
-constexpr uint32_t kBandMinGroups = 2048;
-struct BandShape { int rows; uint32_t slots; bool narrow; uint32_t rb; };  // rb: strip bytes of the chosen form (16-row bands of packed RGB: four bytes per pixel)
-static uint32_t band_slots(int r, float scy) { return vpf_bound_band_slots(r, scy); }  // (vpf_plan_bounds.h: checked on the CPU against the tap arithmetic)
-// The strips a launch ALLOCATES: the rows its bands really touch (vpf_band_rows_exact: a walk over the bands with make_tap's arithmetic),
-// never more than the closed-form bound that chose the band height.  1080p -> 720p with 4-row bands: 6 strips instead of 8, five
-// workgroups per CU instead of four.  The last shapes are remembered per thread (a launch per frame would walk dh / r taps every time).
-static uint32_t band_slots_exact(int r, int njobs, const ResizeJob* jobs, uint32_t bound) {
-  struct Seen { int r; uint32_t sh, dh, rows; };
-  static thread_local Seen seen[8];
-  static thread_local unsigned next = 0;
-  uint32_t most = 1;
-  for (int p = 0; p < njobs; p++) {
-    const ResizeJob& j = jobs[p];
-    uint32_t rows = 0;
-    for (const Seen& e : seen)
-      if (e.r == r && e.sh == j.sh && e.dh == j.dh && e.rows) rows = e.rows;
-    if (!rows) {
-      rows = vpf_band_rows_exact(r, j.sh, j.dh, (float)j.sh / (float)j.dh);
-      seen[next++ & 7] = Seen{r, j.sh, j.dh, rows};
+// one plane of one frame: the scalar-argument kernel entries (kernarg preload, vpf_internal.h)
+static hipError_t launch_resize_single(hipStream_t st, const ResizeJob& j, const ResizeLaunch& l, const BatchArgsL& a) {
+  const uint8_t* src = a.f[0].s[j.k];
+  uint8_t* dst = a.f[0].d[j.k];
+  const uint32_t sp = a.f[0].sp[j.k], dp = a.f[0].dp[j.k], sw = j.sw, sh = j.sh, dw = j.dw, dh = j.dh;
+  const float scx = l.scx, scy = l.scy;
+  const int vec_ok = l.vec_ok;
+  const dim3 grid(l.gx, l.gy), block(l.threads);
+  int fam = l.family;
+  // 8-bit Lanczos: the matrix-core kernel (k_lanczos_mfma.hip) may decline; then the tile shape planned for this plane, or the gather form
+  if (fam == RESIZE_LZ_MFMA) fam = launch_lanczos_mfma(st, 1, &j, 1, a) ? RESIZE_NONE : l.fallback;
+  switch (fam) {
+    case RESIZE_NONE: break;
+    case RESIZE_HALF3: VPF_LAUNCH(k_resize_half3_r16, grid, block, 0, st, src, sp, dst, dp, sw, l.a0, l.a1); break;
+    case RESIZE_HALF: with_ch(j.ch, [&](auto C) { VPF_LAUNCH_T(k_resize_half, (C), grid, 0, st, src, sp, dst, dp, dw, dh); }); break;
+    case RESIZE_TILE:
+      with_ch(j.ch, [&](auto C) { with_value<8, 4>(l.wpb, [&](auto W) {
+        VPF_LAUNCH_TN(k_resize_tile, (C, W), grid, block, l.lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, l.a0, l.a1, l.a2, l.a3, vec_ok); }); });
+      break;
+    case RESIZE_LZ_TILE:
+      with_ch(j.ch, [&](auto C) { with_value<8, 4>(l.wpb, [&](auto W) {
+        VPF_LAUNCH_TN(k_resize_lztile, (C, W), grid, block, l.lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, l.a0, l.a1, l.a2, l.a3, vec_ok); }); });
+      break;
+    case RESIZE_LZ_GATHER: with_ch(j.ch, [&](auto C) { VPF_LAUNCH_T(k_resize_lanczos, (C), grid, 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy); }); break;
+    case RESIZE_ROWPAIR:
+      with_ch(j.ch, [&](auto C) { with_value<1, 2, 3, 4>(l.it, [&](auto IT) {
+        VPF_LAUNCH_T(k_resize_lds, (C, IT), grid, l.lds, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, vec_ok, l.a0); }); });
+      break;
+    case RESIZE_F32_TILE: {  // the float tile task has no scalar-argument entry: the small frame table with this one plane in it
+      const PlaneGeom g{sw, sh, dw, dh, scx, scy, vec_ok, l.a0, l.a1, l.a2, l.a3};
+      BatchArgs b;
+      std::memset(&b, 0, sizeof(b));
+      b.f[0].s[0] = src; b.f[0].sp[0] = sp; b.f[0].d[0] = dst; b.f[0].dp[0] = dp;
+      with_ch_f32(j.ch, [&](auto C) { with_bool(l.lz, [&](auto LZ) { with_value<8, 4>(l.wpb, [&](auto W) {
+        // (the generic kernel over the task: VPF_LAUNCH_TN spells K<targs>, this instantiation is k_plane_batch<TileTaskF32<targs>>)
+        if (log_level() >= 2 || trace_on()) note_instantiation("k_plane_batch<TileTaskF32", C, LZ, W);
+        (void)hipGetLastError();
+        hipLaunchKernelGGL((k_plane_batch<TileTaskF32<decltype(C)::value, decltype(LZ)::value, decltype(W)::value>>), grid, block, l.lds, st, b, 0, g);
+      }); }); });
+      break;
     }
-    most = rows > most ? rows : most;
+    case RESIZE_F32_GATHER:
+      with_ch_f32(j.ch, [&](auto C) { with_value<VPF_INTERP_LANCZOS3, VPF_INTERP_LINEAR, VPF_INTERP_NEAREST>(l.eff, [&](auto I) {
+        VPF_LAUNCH_T(k_resize_f32, (C, I), grid, 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy); }); });
+      break;
+    default:  // RESIZE_GATHER
+      with_ch(j.ch, [&](auto C) { with_value<VPF_INTERP_LINEAR, VPF_INTERP_NEAREST>(l.eff, [&](auto I) {
+        VPF_LAUNCH_T(k_resize, (C, I), grid, 0, st, src, sp, sw, sh, dst, dp, dw, dh, scx, scy, vec_ok); }); });
   }
-  return most < bound ? most : bound;
-}
-// pixels per lane for the 1-channel planes of a band launch: 8 (512 columns per wave) when such chunks fill every 1-channel row to >= 80 %
-// (1280 px: 3 chunks, 83 %; the 640-px chroma planes of a 720p YUV420 frame: 2 chunks, 62 % -> 4)
-static int band_p1(int njobs, const ResizeJob* jobs) {
-  bool any = false;
-  const bool force8 = (tuning(VPF_TUNE_RESIZE_BAND) >> 17) & 1;  // | 0x20000: 8 pixels per lane on 1-channel planes however well 512-column chunks fill them (measurement knob)
-  for (int p = 0; p < njobs; p++) {
-    if (jobs[p].ch != 1) continue;
-    any = true;
-    if (!force8 && (double)jobs[p].dw < 0.8 * 512.0 * ((jobs[p].dw + 511) / 512)) return 4;
-  }
-  return any ? 8 : 4;
-}
-// strip bytes of the widest plane for a band launch (RowBandTask: 64 * band_px(ch, p1) columns per wave); 0 when some plane has no LDS path
-static uint32_t band_strip_bytes(int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a, int p1) {
-  uint32_t rbmax = 0;
-  for (int p = 0; p < njobs; p++) {
-    const ResizeJob& j = jobs[p];
-    bool al = true;
-    for (uint32_t i = 0; i < n; i++) al = al && !(((uintptr_t)a.f[i].s[j.k] | a.f[i].sp[j.k]) & 15);
-    const uint32_t rb = al ? lds_strip_bytes(j.ch, j.sw, j.dw, a.f[0].s[j.k], a.f[0].sp[j.k], kResizeRowBytes, 64u * band_px(j.ch, p1)) : 0;
-    if (!rb) return 0;
-    rbmax = rb > rbmax ? rb : rbmax;
-  }
-  return rbmax;
-}
-static BandShape band_rows(int njobs, const ResizeJob* jobs, uint32_t rb, uint32_t n, int p1 = 4) {
-  const int forced = tuning(VPF_TUNE_RESIZE_BAND) & 0xff;  // (bits 8..: bands per wave of the march form, plan_band)
-  if (forced == 1 || rb == 0 || rb > 2048) return {1, 0, false, rb};
-  const uint32_t rb_packed = rb;
-  float scy = 0.f;
-  for (int p = 0; p < njobs; p++) {
-    const ResizeJob& j = jobs[p];
-    if (j.sw % j.dw == 0 && j.sh % j.dh == 0 && ((j.sw / j.dw) & 1) && ((j.sh / j.dh) & 1)) return {1, 0, false, rb};
-    const float s = (float)j.sh / (float)j.dh;
-    scy = s > scy ? s : scy;
-  }
-  if (scy > 2.0f) return {1, 0, false, rb};
-  for (int r = 16; r >= 2; r >>= 1) {
-    if (forced && forced != r) continue;
-    rb = rb_packed;
-    if (r == 16)  // RowBandTask<3, 16, 1>::kPx4: its strips hold packed RGB four bytes per pixel
-      for (int p = 0; p < njobs; p++)
-        if (jobs[p].ch == 3) {
-          const uint32_t rb4 = vpf_bound_strip_bytes_px4(jobs[p].sw, jobs[p].dw, 1024u, 256u);
-          rb = !rb4 ? 4096u : rb4 > rb ? rb4 : rb;
-        }
-    const bool narrow = r >= 8 && rb <= 1024;  // the IT = 1 instantiations (8 and 16 rows)
-    if (r == 16 && !narrow) continue;
-    const uint32_t slots = band_slots(r, scy);
-    if (slots > (uint32_t)(narrow ? 2 * kBandSlots : kBandSlots) || 4u * slots * rb + 16u > 64u * 1024u) continue;
-    uint64_t groups = 0;
-    for (int p = 0; p < njobs; p++) groups += (uint64_t)((jobs[p].dw + 64u * band_px(jobs[p].ch, p1) - 1) / (64u * band_px(jobs[p].ch, p1))) * ((jobs[p].dh + 4 * r - 1) / (4 * r)) * n;
-    if (forced || groups >= kBandMinGroups) return {r, band_slots_exact(r, njobs, jobs, slots), narrow, rb};
-  }
-  return {1, 0, false, rb_packed};
-}
-// the whole decision: 8 pixels per lane on the 1-channel planes only with the 16-slot (narrow-strip) instantiations that exist for it.
-// Where that form would run 8-row bands on a DOWN-scale (every plane's vertical factor in [1, 2]) the launch takes the MARCH form instead
-// (RowBand4wm): bands of 4 rows, nb of them per wave one below the other — the next band's source rows are requested while this band is
-// blended, the walk's lerps and the column taps carry over — with half the LDS per wave (four waves per SIMD instead of three) and the
-// wave's fixed part paid once per 4 nb rows.  nb = 2 or 3 while the launch keeps kBandMinGroups workgroups.  Measured on the 1- / 2-channel
-// planes of Y / NV12 (profiles/r04_bilinear_march.txt: Y 1080p -> 720p 0.85 -> 0.79 us, NV12 1.14 -> 1.06); 3-channel planes and up-scales
-// lose with it and keep their forms.  VPF_TUNE_RESIZE_BAND = 4 | nb << 8 forces it where it applies.
-struct BandPlan { int rows; uint32_t slots; bool narrow; int p1; uint32_t rb; uint32_t nb; };
-static BandPlan plan_band(int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a) {
-  const int p1 = band_p1(njobs, jobs), knob = tuning(VPF_TUNE_RESIZE_BAND) & 0xffff, forced_nb = (knob & 0xff) == 4 ? knob >> 8 : 0;  // (other row counts: the field is the persistent launch's chunk)
-  if (p1 == 8) {
-    const uint32_t rb = band_strip_bytes(njobs, jobs, n, a, 8);
-    const BandShape bs = band_rows(njobs, jobs, rb, n, 8);
-    bool down = rb != 0 && rb <= 1024;
-    float scy = 1.f;
-    for (int p = 0; p < njobs && down; p++) {
-      const float s = (float)jobs[p].sh / (float)jobs[p].dh;
-      down = s >= 1.0f && s <= 2.0f;
-      scy = s > scy ? s : scy;
-    }
-    if (down && (forced_nb ? bs.rows == 4 : ((knob & 0xff) == 0 && bs.rows == 8 && bs.narrow))) {
-      uint64_t groups = 0;
-      for (int p = 0; p < njobs; p++) groups += (uint64_t)((jobs[p].dw + 64u * band_px(jobs[p].ch, 8) - 1) / (64u * band_px(jobs[p].ch, 8))) * ((jobs[p].dh + 15) / 16) * n;
-      const uint32_t nb = forced_nb ? (uint32_t)forced_nb : (uint32_t)std::min<uint64_t>(3, groups / kBandMinGroups);
-      const uint32_t slots = band_slots_exact(4, njobs, jobs, band_slots(4, scy));
-      if (nb >= (forced_nb ? 1u : 2u) && slots <= 9u && 4u * slots * rb + 16u <= 64u * 1024u) return {4, slots, true, 8, rb, nb};
-    }
-    if (bs.rows >= 8 && bs.narrow) return {bs.rows, bs.slots, true, 8, bs.rb, 0};
-  }
-  const uint32_t rb = band_strip_bytes(njobs, jobs, n, a, 4);
-  const BandShape bs = band_rows(njobs, jobs, rb, n, 4);
-  return {bs.rows, bs.slots, bs.narrow, 4, bs.rb, 0};
+  return hipGetLastError();
 }
 
-hipError_t launch_resize_jobs(hipStream_t st, bool f32, int interp, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a) {
-  enum Fam { FAM_GATHER, FAM_LZ_GATHER, FAM_LZ_MFMA, FAM_LZ_TILE, FAM_HALF, FAM_HALF3, FAM_TILE, FAM_ROWPAIR };
-  bool lz_tile_ok[3] = {false, false, false};  // a Lanczos plane the tiled kernel may take when the matrix-core kernel does not
-  const int tune = tuning(VPF_TUNE_NV12_RGB_VARIANT);
-  if (njobs < 1 || njobs > 3 || !n || n > (uint32_t)kMaxBatch) return hipErrorInvalidValue;
-  Fam fam[3];
-  int eff[3];
-  PlaneGeom g[3];
-  uint32_t rowb[3] = {0, 0, 0};
-  // bilinear up-scales: the tiled kernel for a single frame, the row-band kernel (8 or 4 destination rows per wave, each source row's
-  // horizontal lerp evaluated once per band, no barriers) when the launch is large enough for it — 1080p -> 4K batched 11.9 -> 6.9 us / frame
-  bool band_up = !f32 && interp == VPF_INTERP_LINEAR && tune != 43 && tune != 9;
-  if (band_up) band_up = plan_band(njobs, jobs, n, a).rows >= 4;
-  for (int p = 0; p < njobs; p++) {
+hipError_t launch_resize_planned(hipStream_t st, bool f32, int interp, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a, uint32_t call_n) {
+  ResizeShape q{};
+  q.f32 = f32; q.interp = interp; q.njobs = njobs; q.n = n; q.call_n = call_n;
+  if (njobs >= 1 && njobs <= 3 && n <= (uint32_t)kMaxBatch)
+    for (int p = 0; p < njobs; p++) {
+      const int k = jobs[p].k;
+      q.jobs[p] = jobs[p];
+      for (uint32_t i = 0; i < n; i++) {
+        q.src_bits[p] |= (uintptr_t)a.f[i].s[k] | a.f[i].sp[k];
+        q.dst_bits[p] |= (uintptr_t)a.f[i].d[k] | a.f[i].dp[k];
+      }
+    }
+  q.variant = tuning(VPF_TUNE_NV12_RGB_VARIANT); q.tile = tuning(VPF_TUNE_RESIZE_TILE); q.band = tuning(VPF_TUNE_RESIZE_BAND); q.mfma = tuning(VPF_TUNE_RESIZE_MFMA);
+  const ResizePlan P = resize_plan(q);
+  if (!P.ok) return hipErrorInvalidValue;
+  if (P.single) return launch_resize_single(st, jobs[0], P.plane[0], a);
+  auto geom = [&](int p, const ResizeLaunch& l) {
     const ResizeJob& j = jobs[p];
-    const float scx = (float)j.sw / (float)j.dw, scy = (float)j.sh / (float)j.dh;
-    const bool odd_int = j.sw % j.dw == 0 && j.sh % j.dh == 0 && ((j.sw / j.dw) & 1) && ((j.sh / j.dh) & 1) && j.sw < (1u << 22) && j.sh < (1u << 22) &&
-                         tune != 40 && tune != 9;  // every filter returns the centre sample (see launch_resize)
-    eff[p] = interp;
-    if (f32) {
-      if (interp != VPF_INTERP_NEAREST && odd_int) eff[p] = VPF_INTERP_NEAREST;
-      g[p] = PlaneGeom{j.sw, j.sh, j.dw, j.dh, scx, scy, 0, 0, 0, 0, 0};
-      fam[p] = FAM_GATHER;
-      continue;
-    }
-    if (interp == VPF_INTERP_LANCZOS3 && odd_int) eff[p] = VPF_INTERP_NEAREST;
-    const int vec_ok = planes_aligned(a, n, j.k, 0, j.ch == 2 ? 7 : 3) ? 1 : 0;
-    g[p] = PlaneGeom{j.sw, j.sh, j.dw, j.dh, scx, scy, vec_ok, 0, 0, 0, 0};
-    const bool src16 = tune != 9 && planes_aligned(a, n, j.k, 15, 0);
-    if (eff[p] == VPF_INTERP_LINEAR && j.sw == 2 * j.dw && j.sh == 2 * j.dh && j.dw % 4 == 0 && tune != 40 && tune != 9 &&
-        planes_aligned(a, n, j.k, 7, j.ch == 2 ? 7 : 3)) {
-      if (j.ch == 3 && j.sw % 32 == 0 && planes_aligned(a, n, j.k, 15, 15)) {
-        const uint32_t chunks = (j.sw + 1023) / 1024;
-        g[p].a0 = chunks; g[p].a1 = chunks * j.dh;
-        fam[p] = FAM_HALF3;
-      } else {
-        fam[p] = FAM_HALF;
-      }
-    } else if (eff[p] == VPF_INTERP_LANCZOS3) {
-      fam[p] = src16 ? FAM_LZ_MFMA : FAM_LZ_GATHER;
-      lz_tile_ok[p] = src16 && tune != 40;
-    } else if (eff[p] == VPF_INTERP_LINEAR && (scy < 1.0f || tune == 43) && tune != 40 && src16 && !band_up) {
-      fam[p] = FAM_TILE;
-    } else if (eff[p] == VPF_INTERP_LINEAR && src16 && (rowb[p] = lds_strip_bytes(j.ch, j.sw, j.dw, a.f[0].s[j.k], a.f[0].sp[j.k], kResizeRowBytes)) != 0) {
-      fam[p] = FAM_ROWPAIR;
-    } else {
-      fam[p] = FAM_GATHER;
-    }
-  }
-  // ---- every plane tiled: one launch for the whole format
-  bool all_tile = !f32, all_rowpair = !f32;
-  for (int p = 0; p < njobs; p++) {
-    all_tile = all_tile && fam[p] == FAM_TILE && eff[p] == eff[0];
-    all_rowpair = all_rowpair && fam[p] == FAM_ROWPAIR;
-  }
-  {  // every plane Lanczos: one matrix-core launch for the whole format (k_lanczos_mfma.hip); planes it cannot take fall back to the gather form
-    bool all_mfma = !f32;
-    for (int p = 0; p < njobs; p++) all_mfma = all_mfma && fam[p] == FAM_LZ_MFMA;
-    // the tiled separable kernel for every plane in ONE launch; false when it does not apply
-    auto tile_all_planes = [&]() -> bool {
-      int ch[3]; uint32_t dw[3], dh[3]; float sx[3], sy[3];
-      for (int p = 0; p < njobs; p++) { ch[p] = jobs[p].ch; dw[p] = jobs[p].dw; dh[p] = jobs[p].dh; sx[p] = g[p].scx; sy[p] = g[p].scy; }
-      const TileShape tl = plan_tile(true, njobs, ch, dw, dh, sx, sy, n);
-      if (!tl.ok) return false;
-      PlaneTable t{};
-      t.np = (uint32_t)njobs;
-      uint32_t gx = 0, gy = 0;
-      for (int p = 0; p < njobs; p++) {
-        t.g[p] = g[p]; t.k[p] = (uint32_t)jobs[p].k; t.ch[p] = (uint32_t)jobs[p].ch; t.by0[p] = gy;
-        t.g[p].a0 = tl.ty; t.g[p].a1 = tl.nr; t.g[p].a2 = tl.rowq; t.g[p].a3 = tl.lshift;
-        gx = std::max(gx, (jobs[p].dw + 63) / 64);
-        gy += (jobs[p].dh + tl.ty - 1) / tl.ty;
-      }
-      if (tl.wpb == 8) launch_planes_mp<TileLz8>(st, dim3(gx, gy, n), tl.lds, a, t);
-      else launch_planes_mp<TileLz4>(st, dim3(gx, gy, n), tl.lds, a, t);
-      return true;
-    };
-    // ONE frame of a multi-plane format per dispatch with a small destination (all planes together <= 1 MB: up to ~1100 x 640): a lone launch
-    // of the matrix-core kernel is a latency chain of 8-9 us whatever the picture (lanczos_single_prefers_tile above has the single-plane
-    // rule), the tile kernel — whose time follows the destination — leaves such a frame after 6-7 (profiles/r04_lanczos_single_multiplane.txt:
-    // YUV420 1080p -> 224 x 224 5.9 against 7.9 us, NV12 1080p -> 416 x 416 6.8 against 9.0; 1080p -> 720p stays on the matrix cores, 7.5
-    // against 8.3).  Only where ONE tile launch takes every plane (the chroma plane of NV12 at 8 x falls out of its windows).
-    if (all_mfma && n == 1 && njobs > 1 && !(tuning(VPF_TUNE_RESIZE_MFMA) & 0xfffff)) {
-      uint64_t dst_b = 0;
-      bool tile_ok = true;
-      for (int p = 0; p < njobs; p++) { dst_b += (uint64_t)jobs[p].dw * jobs[p].dh * (uint32_t)jobs[p].ch; tile_ok = tile_ok && lz_tile_ok[p]; }
-      if (tile_ok && dst_b <= 1000000ull && tile_all_planes()) return hipGetLastError();
-    }
-    if (all_mfma && launch_lanczos_mfma(st, njobs, jobs, n, a)) return hipGetLastError();
-    for (int p = 0; p < njobs; p++)
-      if (fam[p] == FAM_LZ_MFMA && !launch_lanczos_mfma(st, 1, &jobs[p], n, a)) fam[p] = FAM_LZ_GATHER;
-    // what the matrix-core kernel does not take (the strongest down-scales): the tiled separable kernel — one launch for the whole format when
-    // every plane is in that position, else plane by plane — and the gather kernel for what is left
-    bool all_lzt = !f32;
-    for (int p = 0; p < njobs; p++) all_lzt = all_lzt && fam[p] == FAM_LZ_GATHER && lz_tile_ok[p];
-    if (all_lzt && tile_all_planes()) return hipGetLastError();
-    for (int p = 0; p < njobs; p++)
-      if (fam[p] == FAM_LZ_GATHER && lz_tile_ok[p]) {
-        const float sx = g[p].scx, sy = g[p].scy;
-        const TileShape t1 = plan_tile(true, 1, &jobs[p].ch, &jobs[p].dw, &jobs[p].dh, &sx, &sy, n);
-        if (!t1.ok) continue;
-        fam[p] = FAM_LZ_TILE;
-        g[p].a0 = t1.ty; g[p].a1 = t1.nr; g[p].a2 = t1.rowq; g[p].a3 = t1.lshift;
-        rowb[p] = t1.lds | ((uint32_t)t1.wpb << 24);  // carried to the launch below
-      }
-  }
-  TileShape ts{false, 0, 0, 0, 0, 0, 4};
-  if (all_tile) {
-    int ch[3]; uint32_t dw[3], dh[3]; float sx[3], sy[3];
-    for (int p = 0; p < njobs; p++) { ch[p] = jobs[p].ch; dw[p] = jobs[p].dw; dh[p] = jobs[p].dh; sx[p] = g[p].scx; sy[p] = g[p].scy; }
-    ts = plan_tile(false, njobs, ch, dw, dh, sx, sy, n);
-    if (!ts.ok) {  // the span does not fit a strip: every plane falls back to its gather form
-      all_tile = false;
-      for (int p = 0; p < njobs; p++) fam[p] = FAM_GATHER;
-    }
-  } else {
-    for (int p = 0; p < njobs; p++)
-      if (fam[p] == FAM_TILE) {  // mixed families: this plane is tiled on its own
-        const float sx = g[p].scx, sy = g[p].scy;
-        const TileShape t1 = plan_tile(false, 1, &jobs[p].ch, &jobs[p].dw, &jobs[p].dh, &sx, &sy, n);
-        if (!t1.ok) { fam[p] = FAM_GATHER; continue; }
-        g[p].a0 = t1.ty; g[p].a1 = t1.nr; g[p].a2 = t1.rowq; g[p].a3 = t1.lshift;
-        rowb[p] = t1.lds | ((uint32_t)t1.wpb << 24);  // carried to the launch below
-      }
-  }
-  if (all_tile || all_rowpair) {
+    return PlaneGeom{j.sw, j.sh, j.dw, j.dh, P.plane[p].scx, P.plane[p].scy, P.plane[p].vec_ok, l.a0, l.a1, l.a2, l.a3};
+  };
+  // ONE launch for every plane of the format
+  auto launch_all = [&]() -> hipError_t {
+    const ResizeLaunch& m = P.mp;
     PlaneTable t{};
     t.np = (uint32_t)njobs;
-    uint32_t gx = 0, gy = 0, it = 1, rb = 0;
-    for (int p = 0; p < njobs && all_rowpair; p++) rb = rowb[p] > rb ? rowb[p] : rb;
-    const BandPlan bs = all_rowpair ? plan_band(njobs, jobs, n, a) : BandPlan{1, 0, false, 4, 0, 0};
-    const int band = bs.rows;
-    if (band > 1) rb = bs.rb;
-    const uint32_t band_nb = bs.nb ? bs.nb : 1u;  // bands per wave (the march form)
-    for (int p = 0; p < njobs; p++) {
-      t.g[p] = g[p]; t.k[p] = (uint32_t)jobs[p].k; t.ch[p] = (uint32_t)jobs[p].ch; t.by0[p] = gy;
-      if (all_tile) {
-        t.g[p].a0 = ts.ty; t.g[p].a1 = ts.nr; t.g[p].a2 = ts.rowq; t.g[p].a3 = ts.lshift;
-        const uint32_t bx = (jobs[p].dw + 63) / 64;
-        gx = bx > gx ? bx : gx;
-        gy += (jobs[p].dh + ts.ty - 1) / ts.ty;
-      } else {
-        const uint32_t wcols = band > 1 ? 64u * band_px(jobs[p].ch, bs.p1) : 256u, bx = (jobs[p].dw + wcols - 1) / wcols;
-        gx = bx > gx ? bx : gx;
-        gy += (jobs[p].dh + 4 * band * band_nb - 1) / (4 * band * band_nb);
-      }
-    }
-    const dim3 grid(gx, gy, n);
-    if (all_tile) {
-      if (ts.wpb == 8) launch_planes_mp<TileBl8>(st, grid, ts.lds, a, t);
-      else launch_planes_mp<TileBl4>(st, grid, ts.lds, a, t);
-    } else {
-      for (int p = 0; p < njobs; p++) { t.g[p].a0 = rb / 16; t.g[p].a1 = bs.slots; t.g[p].a2 = bs.nb; }  // one strip size for the launch (the widest plane's)
-      it = (rb + 1023) / 1024;
-      const uint32_t lds = band > 1 ? 4 * bs.slots * rb + 16 : 4 * 2 * rb + 16;
+    for (int p = 0; p < njobs; p++) { t.g[p] = geom(p, m); t.k[p] = (uint32_t)jobs[p].k; t.ch[p] = (uint32_t)jobs[p].ch; t.by0[p] = P.by0[p]; }
 #ifdef VPF_LAB_FORMS
-      // the persistent form for the band kernels (lab builds, VPF_TUNE_RESIZE_BAND | 0x10000): chunks of bands instead of a grid
-      const int pknob = (tuning(VPF_TUNE_RESIZE_BAND) >> 16) & 1;
-      if (band > 1 && pknob == 1) {
-        // chunks of `chunk` bands (knob bits 8..15; default 2), one counter per XCD; | 0x40000: a wave whose counter has run dry visits the other seven
-        uint32_t nbx[3] = {0, 0, 0}, nbands[3] = {0, 0, 0};
-        for (int p = 0; p < njobs; p++) {
-          const uint32_t wcols = 64u * band_px(jobs[p].ch, bs.p1);
-          nbx[p] = (jobs[p].dw + wcols - 1) / wcols; nbands[p] = (jobs[p].dh + band - 1) / band;
-        }
-        const uint32_t chunk = ((tuning(VPF_TUNE_RESIZE_BAND) >> 8) & 0xff) ? (uint32_t)((tuning(VPF_TUNE_RESIZE_BAND) >> 8) & 0xff) : 2u;
-        const uint32_t hops = ((tuning(VPF_TUNE_RESIZE_BAND) >> 19) & 1) ? 0u : ((tuning(VPF_TUNE_RESIZE_BAND) >> 18) & 1) ? 8u : 1u;  // | 0x80000 (measurement): no counters, a wave strides through its XCD's share
-        bool done = false;
-        if (band == 4 && bs.p1 == 8) done = launch_planes_mp_persist<RowBand4wm>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 16 && bs.p1 == 8) done = launch_planes_mp_persist<RowBand16w>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 8 && bs.p1 == 8) done = launch_planes_mp_persist<RowBand8w>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 16) done = launch_planes_mp_persist<RowBand16n>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 8 && bs.narrow) done = launch_planes_mp_persist<RowBand8n>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 8) done = launch_planes_mp_persist<RowBand8>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 4) done = launch_planes_mp_persist<RowBand4>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        else if (band == 2) done = launch_planes_mp_persist<RowBand2>(st, lds, a, t, n, nbx, nbands, chunk, hops);
-        if (done) return hipGetLastError();
+    // the persistent form for the band kernels (lab builds, VPF_TUNE_RESIZE_BAND | 0x10000): chunks of bands instead of a grid
+    if (m.family == RESIZE_BAND && ((q.band >> 16) & 1)) {
+      // chunks of `chunk` bands (knob bits 8..15; default 2), one counter per XCD; | 0x40000: a wave whose counter has run dry visits the other seven
+      uint32_t nbx[3] = {0, 0, 0}, nbands[3] = {0, 0, 0};
+      for (int p = 0; p < njobs; p++) {
+        const uint32_t wcols = 64u * band_px(jobs[p].ch, m.p1);
+        nbx[p] = (jobs[p].dw + wcols - 1) / wcols; nbands[p] = (jobs[p].dh + m.rows - 1) / m.rows;
       }
-#endif  // VPF_LAB_FORMS
-      if (band == 4 && bs.p1 == 8) launch_planes_mp<RowBand4wm>(st, grid, lds, a, t);
-      else       if (band == 16 && bs.p1 == 8) launch_planes_mp<RowBand16w>(st, grid, lds, a, t);
-      else if (band == 8 && bs.p1 == 8) launch_planes_mp<RowBand8w>(st, grid, lds, a, t);
-      else if (band == 16) launch_planes_mp<RowBand16n>(st, grid, lds, a, t);
-      else if (band == 8 && bs.narrow) launch_planes_mp<RowBand8n>(st, grid, lds, a, t);
-      else if (band == 8) launch_planes_mp<RowBand8>(st, grid, lds, a, t);
-      else if (band == 4) launch_planes_mp<RowBand4>(st, grid, lds, a, t);
-      else if (band == 2) launch_planes_mp<RowBand2>(st, grid, lds, a, t);
-      else if (it == 1) launch_planes_mp<RowPair1>(st, grid, lds, a, t);
-      else if (it == 2) launch_planes_mp<RowPair2>(st, grid, lds, a, t);
-      else if (it == 3) launch_planes_mp<RowPair3>(st, grid, lds, a, t);
-      else launch_planes_mp<RowPair4>(st, grid, lds, a, t);
+      const uint32_t chunk = ((q.band >> 8) & 0xff) ? (uint32_t)((q.band >> 8) & 0xff) : 2u;
+      const uint32_t hops = ((q.band >> 19) & 1) ? 0u : ((q.band >> 18) & 1) ? 8u : 1u;  // | 0x80000 (measurement): no counters, a wave strides through its XCD's share
+      bool done = false;
+      with_band_form(m, [&](auto form) { done = launch_form_persist(form, st, m.lds, a, t, n, nbx, nbands, chunk, hops); });
+      if (done) return hipGetLastError();
     }
+#endif  // VPF_LAB_FORMS
+    with_form(m.family, m, [&](auto form) { launch_form_all(form, st, dim3(m.gx, m.gy, m.gz), m.lds, a, t); });
     return hipGetLastError();
+  };
+  // 8-bit Lanczos: the order resize_plan names.  The matrix-core launcher (k_lanczos_mfma.hip) declines at run time what its windows, its table
+  // arena or the device do not allow; a plane it declined takes the fallback planned for it.
+  if (P.lz_tile_all_first) return launch_all();
+  if (P.lz_mfma_all && launch_lanczos_mfma(st, njobs, jobs, n, a)) return hipGetLastError();
+  bool declined[3] = {false, false, false}, all_declined = true;
+  for (int p = 0; p < njobs; p++) {
+    if (P.plane[p].family == RESIZE_LZ_MFMA) declined[p] = !launch_lanczos_mfma(st, 1, &jobs[p], n, a);
+    all_declined = all_declined && declined[p];
   }
+  if ((P.lz_tile_all_fallback && all_declined) || P.all) return launch_all();
   // ---- otherwise: one launch per plane over all frames
   for (int p = 0; p < njobs; p++) {
     const ResizeJob& j = jobs[p];
-    if (fam[p] == FAM_LZ_MFMA) {  // launched above
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      continue;
-    }
-    const dim3 grid1((j.dw + 63) / 64, (j.dh + 3) / 4, n), grid4(((j.dw + 3) / 4 + 63) / 64, (j.dh + 3) / 4, n);
-    if (f32 && (eff[p] == VPF_INTERP_LANCZOS3 || (eff[p] == VPF_INTERP_LINEAR && g[p].scy < 1.0f && tune == 43)) && tune != 9 && tune != 40 && planes_aligned(a, n, j.k, 15, 0)) {
-      const bool lz = eff[p] == VPF_INTERP_LANCZOS3;
-      const float sx = g[p].scx, sy = g[p].scy;
-      const TileShape t = plan_tile(lz, 1, &j.ch, &j.dw, &j.dh, &sx, &sy, n, 4);
-      if (t.ok) {
-        g[p].vec_ok = planes_aligned(a, n, j.k, 0, 15) ? 1 : 0;
-        g[p].a0 = t.ty; g[p].a1 = t.nr; g[p].a2 = t.rowq; g[p].a3 = t.lshift;
-        const dim3 tgrid((j.dw + 63) / 64, (j.dh + t.ty - 1) / t.ty, n);
-#define VPF_TFB(C, L) do { if (t.wpb == 8) launch_plane_batch<TileTaskF32<C, L, 8>>(st, tgrid, t.lds, a, j.k, g[p]); else launch_plane_batch<TileTaskF32<C, L, 4>>(st, tgrid, t.lds, a, j.k, g[p]); } while (0)
-        if (j.ch == 3) { if (lz) VPF_TFB(3, true); else VPF_TFB(3, false); } else { if (lz) VPF_TFB(1, true); else VPF_TFB(1, false); }
-#undef VPF_TFB
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    if (f32) {
-#define VPF_F32B(C) do { if (eff[p] == VPF_INTERP_LANCZOS3) launch_plane_batch<FloatGatherTask<C, VPF_INTERP_LANCZOS3>>(st, grid1, 0, a, j.k, g[p]); \
-                         else if (eff[p] == VPF_INTERP_LINEAR) launch_plane_batch<FloatGatherTask<C, VPF_INTERP_LINEAR>>(st, grid1, 0, a, j.k, g[p]); \
-                         else launch_plane_batch<FloatGatherTask<C, VPF_INTERP_NEAREST>>(st, grid1, 0, a, j.k, g[p]); } while (0)
-      if (j.ch == 3) VPF_F32B(3); else VPF_F32B(1);
-#undef VPF_F32B
-    } else if (fam[p] == FAM_HALF3) {
-      launch_plane_batch<Half3R16Task>(st, dim3((g[p].a1 + 3) / 4, 1, n), 0, a, j.k, g[p]);
-    } else if (fam[p] == FAM_HALF) {
-      const dim3 hgrid((j.dw / 4 + 63) / 64, (j.dh + 3) / 4, n);
-      if (j.ch == 1) launch_plane_batch<HalfTask<1>>(st, hgrid, 0, a, j.k, g[p]);
-      else if (j.ch == 2) launch_plane_batch<HalfTask<2>>(st, hgrid, 0, a, j.k, g[p]);
-      else launch_plane_batch<HalfTask<3>>(st, hgrid, 0, a, j.k, g[p]);
-    } else if (fam[p] == FAM_TILE) {
-      const uint32_t lds = rowb[p] & 0xffffffu, wpb = rowb[p] >> 24;
-      const dim3 tgrid((j.dw + 63) / 64, (j.dh + g[p].a0 - 1) / g[p].a0, n);
-#define VPF_TILEB(C) do { if (wpb == 8) launch_plane_batch<TileTask<C, 8>>(st, tgrid, lds, a, j.k, g[p]); \
-                          else launch_plane_batch<TileTask<C, 4>>(st, tgrid, lds, a, j.k, g[p]); } while (0)
-      if (j.ch == 1) VPF_TILEB(1); else if (j.ch == 2) VPF_TILEB(2); else VPF_TILEB(3);
-#undef VPF_TILEB
-    } else if (fam[p] == FAM_LZ_TILE) {
-      const uint32_t lds = rowb[p] & 0xffffffu, wpb = rowb[p] >> 24;
-      const dim3 tgrid((j.dw + 63) / 64, (j.dh + g[p].a0 - 1) / g[p].a0, n);
-#define VPF_LZTB(C) do { if (wpb == 8) launch_plane_batch<LanczosTileTask<C, 8>>(st, tgrid, lds, a, j.k, g[p]); \
-                         else launch_plane_batch<LanczosTileTask<C, 4>>(st, tgrid, lds, a, j.k, g[p]); } while (0)
-      if (j.ch == 1) VPF_LZTB(1); else if (j.ch == 2) VPF_LZTB(2); else VPF_LZTB(3);
-#undef VPF_LZTB
-    } else if (fam[p] == FAM_ROWPAIR) {
-      g[p].a0 = rowb[p] / 16;
-      const BandPlan bs = plan_band(1, &j, n, a);
-      const int band = bs.rows;
-      if (band > 1) {
-        g[p].a0 = bs.rb / 16; g[p].a1 = bs.slots; g[p].a2 = bs.nb;
-        const uint32_t wcols = 64u * band_px(j.ch, bs.p1), nbw = bs.nb ? bs.nb : 1u;
-        const dim3 bgrid((j.dw + wcols - 1) / wcols, (j.dh + 4 * band * nbw - 1) / (4 * band * nbw), n);
-        const uint32_t blds = 4 * bs.slots * bs.rb + 16;
-#define VPF_RBB(C) do { if (band == 4 && bs.p1 == 8) launch_plane_batch<RowBandTask<C, 4, 1, 8, true>>(st, bgrid, blds, a, j.k, g[p]); else if (band == 16 && bs.p1 == 8) launch_plane_batch<RowBandTask<C, 16, 1, 8>>(st, bgrid, blds, a, j.k, g[p]); else if (band == 8 && bs.p1 == 8) launch_plane_batch<RowBandTask<C, 8, 1, 8>>(st, bgrid, blds, a, j.k, g[p]); \
-                        else if (band == 16) launch_plane_batch<RowBandTask<C, 16, 1>>(st, bgrid, blds, a, j.k, g[p]); else if (band == 8 && bs.narrow) launch_plane_batch<RowBandTask<C, 8, 1>>(st, bgrid, blds, a, j.k, g[p]); \
-                        else if (band == 8) launch_plane_batch<RowBandTask<C, 8>>(st, bgrid, blds, a, j.k, g[p]); else if (band == 4) launch_plane_batch<RowBandTask<C, 4>>(st, bgrid, blds, a, j.k, g[p]); \
-                        else launch_plane_batch<RowBandTask<C, 2>>(st, bgrid, blds, a, j.k, g[p]); } while (0)
-        if (j.ch == 1) VPF_RBB(1); else if (j.ch == 2) VPF_RBB(2); else VPF_RBB(3);
-#undef VPF_RBB
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-      const uint32_t it = (rowb[p] + 1023) / 1024, lds = 4 * 2 * rowb[p] + 16;
-#define VPF_RPB(C) do { if (it == 1) launch_plane_batch<RowPairTask<C, 1>>(st, grid4, lds, a, j.k, g[p]); else if (it == 2) launch_plane_batch<RowPairTask<C, 2>>(st, grid4, lds, a, j.k, g[p]); \
-                        else if (it == 3) launch_plane_batch<RowPairTask<C, 3>>(st, grid4, lds, a, j.k, g[p]); else launch_plane_batch<RowPairTask<C, 4>>(st, grid4, lds, a, j.k, g[p]); } while (0)
-      if (j.ch == 1) VPF_RPB(1); else if (j.ch == 2) VPF_RPB(2); else VPF_RPB(3);
-#undef VPF_RPB
-    } else if (fam[p] == FAM_LZ_GATHER) {
-      if (j.ch == 1) launch_plane_batch<LanczosGatherTask<1>>(st, grid1, 0, a, j.k, g[p]);
-      else if (j.ch == 2) launch_plane_batch<LanczosGatherTask<2>>(st, grid1, 0, a, j.k, g[p]);
-      else launch_plane_batch<LanczosGatherTask<3>>(st, grid1, 0, a, j.k, g[p]);
-    } else if (eff[p] == VPF_INTERP_LINEAR) {
-      launch_gather_ch<GatherTask, VPF_INTERP_LINEAR>(st, grid4, a, j, g[p]);
-    } else {
-      launch_gather_ch<GatherTask, VPF_INTERP_NEAREST>(st, grid4, a, j, g[p]);
+    const ResizeLaunch& l = P.plane[p];
+    const int fam = declined[p] ? l.fallback : l.family;
+    const PlaneGeom g = geom(p, l);
+    const dim3 grid(l.gx, l.gy, l.gz);
+    switch (fam) {
+      case RESIZE_LZ_MFMA: break;  // launched above
+      case RESIZE_F32_TILE:
+        with_ch_f32(j.ch, [&](auto C) { with_bool(l.lz, [&](auto LZ) { with_value<8, 4>(l.wpb, [&](auto W) {
+          launch_plane_batch<TileTaskF32<decltype(C)::value, decltype(LZ)::value, decltype(W)::value>>(st, grid, l.lds, a, j.k, g); }); }); });
+        break;
+      case RESIZE_F32_GATHER:
+        with_ch_f32(j.ch, [&](auto C) { with_value<VPF_INTERP_LANCZOS3, VPF_INTERP_LINEAR, VPF_INTERP_NEAREST>(l.eff, [&](auto I) {
+          launch_plane_batch<FloatGatherTask<decltype(C)::value, decltype(I)::value>>(st, grid, 0, a, j.k, g); }); });
+        break;
+      case RESIZE_HALF3: launch_plane_batch<Half3R16Task>(st, grid, 0, a, j.k, g); break;
+      case RESIZE_HALF: with_ch(j.ch, [&](auto C) { launch_plane_batch<HalfTask<decltype(C)::value>>(st, grid, 0, a, j.k, g); }); break;
+      case RESIZE_LZ_GATHER: with_ch(j.ch, [&](auto C) { launch_plane_batch<LanczosGatherTask<decltype(C)::value>>(st, grid, 0, a, j.k, g); }); break;
+      case RESIZE_GATHER:
+        with_ch(j.ch, [&](auto C) { with_value<VPF_INTERP_LINEAR, VPF_INTERP_NEAREST>(l.eff, [&](auto I) {
+          launch_plane_batch<GatherTask<decltype(C)::value, decltype(I)::value>>(st, grid, 0, a, j.k, g); }); });
+        break;
+      default:  // RESIZE_TILE, RESIZE_LZ_TILE, RESIZE_ROWPAIR, RESIZE_BAND
+        with_form(fam, l, [&](auto form) { launch_form_plane(form, st, grid, l.lds, a, j, g); });
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

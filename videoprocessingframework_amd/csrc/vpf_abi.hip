@@ -408,22 +408,13 @@ vpf_status vpf_resize_batch(const vpf_exec* exec, int fmt, int interp, vpf_size 
   if (guard.err != hipSuccess) return status_of(guard.err);
   hipStream_t st = static_cast<hipStream_t>(exec->stream);
   const int np = num_planes(fmt);
-  const bool forced_family = (tuning(VPF_TUNE_RESIZE_MFMA) & 0xffff) >= 2 || (tuning(VPF_TUNE_RESIZE_BAND) & 0xffff) >= 2 || (tuning(VPF_TUNE_RESIZE_BAND) >> 16);  // measurement runs: the batch kernels on one frame
-  if (n == 1 && nj == 1 && !forced_family) {  // one plane of one frame: the scalar-argument kernel entries (kernarg preload)
-    const vpf_plane &s0 = frames[0].src[0], &d0 = frames[0].dst[0];
-    const hipError_t e = f32 ? launch_resize_f32(st, jobs[0].ch, interp, ss.width, ss.height, static_cast<const uint8_t*>(s0.ptr), s0.pitch, ds.width, ds.height,
-                                                 static_cast<uint8_t*>(d0.ptr), d0.pitch)
-                             : launch_resize(st, jobs[0].ch, interp, ss.width, ss.height, static_cast<const uint8_t*>(s0.ptr), s0.pitch, ds.width, ds.height,
-                                             static_cast<uint8_t*>(d0.ptr), d0.pitch);
-    return status_of(e);
-  }
   const uint32_t per = frames_per_dispatch(frame_bytes(fmt, ss) + frame_bytes(fmt, ds), interp != VPF_INTERP_LANCZOS3);  // 128 for small planes, 64 for mid-sized bilinear ones, else 32 (the launchers take the small frame table for up to 32)
   for (uint32_t base = 0; base < n; base += per) {
     const uint32_t m = (n - base < per) ? n - base : per;
     BatchArgsL a;
     for (uint32_t i = 0; i < m; i++) fill_desc(a.f[i], frames[base + i].src, np, frames[base + i].dst, np);
     for (uint32_t i = m; i < ((m + 7u) & ~7u); i++) a.f[i] = a.f[0];  // (entries beyond the batch are never read: blockIdx runs over m frames; a few copies keep the tail of the last cache line defined)
-    const hipError_t e = launch_resize_jobs(st, f32, interp, nj, jobs, m, a);
+    const hipError_t e = launch_resize_planned(st, f32, interp, nj, jobs, m, a, n);  // (one plane of one frame: the scalar-argument entries, resize_plan)
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;

@@ -1,6 +1,7 @@
-// vpf_classes.h — the format classes and frame-table sizes both the launchers (vpf_internal.h) and the HIP-free planning headers
-// (vpf_fused_plan.h, compiled with plain g++ by the CPU tests) name.  No HIP in here.
+// vpf_classes.h — the format classes, frame-table sizes and resize-kernel constants both the launchers and kernels (vpf_internal.h) and the
+// HIP-free planning headers (vpf_fused_plan.h, vpf_resize_plan.h, compiled with plain g++ by the CPU tests) name.  No HIP in here.
 #pragma once
+#include <stdint.h>
 
 namespace vpf {
 
@@ -20,5 +21,18 @@ enum FmtClass : int {
                   // sample is narrowed to 8 bits at the load (p16_to_8, vpf_device.h), from there the code is FC_NV12's
   FC_TENSOR_NHWC = 8,  // FC_TENSOR's elements in ONE interleaved plane per frame (VPF_TENSOR_NHWC): element (y, x, c) at d[0] + y dp[0] + (3 x + c) elem
 };
+
+// one plane of a resize: `ch` interleaved channels (for float surfaces: floats per pixel), `k` = plane index in FrameDesc
+struct ResizeJob {
+  int ch, k;
+  uint32_t sw, sh, dw, dh;
+};
+
+// What the plain resize kernels (k_bilinear_blend.h, k_resize.hip) and the policy that sizes their launches (vpf_resize_plan.h) both name:
+constexpr uint32_t kResizeRowBytes = 4096;  // largest strip (IT = 4 dense 1-KiB loads per source row)
+constexpr int kBandSlots = 8;  // source rows a wave's strips can hold (twice as many when a strip is a single 1-KiB staging pass: IT = 1)
+constexpr int band_px(int ch, int p1) { return ch == 1 ? p1 : 4; }  // pixels per lane of a row-band launch: P1 on 1-channel planes, else 4
+constexpr uint32_t kLzStripQ = 128;  // at most 2 KiB of source bytes per row of a tile
+constexpr int kTileStagePasses = 6;  // staging loads a thread may have in flight (the policy sizes tiles accordingly)
 
 }  // namespace vpf

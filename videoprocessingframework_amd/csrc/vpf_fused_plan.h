@@ -72,8 +72,8 @@ inline FusedPlan fused_plan(const FusedShape& q) {
   // destination alignment the vector stores need: 4 px x element size per lane and plane (1-B elements: the 8-bit classes)
   const uint32_t dmask = nhwc ? 15u : dst_fc == FC_TENSOR ? (q.dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
   p.vec_ok = all_aligned(q.dst_bits, dmask);
-  // strip bytes a wave of the per-tap LDS kernels needs per source row (lds_strip_bytes, k_bilinear_blend.h: 0 under variant 9, the forced
-  // generic form, and for an unaligned source).  lds_strip_bytes looks at frame 0's luma plane only; `rowb` is consumed under lds_ok alone —
+  // strip bytes a wave of the per-tap LDS kernels needs per source row (0 under variant 9, the forced generic form, and for an unaligned
+  // source).  The launcher's lds_strip_bytes looked at frame 0's luma plane only; `rowb` is consumed under lds_ok alone —
   // the LDS size and `rowq` of the band and per-tap LDS families, both picked only where lds_ok holds — and lds_ok asks every plane of every
   // frame for the same 16 B, frame 0's luma plane among them.  So the alignment term of lds_strip_bytes is part of src_bits & 15.
   const uint32_t rowb = variant == 9 ? 0u : vpf_bound_strip_bytes(1, sw, dw, kFusedRowBytes, 256);

@@ -227,17 +227,11 @@ hipError_t launch_tensor_to_yuv(hipStream_t st, bool nv12, const Rgb2YuvCoef& c,
                                 const BatchArgs& a, bool nhwc = false);
 hipError_t launch_relayout(hipStream_t st, int src_fmt, int dst_fmt, uint32_t w, uint32_t h, uint32_t n,
                            const BatchArgs& a);
-hipError_t launch_resize(hipStream_t st, int channels, int interp, uint32_t sw, uint32_t sh, const uint8_t* src,
-                         uint32_t spitch, uint32_t dw, uint32_t dh, uint8_t* dst, uint32_t dpitch);
-hipError_t launch_resize_f32(hipStream_t st, int channels, int interp, uint32_t sw, uint32_t sh, const uint8_t* src,
-                             uint32_t spitch, uint32_t dw, uint32_t dh, uint8_t* dst, uint32_t dpitch);
-// one plane of a resize: `ch` interleaved channels (for float surfaces: floats per pixel), `k` = plane index in FrameDesc
-struct ResizeJob {
-  int ch, k;
-  uint32_t sw, sh, dw, dh;
-};
-// all planes of a format over n <= kMaxBatch same-shape frames in as few launches as possible (k_resize.hip)
-hipError_t launch_resize_jobs(hipStream_t st, bool f32, int interp, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a);
+// (ResizeJob, one plane of a resize: vpf_classes.h)
+// all planes of a format (8-bit, or f32: float surfaces) over n <= kMaxBatch same-shape frames in as few launches as possible, one plane of one
+// frame through the scalar-argument entries: whatever resize_plan (vpf_resize_plan.h) names; `call_n`: the frames of the whole call this dispatch
+// is a part of; k_resize.hip
+hipError_t launch_resize_planned(hipStream_t st, bool f32, int interp, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a, uint32_t call_n);
 // 8-bit Lanczos-3 on the matrix cores (k_lanczos_mfma.hip): every plane in `jobs` over n frames in ONE dispatch; false when it does not apply
 // (window / ring bounds of vpf_plan_bounds.h, 16-B aligned rows) and nothing was launched
 bool launch_lanczos_mfma(hipStream_t st, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a);
