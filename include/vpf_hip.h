@@ -383,6 +383,48 @@ VPF_API vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int src_fm
 VPF_API vpf_rect vpf_letterbox_fit(vpf_size src, vpf_size dst); /* host only */
 
 /*
+ * The same with the boxes in DEVICE memory: the padded ReID / face / OCR crops behind a detector and its NMS that run on the GPU.  No sync, no copy of
+ * the boxes to the host, and a captured graph replays with the boxes, placements and count of REPLAY time.  Where vpf_convert_resize_tensor_rois_dev
+ * stretches every box to dst_size, this entry keeps its aspect: the kernel fits the box into the plane itself, because only the kernel sees the box.
+ * `frames` is a HOST array of the planes of n_frames (1 .. 128) WHOLE frames of src_size = (W, H) (vpf_frame_src), consumed before return.
+ * table->boxes points to DEVICE memory: entry k = five int32 (frame, x, y, width, height) at byte k * box_stride (vpf_roi_dev: a row of a torch.int32
+ * [K, 5] tensor; any multiple of 4 from 20 up); table->dst_rects to job k's placement, four int32 (ix, iy, iw, ih) at byte k * rect_stride (a row of a
+ * torch.int32 [K, 4] tensor: 16; any multiple of 4 from 16 up), or NULL: the kernel fits; table->count to ONE device int32, or NULL.  The kernel reads
+ * all three WHEN IT RUNS on exec->stream; the host never dereferences them: the caller orders their producer before this call on that stream.
+ *   c = clamp(*count, 0, max_n); count == NULL: c = max_n.  max_n (1 .. 65535) is the size of the dispatch.
+ *   job k < c, VALID — the box passes vpf_convert_resize_tensor_rois_dev's test, and with dst_rects also iw >= 1, ih >= 1, ix >= 0, iy >= 0,
+ *        ix + iw <= dw, iy + ih <= dh, evaluated without overflow for any four ints —: every element of the job's WHOLE dst_size planes (dst[c].ptr +
+ *        k * dst_job_stride with dst[c].pitch) is bit for bit what vpf_convert_letterbox_tensor writes for (frames[frame], rect = (x, y, width,
+ *        height), dst_rect), where dst_rect = vpf_letterbox_fit((width, height), dst_size) when dst_rects == NULL and the row's four ints otherwise;
+ *        for the same src_fmt (NV12, YUV420, P10, P12), dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC (dst[0] = the one interleaved plane of job 0), pad and
+ *        colour rules;
+ *   job k < c, INVALID (the box or the placement): every element of its planes takes the epilogue of pad[c], round_to_dtype(fmaf(pad[c], scale[c],
+ *        bias[c])) (0 0 0 when opts == NULL) — what a letterbox job leaves where there is no picture.  No byte of any frame is read;
+ *   job k >= c: NOTHING is written, and neither its box nor its placement is read — the tables may be shorter than max_n.
+ * Every element of every job < c is written exactly once, and nothing else is written.  One dispatch over (16 x 256 tiles of the destination plane,
+ * max_n); every workgroup decides for its own tile whether it is pad, or its source window is converted once into LDS or sampled per tap (identical
+ * bits; the host-table entry decides per job).
+ * Checked on the host before any device access, with vpf_convert_resize_tensor_rois_dev's list and answers, plus VPF_ERR_BAD_ARG for dst_rects not
+ * 4-byte aligned, rect_stride < 16 or not a multiple of 4 (with dst_rects), and a non-zero `reserved`, here or in opts.  Whatever the device tables
+ * hold, the call returns VPF_OK.  Under stream capture the frame and destination pointers are baked into the graph, as in every entry; boxes,
+ * placements and count are read at every replay.
+ */
+typedef struct vpf_letterbox_dev {
+  const vpf_roi_dev* boxes; /* DEVICE: (frame, x, y, width, height), entry k at byte k * box_stride */
+  const int32_t* dst_rects; /* DEVICE: (ix, iy, iw, ih) of job k at byte k * rect_stride, or NULL = fit in the kernel */
+  const int32_t* count;     /* DEVICE: one int32, or NULL = max_n */
+  uint32_t box_stride;      /* >= 20, multiple of 4 */
+  uint32_t rect_stride;     /* >= 16, multiple of 4; ignored when dst_rects == NULL */
+  uint32_t max_n;           /* 1 .. 65535: grid z */
+  uint32_t reserved;        /* must be 0 */
+  vpf_plane dst[3];         /* WHOLE dst_size planes of job 0 (one plane with VPF_TENSOR_NHWC) */
+  uint64_t dst_job_stride;  /* bytes from job k's planes to job k + 1's: multiple of the element size */
+} vpf_letterbox_dev; /* 96 bytes, no implicit padding */
+VPF_API vpf_status vpf_convert_letterbox_tensor_dev(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                    vpf_size dst_size, uint32_t n_frames, const vpf_frame_src* frames, const vpf_letterbox_dev* table,
+                                                    const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts);
+
+/*
  * Fused multi-ROI affine warp -> normalised planar tensor: `n` crops of decoded NV12 / YUV420 frames (or P10 / P12 ones, narrowed to 8 bits at the
  * load: "10 / 12-bit sources" at vpf_convert_resize_tensor) that are NOT axis-aligned (aligned faces, rotated
  * text boxes, oriented detections, flips, shears), each sampled through a 2 x 3 matrix of its own into the ONE size dst_size and normalised, in

@@ -739,6 +739,101 @@ def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_
     return out, placement
 
 
+def letterbox_fit_boxes(boxes, dw, dh) -> torch.Tensor:
+    """The placements device_letterbox_to_normalized_tensor computes for itself when it gets no dst_rects, as a table: `boxes` = the integer [K, 5] table
+    of (surface_index, x, y, w, h) rows -> a torch.int32 [K, 4] table of (ix, iy, iw, ih), row k = the aspect-preserving, centred fit of a w x h picture
+    inside dw x dh (PyNvCodec.LetterboxFit, vpf_letterbox_fit: integer arithmetic, round half up).  Pure torch in int64, on whatever device the boxes
+    live on: no sync.  A row with w < 1 or h < 1 gives zeros — as a dst_rects row an invalid placement, whose output frame is the normalised pad.
+    What a caller needs to map a keypoint or a box of the crop's network back (x_frame = x + (x_dst - ix + 0.5) * w / iw - 0.5, likewise y), and as an
+    explicit `dst_rects` it reproduces the dst_rects=None path bit for bit."""
+    fn = "letterbox_fit_boxes"
+    b = torch.as_tensor(boxes)
+    if b.dim() != 2 or b.shape[1] != 5 or b.dtype.is_floating_point or b.dtype.is_complex or b.dtype == torch.bool:
+        raise ValueError(f"{fn}: boxes must be an integer tensor of shape [K, 5], got {b.dtype} {tuple(b.shape)}")
+    DW, DH = int(dw), int(dh)
+    if not (1 <= DW <= 65536 and 1 <= DH <= 65536):
+        raise ValueError(f"{fn}: dw and dh must lie in 1 .. 65536, got {DW} x {DH}")
+    w, h = b[:, 3].to(torch.int64), b[:, 4].to(torch.int64)
+    bad = (w < 1) | (h < 1)
+    one = torch.ones_like(w)
+    w, h = torch.where(bad, one, w), torch.where(bad, one, h)  # (no division by zero; the row is zeroed below)
+    wide = w * DH >= h * DW  # width-limited
+    num = torch.where(wide, 2 * h * DW + w, 2 * w * DH + h)
+    den = torch.where(wide, 2 * w, 2 * h)
+    q = torch.div(num, den, rounding_mode="floor").clamp(min=1)  # round half up; all operands positive
+    q = torch.minimum(q, torch.where(wide, DH * one, DW * one))
+    iw, ih = torch.where(wide, DW * one, q), torch.where(wide, q, DH * one)
+    ix, iy = torch.div(DW - iw, 2, rounding_mode="floor"), torch.div(DH - ih, 2, rounding_mode="floor")
+    out = torch.stack([ix, iy, iw, ih], dim=1)
+    return torch.where(bad[:, None], torch.zeros_like(out), out).to(torch.int32)
+
+
+def device_letterbox_to_normalized_tensor(resizer, surfaces, boxes, mean, std, count=None, dst_rects=None, pad=(114, 114, 114), dtype=torch.float32,
+                                          bgr=False, out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
+    """letterbox_to_normalized_tensor for boxes that never leave the GPU (PySurfaceConvertResizer.ExecuteLetterboxDevToTensor,
+    vpf_convert_letterbox_tensor_dev): the padded ReID / face / OCR crops behind a detector and its NMS, without synchronisation, without a copy of the
+    boxes to the host, in one dispatch, and capturable in a graph that replays with the boxes, placements and count of replay time.
+    `boxes` and `count` as in device_rois_to_normalized_tensor.  `dst_rects`: a device torch.int32 tensor [K, 4] of (ix, iy, iw, ih) rows on the boxes'
+    device (last stride 1, row stride >= 4), or None: the kernel fits every box into the resizer's destination size itself, aspect-preserving and
+    centred — letterbox_fit_boxes(boxes, dw, dh) is that table, for the way back.  `pad` as in letterbox_to_normalized_tensor.  Returns [K, 3, dh, dw]:
+      rows below the count, valid box and placement      the bits letterbox_to_normalized_tensor gives for that rectangle and placement;
+      rows below the count, invalid box or placement     the normalised pad in every element: nothing is clipped and no surface is read;
+      rows at or behind the count                        NOT WRITTEN: undefined in a fresh tensor (torch.empty), unchanged in `out`.
+    `out`, channels_last, dtype, bgr, the returned tensor and the stream ordering: as device_rois_to_normalized_tensor.  ValueError for what that
+    function refuses, for a bad pad, and for dst_rects on the host or on another device than the boxes, of another dtype or shape."""
+    fn = "device_letterbox_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    try:
+        pad = [operator.index(v) for v in pad]
+    except TypeError:
+        raise ValueError(f"{fn}: pad must hold three integers, got {pad!r}") from None
+    if len(pad) != 3 or any(not 0 <= v <= 255 for v in pad):
+        raise ValueError(f"{fn}: pad must hold three values in 0..255, got {pad}")
+    surfaces = list(surfaces)
+    if not 1 <= len(surfaces) <= 128:
+        raise ValueError(f"{fn}: 1 .. 128 surfaces per call, got {len(surfaces)}")
+    if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda:
+        raise ValueError(f"{fn}: boxes must be a device tensor (for host boxes there is letterbox_to_normalized_tensor)")
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise ValueError(f"{fn}: boxes must be torch.int32 of shape [K, 5], got {boxes.dtype} {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if n > 65535:
+        raise ValueError(f"{fn}: at most 65535 boxes per call, got {n}")
+    if boxes.stride(1) != 1 or (n > 1 and boxes.stride(0) < 5):
+        raise ValueError(f"{fn}: boxes needs unit stride along its rows and a row stride of at least 5, got strides {boxes.stride()}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1:
+            raise ValueError(f"{fn}: count must be a device torch.int32 tensor of one element, or None")
+        if count.device != boxes.device:
+            raise ValueError(f"{fn}: count lives on {count.device}, boxes on {boxes.device}")
+    if dst_rects is not None:
+        if not isinstance(dst_rects, torch.Tensor) or not dst_rects.is_cuda:
+            raise ValueError(f"{fn}: dst_rects must be a device tensor, or None (for host placements there is letterbox_to_normalized_tensor)")
+        if dst_rects.dtype != torch.int32 or dst_rects.dim() != 2 or tuple(dst_rects.shape) != (n, 4):
+            raise ValueError(f"{fn}: dst_rects must be torch.int32 of shape [{n}, 4], got {dst_rects.dtype} {tuple(dst_rects.shape)}")
+        if dst_rects.device != boxes.device:
+            raise ValueError(f"{fn}: dst_rects lives on {dst_rects.device}, boxes on {boxes.device}")
+        if dst_rects.stride(1) != 1 or (n > 1 and dst_rects.stride(0) < 4):
+            raise ValueError(f"{fn}: dst_rects needs unit stride along its rows and a row stride of at least 4, got strides {dst_rects.stride()}")
+    w, h = resizer.DstSize()
+    if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != boxes.device:
+        raise ValueError(f"{fn}: out lives on {out.device}, boxes on {boxes.device}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last, boxes.device)
+    if n == 0:
+        return out
+    elem = out.element_size()
+    with _on_task_stream(resizer, out.device):
+        ok = resizer.ExecuteLetterboxDevToTensor(surfaces, boxes.data_ptr(), n, count.data_ptr() if count is not None else 0,
+                                                 dst_rects.data_ptr() if dst_rects is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype],
+                                                 [float(m) for m in mean], [float(v) for v in std], cc_ctx, bool(bgr), pad, s2 * elem, s1 * elem,
+                                                 (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (boxes.stride(0) if n > 1 else 5),
+                                                 4 * (dst_rects.stride(0) if dst_rects is not None and n > 1 else 4))
+    if not ok:
+        _refused(fn, _RESIZER_REFUSED)
+    return out
+
+
 def from_normalized_tensor(converter, tensor, mean, std, bgr=False, cc_ctx=None, out=None, channels_last=False):
     """A model's output -> NV12 / YUV420 surfaces for the encoder, in one pass (PyTensorToSurface.ExecuteBatch): `tensor` is [N, 3, H, W] or
     [3, H, W] of float32 / float16 / bfloat16 on the device, normalised with torchvision's mean / std (per input plane; B G R planes when

@@ -32,7 +32,7 @@ EXPORTS = [
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
     "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
-    "vpf_convert_persp_tensor",
+    "vpf_convert_persp_tensor", "vpf_convert_letterbox_tensor_dev",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -112,6 +112,13 @@ class RoisDev(C.Structure):
     """vpf_rois_dev: where the boxes and their count lie (device pointers), how many jobs the dispatch holds, job 0's planes and the stride"""
     _fields_ = [("boxes", C.c_void_p), ("count", C.c_void_p), ("box_stride", C.c_uint32), ("max_n", C.c_uint32), ("dst", Plane * 3),
                 ("dst_job_stride", C.c_uint64)]
+
+
+class LetterboxDev(C.Structure):
+    """vpf_letterbox_dev: where the boxes, the optional placements and the count lie (device pointers), how many jobs the dispatch holds, job 0's WHOLE
+    planes and the stride"""
+    _fields_ = [("boxes", C.c_void_p), ("dst_rects", C.c_void_p), ("count", C.c_void_p), ("box_stride", C.c_uint32), ("rect_stride", C.c_uint32),
+                ("max_n", C.c_uint32), ("reserved", C.c_uint32), ("dst", Plane * 3), ("dst_job_stride", C.c_uint64)]
 
 
 class WarpsDev(C.Structure):
@@ -217,6 +224,8 @@ def lib() -> C.CDLL:
         L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
         L.vpf_convert_warp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(WarpsDev), PN,
                                                   C.POINTER(WarpOpts)]
+        L.vpf_convert_letterbox_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(LetterboxDev), PN,
+                                                       C.POINTER(LetterboxOpts)]
         L.vpf_letterbox_fit.argtypes = [Size, Size]
         L.vpf_letterbox_fit.restype = Rect
         L.vpf_tensor_convert_supported.argtypes = [C.c_int] * 3
@@ -529,6 +538,31 @@ def convert_letterbox_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, jobs, no
                                             C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
     if check:
         _check(st, "vpf_convert_letterbox_tensor")
+    return st
+
+
+def make_letterbox_dev(boxes_ptr, max_n, dst, dst_job_stride, count_ptr=None, dst_rects_ptr=None, box_stride=20, rect_stride=16, reserved=0) -> LetterboxDev:
+    """vpf_letterbox_dev: boxes_ptr / dst_rects_ptr / count_ptr are DEVICE addresses (dst_rects_ptr None: the kernel fits every box into the plane;
+    count_ptr None: max_n jobs), dst = job 0's WHOLE planes as in planes(), dst_job_stride = bytes from one job's planes to the next's"""
+    t = LetterboxDev()
+    t.boxes, t.dst_rects, t.count = boxes_ptr or None, dst_rects_ptr or None, count_ptr or None
+    t.box_stride, t.rect_stride, t.max_n, t.reserved, t.dst_job_stride = box_stride, rect_stride, max_n, reserved, dst_job_stride
+    d = planes(dst)
+    for k in range(3):
+        t.dst[k].ptr, t.dst[k].pitch = d[k].ptr, d[k].pitch
+    return t
+
+
+def convert_letterbox_tensor_dev(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, frames, table: LetterboxDev, norm: TensorNorm, opts: LetterboxOpts = None,
+                                 n_frames=None, check=True) -> int:
+    """frames: FrameSrc array from make_frame_srcs() (at most 128), table: make_letterbox_dev(), opts: make_letterbox_opts() or None; the kernel reads
+    boxes, placements and count when it runs on ex.stream: no sync, no copy, capturable"""
+    st = lib().vpf_convert_letterbox_tensor_dev(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                                (len(frames) if frames is not None else 0) if n_frames is None else n_frames, frames,
+                                                C.byref(table) if table is not None else None, C.byref(norm) if norm is not None else None,
+                                                C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_letterbox_tensor_dev")
     return st
 
 

@@ -363,6 +363,32 @@ public:
     return TASK_EXEC_SUCCESS == task_->RunTensorLetterbox(a.data(), (uint32_t)a.size(), index.data(), rects.data(), drects.data(), (uint32_t)rois.size(),
                                                           planes.data(), norm, &opts, cc.get());
   }
+  // additive: up to max_n letterbox jobs whose boxes lie in DEVICE memory -> a normalised planar tensor [max_n, 3, dh, dw] at device address `dst`
+  // (vpf_convert_letterbox_tensor_dev): ExecuteRoisDevToTensor's boxes and count, plus job k's placement, four int32 (ix, iy, iw, ih) at rects +
+  // k rect_stride (rects 0: the kernel fits box k into dw x dh), `pad` (per output channel) wherever the frame shows no picture;
+  // std::invalid_argument (ValueError) for a pad value outside 0..255
+  bool ExecuteLetterboxDevToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t boxes, uint32_t max_n, uint64_t count, uint64_t rects,
+                                   uint64_t dst, uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std,
+                                   std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::vector<int64_t>& pad, uint64_t row_pitch,
+                                   uint64_t plane_stride, uint64_t frame_stride, bool channels_last, uint32_t box_stride, uint32_t rect_stride) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (pad.size() != 3) throw std::invalid_argument("pad needs three values");
+    vpf_letterbox_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    for (int c = 0; c < 3; c++) {
+      if (pad[c] < 0 || pad[c] > 255) throw std::invalid_argument("pad values must lie in 0..255");
+      opts.pad[c] = (uint8_t)pad[c];
+    }
+    if (src.empty() || src.size() > 128 || !boxes || !max_n || !dst) return false;
+    std::vector<vpf_plane> planes;  // two jobs' planes: the second minus the first is the stride from job to job
+    if (!tensor_planes(dst, dtype, 2, task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    const uint64_t job_stride = (uint64_t)((uintptr_t)planes[channels_last ? 1 : 3].ptr - (uintptr_t)planes[0].ptr);
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    return TASK_EXEC_SUCCESS == task_->RunTensorLetterboxDev(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)boxes, box_stride,
+                                                             (const void*)(uintptr_t)rects, rect_stride, max_n, (const void*)(uintptr_t)count, planes.data(),
+                                                             job_stride, norm, &opts, cc.get());
+  }
   size_t GetStream() const { return (size_t)task_->GetStream(); }
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
@@ -906,6 +932,18 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "K letterbox jobs: rectangle rois[i] = (surface_index, x, y, w, h) resized into dst_rects[i] = (ix, iy, iw, ih) of its [3, dh, dw] frame of the "
            "planar tensor at device address ptr, pad (per output channel, 0..255) everywhere else in the frame, normalised (strides in bytes, 0 = "
            "contiguous); one dispatch per 82 regions.  ValueError for a bad pad and for rois / dst_rects of different lengths")
+      .def("ExecuteLetterboxDevToTensor", &PySurfaceConvertResizer::ExecuteLetterboxDevToTensor, py::arg("surfaces"), py::arg("boxes_ptr"), py::arg("max_n"),
+           py::arg("count_ptr"), py::arg("rects_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
+           py::arg("bgr") = false, py::arg("pad") = std::vector<int64_t>{0, 0, 0}, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::arg("box_stride") = 20u, py::arg("rect_stride") = 16u,
+           py::call_guard<py::gil_scoped_release>(),
+           "Up to max_n letterbox jobs whose boxes lie in DEVICE memory: entry k = five int32 (surface_index, x, y, w, h) at boxes_ptr + k box_stride, its "
+           "placement four int32 (ix, iy, iw, ih) at rects_ptr + k rect_stride (0 = the kernel fits the box into the task's destination size, "
+           "aspect-preserving and centred), the first *count_ptr (a device int32; 0 = max_n) of them resized into their placement of frame k of a planar "
+           "tensor [max_n, 3, dh, dw] at device address ptr, pad (per output channel, 0..255) everywhere else in the frame, normalised (strides in bytes, "
+           "0 = contiguous).  The kernel reads boxes, placements and count when it runs on the task's stream: no sync, no copy to the host, capturable.  "
+           "An invalid box or placement gives a frame of the normalised pad; frames at or behind the count are not written.  At most 128 surfaces; one "
+           "dispatch.  ValueError for a bad pad")
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 

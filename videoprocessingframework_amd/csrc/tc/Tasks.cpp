@@ -671,6 +671,31 @@ TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, 
                                                      io.data(), &norm, opts);
   return exec_status(st, "letterbox regions into a tensor");
 }
+TaskExecStatus ConvertResizeSurface::RunTensorLetterboxDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride,
+                                                           const void* dst_rects, uint32_t rect_stride, uint32_t max_n, const void* count,
+                                                           const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm,
+                                                           const vpf_letterbox_opts* opts, const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorLetterboxDev");
+  if (!frames || !n_frames || n_frames > kMaxDevFrames || !boxes || !dst || !max_n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
+  vpf_letterbox_dev table;
+  std::memset(&table, 0, sizeof(table));
+  table.boxes = static_cast<const vpf_roi_dev*>(boxes);
+  table.dst_rects = static_cast<const int32_t*>(dst_rects);
+  table.count = static_cast<const int32_t*>(count);
+  table.box_stride = box_stride;
+  table.rect_stride = rect_stride;
+  table.max_n = max_n;
+  tensor_job_planes(dst, 0, norm, table.dst);
+  table.dst_job_stride = dst_job_stride;
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_letterbox_tensor_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames,
+                                                         fr.data(), &table, &norm, opts);
+  return exec_status(st, "letterbox device-resident regions into a tensor");
+}
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
 // ------------------------------------------------------------------------------------------ TensorToSurface

@@ -91,6 +91,12 @@ public:
   TaskExecStatus RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, const vpf_rect* dst_rects,
                                     uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts,
                                     const ColorspaceConversionContext* ctx);
+  // up to max_n letterbox jobs whose boxes lie in DEVICE memory (vpf_convert_letterbox_tensor_dev): RunTensorRoisDev's boxes and count, plus job k's
+  // placement, four int32 (ix, iy, iw, ih) at dst_rects + k rect_stride, or nullptr: the kernel fits box k into the task's destination size
+  // (vpf_letterbox_fit).  dst = the WHOLE planes of job 0; opts == nullptr: pad 0 0 0.  The same colour-context rules as RunTensor.
+  TaskExecStatus RunTensorLetterboxDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride, const void* dst_rects,
+                                       uint32_t rect_stride, uint32_t max_n, const void* count, const vpf_plane* dst, uint64_t dst_job_stride,
+                                       const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts, const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on
 
 private:

@@ -2,6 +2,7 @@
 // kernarg packing.  No CPU fallback of any kind: every success path ends in a HIP kernel launch.
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +12,7 @@
 
 #include "vpf_coef.h"
 #include "vpf_internal.h"
+#include "vpf_job_bounds.h"
 
 namespace vpf {
 
@@ -298,6 +300,31 @@ static void fill_job0_dst(uint8_t* d[3], uint32_t dp[3], const vpf_plane* dst, c
   vpf_plane p[3];
   const int nd = tensor_planes(dst, l, p);
   for (int k = 0; k < nd; k++) { d[k] = static_cast<uint8_t*>(p[k].ptr); dp[k] = p[k].pitch; }
+}
+// The entries whose boxes lie in DEVICE memory (vpf_convert_resize_tensor_rois_dev, vpf_convert_letterbox_tensor_dev): everything they can check without
+// a box — the pointers, the sizes, 1 .. 128 frames, 1 .. 65535 jobs, the box table's alignment and stride, the job stride, every frame's planes and
+// job 0's planes.  The host never dereferences `boxes` or `count`.
+static bool dev_boxes_ok(const vpf_exec* exec, int sf, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames, const vpf_roi_dev* boxes,
+                         const int32_t* count, uint32_t box_stride, uint32_t max_n, const vpf_plane* dst, uint64_t dst_job_stride, const TensorLayout& l) {
+  if (!exec || !frames || !dims_ok(ss) || !dims_ok(ds)) return false;
+  if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !max_n || max_n > 65535u) return false;
+  if (!boxes || (((uintptr_t)boxes | (uintptr_t)count) & 3u) || box_stride < sizeof(vpf_roi_dev) || (box_stride & 3u) || (dst_job_stride & (l.elem - 1)))
+    return false;
+  for (uint32_t i = 0; i < n_frames; i++)
+    if (!tensor_src_ok(sf, ss.width, frames[i].src)) return false;
+  return tensor_planes_ok(dst, l, ds.width);
+}
+// ... and what their kernels get of it (RoiDevArgs, LetterboxDevArgs: the same members)
+template <class Args>
+static void fill_dev_boxes(Args& a, const vpf_frame_src* frames, uint32_t n_frames, int ns, const vpf_roi_dev* boxes, const int32_t* count, uint32_t box_stride,
+                           uint32_t max_n, const vpf_plane* dst, uint64_t dst_job_stride, const TensorLayout& l) {
+  std::memset(&a, 0, sizeof(a));
+  fill_frame_srcs(a.f, frames, n_frames, ns);
+  fill_job0_dst(a.d, a.dp, dst, l);
+  a.boxes = reinterpret_cast<const int32_t*>(boxes);
+  a.count = count;
+  a.job_stride = dst_job_stride;
+  a.box_stride = box_stride; a.max_n = max_n; a.n_frames = n_frames;
 }
 // The epilogue of a tensor launch.  `fill`: the three pad (letterbox) or border (warp) bytes per OUTPUT channel, swapped like the parameters, or
 // null for zeros; `mode`: the warp's border mode, bits 24 .. 31 of TensorEpi::pad.
@@ -610,47 +637,25 @@ vpf_status vpf_convert_resize_tensor_rois_dev(const vpf_exec* exec, int sf, int 
   const Mark mark("vpf_convert_resize_tensor_rois_dev");
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (const vpf_status refused = norm_status(norm)) return refused;
-  if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
   const TensorLayout l = layout_of(*norm);
-  if (!table->boxes || (((uintptr_t)table->boxes | (uintptr_t)table->count) & 3u) || table->box_stride < sizeof(vpf_roi_dev) || (table->box_stride & 3u) ||
-      (table->dst_job_stride & (l.elem - 1)))
+  if (!table || !dev_boxes_ok(exec, sf, ss, ds, n_frames, frames, table->boxes, table->count, table->box_stride, table->max_n, table->dst, table->dst_job_stride, l))
     return VPF_ERR_BAD_ARG;
-  for (uint32_t i = 0; i < n_frames; i++)
-    if (!tensor_src_ok(sf, ss.width, frames[i].src)) return VPF_ERR_BAD_ARG;
-  if (!tensor_planes_ok(table->dst, l, ds.width)) return VPF_ERR_BAD_ARG;
   DeviceGuard guard(exec->device);
   if (guard.err != hipSuccess) return status_of(guard.err);
   Yuv2RgbCoef c;
   make_yuv2rgb(cs, cr, &c);
   const TensorEpi te = make_epi(*norm);
   RoiDevArgs a;
-  std::memset(&a, 0, sizeof(a));
-  fill_frame_srcs(a.f, frames, n_frames, num_planes(sf));
-  fill_job0_dst(a.d, a.dp, table->dst, l);
-  a.boxes = reinterpret_cast<const int32_t*>(table->boxes);
-  a.count = table->count;
-  a.job_stride = table->dst_job_stride;
-  a.box_stride = table->box_stride; a.max_n = table->max_n; a.n_frames = n_frames;
+  fill_dev_boxes(a, frames, n_frames, num_planes(sf), table->boxes, table->count, table->box_stride, table->max_n, table->dst, table->dst_job_stride, l);
   return status_of(launch_convert_resize_rois_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height, te, l.nhwc));
 }
 
 // The aspect-preserving placement of a w x h picture inside dw x dh (include/vpf_hip.h): integers only, 64-bit products.
 vpf_rect vpf_letterbox_fit(vpf_size src, vpf_size dst) {
   vpf_rect r = {0u, 0u, 0u, 0u};
-  const uint64_t w = src.width, h = src.height, dw = dst.width, dh = dst.height;
-  if (!w || !h || !dw || !dh) return r;
-  uint64_t iw, ih;
-  if (w * dh >= h * dw) {  // width-limited
-    iw = dw;
-    ih = (2 * h * dw + w) / (2 * w);  // round half up
-    ih = ih < 1 ? 1 : (ih > dh ? dh : ih);
-  } else {
-    ih = dh;
-    iw = (2 * w * dh + h) / (2 * h);
-    iw = iw < 1 ? 1 : (iw > dw ? dw : iw);
-  }
-  r.x = (uint32_t)((dw - iw) / 2); r.y = (uint32_t)((dh - ih) / 2); r.width = (uint32_t)iw; r.height = (uint32_t)ih;
+  if (!src.width || !src.height || !dst.width || !dst.height) return r;
+  const LetterboxFit f = letterbox_fit_ints(src.width, src.height, dst.width, dst.height);  // (vpf_job_bounds.h: the device-table kernel runs it too)
+  r.x = f.ix; r.y = f.iy; r.width = f.iw; r.height = f.ih;
   return r;
 }
 
@@ -690,6 +695,33 @@ vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, in
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
+}
+
+// The same with the boxes, the optional placements and the count in DEVICE memory (include/vpf_hip.h): every check that needs no box happens here
+// (dev_boxes_ok: the device-ROI entry's list), the guards and the fit in the kernel (k_convert_letterbox_dev.hip); one dispatch.
+static_assert(sizeof(vpf_letterbox_dev) == 96 && offsetof(vpf_letterbox_dev, box_stride) == 24 && offsetof(vpf_letterbox_dev, dst) == 40 &&
+                  offsetof(vpf_letterbox_dev, dst_job_stride) == 88,
+              "vpf_letterbox_dev has no implicit padding");
+vpf_status vpf_convert_letterbox_tensor_dev(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames,
+                                            const vpf_frame_src* frames, const vpf_letterbox_dev* table, const vpf_tensor_norm* norm,
+                                            const vpf_letterbox_opts* opts) {
+  const Mark mark("vpf_convert_letterbox_tensor_dev");
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (const vpf_status refused = norm_status(norm, false, opts && opts->reserved)) return refused;
+  const TensorLayout l = layout_of(*norm);
+  if (!table || !dev_boxes_ok(exec, sf, ss, ds, n_frames, frames, table->boxes, table->count, table->box_stride, table->max_n, table->dst, table->dst_job_stride, l))
+    return VPF_ERR_BAD_ARG;
+  if (((uintptr_t)table->dst_rects & 3u) || (table->dst_rects && (table->rect_stride < 16u || (table->rect_stride & 3u))) || table->reserved) return VPF_ERR_BAD_ARG;
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  const TensorEpi te = make_epi(*norm, opts ? opts->pad : nullptr);
+  LetterboxDevArgs a;
+  fill_dev_boxes(a, frames, n_frames, num_planes(sf), table->boxes, table->count, table->box_stride, table->max_n, table->dst, table->dst_job_stride, l);
+  a.rects = table->dst_rects;
+  a.rect_stride = table->dst_rects ? table->rect_stride : 0u;
+  return status_of(launch_convert_letterbox_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height, te, l.nhwc));
 }
 
 // Many affine warps of decoded frames -> one batch of normalised planes (include/vpf_hip.h): per-job matrices, kWarpBatch jobs per job table,

@@ -160,6 +160,24 @@ struct LetterboxArgs {
 static_assert(sizeof(LetterboxDesc) == 112 && sizeof(LetterboxArgs) == 82 * 112 + 32 && sizeof(LetterboxArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
               "the letterbox job table must not outgrow the largest frame table");
 
+// The arguments of a letterbox launch whose boxes live in DEVICE memory (vpf_convert_letterbox_tensor_dev, k_convert_letterbox_dev.hip): RoiDevArgs plus
+// where the optional placements lie.  The kernel reads (frame, x, y, w, h) and, with `rects`, (ix, iy, iw, ih) of job blockIdx.z when it runs; without,
+// it fits the box into the plane itself (letterbox_fit_ints, vpf_job_bounds.h).  The pad bytes travel in TensorEpi::pad as in LetterboxArgs.
+// 5 240 B, below the largest argument block.
+struct LetterboxDevArgs {
+  FrameSrcDesc f[kRoiDevFrames];
+  const int32_t* boxes;  // device: five ints per job, box_stride bytes apart
+  const int32_t* rects;  // device: four ints per job, rect_stride bytes apart; null: the kernel fits
+  const int32_t* count;  // device, or null: max_n
+  uint8_t* d[3];         // job 0's WHOLE planes (kernel channel order); job k's lie k * job_stride bytes further
+  uint64_t job_stride;
+  uint32_t dp[3];
+  uint32_t box_stride, rect_stride, max_n, n_frames, pad;
+  TensorEpi e;
+};
+static_assert(sizeof(LetterboxDevArgs) == 128 * 40 + 120 && sizeof(LetterboxDevArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
+              "the device-letterbox arguments must not outgrow the largest frame table");
+
 // The job table of a multi-ROI affine warp (vpf_convert_warp_tensor, k_convert_warp.hip): per job the planes of the WHOLE source frame and of the
 // destination and the inverse matrix m = (m00 m01 m02; m10 m11 m12), destination pixel -> source coordinates in luma pixels.  96 B like RoiDesc,
 // so the same 96 jobs per table.  The three border bytes (kernel channel order R G B) and the border mode travel in TensorEpi::pad:
@@ -266,6 +284,11 @@ hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoe
 // dw x dh: ONE dispatch, every tile staged or per tap by its own window; a.e is set here; k_convert_roi_dev.hip
 hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
                                           const TensorEpi& te, bool nhwc = false);
+// up to a.max_n letterbox jobs whose boxes (and, with a.rects, placements) the kernel reads from device memory, on frames of W x H pixels -> FC_TENSOR
+// (nhwc: FC_TENSOR_NHWC) planes of dw x dh: ONE dispatch, every tile padded, staged or per tap by its own window; `te.pad` carries the pad bytes;
+// a.e is set here; k_convert_letterbox_dev.hip
+hipError_t launch_convert_letterbox_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, LetterboxDevArgs& a, uint32_t dw,
+                                        uint32_t dh, const TensorEpi& te, bool nhwc = false);
 // up to a.max_n jobs whose matrices the kernel reads from device memory, on frames of W x H pixels -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of
 // dw x dh: ONE dispatch, every tile staged or per tap by its own window; `max_step` sizes the dynamic LDS (warp_dev_lds_bytes, vpf_job_bounds.h);
 // `te.pad` carries border and mode; a.e is set here; k_convert_warp_dev.hip

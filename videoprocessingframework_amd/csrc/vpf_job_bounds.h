@@ -5,6 +5,9 @@
 //   ROI   roi_strip_need: the largest workgroup strip of a job, WALKED with the kernel's own fp32 tap arithmetic, and the policy's two limits
 //   letterbox  letterbox_strip_need: the same walk over tiles laid on the destination plane and clipped to the picture (k_convert_letterbox.hip;
 //         tests/test_letterbox_bounds_cpu.py through tests/c/letterbox_bounds_capi.cpp)
+//         letterbox_fit_ints / letterbox_dev_rect_ok / letterbox_tile_window: the fit (vpf_letterbox_fit's integers), the placement's guard and the
+//         per-tile window of the device-table form (k_convert_letterbox_dev.hip; tests/test_letterbox_dev_cpu.py through
+//         tests/c/letterbox_dev_bounds_capi.cpp)
 //   warp  warp_xy / warp_window / warp_strip: what the kernel computes per tile; warp_need: the launcher's closed-form bound over all tiles;
 //         warp_dev_job_ok / warp_dev_lds_bytes: the guard and the LDS bound of the device-table form (k_convert_warp_dev.hip;
 //         tests/test_warps_dev_bounds_cpu.py through tests/c/warp_dev_bounds_capi.cpp)
@@ -142,6 +145,57 @@ static inline RoiStripNeed letterbox_strip_need(uint32_t x, uint32_t w, uint32_t
   }
   const uint32_t cols = iw < 256 ? iw : 256, brows = ih < kBand ? ih : kBand;
   return RoiStripNeed{rows * rowbytes, (double)rows * (rowbytes / 4) / ((double)cols * brows)};
+}
+
+// ------------------------------------------------------------------------------------------
+// Device-resident boxes for the letterbox (k_convert_letterbox_dev.hip, vpf_convert_letterbox_tensor_dev; tests/test_letterbox_dev_cpu.py through
+// tests/c/letterbox_dev_bounds_capi.cpp).  The kernel reads the box — and the placement, where the caller gives one — from device memory, so the
+// fit, the placement's guard and staged or per tap PER TILE happen in the kernel.
+// ------------------------------------------------------------------------------------------
+// The aspect-preserving, centred placement of a w x h picture inside dw x dh (vpf_letterbox_fit, include/vpf_hip.h), integers only: 64-bit
+// products and ONE 64-bit division.  With sides <= 65536 the largest intermediate is 2 * 2^16 * 2^16 + 2^16 < 2^34.  Every side >= 1.
+struct LetterboxFit { uint32_t ix, iy, iw, ih; };
+static VPF_JB_HDI LetterboxFit letterbox_fit_ints(uint32_t w32, uint32_t h32, uint32_t dw32, uint32_t dh32) {
+  const uint64_t w = w32, h = h32, dw = dw32, dh = dh32;
+  const bool wide = w * dh >= h * dw;  // width-limited
+  // the free side: round half up of (short side of the picture x the limiting side of the plane) / the long side of the picture
+  const uint64_t num = wide ? 2 * h * dw + w : 2 * w * dh + h, den = wide ? 2 * w : 2 * h, lim = wide ? dh : dw;
+  uint64_t q = num / den;
+  q = q < 1 ? 1 : (q > lim ? lim : q);
+  const uint64_t iw = wide ? dw : q, ih = wide ? q : dh;
+  return LetterboxFit{(uint32_t)((dw - iw) / 2), (uint32_t)((dh - ih) / 2), (uint32_t)iw, (uint32_t)ih};
+}
+// The guard of an explicit placement: four untrusted ints must name a non-empty rectangle inside the dw x dh plane.  As roi_dev_box_ok: unsigned
+// compares, no sums — iw <= dw before dw - iw, so no operation can wrap.
+static VPF_JB_HDI bool letterbox_dev_rect_ok(int32_t ix, int32_t iy, int32_t iw, int32_t ih, uint32_t dw, uint32_t dh) {
+  return iw >= 1 && ih >= 1 && ix >= 0 && iy >= 0 && (uint32_t)iw <= dw && (uint32_t)ih <= dh && (uint32_t)ix <= dw - (uint32_t)iw &&
+         (uint32_t)iy <= dh - (uint32_t)ih;
+}
+// The source window of ONE tile of the PLANE (columns xs .. xe, rows Y0 .. Y1) that MEETS the picture (xs <= ix + iw - 1, xe >= ix, rows likewise;
+// the caller tests that): the tile's range clipped to the picture exactly as letterbox_strip_need and k_lb_strip clip it, then roi_tile_window on the
+// clipped picture columns and rows.  `cxs .. cye`: the clipped range in picture pixels.
+struct LetterboxTileWin {
+  RoiTileWin w;
+  uint32_t cxs, cxe, cys, cye;
+};
+static VPF_JB_HDI LetterboxTileWin letterbox_tile_window(uint32_t x, uint32_t w, uint32_t h, float scx, float scy, uint32_t ix, uint32_t iy, uint32_t iw,
+                                                         uint32_t ih, uint32_t xs, uint32_t xe, uint32_t Y0, uint32_t Y1) {
+  LetterboxTileWin t;
+  const uint32_t ixe = ix + iw - 1, iye = iy + ih - 1;
+  t.cxs = (xs > ix ? xs : ix) - ix; t.cxe = (xe < ixe ? xe : ixe) - ix;
+  t.cys = (Y0 > iy ? Y0 : iy) - iy; t.cye = (Y1 < iye ? Y1 : iye) - iy;
+  t.w = roi_tile_window(x, w, h, scx, scy, t.cxs, t.cxe, t.cys, t.cye);
+  return t;
+}
+// ... and what the policy looks at: `conv` counts against the picture pixels a tile can hold (min(iw, 256) x min(ih, 16)), as letterbox_strip_need's
+// does, so over the tiles that meet the picture the largest `bytes` and `conv` are the job's.  The tile is staged by roi_tile_staged under the
+// dispatch's roi_dev_lds_bytes(dw, dh), which stays a bound: conv <= kRoiConvMax = 3 means rows x (rowbytes / 4) <= 3 x min(iw, 256) x min(ih, 16),
+// hence bytes = rows x rowbytes <= 12 B x the picture pixels of a tile <= 12 B x min(dw, 256) x min(dh, 16), the plane pixels of a tile (iw <= dw,
+// ih <= dh) — what roi_dev_lds_bytes returns before its cap at kRoiStripMax; above the cap the tile samples per tap, as the host policy has it.
+// Were this argument wrong, k_lb_dev's own test rows x rowbytes > lds_bytes -> per tap keeps it from becoming an overrun.
+static VPF_JB_HDI RoiStripNeed letterbox_tile_need_of(const RoiTileWin& t, uint32_t iw, uint32_t ih) {
+  const uint32_t cols = iw < 256 ? iw : 256, brows = ih < 4 * kRoiBandRows ? ih : 4 * kRoiBandRows;
+  return RoiStripNeed{t.rows * t.rowbytes, (double)t.rows * (t.rowbytes / 4) / ((double)cols * brows)};
 }
 
 // ------------------------------------------------------------------------------------------
