@@ -1,6 +1,7 @@
 // tests/c/resize_plan_capi.cpp — the policy of the plain resize launches (csrc/vpf_resize_plan.h: what launch_resize_planned of k_resize.hip
 // dispatches on) behind C symbols, for tests/test_resize_plan_cpu.py.  Compiled with plain g++: no HIP.  (The plan is the same under
 // -DVPF_LAB_FORMS: the lab build's persistent launch decodes its knob bits at its dispatch.)
+#include "vpf_lzm_plan.h"
 #include "vpf_resize_plan.h"
 
 #include <cstring>
@@ -33,6 +34,19 @@ void rp_plan(int f32, int interp, int njobs, uint32_t n, uint32_t call_n, const 
   for (int i = 0; i < 9; i++) out[i] = head[i];
   put_launch(P.mp, out + 9);
   for (int p = 0; p < 3; p++) put_launch(P.plane[p], out + 9 + 22 * (p + 1));
+}
+
+// what launch_lanczos_mfma (k_lanczos_mfma.hip) does with `njobs` planes of n frames: lzm_launch of vpf_lzm_plan.h for the product build.  bits, pitches:
+// per plane the OR of pointer | pitch on both sides and {source, destination} pitch of the frames (all frames alike) -> the form's name, nullptr = declined
+const char* rp_lzm_form(int njobs, const uint32_t* jobs, const uint64_t* bits, const uint32_t* pitches, uint32_t n, int variant, int mfma) {
+  vpf::LzmPlaneIn in[3] = {};
+  vpf::LzmFramesIn fr[3] = {};
+  for (int p = 0; p < njobs && p < 3; p++) {
+    in[p] = vpf::LzmPlaneIn{(int)jobs[6 * p], jobs[6 * p + 2], jobs[6 * p + 3], jobs[6 * p + 4], jobs[6 * p + 5]};
+    fr[p] = vpf::LzmFramesIn{bits[p], pitches[2 * p], pitches[2 * p + 1]};
+  }
+  const vpf::LzmLaunch L = vpf::lzm_launch(njobs, in, fr, n, variant, mfma, false);
+  return L.ok() ? vpf::kLzmForms[L.form].name : nullptr;
 }
 
 // out = {ok, ty, nr, lds, rowq, lshift, wpb}

@@ -80,6 +80,18 @@ CASES = [
     ("lanczos, matrix cores off, variant 40", RGB, LANCZOS3, 96, 64, 64, 40, 3, (40, 0, 0, 1), 0, [PB("LanczosGatherTask<3>")]),
     ("lanczos nv12, chroma off, matrix cores off", NV12, LANCZOS3, 96, 64, 64, 40, 2, (0, 0, 0, 1), (0, 1), [PB("LanczosTileTask<1, 8>"), PB("LanczosGatherTask<2>")]),
     ("lanczos source off by one", Y, LANCZOS3, 96, 64, 64, 40, 1, (0, 0, 0, 0), 1, ["(k_resize_lanczos<1>)"]),
+    # the forms of the matrix-core launch (csrc/vpf_lzm_plan.h: kLzmForms) at two frames: the ring of two, the 8-tile strips (forced: the planner takes
+    # 4-tile strips on planes this small), the two- and three-chunk windows of strong horizontal down-scales, half tiles
+    ("lanczos up: ring of two, 4-tile strips", Y, LANCZOS3, 16, 32, 16, 64, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma4u")]),
+    ("lanczos up: ring of two, 8-tile strips", Y, LANCZOS3, 16, 32, 16, 64, 2, (0, 0, 0, 0x800), 0, [MFMA("LzMfma8u")]),
+    ("lanczos 8-tile strips, narrow", Y, LANCZOS3, 16, 64, 16, 40, 2, (0, 0, 0, 0x800), 0, [MFMA("LzMfma8n")]),
+    ("lanczos 8-tile strips", RGB, LANCZOS3, 48, 32, 24, 64, 2, (0, 0, 0, 0x800), 0, [MFMA("LzMfma8")]),
+    ("lanczos 8-tile strips, wide", RGB, LANCZOS3, 96, 32, 48, 64, 2, (0, 0, 0, 0x800), 0, [MFMA("LzMfma8w")]),
+    ("lanczos two-chunk windows, 256-B rows", RGB, LANCZOS3, 48, 32, 16, 64, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma4k4")]),
+    ("lanczos two-chunk windows, 384-B rows", RGB, LANCZOS3, 96, 32, 16, 64, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma4k6")]),
+    ("lanczos two-chunk windows, 512-B rows", RGB, LANCZOS3, 160, 32, 24, 64, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma4k8")]),
+    ("lanczos three-chunk windows, 2-tile strips", Y, LANCZOS3, 160, 32, 16, 64, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma2k6")]),
+    ("lanczos half tiles (8 destination rows per tile)", Y, LANCZOS3, 128, 128, 40, 16, 2, (0, 0, 0, 0), 0, [MFMA("LzMfma4")]),
     # float surfaces
     ("float lanczos tiled, packed", RGB_32F, LANCZOS3, 96, 64, 64, 40, 1, (0, 0, 0, 0), 0, ["(k_plane_batch<TileTaskF32<3, true, 8>>)"]),
     ("float lanczos tiled, planar", RGB_32F_PLANAR, LANCZOS3, 96, 64, 64, 40, 2, (0, 0, 0, 0), 0, [PB("TileTaskF32<1, true, 8>")] * 3),

@@ -1,8 +1,11 @@
 """Host-side planning of the matrix-core Lanczos launch (csrc/vpf_lzm_plan.h, compiled here with g++: no HIP, no GPU):
   * the launch-shape planner against the measured sweeps in profiles/ — the cost model must keep picking shapes close to the best measured;
   * the weight-table cache against its contract (what makes "a table in use can never change" and "a stream never reads a table whose
-    build it is not ordered behind" true)."""
+    build it is not ordered behind" true);
+  * the launch description (lzm_launch: what launch_lanczos_mfma of csrc/k_lanczos_mfma.hip dispatches on) against the launches recorded from the launcher
+    as it was before (tests/golden/lzm_launch_kat.json), its refusals in order, the form table, and invariants restated over a seeded sweep."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -19,7 +22,7 @@ def lzp():
     so = os.path.join(out, "liblzm_plan_capi.so")
     src = os.path.join(ROOT, "tests", "c", "lzm_plan_capi.cpp")
     hdr = os.path.join(ROOT, "videoprocessingframework_amd", "csrc")
-    deps = [src, os.path.join(hdr, "vpf_lzm_plan.h"), os.path.join(hdr, "vpf_plan_bounds.h")]
+    deps = [src, os.path.join(hdr, "vpf_lzm_plan.h"), os.path.join(hdr, "vpf_plan_bounds.h"), os.path.join(hdr, "vpf_classes.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         compile_to(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", *extra, "-I", hdr, src, "-o", so, "-lm", "-pthread"], so)
     L = C.CDLL(so)
@@ -47,7 +50,50 @@ def lzp():
     L.lzp_ws_n.argtypes = [C.POINTER(C.c_uint64)]
     L.lzp_table_bytes_bound.restype = C.c_uint64
     L.lzp_table_bytes_bound.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
+    L.lzp_launch.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.lzp_form.restype = C.c_char_p
+    L.lzp_form.argtypes = [C.c_int, C.POINTER(C.c_uint32)]
+    L.lzp_form_of.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]
+    L.lzp_cache_begin.argtypes = [C.c_void_p, C.c_int]
+    L.lzp_cache_get.restype = C.c_uint32
+    L.lzp_cache_get.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64]
+    L.lzp_cache_end.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
+    assert (L.lzp_launch_head(), L.lzp_launch_plane()) == (len(LAUNCH_HEAD), len(LAUNCH_PLANE) + 2 * len(TABLE_REQ))
     return L
+
+
+LAUNCH_HEAD = ("why", "form", "tables", "pair", "up2", "gx", "gy", "gz", "rts", "rows", "pitch", "lds", "a2", "lds_tabled", "a2_tabled")
+LAUNCH_PLANE = ("sw", "sh", "dw", "dh", "scx", "scy", "by0")
+TABLE_REQ = ("kind", "k0", "k1", "k2", "k3", "bytes", "gx", "gy", "cols")
+(OK, NO_SWITCHED_OFF, NO_COUNTS, NO_SIZE, NO_ALIGNMENT, NO_PITCH, NO_ROWS, NO_PLAN, NO_PAIR_HALF_TILES, NO_FORM) = range(10)   # LzmDecline
+ALIGNED = (0x7F00_0000_0000 | 0x7F80_0000_0000 | 256, 256, 256)   # a frame table that refuses nothing: {OR of pointer | pitch, largest pitches}
+
+
+def launch(L, planes, n, tune=0, knob=0, pair_build=False, frames=None, njobs=None):
+    """lzm_launch (csrc/vpf_lzm_plan.h) -> the description as a dict; planes: [(ch, sw, sh, dw, dh)]; frames: per plane (bits, sp_max, dp_max)"""
+    a = (C.c_uint32 * 15)(*[v for p in planes for v in p])
+    f = (C.c_uint64 * 9)(*[v for p in (frames or [ALIGNED] * len(planes)) for v in p])
+    out = (C.c_uint64 * (len(LAUNCH_HEAD) + 3 * (len(LAUNCH_PLANE) + 2 * len(TABLE_REQ))))()
+    L.lzp_launch(len(planes) if njobs is None else njobs, a, f, n, tune, knob, int(pair_build), out)
+    d = dict(zip(LAUNCH_HEAD, out))
+    d["plane"] = []
+    for p in range(len(planes)):
+        o = list(out[len(LAUNCH_HEAD) + 25 * p:len(LAUNCH_HEAD) + 25 * (p + 1)])
+        q = dict(zip(LAUNCH_PLANE, o))
+        q["ctab"], q["rtab"] = dict(zip(TABLE_REQ, o[7:16])), dict(zip(TABLE_REQ, o[16:25]))
+        d["plane"].append(q)
+    return d
+
+
+def fbits(a, b):
+    """the bits of (float)a / (float)b"""
+    return int((np.float32(a) / np.float32(b)).view(np.uint32))
+
+
+def form(L, f):
+    out = (C.c_uint32 * 6)()
+    name = L.lzp_form(f, out)
+    return dict(name=name.decode(), nt=out[0], pf=out[1], kc=out[2], up2=bool(out[3]), pair=bool(out[4]), max_lds=out[5])
 
 
 def plan(L, planes, n, forced=0, tables=True, up2=True):
@@ -458,3 +504,219 @@ def test_workspace_bound_covers_every_plan(lzp):
                 rows = 16 * tiles
                 need = (strips * nt * 2048 + 255) // 256 * 256 + (((dh + rows - 1) // rows) * ((rows + 63) // 64) * 8192 + 255) // 256 * 256
                 assert need <= bound, (ch, dw, dh, nt, tiles)
+    # ... and what the launch REALLY asks for (lzm_launch's own table requests: x K chunks, half tiles included), per plane, over the seeded sweep
+    worst, frames_seen = 0.0, set()
+    for planes, n, knob, pair_build, d in launch_sweep(lzp):
+        for (ch, _, _, dw, dh), q in zip(planes, d["plane"]):
+            need = sum((q[t]["bytes"] + 255) // 256 * 256 for t in ("ctab", "rtab"))
+            bound = lzp.lzp_table_bytes_bound(ch, dw, dh)
+            assert need <= bound, (planes, n, hex(knob), need, bound)
+            worst = max(worst, need / bound)
+        frames_seen.add(n)
+    assert frames_seen == {1, 2, 8, 32, 33, 128} and 0.5 < worst <= 1.0, (frames_seen, worst)   # (the sweep comes close to the bound)
+
+
+_SWEEP = []
+
+
+def launch_sweep(L):
+    """[(planes, frames, VPF_TUNE_RESIZE_MFMA, pair form in the build, lzm_launch's answer)] of every call of a seeded sweep that the launcher takes: sizes
+    2 .. 4096, one plane of 1 - 3 channels or the planes of NV12 / YUV420, factors from 3 x up to 10 x down on each axis, forced shapes, tables off, no ring
+    of two, the lab build's pair form; 1, 2, 8, 32, 33 and 128 frames.  Computed once for the tests below."""
+    if _SWEEP:
+        return _SWEEP
+    rng = np.random.default_rng(21)
+    sizes = [2, 16, 61, 64, 224, 256, 416, 640, 720, 1080, 1280, 1920, 2160, 3840, 4096]
+    knobs = [0, 0, 0, 0x10000, 0x80000, 8 << 8, 4 << 8, (4 << 8) | 2, (8 << 8) | 5, 7, (8 << 8) | 0x10000, (4 << 8) | 0x80000, 0x20000, 0x20003]
+    refused = {}
+    for _ in range(9000):
+        pick = lambda: int(rng.choice(sizes)) if rng.random() < 0.4 else int(rng.integers(2, 4097))   # noqa: E731
+        dw, dh = pick(), pick()
+        sw, sh = (min(4096, max(2, int(d * f))) for d, f in zip((dw, dh), np.exp(rng.uniform(np.log(0.33), np.log([10.5, 6.5])))))
+        kind = int(rng.integers(5))
+        planes = [(kind + 1, sw, sh, dw, dh)] if kind < 3 else [(1, sw, sh, dw, dh), (2, (sw + 1) // 2, (sh + 1) // 2, (dw + 1) // 2, (dh + 1) // 2)] if kind == 3 else \
+            [(1, sw, sh, dw, dh)] + [(1, (sw + 1) // 2, (sh + 1) // 2, (dw + 1) // 2, (dh + 1) // 2)] * 2
+        n, knob, pair_build = int(rng.choice([1, 2, 8, 32, 33, 128])), int(rng.choice(knobs)), bool(rng.random() < 0.5)
+        d = launch(L, planes, n, knob=knob, pair_build=pair_build)
+        if d["why"] == OK:
+            _SWEEP.append((planes, n, knob, pair_build, d))
+        refused[d["why"]] = refused.get(d["why"], 0) + 1
+    assert len(_SWEEP) > 4000 and set(refused) == {OK, NO_ROWS, NO_PLAN, NO_PAIR_HALF_TILES}, (len(_SWEEP), refused)
+    return _SWEEP
+
+
+def test_form_table(lzp):
+    """the sixteen forms (thirteen in the product build) by name, and lzm_form_of as the one map from a planned shape to a form: every row is reached by
+    its own (nt, kc, span, up2, pair) at both ends of the spans its staging loads cover, and by nothing else"""
+    names = [form(lzp, f)["name"] for f in range(lzp.lzp_forms())]
+    assert names == ["LzMfma8", "LzMfma8n", "LzMfma8w", "LzMfma4", "LzMfma4n", "LzMfma8u", "LzMfma4u", "LzMfma8uw", "LzMfma4k4", "LzMfma4k6", "LzMfma4k8", "LzMfma2k6",
+                     "LzMfma2k8", "LzPair", "LzPairN", "LzPairW"] and lzp.lzp_product_forms() == 13
+    spans = {1: {2: (16, 128), 4: (129, 256), 5: (257, 320)}, 2: {4: (16, 256), 6: (257, 384), 8: (385, 512)}, 3: {6: (16, 384), 8: (385, 512)}}   # lzm_pf_of
+    rows = set()
+    for f in range(lzp.lzp_forms()):
+        i = form(lzp, f)
+        assert i["pair"] == (f >= 13) and not (i["pair"] and i["up2"]) and i["max_lds"] <= 80 * 1024, i
+        for span in spans[i["kc"]][i["pf"]]:
+            assert lzp.lzp_form_of(i["nt"], i["kc"], span, i["up2"], i["pair"]) == f, (i, span)
+        rows.add((i["nt"], i["pf"], i["kc"], i["up2"], i["pair"]))
+    assert len(rows) == lzp.lzp_forms()   # no two rows answer the same question
+    assert lzp.lzp_form_of(4, 1, 300, 0, 0) == lzp.lzp_forms() and lzp.lzp_form_of(2, 1, 64, 0, 0) == lzp.lzp_forms() and lzp.lzp_form_of(8, 2, 64, 0, 0) == lzp.lzp_forms()
+    # no form needs the LDS attribute today: the largest workgroup is LzMfma4k8's (a form that grows past 64 KiB gets it set at the dispatch)
+    assert max(form(lzp, f)["max_lds"] for f in range(lzp.lzp_forms())) == form(lzp, names.index("LzMfma4k8"))["max_lds"] == 56320
+
+
+def test_launch_refusals(lzp):
+    """the refusals in the launcher's order: knobs, counts, then per plane size, alignment, the 24- / 32-bit offset limits, the ring's vertical reach; then
+    the planner, then the pair form's whole tiles"""
+    base, al = [(3, 1920, 1080, 1280, 720)], ALIGNED
+    why = lambda planes=base, n=2, frames=None, **kw: launch(lzp, planes, n, frames=frames, **kw)["why"]   # noqa: E731
+    assert why() == OK
+    assert (why(tune=9), why(tune=40), why(knob=1), why(knob=0x10001), why(tune=43)) == (NO_SWITCHED_OFF,) * 4 + (OK,)
+    assert (why(n=0), why(n=129), why(n=128), why(njobs=0), why(njobs=4)) == (NO_COUNTS, NO_COUNTS, OK, NO_COUNTS, NO_COUNTS)
+    assert why(n=0, knob=1) == NO_SWITCHED_OFF and why([(3, 1 << 22, 1080, 1280, 720)], n=0) == NO_COUNTS   # (the order)
+    for i in range(1, 5):
+        big = list(base[0])
+        big[i] = 1 << 22
+        assert why([tuple(big)], frames=[(al[0] | 8, 256, 256)]) == NO_SIZE
+    assert why(frames=[(al[0] | 8, 256, 256)]) == NO_ALIGNMENT and why(frames=[(al[0] | 16, 256, 256)]) == OK
+    assert why(frames=[(al[0] | 8, 1 << 24, 256)]) == NO_ALIGNMENT   # (alignment is asked before the pitch)
+    low = [(3, 192, 108, 128, 72)]   # (few rows: the 24-bit limit alone)
+    assert (why(low, frames=[(al[0], 1 << 24, 256)]), why(low, frames=[(al[0], 256, 1 << 24)]), why(low, frames=[(al[0], (1 << 24) - 16, (1 << 24) - 16)])) == (NO_PITCH, NO_PITCH, OK)
+    tall = [(1, 64, 4096, 64, 4000)]   # sh x sp and dh x dp against 2^32
+    assert why(tall, frames=[(al[0], 1 << 20, 256)]) == NO_PITCH and why(tall, frames=[(al[0], (1 << 20) - 16, 256)]) == OK
+    assert why(tall, frames=[(al[0], 256, (1 << 32) // 4000 // 16 * 16 + 16)]) == NO_PITCH and why(tall, frames=[(al[0], 256, (1 << 32) // 4000 // 16 * 16)]) == OK
+    assert why(base + [(1, 1920, 1080, 1280, 720)], frames=[al, (al[0] | 4, 256, 256)]) == NO_ALIGNMENT   # (any plane)
+    assert why([(3, 1920, 1080, 120, 120)]) == NO_ROWS and why(frames=[(al[0], 1 << 24, 256)], planes=[(3, 1920, 1080, 120, 120)]) == NO_PITCH
+    assert why([(3, 1920, 1080, 224, 400)]) == NO_PLAN   # packed RGB beyond the two-chunk windows: by force only
+    assert why([(3, 1920, 1080, 960, 270)], knob=0x20000, pair_build=True) == NO_PAIR_HALF_TILES and why([(3, 1920, 1080, 960, 270)], knob=0x20000) == OK
+
+
+def test_launch_invariants(lzp):
+    """restated without the golden file, over the seeded sweep: the form is a function of the plan's (nt, kc, span, up2) and the pair bit alone, the grid covers
+    every destination byte and row of every plane, the by0 are the running band sums, both LDS outcomes fit, the table requests are what the build kernels
+    and the cache are keyed by"""
+    forms_seen, builds_seen, rts_seen = set(), set(), set()
+    for planes, n, knob, pair_build, d in launch_sweep(lzp):
+        what = (planes, n, hex(knob), pair_build, d)
+        pair = pair_build and bool(knob & 0x20000)
+        forced = knob & 0xffff
+        P = plan(lzp, planes, n, ((8 << 8) | (forced & 0xff)) if pair else forced, tables=not knob & 0x10000, up2=not pair and not knob & 0x80000)
+        assert P["ok"] and d["form"] == lzp.lzp_form_of(P["nt"], P["kc"], P["span"], P["up2"], pair) and (bool(d["pair"]), bool(d["tables"])) == (pair, not knob & 0x10000), what
+        f = form(lzp, d["form"])
+        assert (f["nt"], f["kc"], f["up2"], f["pair"]) == (P["nt"], P["kc"], P["up2"], pair) and 64 * f["pf"] >= P["span"] and d["pitch"] == 64 * f["pf"] + 32 == P["pitch"], what
+        assert d["form"] < (16 if pair_build else 13), what   # a form this build has: the dispatch can launch it, and set its LDS attribute
+        forms_seen.add(f["name"])
+        rts_seen.add(d["rts"])
+        assert d["rts"] == P["rts"] and d["rows"] == P["r"] << P["rts"] and d["gz"] == n and bool(d["up2"]) == P["up2"], what
+        by0 = 0
+        for (ch, sw, sh, dw, dh), q in zip(planes, d["plane"]):
+            strips, bands = -(-dw * ch // (16 * f["nt"])), -(-dh // d["rows"])
+            assert (2 if pair else 4) * d["gx"] >= strips and q["by0"] == by0, what   # a workgroup: four strips (the pair form: two)
+            assert (q["sw"], q["sh"], q["dw"], q["dh"]) == (sw, sh, dw, dh) and (q["scx"], q["scy"]) == (fbits(sw, dw), fbits(sh, dh)), what
+            by0 += bands
+            c, r = q["ctab"], q["rtab"]
+            groups = -(-d["rows"] // (4 << d["rts"]))   # groups of four tiles per band
+            assert (c["kind"], c["k0"], c["k1"], c["k2"], c["k3"]) == (0, ch, sw, dw, f["nt"] | f["kc"] << 8) and (c["gx"], c["gy"]) == (strips, 1), what
+            assert c["bytes"] == strips * f["nt"] * f["kc"] * 2048 and c["cols"] == {(8, 1): 0, (4, 2): 1, (2, 3): 2, (4, 1): 3}[(f["nt"], f["kc"])], what
+            assert (r["kind"], r["k0"], r["k1"], r["k2"], r["k3"]) == (1, sh, dh, d["rows"], d["rts"] | int(P["up2"]) << 8) and (r["gx"], r["gy"]) == (groups, bands), what
+            assert r["bytes"] == bands * groups * 8192, what
+            builds_seen.add(c["cols"])
+        assert d["gy"] == by0 and d["gx"] == max(-(-(-(-p[3] * p[0] // (16 * f["nt"]))) // (2 if pair else 4)) for p in planes), what
+        # the two LDS outcomes
+        run = 16 * d["pitch"] + 16 * (16 * f["nt"] + 16)
+        assert d["lds_tabled"] <= d["lds"] <= 80 * 1024 and d["a2_tabled"] <= d["a2"] == P["wave_lds"] and d["lds"] <= f["max_lds"], what
+        if pair:
+            assert d["lds"] == d["lds_tabled"] == f["max_lds"] and d["a2"] == d["a2_tabled"], what
+        else:
+            assert d["lds"] == P["group_lds"] == 4 * d["a2"] + 16384 and d["lds_tabled"] == 4 * d["a2_tabled"] + 16384, what
+            assert d["a2_tabled"] == (min(run, d["a2"]) if d["tables"] else d["a2"]) and d["a2"] >= run, what
+    assert forms_seen >= {"LzMfma8", "LzMfma8n", "LzMfma8w", "LzMfma4", "LzMfma4n", "LzMfma8u", "LzMfma4u", "LzMfma4k4", "LzMfma4k6", "LzMfma4k8", "LzMfma2k6",
+                          "LzPair", "LzPairN", "LzPairW"}, forms_seen   # (LzMfma8uw: behind the volume gate, below)
+    # LzMfma2k8 (spans above 384 B on 2-tile strips) is planned for no shape: a tile's taps fit a 192-B window only where the second tile's window starts
+    # less than 192 B behind the first (vpf_bound_lzm_span_win), so such a strip spans at most 384 B.  The form stays in the table and the dispatch
+    assert "LzMfma2k8" not in forms_seen
+    assert builds_seen == {0, 1, 2, 3} and rts_seen == {3, 4}
+    wide = launch(lzp, [(3, 2560, 1440, 3840, 2160)], 32)
+    assert form(lzp, wide["form"])["name"] == "LzMfma8uw"
+    half = launch(lzp, [(1, 128, 128, 40, 16)], 2)   # the half-tile row of tests/cases_resize_families.py
+    assert (form(lzp, half["form"])["name"], half["rts"], half["rows"]) == ("LzMfma4", 3, 16)
+
+
+ARENA, WORKSPACE, STREAM = 0x7E00_0000_0000, 0x7D00_0000_0000, 0x5000   # the made-up addresses of the recording (the golden file's "layout")
+
+
+def c_hexfloat(bits):
+    """printf("%a") of the float with these bits"""
+    m, e = float(np.uint32(bits).view(np.float32)).hex().split("p")
+    return m.rstrip("0").rstrip(".") + "p" + e
+
+
+def replay_launcher(L, row):
+    """launch_lanczos_mfma (csrc/k_lanczos_mfma.hip) step by step on lzm_launch's answer: reduce the frame table, plan, hand out the tables — workspace first,
+    then the arena, through the real LzmWorkspace / LzmTableCache with the recording stand-in for the events — queue the builds, pick the LDS outcome, dispatch
+    -> (what the launcher returns, its selection label, its launches in the golden file's form)"""
+    lab, tune, knob, mode, cap, n, njobs, jobs, mis, _, _, _ = row
+    frames = []
+    for ch, k, sw, _, dw, _ in jobs:
+        bits = sp_max = dp_max = 0
+        for i in range(n if n <= 128 else 0):
+            on = not mis[4] or i + 1 == n
+            sp, dp = (ch * sw + 255) // 256 * 256 + (mis[2] if on else 0), (ch * dw + 255) // 256 * 256 + (mis[3] if on else 0)
+            bits |= (0x7F00_0000_0000 + (k << 36) + (i << 28) + (mis[0] if on else 0)) | sp | (0x7F80_0000_0000 + (k << 36) + (i << 28) + (mis[1] if on else 0)) | dp
+            sp_max, dp_max = max(sp_max, sp), max(dp_max, dp)
+        frames.append((bits, sp_max, dp_max))
+    d = launch(L, [(j[0], j[2], j[3], j[4], j[5]) for j in jobs], n, tune, knob, bool(lab), frames, njobs)
+    if d["why"] != OK:
+        return 0, None, []
+    f, out, ptrs = form(L, d["form"]), [], []
+    cache = L.lzp_cache_new(0 if mode == 1 else 4 << 20)
+    ws, touched, locked = (C.c_uint64 * 40)(), C.c_uint32(0), False
+    try:
+        for q in d["plane"] if d["tables"] else []:
+            for t, r in enumerate((q["ctab"], q["rtab"])):
+                key = [r[x] for x in ("kind", "k0", "k1", "k2", "k3")]
+                h = L.lzp_ws_get(ws, {2: 64 << 20, 3: 256 + 8192, 4: 256 + 65536}[mode], STREAM, 0, cap, *key, r["bytes"], C.byref(touched)) if mode >= 2 else 0
+                base = WORKSPACE
+                if not h & ~B:
+                    if not locked:
+                        L.lzp_cache_begin(cache, 0)
+                        locked = True
+                    h, base = L.lzp_cache_get(cache, STREAM, 0, cap, (C.c_uint32 * 5)(*key), r["bytes"]), ARENA
+                ptrs.append(base + 16 * (h & ~B) if h & ~B else 0)
+                if h & B:
+                    args = [r["k0"], q["sw"], q["dw"], c_hexfloat(q["scx"])] if t == 0 else [q["sh"], q["dh"], c_hexfloat(q["scy"]), d["rows"], d["rts"], d["up2"]]
+                    out.append([("cols<%d, %d>" % ((8, 1), (4, 2), (2, 3), (4, 1))[r["cols"]]) if t == 0 else "rows", r["gx"], r["gy"], 1, 64, 0] + [str(a) for a in args] + ["p%x" % ptrs[-1]])
+        ctab, rtab = (ptrs[0::2] + [0, 0, 0])[:3], (ptrs[1::2] + [0, 0, 0])[:3]
+        if d["pair"] and not (ptrs and all(ptrs)):
+            return 0, None, out   # the two-role form reads both tables
+        tabled = bool(d["tables"]) and all(ctab[:len(jobs)])
+        lds, a2 = (d["lds_tabled"], d["a2_tabled"]) if tabled else (d["lds"], d["a2"])
+        table = [w for p in range(3) for w in (([d["plane"][p][x] for x in ("sw", "sh", "dw", "dh", "scx", "scy")] + [0, d["pitch"], d["rows"], a2, d["rts"]]) if p < len(jobs) else [0] * 11)]
+        table += ([q["by0"] for q in d["plane"]] + [0, 0])[:3] + ([j[1] for j in jobs] + [0, 0])[:3] + ([j[0] for j in jobs] + [0, 0])[:3] + [len(jobs)]
+        out.append(["%s/%d" % (f["name"], 32 if n <= 32 else 128), d["gx"], d["gy"], d["gz"], 256, lds, " ".join("%x" % w for w in table),
+                    " ".join("%x %x" % (p & 0xffffffff, p >> 32) for p in ctab + rtab)])
+        return 1, "k_lanczos_mfma<%s>" % f["name"], out
+    finally:
+        if locked:
+            L.lzp_cache_end(cache, STREAM, 0, cap, 1)
+        L.lzp_cache_free(cache)
+
+
+def test_recorded_launches(lzp):
+    """tests/golden/lzm_launch_kat.json: what launch_lanczos_mfma launched at the commit before its policy became lzm_launch (hash in the file), recorded without
+    a device — every build launch and the main launch with grid, block, dynamic LDS and arguments, with tables on, off, a table budget of 0, and with a
+    caller's workspace of three sizes; the refusals; the lab build's pair forms.  The launcher's sequence, restated above on the plan, leaves the same lines"""
+    doc = json.load(open(os.path.join(ROOT, "tests", "golden", "lzm_launch_kat.json")))
+    assert doc["columns"] == ["lab_build", "variant", "mfma", "mode", "capturing", "n", "njobs", "jobs", "misalignment", "ret", "label", "launches"]
+    assert len(doc["parent_commit"]) == 40 and 150 <= len(doc["rows"]) <= 400
+    labels, builds, outcomes = set(), set(), set()
+    for row in doc["rows"]:
+        got = replay_launcher(lzp, row)
+        assert got == (row[9], row[10], row[11]), (row[:9], got, row[9:])
+        labels.add(row[10])
+        builds |= {l[0] for l in row[11][:-1]}
+        outcomes.add((row[9], row[3], bool(row[2] & 0x10000), len(row[11]) > 1))
+    assert labels == {None} | {"k_lanczos_mfma<%s>" % form(lzp, f)["name"] for f in range(16) if f != 12}, labels   # (LzMfma2k8: no shape reaches it)
+    assert builds >= {"cols<8, 1>", "cols<4, 2>", "cols<2, 3>", "cols<4, 1>", "rows"}
+    assert outcomes >= {(1, 0, False, True), (1, 0, True, False), (1, 1, False, False), (1, 2, False, True), (1, 3, False, True), (0, 0, False, False), (0, 1, False, False)}, outcomes
+    assert any(r[0] and r[3] == 1 and not r[9] and r[2] & 0x20000 and not r[1] and not any(r[8]) for r in doc["rows"])   # the pair form without its tables declines

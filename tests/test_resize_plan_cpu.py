@@ -18,7 +18,7 @@ import subprocess
 
 import pytest
 
-from cases_resize_families import CASES, LANCZOS3, LINEAR, MP, NEAREST, PB, RGB_32F, RGB_32F_PLANAR, planes_of
+from cases_resize_families import CASES, LANCZOS3, LINEAR, MFMA, MP, NEAREST, PB, RGB_32F, RGB_32F_PLANAR, planes_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 (NONE, GATHER, ROWPAIR, BAND, TILE, HALF, HALF3, LZ_MFMA, LZ_TILE, LZ_GATHER, F32_TILE, F32_GATHER) = range(12)   # ResizeFamily (csrc/vpf_resize_plan.h)
@@ -39,6 +39,7 @@ def L(tmp_path_factory):
     lib.rp_plan_tile.argtypes, lib.rp_plan_tile.restype = [C.c_int, C.c_int, C.c_int, C.POINTER(u32), u32, C.c_int, C.POINTER(u32)], None
     for f, a in (("rp_band_slots", [C.c_int, u32, u32]), ("rp_band_rows_exact", [C.c_int, u32, u32]), ("rp_strip_bytes", [C.c_int, u32, u32, u32]), ("rp_strip_bytes_px4", [u32, u32])):
         getattr(lib, f).argtypes, getattr(lib, f).restype = a, u32
+    lib.rp_lzm_form.argtypes, lib.rp_lzm_form.restype = [C.c_int, C.POINTER(u32), C.POINTER(u64), C.POINTER(u32), u32, C.c_int, C.c_int], C.c_char_p
     assert (lib.rp_small_batch(), lib.rp_max_batch(), lib.rp_launch_words()) == (32, 128, len(FIELDS))
     return lib
 
@@ -91,17 +92,19 @@ def geom(j, pl, l):
 
 
 def replay(P, jobs, mfma_takes):
-    """the launches of launch_resize_planned (csrc/k_resize.hip) in its order; mfma_takes(planes) stands for launch_lanczos_mfma's answer.
+    """the launches of launch_resize_planned (csrc/k_resize.hip) in its order; mfma_takes(the jobs it is handed) stands for launch_lanczos_mfma's answer:
+    the label of its launch, or None where it declines.
     A launch: [label, gx, gy, gz, block, lds, k, PlaneGeom words] — k = -1, every plane: [PlaneGeom words per plane, by0, k, ch per plane], the used
-    part of the PlaneTable — or ["mfma", planes]"""
+    part of the PlaneTable — or [the matrix-core launcher's label, planes]"""
     assert P["ok"]
     out = []
     if P["single"]:
         j, l = jobs[0], P["plane"][0]
         fam = l["family"]
         if fam == LZ_MFMA:
-            if mfma_takes(1):
-                return [["mfma", 1]]
+            took = mfma_takes([j])
+            if took:
+                return [[took, 1]]
             fam = l["fallback"]
         return [[label_of(l, fam, j[0], True, False), l["gx"], l["gy"], 1, l["threads"], l["lds"], 0, geom(j, l, l)]]
 
@@ -111,13 +114,15 @@ def replay(P, jobs, mfma_takes):
         return out + [[label_of(m, m["family"], 0, False, True), m["gx"], m["gy"], m["gz"], m["threads"], m["lds"], -1, table]]
     if P["lz_tile_all_first"]:
         return every_plane()
-    if P["lz_mfma_all"] and mfma_takes(len(jobs)):
-        return [["mfma", len(jobs)]]
+    took = P["lz_mfma_all"] and mfma_takes(jobs)
+    if took:
+        return [[took, len(jobs)]]
     declined = []
     for p, l in enumerate(P["plane"][:len(jobs)]):
-        declined.append(l["family"] == LZ_MFMA and not mfma_takes(1))
-        if l["family"] == LZ_MFMA and not declined[-1]:
-            out.append(["mfma", 1])
+        took = l["family"] == LZ_MFMA and mfma_takes([jobs[p]])
+        declined.append(l["family"] == LZ_MFMA and not took)
+        if took:
+            out.append([took, 1])
     if (P["lz_tile_all_fallback"] and all(declined)) or P["all"]:
         return every_plane()
     for p, (j, l) in enumerate(zip(jobs, P["plane"])):
@@ -152,8 +157,8 @@ def test_recorded_launches(L, kat):
         P = plan(L, f32, interp, jobs, n, call_n, [int(v, 16) for v in sb], [int(v, 16) for v in db], knobs)
         todo = list(want)   # the matrix-core launches come first in a dispatch: the record's head says what that launcher took
 
-        def mfma_takes(planes):
-            return bool(todo) and todo[0] == ["mfma", planes] and bool(todo.pop(0))
+        def mfma_takes(js):   # (the record names the launcher, not its form: tests/golden/lzm_launch_kat.json has the forms)
+            return "mfma" if todo and todo[0] == ["mfma", len(js)] and todo.pop(0) else None
         got = replay(P, jobs, mfma_takes)
         assert len(got) == len(want) and all(same_launch(g, w, kat["label_prefixes"]) for g, w in zip(got, want)), (row[:11], got, want)
         labels |= {w[0] for w in want}
@@ -171,7 +176,9 @@ def case_bits(fmt, sw, sh, dw, dh, n, off):
 
 
 def test_rows_of_the_gpu_case_table(L):
-    seen = set()
+    """... the matrix-core rows by the exact form: lzm_launch (csrc/vpf_lzm_plan.h) is asked what launch_lanczos_mfma is asked — the planes it is handed, the
+    frames of the dispatch, the planes' alignment and pitches, the two knobs"""
+    seen, forms = set(), set()
     for name, fmt, interp, sw, sh, dw, dh, n, knobs, off, want in CASES:
         f32, jobs = jobs_of(fmt, sw, sh, dw, dh)
         sb, db = case_bits(fmt, sw, sh, dw, dh, n, off)
@@ -179,11 +186,17 @@ def test_rows_of_the_gpu_case_table(L):
         for base in range(0, n, 32 if interp == LANCZOS3 else 128):   # frames_per_dispatch (csrc/vpf_abi.hip) for planes this small
             m = min(n - base, 32 if interp == LANCZOS3 else 128)
             P = plan(L, f32, interp, jobs, m, n, sb, db, knobs)
-            # (with a device the matrix-core launcher takes these small planes unless it is switched off or a source row is not 16-B aligned)
-            got += replay(P, jobs, lambda planes: (knobs[3] & 0xffff) != 1 and not any(v % 16 for v in sb))
-        assert [g[0] for g in got] == [w if not w.startswith("k_lanczos_mfma<") else "mfma" for w in want], (name, [g[0] for g in got])
+
+            def mfma_takes(js):
+                form = L.rp_lzm_form(len(js), (C.c_uint32 * 18)(*[v for j in js for v in j]), (C.c_uint64 * 3)(*[sb[j[1]] | db[j[1]] for j in js]),
+                                     (C.c_uint32 * 6)(*[(j[0] * w + 255) // 256 * 256 for j in js for w in (j[2], j[4])]), m, knobs[0], knobs[3])   # (8-bit planes: case_bits)
+                return MFMA(form.decode()) if form else None
+            got += replay(P, jobs, mfma_takes)
+        assert [g[0] for g in got] == want, (name, [g[0] for g in got])
+        forms |= {g[0] for g in got if g[0].startswith("k_lanczos_mfma<")}
         seen |= {P["mp"]["family"]} if P["all"] else {l["family"] for l in P["plane"][:len(jobs)]}
     assert seen >= {GATHER, ROWPAIR, BAND, TILE, HALF, HALF3, LZ_MFMA, LZ_TILE, LZ_GATHER, F32_TILE, F32_GATHER}, seen
+    assert forms == {MFMA("LzMfma" + f) for f in ("8", "8n", "8w", "4", "4n", "8u", "4u", "4k4", "4k6", "4k8", "2k6")}, forms   # (8uw: large launches only; 2k8: no shape)
 
 
 def sweep_inputs():

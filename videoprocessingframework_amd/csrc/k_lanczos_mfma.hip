@@ -46,6 +46,7 @@
 // VGPRs: 2 x 4 x NT x KC column operands + 2 x 4 x NT ring + two staging sets: NT = 8 -> two waves per SIMD, NT = 4 -> three (KC = 2: two).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <atomic>
 #include <mutex>
@@ -949,6 +950,9 @@ template <int CH> struct LzMfma2k8 : LanczosMfmaTask<CH, 2, 8, 3> {};  // ... 51
 template <int CH> struct LzPair : LanczosPairTask<CH, 4> {};    // the two-role form: two 8-tile strips per workgroup, three workgroups per CU
 template <int CH> struct LzPairN : LanczosPairTask<CH, 2> {};
 template <int CH> struct LzPairW : LanczosPairTask<CH, 5> {};
+constexpr bool kLzmPairForms = true;
+#else
+constexpr bool kLzmPairForms = false;  // (the two-role form lives in the lab build: tools/lab/libvpfhip_forms.so)
 #endif
 
 // all planes of up to 32 frames in one dispatch (the k_planes_mp scheme of k_resize_common.h, with this family's register budget:
@@ -972,11 +976,41 @@ __global__ __launch_bounds__(256, TaskCH<3>::kGroupsPerCu) void k_lanczos_mfma(c
   }
 }
 
-// Two workgroups per CU share its 160 KB of LDS: up to 80 KB per workgroup, which is above the 64 KB a kernel gets without asking
-// (a 2x down-scale with 8-tile strips stages 544-B rows: 76 KB).  hipFuncSetAttribute is per device and not a stream operation: done
+// ---- The host side.  WHAT a call launches is lzm_launch (vpf_lzm_plan.h: a pure function of the shapes, the frame table's alignment and pitches
+// and the two knobs, tested on the CPU); launch_lanczos_mfma below reduces the frame table, asks it once, hands out the weight tables and
+// dispatches on the answer.  A form (LzmForm) becomes its alias struct in ONE place: with_lzm_form calls f(LzmFormTag<alias>) (not for a form
+// this build does not have)
+template <template <int> class TaskCH> struct LzmFormTag {};
+template <class F>
+static void with_lzm_form(LzmForm form, F&& f) {
+  switch (form) {
+    case LZM_8: f(LzmFormTag<LzMfma8>{}); break;
+    case LZM_8N: f(LzmFormTag<LzMfma8n>{}); break;
+    case LZM_8W: f(LzmFormTag<LzMfma8w>{}); break;
+    case LZM_4: f(LzmFormTag<LzMfma4>{}); break;
+    case LZM_4N: f(LzmFormTag<LzMfma4n>{}); break;
+    case LZM_8U: f(LzmFormTag<LzMfma8u>{}); break;
+    case LZM_4U: f(LzmFormTag<LzMfma4u>{}); break;
+    case LZM_8UW: f(LzmFormTag<LzMfma8uw>{}); break;
+    case LZM_4K4: f(LzmFormTag<LzMfma4k4>{}); break;
+    case LZM_4K6: f(LzmFormTag<LzMfma4k6>{}); break;
+    case LZM_4K8: f(LzmFormTag<LzMfma4k8>{}); break;
+    case LZM_2K6: f(LzmFormTag<LzMfma2k6>{}); break;
+    case LZM_2K8: f(LzmFormTag<LzMfma2k8>{}); break;
+#ifdef VPF_LAB_FORMS
+    case LZM_PAIR: f(LzmFormTag<LzPair>{}); break;
+    case LZM_PAIR_N: f(LzmFormTag<LzPairN>{}); break;
+    case LZM_PAIR_W: f(LzmFormTag<LzPairW>{}); break;
+#endif
+    default: break;
+  }
+}
+
+// Two workgroups per CU share its 160 KB of LDS: up to 80 KB per workgroup, which is above the 64 KB a kernel gets without asking.
+// hipFuncSetAttribute is per device and not a stream operation: done
 // once per device and kernel, outside any capture-sensitive path (it neither allocates nor synchronises).
 template <template <int> class TaskCH>
-static bool lzm_big_lds_ok() {
+static bool lzm_big_lds_ok(LzmFormTag<TaskCH>) {
   static std::atomic<uint64_t> done{0}, failed{0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return false;
@@ -988,9 +1022,26 @@ static bool lzm_big_lds_ok() {
   done.fetch_or(bit, std::memory_order_release);
   return e == hipSuccess;
 }
+// (grid.z = the frames of the launch: up to 32 take the small frame table, more the large one — two instantiations of the same kernel)
+template <template <int> class TaskCH>
+static void launch_lzm_form(LzmFormTag<TaskCH>, hipStream_t st, dim3 grid, uint32_t lds, const BatchArgsL& a, const PlaneTable& t, const LzmTableArgs& wt) {
+  (void)hipGetLastError();
+  if (grid.z <= (uint32_t)kSmallBatch) hipLaunchKernelGGL((k_lanczos_mfma<TaskCH, BatchArgs>), grid, dim3(256), lds, st, small_batch(a, grid.z), t, wt);
+  else hipLaunchKernelGGL((k_lanczos_mfma<TaskCH, BatchArgsL>), grid, dim3(256), lds, st, a, t, wt);
+}
+// the build kernel of one table request of plane `q`
+static void launch_lzm_build(hipStream_t st, const LzmLaunch& L, const LzmLaunchPlane& q, const LzmTableReq& r, u32x4* out) {
+  (void)hipGetLastError();
+  const dim3 grid(r.gx, r.gy), block(64);
+  if (r.kind == 1) { hipLaunchKernelGGL(k_lzm_build_rows, grid, block, 0, st, q.sh, q.dh, q.scy, L.rows, L.rts, (uint32_t)L.up2, out); return; }
+  switch (r.cols) {  // (r.k0 = the plane's channels)
+    case LZM_COLS_8_1: hipLaunchKernelGGL((k_lzm_build_cols<8, 1>), grid, block, 0, st, r.k0, q.sw, q.dw, q.scx, out); break;
+    case LZM_COLS_4_2: hipLaunchKernelGGL((k_lzm_build_cols<4, 2>), grid, block, 0, st, r.k0, q.sw, q.dw, q.scx, out); break;
+    case LZM_COLS_2_3: hipLaunchKernelGGL((k_lzm_build_cols<2, 3>), grid, block, 0, st, r.k0, q.sw, q.dw, q.scx, out); break;
+    default: hipLaunchKernelGGL((k_lzm_build_cols<4, 1>), grid, block, 0, st, r.k0, q.sw, q.dw, q.scx, out); break;
+  }
+}
 
-// the per-shape weight tables' bookkeeping (vpf_lzm_plan.h); VPF_HIP_LANCZOS_TABLE_KB shrinks the part of the arena that is handed out
-// (0 = no tables at all): a test knob for the "arena full" path, read once
 // HIP events behind the fallback arena's bookkeeping (vpf_lzm_plan.h: LzmSync).  The caller of launch_lanczos_mfma holds a DeviceGuard: the
 // current device is the one the launch — and these events — belong to.
 static std::atomic<u32x4*> g_lzm_arena_base[64];  // the static arena's address per device (lzm_arena_base)
@@ -1033,7 +1084,8 @@ struct LzmHipSync final : LzmSync {
     return cs != hipStreamCaptureStatusNone ? 1 : 0;
   }
 };
-// VPF_HIP_LANCZOS_TABLE_KB shrinks the part of the arena that is handed out (0 = no tables at all): a test knob, read once
+// the per-shape weight tables' bookkeeping (vpf_lzm_plan.h); VPF_HIP_LANCZOS_TABLE_KB shrinks the part of the arena that is handed out
+// (0 = no tables at all): a test knob for the "arena full" path, read once
 static LzmTableCache& lzm_tables() {
   static LzmHipSync sync;
   static LzmTableCache cache([] {
@@ -1059,148 +1111,101 @@ thread_local vpf_workspace* t_lzm_workspace = nullptr;
 void set_lanczos_workspace(vpf_workspace* ws) { t_lzm_workspace = ws; }
 uint64_t lanczos_table_bytes_bound(int ch, uint32_t dw, uint32_t dh) { return lzm_table_bytes_bound(ch, dw, dh); }
 
-bool launch_lanczos_mfma(hipStream_t st, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a) {
-  const int tune = tuning(VPF_TUNE_NV12_RGB_VARIANT), knob = tuning(VPF_TUNE_RESIZE_MFMA);
-  const int forced = knob & 0xffff;           // 0 policy | 1 off | (nt << 8 | band rows / 16): measurement and test knob
-  const bool tables = !(knob & 0x10000);      // | 0x10000: evaluate the weights in the kernel (the path a full arena takes)
-#ifdef VPF_LAB_FORMS
-  const bool pair = (knob & 0x20000) != 0;    // | 0x20000: the two-role form (LanczosPairTask): 8-tile strips only
-#else
-  constexpr bool pair = false;                // (the two-role form lives in the lab build: tools/lab/libvpfhip_forms.so)
-#endif
-  if (tune == 9 || tune == 40 || forced == 1) return false;
-  if (njobs < 1 || njobs > 3 || !n || n > (uint32_t)kMaxBatch) return false;
-  for (int p = 0; p < njobs; p++) {
-    const ResizeJob& j = jobs[p];
-    if (j.sw >= (1u << 22) || j.sh >= (1u << 22) || j.dw >= (1u << 22) || j.dh >= (1u << 22)) return false;
-    for (uint32_t i = 0; i < n; i++) {
-      if ((((uintptr_t)a.f[i].s[j.k] | a.f[i].sp[j.k] | (uintptr_t)a.f[i].d[j.k] | a.f[i].dp[j.k]) & 15)) return false;
-      // the kernel addresses a plane with 32-bit offsets built by 24-bit multiplies
-      if (a.f[i].sp[j.k] >= (1u << 24) || a.f[i].dp[j.k] >= (1u << 24) || (uint64_t)j.sh * a.f[i].sp[j.k] >= (1ull << 32) || (uint64_t)j.dh * a.f[i].dp[j.k] >= (1ull << 32)) return false;
-    }
-    if (!lzm_shape(j.ch, j.sw, j.sh, j.dw, j.dh).rows_ok) return false;
+// The tables of ONE launch.  Where they live: the caller's workspace when there is one on this thread and it is large enough for every plane,
+// else the static arena (its cache is locked from the first lookup to the launch: builds and the kernel are queued under the lock).
+// Leaves the arena's lock on every way out; the launch's entries get their "last use" event once the kernel is queued (not under capture:
+// an event recorded there would be a node of the graph, and entries a graph was captured with are simply not handed back: LzmTableCache::get)
+class LzmLaunchTables {
+ public:
+  LzmLaunchTables(hipStream_t st, int dev, bool capturing) : st_(st), dev_(dev), capturing_(capturing) {}
+  ~LzmLaunchTables() {
+    if (!locked_) return;
+    if (launched && n_ids_ && !capturing_) lzm_tables().used(st_, dev_, ids_, n_ids_);
+    lzm_tables().end();
   }
-  LzmPlaneIn in[3];
-  for (int p = 0; p < njobs; p++) in[p] = LzmPlaneIn{jobs[p].ch, jobs[p].sw, jobs[p].sh, jobs[p].dw, jobs[p].dh};
-  // launch shape by the cost model of vpf_lzm_plan.h (| 0x80000: never the ring of two, the measurement and test knob)
-  const LzmPlan plan = lzm_plan(njobs, in, n, pair ? ((8 << 8) | (forced & 0xff)) : forced, tables, !pair && !(knob & 0x80000));
-  if (!plan.ok) return false;
-  const int nt = plan.nt, kc = plan.kc;
-  const uint32_t rts = (uint32_t)plan.rts;  // log2 of the destination rows per tile: 4, or 3 (half tiles)
-  if (pair && rts != 4) return false;
-  const uint32_t band_tiles = plan.band_tiles, span = plan.span, pitch = plan.pitch, wave_lds = plan.wave_lds;
-  const bool narrow = span <= 2u * 64u;  // two staging loads per lane and tile cover the strip
-  const bool up2 = plan.up2;  // the ring of two (LanczosMfmaTask<.., UP2>): narrow strips, every plane's destination tiles within two source tiles
-  PlaneTable t{};
-  LzmTableArgs wt{};
-  t.np = (uint32_t)njobs;
-  uint32_t gx = 0, gy = 0;
+  // one table of one plane: -> its address (nullptr: evaluate the weights in the kernel), building it first — build(address) — where nobody has
+  template <class Build>
+  const u32x4* get(const LzmTableReq& r, Build&& build) {
+    if (wrec_) {
+      const LzmTableCache::Hit h = wrec_->get(wsp_->bytes, st_, dev_, capturing_, r.kind, r.k0, r.k1, r.k2, r.k3, r.bytes, &ws_touched_);
+      if (h.off16) {
+        u32x4* const p = static_cast<u32x4*>(wsp_->ptr) + h.off16;
+        if (h.build) build(p);
+        return p;
+      }
+    }
+    if (!locked_) { lzm_tables().begin(dev_); locked_ = true; arena_ = lzm_arena_base(dev_); }
+    if (!arena_) return nullptr;
+    const LzmTableCache::Hit h = lzm_tables().get(st_, dev_, capturing_, r.kind, r.k0, r.k1, r.k2, r.k3, r.bytes);
+    if (!h.off16) return nullptr;
+    if (h.build) { build(arena_ + h.off16); lzm_tables().built(h.id, st_, capturing_); }
+    ids_[n_ids_++] = h.id;
+    return arena_ + h.off16;
+  }
+  bool launched = false;  // the kernel that reads the tables has been queued
+
+ private:
+  const hipStream_t st_;
+  const int dev_;
+  const bool capturing_;
+  vpf_workspace* const wsp_ = t_lzm_workspace;
+  LzmWorkspace* const wrec_ = wsp_ && wsp_->ptr && ((uintptr_t)wsp_->ptr & 255u) == 0 ? reinterpret_cast<LzmWorkspace*>(wsp_->opaque) : nullptr;
+  uint32_t ws_touched_ = 0;  // the workspace entries this launch has been given (hit or added): never dropped under it
+  bool locked_ = false;      // the arena's cache: locked at the first lookup; the entries it handed out
+  u32x4* arena_ = nullptr;
+  int ids_[6], n_ids_ = 0;
+};
+
+bool launch_lanczos_mfma(hipStream_t st, int njobs, const ResizeJob* jobs, uint32_t n, const BatchArgsL& a) {
+  LzmPlaneIn in[3] = {};
+  LzmFramesIn fr[3] = {};
+  if (njobs >= 1 && njobs <= 3 && n <= (uint32_t)kMaxBatch)  // (else lzm_launch declines before it reads them)
+    for (int p = 0; p < njobs; p++) {
+      const ResizeJob& j = jobs[p];
+      in[p] = LzmPlaneIn{j.ch, j.sw, j.sh, j.dw, j.dh};
+      for (uint32_t i = 0; i < n; i++) {
+        const FrameDesc& f = a.f[i];
+        fr[p].bits |= (uintptr_t)f.s[j.k] | f.sp[j.k] | (uintptr_t)f.d[j.k] | f.dp[j.k];
+        fr[p].sp_max = std::max(fr[p].sp_max, f.sp[j.k]);
+        fr[p].dp_max = std::max(fr[p].dp_max, f.dp[j.k]);
+      }
+    }
+  const LzmLaunch L = lzm_launch(njobs, in, fr, n, tuning(VPF_TUNE_NV12_RGB_VARIANT), tuning(VPF_TUNE_RESIZE_MFMA), kLzmPairForms);
+  if (!L.ok()) return false;
   int dev = 0;
   bool capturing = false;
-  // where this launch's tables live: the caller's workspace when there is one on this thread and it is large enough for every plane,
-  // else the static arena (its cache is locked from the first lookup to the launch: builds and the kernel are queued under the lock)
-  vpf_workspace* const wsp = tables ? t_lzm_workspace : nullptr;
-  LzmWorkspace* const wrec = wsp && wsp->ptr && ((uintptr_t)wsp->ptr & 255u) == 0 ? reinterpret_cast<LzmWorkspace*>(wsp->opaque) : nullptr;
-  bool arena_locked = false;
-  int arena_ids[6], n_arena = 0;
-  u32x4* arena = nullptr;
-  if (tables) {
+  if (L.tables) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return false;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
     capturing = cs != hipStreamCaptureStatusNone;
   }
-  uint32_t ws_touched = 0;  // the workspace entries this launch has been given (hit or added): never dropped under it
-  // one table of one plane: -> its address (nullptr: evaluate the weights in the kernel), building it first where nobody has
-  auto table = [&](uint32_t kind, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, uint64_t bytes, auto&& build) -> const u32x4* {
-    if (wrec) {
-      const LzmTableCache::Hit h = wrec->get(wsp->bytes, st, dev, capturing, kind, k0, k1, k2, k3, bytes, &ws_touched);
-      if (h.off16) {
-        u32x4* const p = static_cast<u32x4*>(wsp->ptr) + h.off16;
-        if (h.build) { (void)hipGetLastError(); build(p); }
-        return p;
-      }
-    }
-    if (!arena_locked) { lzm_tables().begin(dev); arena_locked = true; arena = lzm_arena_base(dev); }
-    if (!arena) return nullptr;
-    const LzmTableCache::Hit h = lzm_tables().get(st, dev, capturing, kind, k0, k1, k2, k3, bytes);
-    if (!h.off16) return nullptr;
-    if (h.build) { (void)hipGetLastError(); build(arena + h.off16); lzm_tables().built(h.id, st, capturing); }
-    arena_ids[n_arena++] = h.id;
-    return arena + h.off16;
-  };
+  LzmLaunchTables tables(st, dev, capturing);
+  LzmTableArgs wt{};
+  int ncols = 0, nrows = 0;  // planes that have their column / row table
+  for (int p = 0; p < njobs && L.tables; p++) {
+    const LzmLaunchPlane& q = L.plane[p];
+    ncols += (wt.ctab[p] = tables.get(q.ctab, [&](u32x4* out) { launch_lzm_build(st, L, q, q.ctab, out); })) != nullptr;
+    nrows += (wt.rtab[p] = tables.get(q.rtab, [&](u32x4* out) { launch_lzm_build(st, L, q, q.rtab, out); })) != nullptr;
+  }
+  if (L.pair && ncols + nrows != 2 * njobs) return false;  // the two-role form reads both tables
+  const bool tabled = ncols == njobs;  // every plane has its column table: the smaller LDS outcome
+  const uint32_t lds = tabled ? L.lds_tabled : L.lds, a2 = tabled ? L.a2_tabled : L.a2;
+  PlaneTable t{};
+  t.np = (uint32_t)njobs;
   for (int p = 0; p < njobs; p++) {
-    const ResizeJob& j = jobs[p];
-    const float scx = (float)j.sw / (float)j.dw, scy = (float)j.sh / (float)j.dh;
-    const uint32_t rows = band_tiles << rts;
-    if (tables) {
-      const uint32_t strips = (j.dw * (uint32_t)j.ch + 16u * nt - 1) / (16u * nt), bands = (j.dh + rows - 1) / rows, gpb = (rows + (4u << rts) - 1) >> (rts + 2u);
-      wt.ctab[p] = table(0, (uint32_t)j.ch, j.sw, j.dw, (uint32_t)nt | (uint32_t)kc << 8, (uint64_t)strips * nt * kc * 2048u, [&](u32x4* out) {
-        if (nt == 8) hipLaunchKernelGGL((k_lzm_build_cols<8, 1>), dim3(strips), dim3(64), 0, st, (uint32_t)j.ch, j.sw, j.dw, scx, out);
-        else if (kc == 2) hipLaunchKernelGGL((k_lzm_build_cols<4, 2>), dim3(strips), dim3(64), 0, st, (uint32_t)j.ch, j.sw, j.dw, scx, out);
-        else if (kc == 3) hipLaunchKernelGGL((k_lzm_build_cols<2, 3>), dim3(strips), dim3(64), 0, st, (uint32_t)j.ch, j.sw, j.dw, scx, out);
-        else hipLaunchKernelGGL((k_lzm_build_cols<4, 1>), dim3(strips), dim3(64), 0, st, (uint32_t)j.ch, j.sw, j.dw, scx, out);
-      });
-      wt.rtab[p] = table(1, j.sh, j.dh, rows, rts | (uint32_t)up2 << 8, (uint64_t)bands * gpb * kLzmWmBytes, [&](u32x4* out) {
-        hipLaunchKernelGGL(k_lzm_build_rows, dim3(gpb, bands), dim3(64), 0, st, j.sh, j.dh, scy, rows, rts, (uint32_t)up2, out);
-      });
-    }
-    t.g[p] = PlaneGeom{j.sw, j.sh, j.dw, j.dh, scx, scy, 0, pitch, rows, wave_lds, rts};
-    t.k[p] = (uint32_t)j.k; t.ch[p] = (uint32_t)j.ch; t.by0[p] = gy;
-    const uint32_t strips_p = (j.dw * j.ch + 16u * nt - 1) / (16u * nt), bxs = pair ? (strips_p + 1) / 2 : (strips_p + 3) / 4;
-    gx = bxs > gx ? bxs : gx;
-    gy += (j.dh + rows - 1) / rows;
+    const LzmLaunchPlane& q = L.plane[p];
+    t.g[p] = PlaneGeom{q.sw, q.sh, q.dw, q.dh, q.scx, q.scy, 0, L.pitch, L.rows, a2, L.rts};
+    t.k[p] = (uint32_t)jobs[p].k; t.ch[p] = (uint32_t)jobs[p].ch; t.by0[p] = q.by0;
   }
-  // leaves the arena's lock on every way out; the launch's entries get their "last use" event once the kernel is queued (not under capture:
-  // an event recorded there would be a node of the graph, and entries a graph was captured with are simply not handed back: see below)
-  struct ArenaUnlock {
-    bool& locked; hipStream_t st; int dev; bool capturing; int* ids; int& n; bool launched = false;
-    ~ArenaUnlock() {
-      if (!locked) return;
-      if (launched && n && !capturing) lzm_tables().used(st, dev, ids, n);
-      lzm_tables().end();
-    }
-  } unlock{arena_locked, st, dev, capturing, arena_ids, n_arena};
-  const dim3 grid(gx, gy, n);
-  // a wave's LDS = the staged tile + the out tile, or — larger for the narrow strips — the scratch the column weights are composed in: not
-  // needed when every plane's column table is there (a 4-tile up-scale strip: 48 -> 31 KiB per workgroup, a fourth workgroup per CU)
-  uint32_t lds = pair ? lzm_pair_group_lds(lzm_pf_of(span)) : plan.group_lds;
-  if (!pair && tables) {
-    bool all = true;
-    for (int p = 0; p < njobs; p++) all = all && wt.ctab[p] != nullptr;
-    const uint32_t run = 16u * pitch + 16u * lzm_out_pitch(nt);
-    if (all && run < wave_lds) {
-      for (int p = 0; p < njobs; p++) t.g[p].a2 = run;
-      lds = 4u * run + 2u * kLzmWmBytes;
-    }
-  }
-  if (pair) for (int p = 0; p < njobs; p++) if (!wt.ctab[p] || !wt.rtab[p]) return false;  // the two-role form reads both tables
-  if (lds > 64u * 1024u && !(kc == 3 ? (lzm_pf_of(span, 3) == 8 ? lzm_big_lds_ok<LzMfma2k8>() : lzm_big_lds_ok<LzMfma2k6>()) : kc == 2 ? (lzm_pf_of(span, 2) == 8 ? lzm_big_lds_ok<LzMfma4k8>() : lzm_pf_of(span, 2) == 6 ? lzm_big_lds_ok<LzMfma4k6>() : lzm_big_lds_ok<LzMfma4k4>())
-                             : nt == 8 ? (span > 4u * 64u ? lzm_big_lds_ok<LzMfma8w>() : lzm_big_lds_ok<LzMfma8>()) : lzm_big_lds_ok<LzMfma4>())) return false;
-#define VPF_LZM_GO(K) do { if (log_level() >= 2 || trace_on()) note_kernel("k_lanczos_mfma<" #K ">"); (void)hipGetLastError(); \
-                           if (n <= (uint32_t)kSmallBatch) hipLaunchKernelGGL((k_lanczos_mfma<K, BatchArgs>), grid, dim3(256), lds, st, small_batch(a, n), t, wt); \
-                           else hipLaunchKernelGGL((k_lanczos_mfma<K, BatchArgsL>), grid, dim3(256), lds, st, a, t, wt); \
-                           unlock.launched = true; } while (0)
-  if (kc == 3 && lzm_pf_of(span, 3) == 8) VPF_LZM_GO(LzMfma2k8);
-  else if (kc == 3) VPF_LZM_GO(LzMfma2k6);
-  else if (kc == 2 && lzm_pf_of(span, 2) == 8) VPF_LZM_GO(LzMfma4k8);
-  else if (kc == 2 && lzm_pf_of(span, 2) == 6) VPF_LZM_GO(LzMfma4k6);
-  else if (kc == 2) VPF_LZM_GO(LzMfma4k4);
-#ifdef VPF_LAB_FORMS
-  else if (pair && nt == 8 && narrow) VPF_LZM_GO(LzPairN);
-  else if (pair && nt == 8 && span > 4u * 64u) VPF_LZM_GO(LzPairW);
-  else if (pair && nt == 8) VPF_LZM_GO(LzPair);
-#endif
-  else if (nt == 8 && up2 && !narrow) VPF_LZM_GO(LzMfma8uw);
-  else if (nt == 8 && up2) VPF_LZM_GO(LzMfma8u);
-  else if (up2) VPF_LZM_GO(LzMfma4u);
-  else if (nt == 8 && narrow) VPF_LZM_GO(LzMfma8n);
-  else if (nt == 8 && span > 4u * 64u) VPF_LZM_GO(LzMfma8w);
-  else if (nt == 8) VPF_LZM_GO(LzMfma8);
-  else if (narrow) VPF_LZM_GO(LzMfma4n);
-  else VPF_LZM_GO(LzMfma4);
-#undef VPF_LZM_GO
-  return true;
+  with_lzm_form(L.form, [&](auto form) {
+    if (lds > kLzmPlainLds && !lzm_big_lds_ok(form)) return;
+    char label[48];
+    if (log_level() >= 2 || trace_on()) { std::snprintf(label, sizeof label, "k_lanczos_mfma<%s>", kLzmForms[L.form].name); note_kernel(label); }
+    launch_lzm_form(form, st, dim3(L.gx, L.gy, L.gz), lds, a, t, wt);
+    tables.launched = true;
+  });
+  return tables.launched;
 }
 
 }  // namespace vpf

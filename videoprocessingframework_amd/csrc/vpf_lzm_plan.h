@@ -1,5 +1,5 @@
-// vpf_lzm_plan.h — host-side planning of the matrix-core Lanczos launch (k_lanczos_mfma.hip): which strip width and band height, and the
-// bookkeeping of the per-shape weight tables.  No HIP in here: the launcher includes it, and tests/test_lzm_plan_cpu.py compiles the same
+// vpf_lzm_plan.h — host-side planning of the matrix-core Lanczos launch (k_lanczos_mfma.hip): which strip width and band height (lzm_plan), the
+// whole launch as a description (lzm_launch: refusals, kernel form, grid, table requests, LDS), and the bookkeeping of the per-shape weight tables.  No HIP in here: the launcher includes it, and tests/test_lzm_plan_cpu.py compiles the same
 // header with g++ and checks the planner against the measured sweeps in profiles/ and the table cache against its contract.
 #pragma once
 #include <stdint.h>
@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "vpf_classes.h"
 #include "vpf_plan_bounds.h"
 
 namespace vpf {
@@ -275,6 +276,147 @@ inline LzmPlan lzm_plan(int njobs, const LzmPlaneIn* jobs, uint32_t n, int force
     }
   }
   return P;
+}
+
+// ---- the launch itself (launch_lanczos_mfma, k_lanczos_mfma.hip) as a pure function: the refusals, the kernel form, the grid, the planes' geometry
+// words, the weight tables the launch asks for and the dynamic LDS.  The launcher reduces the frame table, asks once, hands out the tables and
+// dispatches on the answer; tests/test_lzm_plan_cpu.py asks the same function without a device.
+//
+// The forms: one row per instantiation of the kernel (the alias structs of k_lanczos_mfma.hip carry the same names and template arguments; the
+// unit's with_lzm_form turns a form into its alias).  `name` is what the selection log prints between "k_lanczos_mfma<" and ">".
+enum LzmForm : int {
+  LZM_8, LZM_8N, LZM_8W, LZM_4, LZM_4N, LZM_8U, LZM_4U, LZM_8UW, LZM_4K4, LZM_4K6, LZM_4K8, LZM_2K6, LZM_2K8,
+  LZM_PAIR, LZM_PAIR_N, LZM_PAIR_W,  // the two-role form: lab builds only (tools/lab/libvpfhip_forms.so)
+  LZM_FORMS
+};
+constexpr int kLzmProductForms = LZM_PAIR;
+struct LzmFormInfo { const char* name; int nt, pf, kc; bool up2, pair; };  // nt: N-tiles per wave; pf: staging loads per lane and source tile; kc: K chunks per window
+constexpr LzmFormInfo kLzmForms[LZM_FORMS] = {
+    {"LzMfma8", 8, 4, 1, false, false},    // strips of 8 tiles, staged rows of up to 256 B
+    {"LzMfma8n", 8, 2, 1, false, false},   // ... of up to 128 B (up-scales)
+    {"LzMfma8w", 8, 5, 1, false, false},   // ... of up to 320 B (2x down-scales)
+    {"LzMfma4", 4, 4, 1, false, false},
+    {"LzMfma4n", 4, 2, 1, false, false},
+    {"LzMfma8u", 8, 2, 1, true, false},    // the ring of two (up-scales): one K chunk in pass 2
+    {"LzMfma4u", 4, 2, 1, true, false},
+    {"LzMfma8uw", 8, 4, 1, true, false},   // ... on 8-tile strips of 1.5 x up-scales (rows of up to 256 B)
+    {"LzMfma4k4", 4, 4, 2, false, false},  // two-chunk windows (strong horizontal down-scales): staged rows of up to 256 B
+    {"LzMfma4k6", 4, 6, 2, false, false},  // ... 384 B
+    {"LzMfma4k8", 4, 8, 2, false, false},  // ... 512 B
+    {"LzMfma2k6", 2, 6, 3, false, false},  // three-chunk windows, 2-tile strips (factors up to ~10): staged rows of up to 384 B
+    {"LzMfma2k8", 2, 8, 3, false, false},  // ... 512 B
+    {"LzPair", 8, 4, 1, false, true},      // the two-role form: two 8-tile strips per workgroup, three workgroups per CU
+    {"LzPairN", 8, 2, 1, false, true},
+    {"LzPairW", 8, 5, 1, false, true},
+};
+// the ONE map from a planned shape to a form: the row whose strip width, window chunks, ring and role are the plan's and whose staging
+// loads are what the span needs (lzm_pf_of).  LZM_FORMS: no such kernel (the planner never plans one: the CPU test walks its results)
+constexpr LzmForm lzm_form_of(int nt, int kc, uint32_t span, bool up2, bool pair) {
+  for (int f = 0; f < LZM_FORMS; f++)
+    if (kLzmForms[f].nt == nt && kLzmForms[f].kc == kc && kLzmForms[f].pf == lzm_pf_of(span, kc) && kLzmForms[f].up2 == up2 && kLzmForms[f].pair == pair) return (LzmForm)f;
+  return LZM_FORMS;
+}
+// A kernel gets 64 KiB of dynamic LDS without asking; beyond that the launcher sets hipFuncAttributeMaxDynamicSharedMemorySize on the form it is
+// about to launch.  (With today's sixteen forms the largest workgroup is LzMfma4k8's 55 KiB: the CPU test says so, and that no plan exceeds kLzmMaxLds.)
+constexpr uint32_t kLzmPlainLds = 64u * 1024u;
+constexpr uint32_t lzm_form_lds(LzmForm f) { return kLzmForms[f].pair ? lzm_pair_group_lds(kLzmForms[f].pf) : lzm_group_lds(kLzmForms[f].nt, lzm_pitch_of(kLzmForms[f].pf)); }
+
+// what the refusal rules need of one plane's frame table: the OR of pointer | pitch on both sides over the frames, and the largest pitches.
+// Every rule below is monotone in the pitch (sp >= 2^24, sh x sp >= 2^32 ...) and the alignment rule reads an OR: a loop over the frames and
+// one test on these reductions refuse the same calls
+struct LzmFramesIn { uint64_t bits; uint32_t sp_max, dp_max; };
+enum LzmDecline : int {  // in the order the rules are asked
+  LZM_OK = 0,
+  LZM_NO_SWITCHED_OFF,  // VPF_TUNE_NV12_RGB_VARIANT 9 / 40, VPF_TUNE_RESIZE_MFMA 1
+  LZM_NO_COUNTS,        // planes outside 1 .. 3, frames outside 1 .. kMaxBatch
+  LZM_NO_SIZE,          // a side of 2^22 pixels or more
+  LZM_NO_ALIGNMENT,     // a base or pitch that is no multiple of 16
+  LZM_NO_PITCH,         // the kernel addresses a plane with 32-bit offsets built by 24-bit multiplies
+  LZM_NO_ROWS,          // a plane's vertical factor is outside the ring (lzm_shape)
+  LZM_NO_PLAN,          // no strip width holds some plane's taps (lzm_plan)
+  LZM_NO_PAIR_HALF_TILES,  // the two-role form has whole tiles only
+  LZM_NO_FORM,
+};
+enum LzmColsBuild : int { LZM_COLS_8_1, LZM_COLS_4_2, LZM_COLS_2_3, LZM_COLS_4_1 };  // the instantiations of k_lzm_build_cols<NT, KC>
+struct LzmTableReq {
+  uint32_t kind, k0, k1, k2, k3;  // the table's key (LzmKey below, without the device)
+  uint64_t bytes;
+  uint32_t gx, gy;                // grid of its build kernel (64 threads): k_lzm_build_cols<..> (kind 0: `cols` says which) | k_lzm_build_rows (kind 1)
+  int cols;                       // LzmColsBuild
+};
+struct LzmLaunchPlane {
+  uint32_t sw, sh, dw, dh;  // PlaneGeom = {sw, sh, dw, dh, scx, scy, 0, pitch, rows, a2 | a2_tabled, rts}
+  float scx, scy;
+  uint32_t by0;             // first blockIdx.y of the plane
+  LzmTableReq ctab, rtab;
+};
+struct LzmLaunch {
+  LzmDecline why;  // LZM_OK, or why launch_lanczos_mfma declines (its caller takes the tile or gather kernel)
+  LzmForm form;
+  bool tables, pair, up2;
+  uint32_t gx, gy, gz;
+  uint32_t rts, rows, pitch;  // log2 of the destination rows per tile: 4, or 3 (half tiles); destination rows per band; LDS pitch of a staged row
+  // The dynamic LDS has two outcomes, because which applies is known only once the tables have been handed out.
+  // a wave's LDS = the staged tile + the out tile, or — larger for the narrow strips — the scratch the column weights are composed in: not
+  // needed when every plane's column table is there (a 4-tile up-scale strip: 48 -> 31 KiB per workgroup, a fourth workgroup per CU)
+  uint32_t lds, a2;                // ... some plane evaluates its column weights in the kernel: a2 = the plan's wave_lds
+  uint32_t lds_tabled, a2_tabled;  // ... every plane has its column table: a2 = the run part alone (equal to the pair above where that is no smaller)
+  LzmLaunchPlane plane[3];
+  bool ok() const { return why == LZM_OK; }
+};
+// tune, knob: VPF_TUNE_NV12_RGB_VARIANT, VPF_TUNE_RESIZE_MFMA; pair_build: the two-role form exists in this build (-DVPF_LAB_FORMS)
+inline LzmLaunch lzm_launch(int njobs, const LzmPlaneIn* jobs, const LzmFramesIn* frames, uint32_t n, int tune, int knob, bool pair_build) {
+  LzmLaunch L{};
+  const int forced = knob & 0xffff;             // 0 policy | 1 off | (nt << 8 | band rows / 16): measurement and test knob
+  L.tables = !(knob & 0x10000);                 // | 0x10000: evaluate the weights in the kernel (the path a full arena takes)
+  L.pair = pair_build && (knob & 0x20000) != 0; // | 0x20000: the two-role form (LanczosPairTask): 8-tile strips only
+  const bool tables = L.tables, pair = L.pair;
+  auto no = [&](LzmDecline why) { L.why = why; return L; };
+  if (tune == 9 || tune == 40 || forced == 1) return no(LZM_NO_SWITCHED_OFF);
+  if (njobs < 1 || njobs > 3 || !n || n > (uint32_t)kMaxBatch) return no(LZM_NO_COUNTS);
+  for (int p = 0; p < njobs; p++) {
+    const LzmPlaneIn& j = jobs[p];
+    const LzmFramesIn& f = frames[p];
+    if (j.sw >= (1u << 22) || j.sh >= (1u << 22) || j.dw >= (1u << 22) || j.dh >= (1u << 22)) return no(LZM_NO_SIZE);
+    if (f.bits & 15) return no(LZM_NO_ALIGNMENT);
+    // the kernel addresses a plane with 32-bit offsets built by 24-bit multiplies
+    if (f.sp_max >= (1u << 24) || f.dp_max >= (1u << 24) || (uint64_t)j.sh * f.sp_max >= (1ull << 32) || (uint64_t)j.dh * f.dp_max >= (1ull << 32)) return no(LZM_NO_PITCH);
+    if (!lzm_shape(j.ch, j.sw, j.sh, j.dw, j.dh).rows_ok) return no(LZM_NO_ROWS);
+  }
+  // launch shape by the cost model above (| 0x80000: never the ring of two, the measurement and test knob)
+  const LzmPlan plan = lzm_plan(njobs, jobs, n, pair ? ((8 << 8) | (forced & 0xff)) : forced, tables, !pair && !(knob & 0x80000));
+  if (!plan.ok) return no(LZM_NO_PLAN);
+  const int nt = plan.nt, kc = plan.kc;
+  const uint32_t rts = (uint32_t)plan.rts;  // log2 of the destination rows per tile: 4, or 3 (half tiles)
+  if (pair && rts != 4) return no(LZM_NO_PAIR_HALF_TILES);
+  const bool up2 = plan.up2;  // the ring of two (LanczosMfmaTask<.., UP2>): narrow strips, every plane's destination tiles within two source tiles
+  L.form = lzm_form_of(nt, kc, plan.span, up2, pair);
+  if (L.form == LZM_FORMS) return no(LZM_NO_FORM);
+  L.up2 = up2; L.rts = rts; L.pitch = plan.pitch;
+  const uint32_t rows = L.rows = plan.band_tiles << rts;
+  const LzmColsBuild cols = nt == 8 ? LZM_COLS_8_1 : kc == 2 ? LZM_COLS_4_2 : kc == 3 ? LZM_COLS_2_3 : LZM_COLS_4_1;
+  uint32_t gx = 0, gy = 0;
+  for (int p = 0; p < njobs; p++) {
+    const LzmPlaneIn& j = jobs[p];
+    const uint32_t strips = (j.dw * (uint32_t)j.ch + 16u * nt - 1) / (16u * nt), bands = (j.dh + rows - 1) / rows, gpb = (rows + (4u << rts) - 1) >> (rts + 2u);
+    LzmLaunchPlane& q = L.plane[p];
+    q.sw = j.sw; q.sh = j.sh; q.dw = j.dw; q.dh = j.dh;
+    q.scx = (float)j.sw / (float)j.dw; q.scy = (float)j.sh / (float)j.dh;
+    q.by0 = gy;
+    q.ctab = LzmTableReq{0, (uint32_t)j.ch, j.sw, j.dw, (uint32_t)nt | (uint32_t)kc << 8, (uint64_t)strips * nt * kc * 2048u, strips, 1, cols};
+    q.rtab = LzmTableReq{1, j.sh, j.dh, rows, rts | (uint32_t)up2 << 8, (uint64_t)bands * gpb * kLzmWmBytes, gpb, bands, 0};
+    const uint32_t bxs = pair ? (strips + 1) / 2 : (strips + 3) / 4;
+    gx = bxs > gx ? bxs : gx;
+    gy += bands;
+  }
+  L.gx = gx; L.gy = gy; L.gz = n;
+  L.lds = L.lds_tabled = pair ? lzm_pair_group_lds(lzm_pf_of(plan.span)) : plan.group_lds;
+  L.a2 = L.a2_tabled = plan.wave_lds;
+  if (!pair && tables) {
+    const uint32_t run = 16u * plan.pitch + 16u * lzm_out_pitch(nt);
+    if (run < plan.wave_lds) { L.a2_tabled = run; L.lds_tabled = 4u * run + 2u * kLzmWmBytes; }
+  }
+  return L;
 }
 
 // ---- weight-table bookkeeping.  The operand images of a plane shape (column weights per strip, row weights per band) are built once by two
