@@ -169,7 +169,7 @@ def planes_of(call):
 
 # ------------------------------------------------------------------------------------------------ vpf_convert / vpf_convert_batch
 # (source, destination, width, height, alignment thresholds per source plane, per destination plane).  The thresholds restate the launchers' gates
-# (aligned_all of k_yuv2rgb.hip, the loops of k_rgb2yuv.hip, al() of k_relayout.hip): a plane whose pointer and pitch are multiples of t for
+# (convert_aligned of csrc/vpf_convert_plan.h, asked by the rules of all three units): a plane whose pointer and pitch are multiples of t for
 # the first j thresholds t is on tier j, the kernel is picked by the lowest tier of the call, and with ONE plane off A256 two calls take the
 # same kernel exactly when that plane is on the same tier.  1040 x 6 / 640 x 4: the p16x / p16 / r16 converters; 1056 x 4: a multiple of 32
 # above 1024 for the r16 form of NV12 <-> YUV420.

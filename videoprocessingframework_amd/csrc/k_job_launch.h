@@ -1,5 +1,6 @@
 // k_job_launch.h — the host side the fused tensor launchers share (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip,
-// their device-table forms, launch_tensor_to_yuv, the whole-frame launch_convert_resize and the plain launch_resize_planned): the argument check, the destination alignment mask, the run-time -> template-argument
+// their device-table forms, the convert and relayout launchers of k_yuv2rgb.hip, k_rgb2yuv.hip and k_relayout.hip, the whole-frame launch_convert_resize and the
+// plain launch_resize_planned): the argument check, the destination alignment mask, the frame table's alignment bits, the run-time -> template-argument
 // dispatch, the launch of the instantiation it picked and the split of a host job table into its staged and its per-tap dispatch.  Inline functions, function templates over
 // callables and two launch macros: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
 #ifndef VPF_K_JOB_LAUNCH_H_
@@ -8,6 +9,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "vpf_convert_plan.h"
 #include "vpf_internal.h"
 
 namespace vpf {
@@ -49,7 +51,8 @@ inline bool with_tensor_dtype(uint32_t dtype, F&& f) {
 
 // VPF_LAUNCH for the 256-lane instantiation K<TARGS> a dispatcher above picked: VPF_LAUNCH_T(k_roi_strip, (S, D), grid, lds, st, args...).  The
 // selection log (VPF_HIP_LOG=2, roctx markers) gets the template-id the code object and a profiler show — "(k_roi_strip<7, 8>)": FC_NV12 = 0,
-// FC_YUV420 = 1, FC_P16 = 7, FC_TENSOR = 6, FC_TENSOR_NHWC = 8; bools as true / false — written from the same K and TARGS tokens the launch is.
+// FC_YUV420 = 1, FC_YUV444 = 2, FC_RGB = 3, FC_BGR = 4, FC_PLANAR = 5, FC_P16 = 7, FC_TENSOR = 6, FC_TENSOR_NHWC = 8; bools as true / false —
+// written from the same K and TARGS tokens the launch is.
 inline int put_targ(char* p, size_t n, int v) { return std::snprintf(p, n, "%d, ", v); }
 inline int put_targ(char* p, size_t n, bool v) { return std::snprintf(p, n, "%s, ", v ? "true" : "false"); }
 template <class T> struct TableName {};  // a frame table as a template argument: "BatchArgsT<32>", "BatchArgsTE<128>"
@@ -137,6 +140,20 @@ inline void with_frame_table(const BatchArgsL& a, uint32_t n, bool small, const 
   } else {
     f(a, lds);
   }
+}
+
+// ---- the convert and relayout launches (k_yuv2rgb.hip, k_rgb2yuv.hip, k_relayout.hip)
+// What convert_plan (vpf_convert_plan.h) looks at: the bits of every plane formed in ONE pass over the n frames of the dispatch (planes a format
+// does not have are zero in the table, and the plan does not ask for them)
+inline ConvertShape convert_shape(int kind, int src, int dst, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a, int variant) {
+  ConvertShape q{};
+  q.kind = kind; q.src = src; q.dst = dst; q.w = w; q.h = h; q.n = n; q.variant = variant;
+  for (uint32_t i = 0; i < n; i++)
+    for (int k = 0; k < 3; k++) {
+      q.src_bits[k] |= (uintptr_t)a.f[i].s[k] | a.f[i].sp[k];
+      q.dst_bits[k] |= (uintptr_t)a.f[i].d[k] | a.f[i].dp[k];
+    }
+  return q;
 }
 
 // The split of a host job table: `staged_bytes(job)` returns the dynamic LDS the job's strip needs, or kNotStaged for a job that samples per tap

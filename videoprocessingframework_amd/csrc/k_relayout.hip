@@ -9,6 +9,7 @@
 // 1024 px, every global access a dense non-temporal 1-KiB run, packed sides through a wave-private LDS transpose) for
 // 16-px / 16-B regular frames; p4 / p16 kernels (4-16 B per lane, v_perm_b32 shuffles in registers) for 4-B aligned ones;
 // a generic per-pixel kernel for everything else.
+#include "k_job_launch.h"
 #include "vpf_device.h"
 
 namespace vpf {
@@ -89,10 +90,7 @@ __global__ __launch_bounds__(256) void k_rgb_relayout_p4(const BatchArgs args, u
 // ------------------------------------------------------------------------------------------
 // generic per-pixel re-layout: any size / alignment, byte (or element) accesses.
 // ------------------------------------------------------------------------------------------
-enum GenericOp : int {
-  OP_NV12_YUV420, OP_YUV420_NV12, OP_RGB_PLANAR, OP_PLANAR_RGB, OP_SWAP_RB, OP_COPY_Y, OP_Y_YUV444,
-  OP_RGB_RGB32F, OP_RGB32F_PLANAR, OP_P16_NV12, OP_RGB_GRAY, OP_BGR_GRAY, OP_PLANAR_GRAY, OP_PLANAR_SWAP
-};
+// (GenericOp — OP_NV12_YUV420 ... : vpf_convert_plan.h, which names the op a launch takes)
 
 template <int OP>
 __global__ __launch_bounds__(256) void k_relayout_generic(const BatchArgs args, uint32_t w, uint32_t h) {
@@ -458,179 +456,69 @@ __global__ __launch_bounds__(256) void k_p16_to_8_x16_one(VPF_ONE_SRC_PARAMS, ui
   p16_to_8_x16_task(VPF_ONE_FRAME, wsamples, h, ch, chunks_x, n_tasks);
 }
 
-static bool al(const BatchArgs& a, uint32_t n, int ns, int nd, uint32_t s0, uint32_t s12, uint32_t d0, uint32_t d12) {
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < ns; k++)
-      if (((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & ((k ? s12 : s0) - 1)) return false;
-    for (int k = 0; k < nd; k++)
-      if (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & ((k ? d12 : d0) - 1)) return false;
+// host side: convert_plan (vpf_convert_plan.h) decides, this launches the instantiation it names
+static void dispatch_relayout(hipStream_t st, const ConvertPlan& P, const BatchArgs& a) {
+  const dim3 grid(P.gx, P.gy, P.gz);
+  const FrameDesc& f0 = a.f[0];
+  const uint32_t* s = P.a;
+  auto modes = [&](auto&& f) { with_value<0, 1, 2>(P.mode, f); };
+  switch (P.form) {
+    case CF_NV12_YUV420_R16:
+      with_bool(P.mode != 0, [&](auto TO_PLANAR) {
+        if (P.one) VPF_LAUNCH_T(k_nv12_yuv420_r16_one, (TO_PLANAR), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], s[4], s[5], VPF_ONE_DST_ARGS(f0));
+        else VPF_LAUNCH_T(k_nv12_yuv420_r16, (TO_PLANAR), grid, 0, st, a, s[0], s[1], s[2], s[3], s[4], s[5]);
+      });
+      break;
+    case CF_NV12_YUV420_P16: with_bool(P.mode != 0, [&](auto TO_PLANAR) { VPF_LAUNCH_T(k_nv12_yuv420_p16, (TO_PLANAR), grid, 0, st, a, s[0], s[1], s[2]); }); break;
+    case CF_RGB_RELAYOUT_R16:
+      modes([&](auto MODE) {
+        if (P.one) VPF_LAUNCH_T(k_rgb_relayout_r16_one, (MODE), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0));
+        else VPF_LAUNCH_T(k_rgb_relayout_r16, (MODE), grid, 0, st, a, s[0], s[1], s[2], s[3]);
+      });
+      break;
+    case CF_RGB_RELAYOUT_P4: modes([&](auto MODE) { VPF_LAUNCH_T(k_rgb_relayout_p4, (MODE), grid, 0, st, a, s[0], s[1], s[2]); }); break;
+    case CF_COPY_PLANE_P16: with_bool(P.mode != 0, [&](auto FILL) { VPF_LAUNCH_T(k_copy_plane_p16, (FILL), grid, 0, st, a, s[0], s[1], s[2]); }); break;
+    case CF_U8_TO_F32_X4:
+      if (P.one) VPF_LAUNCH(k_u8_to_f32_x4_one<4>, grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0));
+      else VPF_LAUNCH(k_u8_to_f32_x4<4>, grid, dim3(256), 0, st, a, s[0], s[1], s[2], s[3]);
+      break;
+    case CF_U8_TO_F32_P4: VPF_LAUNCH(k_u8_to_f32_p4, grid, dim3(256), 0, st, a, s[0], s[1], s[2]); break;
+    case CF_RGB32F_PLANAR_R4:
+      if (P.one) VPF_LAUNCH(k_rgb32f_planar_r4_one, grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0));
+      else VPF_LAUNCH(k_rgb32f_planar_r4, grid, dim3(256), 0, st, a, s[0], s[1], s[2], s[3]);
+      break;
+    case CF_P16_TO_8_X16:
+      if (P.one) VPF_LAUNCH(k_p16_to_8_x16_one, grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], s[4], VPF_ONE_DST_ARGS(f0));
+      else VPF_LAUNCH(k_p16_to_8_x16, grid, dim3(256), 0, st, a, s[0], s[1], s[2], s[3], s[4]);
+      break;
+    case CF_P16_TO_8_P8: VPF_LAUNCH(k_p16_to_8_p8, grid, dim3(256), 0, st, a, s[0], s[1], s[2], s[3]); break;
+    case CF_GRAY_R16:
+      modes([&](auto SRC) {
+        if (P.one) VPF_LAUNCH_T(k_gray_r16_one, (SRC), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0));
+        else VPF_LAUNCH_T(k_gray_r16, (SRC), grid, 0, st, a, s[0], s[1], s[2], s[3]);
+      });
+      break;
+    case CF_GRAY_P4: modes([&](auto SRC) { VPF_LAUNCH_T(k_gray_p4, (SRC), grid, 0, st, a, s[0], s[1], s[2]); }); break;
+    default:  // (every op but OP_PLANAR_SWAP, which the plan never names)
+      with_value<OP_NV12_YUV420, OP_YUV420_NV12, OP_RGB_PLANAR, OP_PLANAR_RGB, OP_SWAP_RB, OP_COPY_Y, OP_Y_YUV444, OP_RGB_RGB32F, OP_RGB32F_PLANAR, OP_P16_NV12, OP_RGB_GRAY,
+                 OP_BGR_GRAY, OP_PLANAR_GRAY>(P.mode, [&](auto OP) { VPF_LAUNCH_T(k_relayout_generic, (OP), grid, 0, st, a, s[0], s[1]); });
   }
-  return true;
-}
-
-template <int OP>
-static hipError_t go_generic(hipStream_t st, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a) {
-  dim3 grid((w + 63) / 64, (h + 3) / 4, n);
-  VPF_LAUNCH((k_relayout_generic<OP>), grid, dim3(256), 0, st, a, w, h);
-  return hipGetLastError();
 }
 
 hipError_t launch_relayout(hipStream_t st, int sf, int df, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a) {
-  const bool force_generic = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
-  // r16 kernels (dense 1-KiB non-temporal accesses) wherever the frame is 16-px / 16-B regular; tuning value 40 keeps
-  // the narrower p4 / p16 fast paths (A/B measurements, and so the tests still cover them on regular frames)
-  const bool r16 = !force_generic && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && w % 16 == 0;
-  auto row_tasks = [&](uint32_t chunks, uint32_t rows) { return dim3((chunks * rows + 3) / 4, n); };
-  const uint32_t cx = (w + 1023) / 1024;
-  if (r16 && w % 32 == 0 && h % 2 == 0 && ((sf == VPF_FMT_NV12 && df == VPF_FMT_YUV420 && al(a, n, 2, 3, 16, 16, 16, 16)) ||
-                                            (sf == VPF_FMT_YUV420 && df == VPF_FMT_NV12 && al(a, n, 3, 2, 16, 16, 16, 16)))) {
-    const uint32_t cc = (w + 2047) / 2048, luma = cx * h, total = luma + cc * (h / 2);
-    dim3 grid((total + 3) / 4, n);
-    if (n == 1 && sf == VPF_FMT_NV12) VPF_LAUNCH((k_nv12_yuv420_r16_one<true>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, cx, luma, cc, total, VPF_ONE_DST_ARGS(a.f[0]));
-    else if (n == 1) VPF_LAUNCH((k_nv12_yuv420_r16_one<false>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, cx, luma, cc, total, VPF_ONE_DST_ARGS(a.f[0]));
-    else if (sf == VPF_FMT_NV12) VPF_LAUNCH((k_nv12_yuv420_r16<true>), grid, dim3(256), 0, st, a, w, h, cx, luma, cc, total);
-    else VPF_LAUNCH((k_nv12_yuv420_r16<false>), grid, dim3(256), 0, st, a, w, h, cx, luma, cc, total);
-    return hipGetLastError();
-  }
-  if (sf == VPF_FMT_NV12 && df == VPF_FMT_YUV420) {
-    if (!force_generic && w % 16 == 0 && h % 2 == 0 && al(a, n, 2, 3, 16, 16, 16, 8)) {
-      dim3 grid((w / 16 + 63) / 64, (h / 2 + 3) / 4, n);
-      VPF_LAUNCH((k_nv12_yuv420_p16<true>), grid, dim3(256), 0, st, a, w, h, w / 16);
-      return hipGetLastError();
-    }
-    return go_generic<OP_NV12_YUV420>(st, w, h, n, a);
-  }
-  if (sf == VPF_FMT_YUV420 && df == VPF_FMT_NV12) {
-    if (!force_generic && w % 16 == 0 && h % 2 == 0 && al(a, n, 3, 2, 16, 8, 16, 16)) {
-      dim3 grid((w / 16 + 63) / 64, (h / 2 + 3) / 4, n);
-      VPF_LAUNCH((k_nv12_yuv420_p16<false>), grid, dim3(256), 0, st, a, w, h, w / 16);
-      return hipGetLastError();
-    }
-    return go_generic<OP_YUV420_NV12>(st, w, h, n, a);
-  }
-  const bool packed_s = (sf == VPF_FMT_RGB || sf == VPF_FMT_BGR), packed_d = (df == VPF_FMT_RGB || df == VPF_FMT_BGR);
-  if (packed_s && df == VPF_FMT_RGB_PLANAR) {
-    // BGR -> RGB_PLANAR: same de-interleave with planes 0 and 2 exchanged
+  const ConvertPlan P = convert_plan(convert_shape(CONVERT_RELAYOUT, sf, df, w, h, n, a, tuning(VPF_TUNE_NV12_RGB_VARIANT)));
+  if (!P.ok) return hipErrorInvalidValue;
+  if (P.swap_src02 || P.swap_dst02) {  // BGR <-> RGB_PLANAR: the RGB kernel with planes 0 and 2 of the planar side exchanged
     BatchArgs b = a;
-    if (sf == VPF_FMT_BGR)
-      for (uint32_t i = 0; i < n; i++) { std::swap(b.f[i].d[0], b.f[i].d[2]); std::swap(b.f[i].dp[0], b.f[i].dp[2]); }
-    if (r16 && al(b, n, 1, 3, 16, 16, 16, 16)) {
-      if (n == 1) VPF_LAUNCH((k_rgb_relayout_r16_one<0>), row_tasks(cx, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(b.f[0]), w, h, cx, cx * h, VPF_ONE_DST_ARGS(b.f[0]));
-      else VPF_LAUNCH((k_rgb_relayout_r16<0>), row_tasks(cx, h), dim3(256), 0, st, b, w, h, cx, cx * h);
-      return hipGetLastError();
+    for (uint32_t i = 0; i < n; i++) {
+      if (P.swap_src02) { std::swap(b.f[i].s[0], b.f[i].s[2]); std::swap(b.f[i].sp[0], b.f[i].sp[2]); }
+      else { std::swap(b.f[i].d[0], b.f[i].d[2]); std::swap(b.f[i].dp[0], b.f[i].dp[2]); }
     }
-    if (!force_generic && w % 4 == 0 && al(b, n, 1, 3, 4, 4, 4, 4)) {
-      dim3 grid((w / 4 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH((k_rgb_relayout_p4<0>), grid, dim3(256), 0, st, b, w, h, w / 4);
-      return hipGetLastError();
-    }
-    return go_generic<OP_RGB_PLANAR>(st, w, h, n, b);
+    dispatch_relayout(st, P, b);
+  } else {
+    dispatch_relayout(st, P, a);
   }
-  if (sf == VPF_FMT_RGB_PLANAR && packed_d) {
-    BatchArgs b = a;
-    if (df == VPF_FMT_BGR)
-      for (uint32_t i = 0; i < n; i++) { std::swap(b.f[i].s[0], b.f[i].s[2]); std::swap(b.f[i].sp[0], b.f[i].sp[2]); }
-    if (r16 && al(b, n, 3, 1, 16, 16, 16, 16)) {
-      if (n == 1) VPF_LAUNCH((k_rgb_relayout_r16_one<1>), row_tasks(cx, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(b.f[0]), w, h, cx, cx * h, VPF_ONE_DST_ARGS(b.f[0]));
-      else VPF_LAUNCH((k_rgb_relayout_r16<1>), row_tasks(cx, h), dim3(256), 0, st, b, w, h, cx, cx * h);
-      return hipGetLastError();
-    }
-    if (!force_generic && w % 4 == 0 && al(b, n, 3, 1, 4, 4, 4, 4)) {
-      dim3 grid((w / 4 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH((k_rgb_relayout_p4<1>), grid, dim3(256), 0, st, b, w, h, w / 4);
-      return hipGetLastError();
-    }
-    return go_generic<OP_PLANAR_RGB>(st, w, h, n, b);
-  }
-  if (packed_s && packed_d && sf != df) {
-    if (r16 && al(a, n, 1, 1, 16, 16, 16, 16)) {
-      if (n == 1) VPF_LAUNCH((k_rgb_relayout_r16_one<2>), row_tasks(cx, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, cx, cx * h, VPF_ONE_DST_ARGS(a.f[0]));
-      else VPF_LAUNCH((k_rgb_relayout_r16<2>), row_tasks(cx, h), dim3(256), 0, st, a, w, h, cx, cx * h);
-      return hipGetLastError();
-    }
-    if (!force_generic && w % 4 == 0 && al(a, n, 1, 1, 4, 4, 4, 4)) {
-      dim3 grid((w / 4 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH((k_rgb_relayout_p4<2>), grid, dim3(256), 0, st, a, w, h, w / 4);
-      return hipGetLastError();
-    }
-    return go_generic<OP_SWAP_RB>(st, w, h, n, a);
-  }
-  if (sf == VPF_FMT_NV12 && df == VPF_FMT_Y) {
-    if (!force_generic && w % 16 == 0 && al(a, n, 1, 1, 16, 16, 16, 16)) {
-      dim3 grid((w / 16 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH((k_copy_plane_p16<false>), grid, dim3(256), 0, st, a, w, h, w / 16);
-      return hipGetLastError();
-    }
-    return go_generic<OP_COPY_Y>(st, w, h, n, a);
-  }
-  if (sf == VPF_FMT_Y && df == VPF_FMT_YUV444) {
-    if (!force_generic && w % 16 == 0 && al(a, n, 1, 3, 16, 16, 16, 16)) {
-      dim3 grid((w / 16 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH((k_copy_plane_p16<true>), grid, dim3(256), 0, st, a, w, h, w / 16);
-      return hipGetLastError();
-    }
-    return go_generic<OP_Y_YUV444>(st, w, h, n, a);
-  }
-  if (sf == VPF_FMT_RGB && df == VPF_FMT_RGB_32F) {
-    if (r16 && al(a, n, 1, 1, 4, 4, 16, 16)) {
-      const uint32_t wd = 3 * w / 4, cn = (wd + 255) / 256;  // 4 loads + 4 stores per wave: measured 0.74 (2: 0.69, 8: 0.72)
-      if (n == 1) VPF_LAUNCH(k_u8_to_f32_x4_one<4>, row_tasks(cn, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), wd, h, cn, cn * h, VPF_ONE_DST_ARGS(a.f[0]));
-      else VPF_LAUNCH(k_u8_to_f32_x4<4>, row_tasks(cn, h), dim3(256), 0, st, a, wd, h, cn, cn * h);
-      return hipGetLastError();
-    }
-    if (!force_generic && w % 4 == 0 && al(a, n, 1, 1, 4, 4, 16, 16)) {
-      dim3 grid((3 * w / 4 + 63) / 64, (h + 3) / 4, n);
-      VPF_LAUNCH(k_u8_to_f32_p4, grid, dim3(256), 0, st, a, 3 * w, h, 3 * w / 4);
-      return hipGetLastError();
-    }
-    return go_generic<OP_RGB_RGB32F>(st, w, h, n, a);
-  }
-  if (sf == VPF_FMT_RGB_32F && df == VPF_FMT_RGB_32F_PLANAR) {
-    if (!force_generic && tuning(VPF_TUNE_NV12_RGB_VARIANT) != 40 && w % 4 == 0 && al(a, n, 1, 3, 16, 16, 16, 16)) {
-      const uint32_t c4 = (w + 255) / 256;
-      if (n == 1) VPF_LAUNCH(k_rgb32f_planar_r4_one, row_tasks(c4, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, c4, c4 * h, VPF_ONE_DST_ARGS(a.f[0]));
-      else VPF_LAUNCH(k_rgb32f_planar_r4, row_tasks(c4, h), dim3(256), 0, st, a, w, h, c4, c4 * h);
-      return hipGetLastError();
-    }
-    return go_generic<OP_RGB32F_PLANAR>(st, w, h, n, a);
-  }
-  if ((sf == VPF_FMT_P10 || sf == VPF_FMT_P12) && df == VPF_FMT_NV12) {
-    if (r16 && al(a, n, 2, 2, 16, 16, 16, 16)) {
-      const uint32_t ch = (h + 1) / 2;
-      if (n == 1) VPF_LAUNCH(k_p16_to_8_x16_one, row_tasks(cx, h + ch), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, ch, cx, cx * (h + ch), VPF_ONE_DST_ARGS(a.f[0]));
-      else VPF_LAUNCH(k_p16_to_8_x16, row_tasks(cx, h + ch), dim3(256), 0, st, a, w, h, ch, cx, cx * (h + ch));
-      return hipGetLastError();
-    }
-    if (!force_generic && w % 8 == 0 && al(a, n, 2, 2, 16, 16, 8, 8)) {  // luma and chroma rows both hold w 16-bit samples
-      const uint32_t ch = (h + 1) / 2;
-      dim3 grid((w / 8 + 63) / 64, (h + ch + 3) / 4, n);
-      VPF_LAUNCH(k_p16_to_8_p8, grid, dim3(256), 0, st, a, w, h, ch, w / 8);
-      return hipGetLastError();
-    }
-    return go_generic<OP_P16_NV12>(st, w, h, n, a);
-  }
-  if (df == VPF_FMT_Y && (sf == VPF_FMT_RGB || sf == VPF_FMT_BGR || sf == VPF_FMT_RGB_PLANAR)) {
-    const int ns = (sf == VPF_FMT_RGB_PLANAR) ? 3 : 1;
-    if (r16 && al(a, n, ns, 1, 16, 16, 16, 16)) {
-      const int gs = sf == VPF_FMT_RGB ? 0 : (sf == VPF_FMT_BGR ? 1 : 2);
-#define VPF_GRAY(S) do { if (n == 1) VPF_LAUNCH((k_gray_r16_one<S>), row_tasks(cx, h), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, cx, cx * h, VPF_ONE_DST_ARGS(a.f[0])); \
-                         else VPF_LAUNCH((k_gray_r16<S>), row_tasks(cx, h), dim3(256), 0, st, a, w, h, cx, cx * h); } while (0)
-      if (gs == 0) VPF_GRAY(0); else if (gs == 1) VPF_GRAY(1); else VPF_GRAY(2);
-#undef VPF_GRAY
-      return hipGetLastError();
-    }
-    if (!force_generic && w % 4 == 0 && al(a, n, ns, 1, 4, 4, 4, 4)) {
-      dim3 grid((w / 4 + 63) / 64, (h + 3) / 4, n);
-      if (sf == VPF_FMT_RGB) VPF_LAUNCH((k_gray_p4<0>), grid, dim3(256), 0, st, a, w, h, w / 4);
-      else if (sf == VPF_FMT_BGR) VPF_LAUNCH((k_gray_p4<1>), grid, dim3(256), 0, st, a, w, h, w / 4);
-      else VPF_LAUNCH((k_gray_p4<2>), grid, dim3(256), 0, st, a, w, h, w / 4);
-      return hipGetLastError();
-    }
-    if (sf == VPF_FMT_RGB) return go_generic<OP_RGB_GRAY>(st, w, h, n, a);
-    if (sf == VPF_FMT_BGR) return go_generic<OP_BGR_GRAY>(st, w, h, n, a);
-    return go_generic<OP_PLANAR_GRAY>(st, w, h, n, a);
-  }
-  return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
 }  // namespace vpf

@@ -218,79 +218,25 @@ __global__ __launch_bounds__(256) void k_rgb_yuv_r16_one(VPF_ONE_SRC_PARAMS, uin
   rgb_yuv_r16_task<SRC, SUB>(VPF_ONE_FRAME, c, w, h, chunks_x, n_tasks);
 }
 
-static bool rgb2yuv_r16_ok(const BatchArgs& a, uint32_t n, int src_fc, bool sub, uint32_t w, uint32_t h) {
-  const int tv = tuning(VPF_TUNE_NV12_RGB_VARIANT);
-  if (tv == 9 || tv == 40 || (w & 15) || (sub && (h & 1))) return false;
-  const int ns = (src_fc == FC_PLANAR) ? 3 : 1;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < ns; k++)
-      if (((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 15) return false;
-    for (int k = 0; k < 3; k++)
-      if (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & ((k && sub) ? 7 : 15)) return false;
-  }
-  return true;
-}
-
-static bool rgb2yuv_fast_ok(const BatchArgs& a, uint32_t n, int src_fc, bool sub, uint32_t w, uint32_t h) {
-  if (tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 || (w & 3) || (h & 1)) return false;
-  const int ns = (src_fc == FC_PLANAR) ? 3 : 1;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < ns; k++)
-      if (((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 3) return false;
-    for (int k = 0; k < 3; k++)
-      if (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & ((k && sub) ? 1 : 3)) return false;
-  }
-  return true;
-}
-
+// host side: convert_plan (vpf_convert_plan.h) decides, this launches the instantiation it names
 hipError_t launch_rgb_to_yuv(hipStream_t st, int src_fc, int dst_fc, const Rgb2YuvCoef& c, uint32_t w, uint32_t h,
                              uint32_t n, const BatchArgs& a) {
-  const bool sub = (dst_fc == FC_YUV420);
-  // (a lone 4K frame used to take the narrower p4 kernel here — a row-pair wave halves the wave count, and p4 won by 8 %;
-  // with the scalar-argument single-frame entry r16 is the faster one again: 0.51 vs 0.47 of 8 TB/s)
-  if (rgb2yuv_r16_ok(a, n, src_fc, sub, w, h)) {
-    const uint32_t chunks = (w + 1023) / 1024, tasks = chunks * (sub ? h / 2 : h);
-    dim3 rgrid((tasks + 3) / 4, n);
-#define VPF_R16(S)                                                                                    \
-  if (n == 1 && sub) VPF_LAUNCH((k_rgb_yuv_r16_one<S, true>), rgrid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c); \
-  else if (n == 1) VPF_LAUNCH((k_rgb_yuv_r16_one<S, false>), rgrid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c); \
-  else if (sub) VPF_LAUNCH((k_rgb_yuv_r16<S, true>), rgrid, dim3(256), 0, st, a, c, w, h, chunks, tasks);   \
-  else VPF_LAUNCH((k_rgb_yuv_r16<S, false>), rgrid, dim3(256), 0, st, a, c, w, h, chunks, tasks);      \
-  return hipGetLastError();
-    switch (src_fc) {
-      case FC_RGB: VPF_R16(FC_RGB)
-      case FC_BGR: VPF_R16(FC_BGR)
-      case FC_PLANAR: VPF_R16(FC_PLANAR)
-      default: return hipErrorInvalidValue;
+  const ConvertPlan P = convert_plan(convert_shape(CONVERT_RGB2YUV, src_fc, dst_fc, w, h, n, a, tuning(VPF_TUNE_NV12_RGB_VARIANT)));
+  if (!P.ok) return hipErrorInvalidValue;
+  const dim3 grid(P.gx, P.gy, P.gz);
+  const FrameDesc& f0 = a.f[0];
+  const uint32_t* s = P.a;
+  with_value<FC_RGB, FC_BGR, FC_PLANAR>(P.src, [&](auto SRC) { with_bool(P.sub, [&](auto SUB) {
+    if (P.form == CF_RGB_YUV_R16) {
+      if (P.one) VPF_LAUNCH_T(k_rgb_yuv_r16_one, (SRC, SUB), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0), c);
+      else VPF_LAUNCH_T(k_rgb_yuv_r16, (SRC, SUB), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);
+    } else if (P.form == CF_RGB_YUV_P4) {
+      VPF_LAUNCH_T(k_rgb_yuv_p4, (SRC, SUB), grid, 0, st, a, c, s[0], s[1], s[2]);
+    } else {
+      VPF_LAUNCH_T(k_rgb_yuv_quad, (SRC, SUB), grid, 0, st, a, c, s[0], s[1]);
     }
-#undef VPF_R16
-  }
-  if (rgb2yuv_fast_ok(a, n, src_fc, sub, w, h)) {
-    dim3 fgrid((w / 4 + 63) / 64, (h / 2 + 3) / 4, n);
-#define VPF_FAST(S)                                                                                  \
-  if (sub) VPF_LAUNCH((k_rgb_yuv_p4<S, true>), fgrid, dim3(256), 0, st, a, c, w, h, w / 4);           \
-  else VPF_LAUNCH((k_rgb_yuv_p4<S, false>), fgrid, dim3(256), 0, st, a, c, w, h, w / 4);              \
+  }); });
   return hipGetLastError();
-    switch (src_fc) {
-      case FC_RGB: VPF_FAST(FC_RGB)
-      case FC_BGR: VPF_FAST(FC_BGR)
-      case FC_PLANAR: VPF_FAST(FC_PLANAR)
-      default: return hipErrorInvalidValue;
-    }
-#undef VPF_FAST
-  }
-  dim3 grid(((w + 1) / 2 + 63) / 64, ((h + 1) / 2 + 3) / 4, n);
-#define VPF_GO(S)                                                                                            \
-  if (sub) VPF_LAUNCH((k_rgb_yuv_quad<S, true>), grid, dim3(256), 0, st, a, c, w, h);                 \
-  else VPF_LAUNCH((k_rgb_yuv_quad<S, false>), grid, dim3(256), 0, st, a, c, w, h);                    \
-  return hipGetLastError();
-  switch (src_fc) {
-    case FC_RGB: VPF_GO(FC_RGB)
-    case FC_BGR: VPF_GO(FC_BGR)
-    case FC_PLANAR: VPF_GO(FC_PLANAR)
-    default: return hipErrorInvalidValue;
-  }
-#undef VPF_GO
 }
 
 // ------------------------------------------------------------------------------------------
@@ -457,37 +403,21 @@ __global__ __launch_bounds__(256) void k_tensor_yuv_r(const BatchArgs args, cons
   }
 }
 
-static bool tensor2yuv_r_ok(const BatchArgs& a, uint32_t n, bool nv12, uint32_t w, uint32_t h, bool nhwc) {
-  if (tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 || (w & 15) || (h & 1)) return false;
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < (nhwc ? 1 : 3); k++)
-      if (((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & 15) return false;
-    if (((uintptr_t)a.f[i].d[0] | a.f[i].dp[0]) & 15) return false;
-    for (int k = 1; k < (nv12 ? 2 : 3); k++)
-      if (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (nv12 ? 15 : 7)) return false;
-  }
-  return true;
-}
-
 hipError_t launch_tensor_to_yuv(hipStream_t st, bool nv12, const Rgb2YuvCoef& c, const TensorPro& t, uint32_t w, uint32_t h, uint32_t n, const BatchArgs& a,
                                 bool nhwc) {
-  hipError_t e = hipErrorInvalidValue;  // (stays for a dtype that is none of the three)
-  if (tensor2yuv_r_ok(a, n, nv12, w, h, nhwc)) {
-    const uint32_t px = t.dtype == VPF_TENSOR_F32 ? 8 : 16;
-    const uint32_t chunks = (w + 64 * px - 1) / (64 * px), tasks = chunks * (h / 2);
-    dim3 rgrid((tasks + 3) / 4, n);
-    with_tensor_dtype(t.dtype, [&](auto DT) { with_bool(nv12, [&](auto NV12) { with_bool(nhwc, [&](auto NHWC) {
-      VPF_LAUNCH_T(k_tensor_yuv_r, (DT, NV12, NHWC), rgrid, 0, st, a, c, t, w, h, chunks, tasks);
-      e = hipGetLastError();
-    }); }); });
-    return e;
-  }
-  dim3 grid(((w + 1) / 2 + 63) / 64, ((h + 1) / 2 + 3) / 4, n);
-  with_bool(nv12, [&](auto NV12) { with_bool(nhwc, [&](auto NHWC) {
-    VPF_LAUNCH_T(k_tensor_yuv_quad, (NV12, NHWC), grid, 0, st, a, c, t, w, h);
-    e = hipGetLastError();
+  ConvertShape q = convert_shape(CONVERT_TENSOR2YUV, 0, 0, w, h, n, a, tuning(VPF_TUNE_NV12_RGB_VARIANT));
+  q.dtype = t.dtype; q.nv12 = nv12; q.nhwc = nhwc;
+  const ConvertPlan P = convert_plan(q);
+  if (!P.ok) return hipErrorInvalidValue;
+  const dim3 grid(P.gx, P.gy, P.gz);
+  const uint32_t* s = P.a;
+  with_bool(P.nv12, [&](auto NV12) { with_bool(P.nhwc, [&](auto NHWC) {
+    if (P.form == CF_TENSOR_YUV_R)
+      with_tensor_dtype(P.dtype, [&](auto DT) { VPF_LAUNCH_T(k_tensor_yuv_r, (DT, NV12, NHWC), grid, 0, st, a, c, t, s[0], s[1], s[2], s[3]); });
+    else
+      VPF_LAUNCH_T(k_tensor_yuv_quad, (NV12, NHWC), grid, 0, st, a, c, t, s[0], s[1]);
   }); });
-  return e;
+  return hipGetLastError();
 }
 
 }  // namespace vpf

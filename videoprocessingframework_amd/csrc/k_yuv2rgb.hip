@@ -17,6 +17,7 @@
 //     v_cvt_pk_u8_f32: 1 cvt + 3 FMA + 3 pack ops per pixel;
 //   * `BatchArgs` carries up to 32 frames in the kernarg segment, blockIdx.y selects the frame, so
 //     one dispatch streams ~600 MB and the ~2 us kernel boundary is amortised.
+#include "k_job_launch.h"
 #include "k_yuv2rgb_tasks.h"
 
 namespace vpf {
@@ -197,133 +198,59 @@ __global__ __launch_bounds__(256) void k_yuv_rgb_generic(const BatchArgs args, c
 
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side: convert_plan (vpf_convert_plan.h) decides, this launches the instantiation it names
 // ---------------------------------------------------------------------------------------------
-static bool aligned_all(const BatchArgs& a, uint32_t n, int nsrc, int ndst, uint32_t src_al, uint32_t dst_al,
-                        uint32_t chroma_al) {
-  for (uint32_t i = 0; i < n; i++) {
-    for (int k = 0; k < nsrc; k++) {
-      uint32_t al = (k == 0) ? src_al : chroma_al;
-      if (((uintptr_t)a.f[i].s[k] | a.f[i].sp[k]) & (al - 1)) return false;
-    }
-    for (int k = 0; k < ndst; k++)
-      if (((uintptr_t)a.f[i].d[k] | a.f[i].dp[k]) & (dst_al - 1)) return false;
-  }
-  return true;
-}
-
-// Kernel selection for 4:2:0 sources.  `variant` is the tuning hint (include/vpf_hip.h): 0 = policy below; a named kernel
-// (4 / 8 / 12 / 30 / 37 / 44 / 45 / 46) is honoured where it applies and falls back down the same chain where it does not; 40 = the
-// narrower p4 path, 9 = the any-input generic kernel.  Every kernel here writes the same pixels.
-//   p16x (45 | 46: 4 workgroups / CU)                                               packed outputs, w >= 1024: blocks numbered straight through the picture
-//   p16  (8: non-temporal stores | 12: allocating stores | 30: 4 workgroups / CU)   packed outputs; w % 16 == 0, h even, 16-B aligned
-//   r16  (37: non-temporal | 44: allocating stores)                                 planar outputs; same conditions
-//        (the straight numbering applied to r16 measured 1 % SLOWER on the 1080p planar batch, 0.779 vs 0.787 in same-box A/B: not kept)
-//   p4   (4)                                                                        4-B aligned planes, any size
-//   generic (9)                                                                     anything
-// Policy (profiles/r01_bench_sweep.log, r02_bench_sweep.log, tools/lab): packed -> p16x (p16 below 1024 px), with the 4-workgroup cap when the launch is a batch (>= 4 frames:
-// a narrower chip-wide write frontier is worth 1-2 %; short single-frame launches want all the waves they can get); planar -> r16
-// (three 1-KiB plane stores per wave), except a lone frame of >= 3 Mpx where the row-pair p16 form wins (kernel 7.3 vs 7.9 us at 4K,
-// but 4.3 vs 3.6 at 1080p: tools/gpu_planar_single.sh).  The alternatives that were measured and dropped (more row pairs per task,
-// one-store-per-wave forms, XCD swizzles, other occupancy caps, byte-stream stores) live in tools/lab/k_lab.hip.
-template <int SRC, int DST>
-static hipError_t launch_420(hipStream_t st, const Yuv2RgbCoef& c, uint32_t w, uint32_t h, uint32_t n,
-                             const BatchArgs& a, int variant) {
-  const int nsrc = (SRC == FC_NV12) ? 2 : 3, ndst = (DST == FC_PLANAR) ? 3 : 1;
-  const bool even = (w % 4 == 0) && (h % 2 == 0);
-  const bool p16_ok = even && (w % 16 == 0) && aligned_all(a, n, nsrc, ndst, 16, 16, SRC == FC_NV12 ? 16 : 8);
-  const bool p4_ok = aligned_all(a, n, nsrc, ndst, 4, 4, SRC == FC_NV12 ? 4 : 2);
-  const bool big_single = n < 4 && (size_t)w * h >= (size_t)3 << 20;
-  const bool p16x_ok = p16_ok && DST != FC_PLANAR && w >= 1024 && (uint64_t)(w / 16) * (h / 2) < (1u << 30);
-  // values of the shared tuning key that name no NV12 / YUV420 -> RGB kernel (43 = a resize-only hint, anything unknown) mean the default policy
-  if (variant != 4 && variant != 8 && variant != 9 && variant != 12 && variant != 30 && variant != 37 && variant != 40 && variant != 44 && variant != 45 && variant != 46) variant = 0;
-  if (variant == 0) variant = p16_ok ? (DST == FC_PLANAR ? (big_single ? 8 : 37) : (n >= 4 ? (p16x_ok ? 46 : 30) : 8)) : 4;  // (single frames: p16x measured level with p16, 0.710 vs 0.717)
-  if ((variant == 45 || variant == 46) && !p16x_ok) variant = variant == 46 ? 30 : 8;  // narrow frames / planar outputs: the chunk-per-row form
-  const bool is_p16 = variant == 8 || variant == 12 || variant == 30, is_r16 = variant == 37 || variant == 44;
-  if ((is_p16 || is_r16) && !p16_ok) variant = 4;
-  if (is_r16 && DST != FC_PLANAR) variant = 4;
-  if (variant != 9 && !p4_ok) variant = 9;  // p16_ok implies p4_ok
-  const FrameDesc& f0 = a.f[0];
-  if (variant == 37 || variant == 44) {
-    const uint32_t chunks = (w + 1023) / 1024, tasks = chunks * h;  // one task per row per chunk (h even)
-    dim3 grid((tasks + 3) / 4, n);
-    if (n == 1 && variant == 37) VPF_LAUNCH((k_nv12_planar_r16_one<true, SRC>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), w, h, chunks, tasks, VPF_ONE_DST_ARGS(f0), c);
-    else if (n == 1) VPF_LAUNCH((k_nv12_planar_r16_one<false, SRC>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), w, h, chunks, tasks, VPF_ONE_DST_ARGS(f0), c);
-    else if (variant == 37) VPF_LAUNCH((k_nv12_planar_r16<true, SRC>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);
-    else VPF_LAUNCH((k_nv12_planar_r16<false, SRC>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);  // allocating stores
-    return hipGetLastError();
-  }
-  if (variant == 45 || variant == 46) {
-    if constexpr (DST != FC_PLANAR) {
-      const uint32_t bpr = w / 16, nb = bpr * (h / 2);
-      dim3 grid((nb + 255) / 256, n);
-      if (n == 1) VPF_LAUNCH((k_nv12_rgb_p16x_one<DST, true, SRC>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), bpr, nb, VPF_ONE_DST_ARGS(f0), c);
-      else if (variant == 45) VPF_LAUNCH((k_nv12_rgb_p16x<DST, true, 0, SRC>), grid, dim3(256), 0, st, a, c, bpr, nb);
-      else VPF_LAUNCH((k_nv12_rgb_p16x<DST, true, 16, SRC>), grid, dim3(256), 0, st, a, c, bpr, nb);  // 40 KiB of LDS -> 4 workgroups / CU
-      return hipGetLastError();
-    }
-  }
-  if (variant == 8 || variant == 12 || variant == 30) {
-    const uint32_t chunks = (w + 1023) / 1024, tasks = chunks * (h / 2);
-    dim3 grid((tasks + 3) / 4, n);
-    if (n == 1 && variant != 12) VPF_LAUNCH((k_nv12_rgb_p16_one<DST, true, SRC>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), w, h, chunks, tasks, VPF_ONE_DST_ARGS(f0), c);
-    else if (n == 1) VPF_LAUNCH((k_nv12_rgb_p16_one<DST, false, SRC>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), w, h, chunks, tasks, VPF_ONE_DST_ARGS(f0), c);
-    else if (variant == 8) VPF_LAUNCH((k_nv12_rgb_p16<DST, true, 0, SRC>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);
-    else if (variant == 12) VPF_LAUNCH((k_nv12_rgb_p16<DST, false, 0, SRC>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);
-    else VPF_LAUNCH((k_nv12_rgb_p16<DST, true, 16, SRC>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);  // 40 KiB of LDS -> 4 workgroups / CU
-    return hipGetLastError();
-  }
-  if (variant != 9) {  // 4, 40 and every fallback
-    const uint32_t chunks = ((w + 3) / 4 + 63) / 64, tasks = chunks * ((h + 1) / 2);
-    dim3 grid((tasks + 3) / 4, n);
-    if (n == 1) VPF_LAUNCH((k_yuv420_rgb_p4_one<SRC, DST>), grid, dim3(256), 0, st, VPF_ONE_SRC_ARGS(f0), w, h, chunks, tasks, VPF_ONE_DST_ARGS(f0), c);
-    else VPF_LAUNCH((k_yuv420_rgb_p4<SRC, DST>), grid, dim3(256), 0, st, a, c, w, h, chunks, tasks);
-    return hipGetLastError();
-  }
-  dim3 grid(((w + 1) / 2 + 63) / 64, ((h + 1) / 2 + 3) / 4, n);
-  VPF_LAUNCH((k_yuv_rgb_generic<SRC, DST>), grid, dim3(256), 0, st, a, c, w, h);
-  return hipGetLastError();
-}
-
-template <int DST>
-static hipError_t launch_444(hipStream_t st, const Yuv2RgbCoef& c, uint32_t w, uint32_t h, uint32_t n,
-                             const BatchArgs& a, int variant) {
-  const int ndst = (DST == FC_PLANAR) ? 3 : 1;
-  if (variant != 9 && variant != 40 && w % 16 == 0 && aligned_all(a, n, 3, ndst, 16, 16, 16)) {
-    const uint32_t chunks = (w + 1023) / 1024, tasks = chunks * h;
-    if (n == 1) VPF_LAUNCH((k_yuv444_rgb_r16_one<DST>), dim3((tasks + 3) / 4, n), dim3(256), 0, st, VPF_ONE_SRC_ARGS(a.f[0]), w, h, chunks, tasks, VPF_ONE_DST_ARGS(a.f[0]), c);
-    else VPF_LAUNCH((k_yuv444_rgb_r16<DST>), dim3((tasks + 3) / 4, n), dim3(256), 0, st, a, c, w, h, chunks, tasks);
-    return hipGetLastError();
-  }
-  if (variant != 9 && w % 4 == 0 && aligned_all(a, n, 3, ndst, 4, 4, 4) && h <= 65535) {
-    dim3 grid((w / 4 + 255) / 256, h, n);
-    VPF_LAUNCH((k_yuv444_rgb_p4<DST, 1>), grid, dim3(256), 0, st, a, c, w, h, w / 4);
-    return hipGetLastError();
-  }
-  dim3 grid(((w + 1) / 2 + 63) / 64, ((h + 1) / 2 + 3) / 4, n);
-  VPF_LAUNCH((k_yuv_rgb_generic<FC_YUV444, DST>), grid, dim3(256), 0, st, a, c, w, h);
-  return hipGetLastError();
+// f(SRC, DST) as constants: FC_NV12 / FC_YUV420 / FC_YUV444 into FC_RGB / FC_BGR / FC_PLANAR (the plan has refused every other class)
+template <class F>
+static void with_yuv_src_dst(int src_fc, int dst_fc, F&& f) {
+  with_value<FC_NV12, FC_YUV420, FC_YUV444>(src_fc, [&](auto src) { with_value<FC_RGB, FC_BGR, FC_PLANAR>(dst_fc, [&](auto dst) { f(src, dst); }); });
 }
 
 hipError_t launch_yuv_to_rgb(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t w, uint32_t h,
                              uint32_t n, const BatchArgs& a, int variant, bool dst_reused) {
-  // VPF_EXEC_DST_REUSED: single-frame launches keep their output in the Infinity Cache (allocating stores) for the next
-  // kernel of the chain: variant 12 = p16 with non-temporal loads only, 44 = planar r16 with plain stores
-  if (variant == 0 && dst_reused && n < 4 && (src_fc == FC_NV12 || src_fc == FC_YUV420)) variant = (dst_fc == FC_PLANAR) ? 44 : 12;
-#define VPF_DST_SWITCH(FN, ...)                                                   \
-  switch (dst_fc) {                                                               \
-    case FC_RGB: return FN<__VA_ARGS__ FC_RGB>(st, c, w, h, n, a, variant);       \
-    case FC_BGR: return FN<__VA_ARGS__ FC_BGR>(st, c, w, h, n, a, variant);       \
-    case FC_PLANAR: return FN<__VA_ARGS__ FC_PLANAR>(st, c, w, h, n, a, variant); \
-    default: return hipErrorInvalidValue;                                         \
-  }
-  switch (src_fc) {
-    case FC_NV12: VPF_DST_SWITCH(launch_420, FC_NV12, )
-    case FC_YUV420: VPF_DST_SWITCH(launch_420, FC_YUV420, )
-    case FC_YUV444: VPF_DST_SWITCH(launch_444, )
-    default: return hipErrorInvalidValue;
-  }
-#undef VPF_DST_SWITCH
+  ConvertShape q = convert_shape(CONVERT_YUV2RGB, src_fc, dst_fc, w, h, n, a, variant);
+  q.dst_reused = dst_reused;
+  const ConvertPlan P = convert_plan(q);
+  if (!P.ok) return hipErrorInvalidValue;
+  const dim3 grid(P.gx, P.gy, P.gz);
+  const FrameDesc& f0 = a.f[0];
+  const uint32_t* s = P.a;
+  with_yuv_src_dst(P.src, P.dst, [&](auto src, auto dst) {
+    constexpr int SRC = decltype(src)::value, DST = decltype(dst)::value;
+    // (the guards keep the instantiations to the ones the plan can name: no r16 / p16 / p4 form of a 4:4:4 source, no planar p16x)
+    if constexpr (SRC != FC_YUV444) {
+      if (P.form == CF_NV12_PLANAR_R16)
+        with_bool(P.nts, [&](auto NTS) {
+          if (P.one) VPF_LAUNCH_T(k_nv12_planar_r16_one, (NTS, SRC), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0), c);
+          else VPF_LAUNCH_T(k_nv12_planar_r16, (NTS, SRC), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);
+        });
+      if constexpr (DST != FC_PLANAR)
+        if (P.form == CF_NV12_RGB_P16X) {
+          if (P.one) VPF_LAUNCH_T(k_nv12_rgb_p16x_one, (DST, true, SRC), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], VPF_ONE_DST_ARGS(f0), c);
+          else if (P.ballast) VPF_LAUNCH_T(k_nv12_rgb_p16x, (DST, true, 16, SRC), grid, 0, st, a, c, s[0], s[1]);
+          else VPF_LAUNCH_T(k_nv12_rgb_p16x, (DST, true, 0, SRC), grid, 0, st, a, c, s[0], s[1]);
+        }
+      if (P.form == CF_NV12_RGB_P16) {
+        if (P.ballast) VPF_LAUNCH_T(k_nv12_rgb_p16, (DST, true, 16, SRC), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);  // (non-temporal stores only)
+        else with_bool(P.nts, [&](auto NTS) {
+          if (P.one) VPF_LAUNCH_T(k_nv12_rgb_p16_one, (DST, NTS, SRC), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0), c);
+          else VPF_LAUNCH_T(k_nv12_rgb_p16, (DST, NTS, 0, SRC), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);
+        });
+      }
+      if (P.form == CF_YUV420_RGB_P4) {
+        if (P.one) VPF_LAUNCH_T(k_yuv420_rgb_p4_one, (SRC, DST), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0), c);
+        else VPF_LAUNCH_T(k_yuv420_rgb_p4, (SRC, DST), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);
+      }
+    } else {
+      if (P.form == CF_YUV444_RGB_R16) {
+        if (P.one) VPF_LAUNCH_T(k_yuv444_rgb_r16_one, (DST), grid, 0, st, VPF_ONE_SRC_ARGS(f0), s[0], s[1], s[2], s[3], VPF_ONE_DST_ARGS(f0), c);
+        else VPF_LAUNCH_T(k_yuv444_rgb_r16, (DST), grid, 0, st, a, c, s[0], s[1], s[2], s[3]);
+      }
+      if (P.form == CF_YUV444_RGB_P4) VPF_LAUNCH_T(k_yuv444_rgb_p4, (DST, 1), grid, 0, st, a, c, s[0], s[1], s[2]);
+    }
+    if (P.form == CF_YUV_RGB_GENERIC) VPF_LAUNCH_T(k_yuv_rgb_generic, (SRC, DST), grid, 0, st, a, c, s[0], s[1]);
+  });
+  return hipGetLastError();
 }
 
 }  // namespace vpf
