@@ -547,6 +547,50 @@ VPF_API vpf_status vpf_convert_persp_tensor(const vpf_exec* exec, int src_fmt, i
                                             uint32_t n, const vpf_persp_io* jobs, const vpf_tensor_norm* norm, const vpf_warp_opts* opts);
 
 /*
+ * The same with the homographies in DEVICE memory: what stands behind a corner-regression network (four corners per document, plate or screen) whose
+ * 3 x 3 matrices are solved on the GPU.  The contract is vpf_convert_warp_tensor_dev's, word for word, with nine coefficients: no sync, no copy of
+ * the matrices to the host, and a captured graph replays with the matrices, frame indices and count of REPLAY time.
+ * `frames` is a HOST array of the planes of n_frames (1 .. 128) WHOLE frames of src_size = (W, H), consumed before return.  table->matrices points
+ * to DEVICE memory: job k = nine floats m00 m01 m02 m10 m11 m12 m20 m21 m22 at byte k * matrix_stride (a row of a float32 [K, 3, 3] or [K, 9]
+ * tensor: 36; any multiple of 4 from 36 up: padded tables); table->frame_index to job k's frame, one int32 at byte k * frame_stride (a multiple of 4
+ * from 4 up), or NULL: every job samples frames[0]; table->count to ONE device int32, or NULL.  The kernel reads all three WHEN IT RUNS on
+ * exec->stream; the host never dereferences them.
+ *   c = clamp(*count, 0, max_n); count == NULL: c = max_n.  max_n (1 .. 65535) is the size of the dispatch.
+ *   job k < c with a VALID entry — 0 <= frame < n_frames and fabsf(m) <= 2^24 for each of the nine coefficients (NaN and the infinities fail it) —:
+ *        every element of its planes is bit for bit what vpf_convert_persp_tensor writes for (frames[frame], m, planes dst[c].ptr + k * dst_job_stride
+ *        with dst[c].pitch), for the same src_fmt (NV12, YUV420, P10, P12), dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC, border mode, border and colour
+ *        rules.  A valid matrix whose w is <= 0 everywhere is legal and writes the border, as there;
+ *   job k < c with an INVALID entry: every element of its planes is round_to_dtype(fmaf(border[c], scale[c], bias[c])) (border 0 0 0 when
+ *        opts == NULL), in BOTH border modes.  No byte of any frame is read;
+ *   job k >= c: NOTHING is written, and neither its matrix nor its frame index is read — the tables may be shorter than max_n.
+ * Nothing outside the planes of jobs < c is ever written.  One dispatch over (32 x 32 destination tiles, max_n); every workgroup decides for its own
+ * tile whether it is the border, sampled per tap or converted once into LDS (identical bits).
+ * max_step is the LDS hint, the affine entry's generalised: a bound, over every valid job and every destination pixel, on
+ * |d sx / d dx| + |d sx / d dy| and on |d sy / d dx| + |d sy / d dy|, the source pixels per destination pixel step (a last row (0, 0, 1):
+ * |m00| + |m01| and |m10| + |m11|).  vpf_persp_max_step returns that bound for ONE host matrix and destination size, or 0 where it has none (some
+ * destination corner with w <= 0): a caller calibrates offline, on matrices of the kind the pipeline produces, and passes the maximum.  The dispatch
+ * takes the LDS of a window of max_step * 31 + 5 pixels per axis (and a rounding slack), cut to the frame, at most 64 KiB; max_step == 0: no hint,
+ * 64 KiB.  Never a correctness input: a tile whose window outgrows the LDS it was given is sampled per tap, with identical bits.
+ * Checked on the host before any device access, with vpf_convert_warp_tensor_dev's list and answers (matrix_stride < 36 in place of < 24).  Whatever
+ * the device tables hold, the call returns VPF_OK.
+ */
+typedef struct vpf_persps_dev {
+  const float* matrices;      /* DEVICE: job k = nine floats m00 .. m22 at byte k * matrix_stride */
+  const int32_t* frame_index; /* DEVICE: job k's frame at byte k * frame_stride; NULL = every job samples frames[0] */
+  const int32_t* count;       /* DEVICE: one int32, or NULL = max_n */
+  uint32_t matrix_stride;     /* >= 36, multiple of 4 (a row of a float32 [K, 3, 3] / [K, 9] tensor: 36) */
+  uint32_t frame_stride;      /* >= 4, multiple of 4; ignored when frame_index == NULL */
+  uint32_t max_n;             /* 1 .. 65535: grid z */
+  float max_step;             /* LDS hint, see above; 0 = none */
+  vpf_plane dst[3];           /* planes of job 0 (one plane with VPF_TENSOR_NHWC) */
+  uint64_t dst_job_stride;    /* bytes from job k's planes to job k + 1's: multiple of the element size */
+} vpf_persps_dev; /* 96 bytes, no implicit padding: the layout of vpf_warps_dev */
+VPF_API vpf_status vpf_convert_persp_tensor_dev(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size, vpf_size dst_size,
+                                                uint32_t n_frames, const vpf_frame_src* frames, const vpf_persps_dev* table, const vpf_tensor_norm* norm,
+                                                const vpf_warp_opts* opts);
+VPF_API float vpf_persp_max_step(const float m[9], vpf_size dst); /* host only; 0: no bound (also for a null, non-finite or oversized input) */
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

@@ -105,7 +105,7 @@ def compare(old_root, new_root, units):
         print(f"== {unit}: {len(new)} kernels ({len(old)} in the old root)")
         for name in sorted(new):
             ins, *res = new[name]
-            o = old.pop(old_name(name), None)
+            o = old.pop(old_name(name) if old_name(name) in old else name, None)  # (an old root that already spells the kernel as the new one does)
             if o is None:
                 print(f"  {name:60s} {len(ins):5d} instr  vgpr {res[0]:3d} sgpr {res[1]:3d} lds {res[2]} scratch {res[3]} spills {res[4]}  NEW: no counterpart in the old root")
                 n_diff += 1

@@ -525,8 +525,20 @@ def quads_to_homographies(quads, size) -> torch.Tensor:
     [K, 3, 3] inverse matrices persps_to_normalized_tensor takes for a destination of size = (dw, dh): matrix k sends the destination corners (0, 0),
     (dw - 1, 0), (dw - 1, dh - 1), (0, dh - 1) to quad k's corners.  Solved in float64 with m22 = 1 (destination (0, 0) maps to a finite point, so that
     normalisation always exists), rounded to float32 once.  Pure torch, on whatever device the quads live on.  A degenerate quad (three corners on a
-    line) has no homography: its matrix holds non-finite values or torch.linalg.solve raises.  ValueError for another shape or dw, dh below 2."""
-    fn = "quads_to_homographies"
+    line) has no homography: its matrix holds non-finite values or torch.linalg.solve raises (on a device input that check is a synchronisation:
+    quads_to_homographies_unchecked has none).  ValueError for another shape or dw, dh below 2."""
+    return _quads_to_homographies("quads_to_homographies", quads, size, True)
+
+
+def quads_to_homographies_unchecked(quads, size) -> torch.Tensor:
+    """quads_to_homographies through torch.linalg.solve_ex(..., check_errors=False): the same factorisation without the read-back of its status, so it
+    never synchronises on a device input — what feeds device_persps_to_normalized_tensor.  Proper quads give the tensor quads_to_homographies gives; a
+    degenerate quad raises nothing and yields whatever the factorisation yields, which that entry either refuses as an invalid job (a coefficient that
+    is not finite or exceeds 2^24: the normalised border) or samples as a legal matrix — it never reads outside a frame."""
+    return _quads_to_homographies("quads_to_homographies_unchecked", quads, size, False)
+
+
+def _quads_to_homographies(fn, quads, size, check_errors):
     q = torch.as_tensor(quads)
     if q.dim() != 3 or tuple(q.shape[1:]) != (4, 2):
         raise ValueError(f"{fn}: quads must have shape [K, 4, 2], got {tuple(q.shape)}")
@@ -550,7 +562,7 @@ def quads_to_homographies(quads, size) -> torch.Tensor:
     a[:, 0::2, 6:8] = -q[:, :, 0:1] * d
     a[:, 1::2, 6:8] = -q[:, :, 1:2] * d
     b = q.reshape(k, 8, 1)
-    h = torch.linalg.solve(a, b).reshape(k, 8)
+    h = (torch.linalg.solve(a, b) if check_errors else torch.linalg.solve_ex(a, b, check_errors=False).result).reshape(k, 8)
     return torch.cat([h, torch.ones((k, 1), dtype=torch.float64, device=q.device)], dim=1).to(torch.float32).reshape(k, 3, 3)
 
 
@@ -595,7 +607,15 @@ def device_warps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, su
     The kernel reads the tables when it runs; this function orders it behind torch's current stream, where their producer ran.  border, border_mode,
     `out`, channels_last, dtype, bgr, the returned tensor and the stream ordering: as warps_to_normalized_tensor.  ValueError for matrices,
     surface_index or count on the host or on another device than each other or `out`, another dtype or shape."""
-    fn = "device_warps_to_normalized_tensor"
+    return _device_matrices_to_tensor("device_warps_to_normalized_tensor", False, resizer, surfaces, matrices, mean, std, surface_index, count, max_step, dtype, bgr,
+                                      border, border_mode, out, cc_ctx, channels_last)
+
+
+def _device_matrices_to_tensor(fn, persp, resizer, surfaces, matrices, mean, std, surface_index, count, max_step, dtype, bgr, border, border_mode, out, cc_ctx,
+                               channels_last):
+    """device_warps_to_normalized_tensor (persp False: [K, 2, 3] / [K, 6]) and device_persps_to_normalized_tensor (persp True: [K, 3, 3] / [K, 9]): the
+    same checks, the same tables, another kernel"""
+    rows, nc = (3, 9) if persp else (2, 6)
     if dtype not in _TENSOR_DTYPES:
         raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
     if border_mode not in _WARP_MODES:
@@ -610,15 +630,15 @@ def device_warps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, su
     if not 1 <= len(surfaces) <= 128:
         raise ValueError(f"{fn}: 1 .. 128 surfaces per call, got {len(surfaces)}")
     if not isinstance(matrices, torch.Tensor) or not matrices.is_cuda:
-        raise ValueError(f"{fn}: matrices must be a device tensor (for host matrices there is warps_to_normalized_tensor)")
-    if matrices.dtype != torch.float32 or not ((matrices.dim() == 3 and tuple(matrices.shape[1:]) == (2, 3)) or (matrices.dim() == 2 and matrices.shape[1] == 6)):
-        raise ValueError(f"{fn}: matrices must be torch.float32 of shape [K, 2, 3] or [K, 6], got {matrices.dtype} {tuple(matrices.shape)}")
+        raise ValueError(f"{fn}: matrices must be a device tensor (for host matrices there is {'persps' if persp else 'warps'}_to_normalized_tensor)")
+    if matrices.dtype != torch.float32 or not ((matrices.dim() == 3 and tuple(matrices.shape[1:]) == (rows, 3)) or (matrices.dim() == 2 and matrices.shape[1] == nc)):
+        raise ValueError(f"{fn}: matrices must be torch.float32 of shape [K, {rows}, 3] or [K, {nc}], got {matrices.dtype} {tuple(matrices.shape)}")
     n = matrices.shape[0]
     if n > 65535:
         raise ValueError(f"{fn}: at most 65535 matrices per call, got {n}")
     inner = matrices.stride()[1:]
-    if inner != ((3, 1) if matrices.dim() == 3 else (1,)) or (n > 1 and matrices.stride(0) < 6):
-        raise ValueError(f"{fn}: the six elements of a matrix must be contiguous and the row stride at least 6, got strides {matrices.stride()}")
+    if inner != ((3, 1) if matrices.dim() == 3 else (1,)) or (n > 1 and matrices.stride(0) < nc):
+        raise ValueError(f"{fn}: the {'nine' if persp else 'six'} elements of a matrix must be contiguous and the row stride at least {nc}, got strides {matrices.stride()}")
     if surface_index is not None:
         if not isinstance(surface_index, torch.Tensor) or not surface_index.is_cuda or surface_index.dtype != torch.int32 or tuple(surface_index.shape) != (n,):
             raise ValueError(f"{fn}: surface_index must be a device torch.int32 tensor of shape [{n}], or None")
@@ -644,14 +664,57 @@ def device_warps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, su
         return out
     elem = out.element_size()
     with _on_task_stream(resizer, out.device):
-        ok = resizer.ExecuteWarpsDevToTensor(surfaces, matrices.data_ptr(), n, surface_index.data_ptr() if surface_index is not None else 0,
-                                             count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean],
-                                             [float(v) for v in std], cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem,
-                                             (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (matrices.stride(0) if n > 1 else 6),
-                                             4 * (surface_index.stride(0) if surface_index is not None and n > 1 else 1), max_step)
+        execute = resizer.ExecutePerspsDevToTensor if persp else resizer.ExecuteWarpsDevToTensor
+        ok = execute(surfaces, matrices.data_ptr(), n, surface_index.data_ptr() if surface_index is not None else 0,
+                     count.data_ptr() if count is not None else 0, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean],
+                     [float(v) for v in std], cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem,
+                     (s0 if n > 1 else 0) * elem, bool(channels_last), 4 * (matrices.stride(0) if n > 1 else nc),
+                     4 * (surface_index.stride(0) if surface_index is not None and n > 1 else 1), max_step)
     if not ok:
         _refused(fn, _RESIZER_REFUSED)
     return out
+
+
+def device_persps_to_normalized_tensor(resizer, surfaces, matrices, mean, std, surface_index=None, count=None, max_step=None, dtype=torch.float32, bgr=False,
+                                       border=(0, 0, 0), border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
+    """persps_to_normalized_tensor for homographies that never leave the GPU (PySurfaceConvertResizer.ExecutePerspsDevToTensor,
+    vpf_convert_persp_tensor_dev): no synchronisation, no copy of the matrices to the host, one dispatch, capturable in a graph that replays with the
+    matrices, surface indices and count of replay time.
+    `matrices`: a device torch.float32 tensor [K, 3, 3] or [K, 9] whose nine elements per job are contiguous (any row stride of at least 9: a slice of a
+    wider table works), e.g. quads_to_homographies_unchecked(corners, size) of a corner-regression network's output.  `surface_index`, `count`
+    and the three kinds of rows (valid: persps_to_normalized_tensor's bits; invalid — a coefficient that is not finite or exceeds 2^24, no such surface —:
+    the normalised border in both modes; at or behind the count: NOT WRITTEN) exactly as device_warps_to_normalized_tensor.
+    `max_step`: a bound on the source pixels per destination pixel step over every job and pixel (homographies_max_step of matrices of the kind the
+    pipeline produces, calibrated offline) that sizes the kernel's LDS; None: the 64 KiB default.  It never changes a pixel.  ValueError as
+    device_warps_to_normalized_tensor."""
+    return _device_matrices_to_tensor("device_persps_to_normalized_tensor", True, resizer, surfaces, matrices, mean, std, surface_index, count, max_step, dtype, bgr,
+                                      border, border_mode, out, cc_ctx, channels_last)
+
+
+def homographies_max_step(matrices, dw, dh) -> float:
+    """The `max_step` hint of device_persps_to_normalized_tensor for HOST matrices ([K, 3, 3] or [K, 9], as persps_to_normalized_tensor takes them) and a
+    dw x dh destination: the maximum of vpf_persp_max_step (PyNvCodec.PerspMaxStep) over them — for every matrix the bound, over the whole destination,
+    on |d sx / d dx| + |d sx / d dy| and |d sy / d dx| + |d sy / d dy|.  0.0 (no hint) as soon as one matrix has no bound (a destination corner at or
+    behind the horizon), and for K == 0.  Meant for calibration, offline: pass the largest value seen to the device entry."""
+    fn = "homographies_max_step"
+    jobs = _matrices_list(matrices, fn, rows=3)
+    try:
+        dw, dh = operator.index(dw), operator.index(dh)
+    except TypeError:
+        raise ValueError(f"{fn}: dw and dh must be integers") from None
+    if not (1 <= dw <= 65536 and 1 <= dh <= 65536):
+        raise ValueError(f"{fn}: dw and dh must lie in 1 .. 65536, got {(dw, dh)}")
+    try:
+        import PyNvCodec as nvc
+    except ImportError:  # package-relative import when used as videoprocessingframework_amd.PytorchNvCodec
+        from .. import PyNvCodec as nvc
+    best = 0.0
+    for m in jobs:
+        step = float(nvc.PerspMaxStep(m, dw, dh))
+        if step == 0.0:
+            return 0.0
+        best = max(best, step)
+    return best
 
 
 def _dst_rects_list(dst_rects, n, w, h, fn):

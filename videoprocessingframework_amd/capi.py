@@ -32,7 +32,7 @@ EXPORTS = [
     "vpf_convert_resize_tensor", "vpf_convert_resize_tensor_batch", "vpf_convert_resize_tensor_rois", "vpf_convert_warp_tensor",
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
     "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
-    "vpf_convert_persp_tensor", "vpf_convert_letterbox_tensor_dev",
+    "vpf_convert_persp_tensor", "vpf_convert_letterbox_tensor_dev", "vpf_convert_persp_tensor_dev", "vpf_persp_max_step",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -126,6 +126,11 @@ class WarpsDev(C.Structure):
     planes and the stride"""
     _fields_ = [("matrices", C.c_void_p), ("frame_index", C.c_void_p), ("count", C.c_void_p), ("matrix_stride", C.c_uint32), ("frame_stride", C.c_uint32),
                 ("max_n", C.c_uint32), ("max_step", C.c_float), ("dst", Plane * 3), ("dst_job_stride", C.c_uint64)]
+
+
+class PerspsDev(C.Structure):
+    """vpf_persps_dev: vpf_warps_dev with nine floats per job (the inverse 3 x 3 matrix): the same 96 bytes"""
+    _fields_ = WarpsDev._fields_
 
 
 class TensorNorm(C.Structure):
@@ -224,6 +229,10 @@ def lib() -> C.CDLL:
         L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
         L.vpf_convert_warp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(WarpsDev), PN,
                                                   C.POINTER(WarpOpts)]
+        L.vpf_convert_persp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(PerspsDev), PN,
+                                                   C.POINTER(WarpOpts)]
+        L.vpf_persp_max_step.argtypes = [C.POINTER(C.c_float), Size]
+        L.vpf_persp_max_step.restype = C.c_float
         L.vpf_convert_letterbox_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(LetterboxDev), PN,
                                                        C.POINTER(LetterboxOpts)]
         L.vpf_letterbox_fit.argtypes = [Size, Size]
@@ -607,3 +616,31 @@ def convert_warp_tensor_dev(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, frames, t
     if check:
         _check(st, "vpf_convert_warp_tensor_dev")
     return st
+
+
+def make_persps_dev(matrices_ptr, max_n, dst, dst_job_stride, frame_index_ptr=None, count_ptr=None, matrix_stride=36, frame_stride=4, max_step=0.0) -> PerspsDev:
+    """vpf_persps_dev: make_warps_dev() for nine floats per job (matrix_stride from 36 up); max_step = the LDS hint (persp_max_step(); 0: none)"""
+    t = PerspsDev()
+    t.matrices, t.frame_index, t.count = matrices_ptr or None, frame_index_ptr or None, count_ptr or None
+    t.matrix_stride, t.frame_stride, t.max_n, t.max_step, t.dst_job_stride = matrix_stride, frame_stride, max_n, max_step, dst_job_stride
+    d = planes(dst)
+    for k in range(3):
+        t.dst[k].ptr, t.dst[k].pitch = d[k].ptr, d[k].pitch
+    return t
+
+
+def convert_persp_tensor_dev(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, frames, table: PerspsDev, norm: TensorNorm, opts=None, n_frames=None, check=True) -> int:
+    """frames: FrameSrc array from make_frame_srcs() (at most 128), table: make_persps_dev(), opts: make_warp_opts() or None; the kernel reads matrices,
+    frame indices and count when it runs on ex.stream: no sync, no copy, capturable"""
+    st = lib().vpf_convert_persp_tensor_dev(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                            (len(frames) if frames is not None else 0) if n_frames is None else n_frames, frames,
+                                            C.byref(table) if table is not None else None, C.byref(norm) if norm is not None else None,
+                                            C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_persp_tensor_dev")
+    return st
+
+
+def persp_max_step(m, dw, dh) -> float:
+    """vpf_persp_max_step: the LDS hint of ONE inverse 3 x 3 matrix (nine floats) for a dw x dh destination, 0.0 where it has no bound"""
+    return float(lib().vpf_persp_max_step((C.c_float * 9)(*[float(v) for v in m]), Size(dw, dh)))

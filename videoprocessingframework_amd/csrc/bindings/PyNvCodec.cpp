@@ -310,6 +310,22 @@ public:
                                uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc,
                                bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode, uint64_t row_pitch, uint64_t plane_stride,
                                uint64_t frame_stride, bool channels_last, uint32_t matrix_stride, uint32_t index_stride, float max_step) {
+    return MatricesDevToTensor(false, src, matrices, max_n, index, count, dst, dtype, mean, std, cc, bgr, border, border_mode, row_pitch, plane_stride, frame_stride,
+                               channels_last, matrix_stride, index_stride, max_step);
+  }
+  // additive: the same for perspective warps (vpf_convert_persp_tensor_dev): job k = nine float32 (m00 .. m22) at matrices + k matrix_stride; max_step: the
+  // bound on the source pixels per destination pixel step (vpf_persp_max_step; 0: none).  Every other argument as ExecuteWarpsDevToTensor
+  bool ExecutePerspsDevToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t matrices, uint32_t max_n, uint64_t index, uint64_t count, uint64_t dst,
+                                uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc,
+                                bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode, uint64_t row_pitch, uint64_t plane_stride,
+                                uint64_t frame_stride, bool channels_last, uint32_t matrix_stride, uint32_t index_stride, float max_step) {
+    return MatricesDevToTensor(true, src, matrices, max_n, index, count, dst, dtype, mean, std, cc, bgr, border, border_mode, row_pitch, plane_stride, frame_stride,
+                               channels_last, matrix_stride, index_stride, max_step);
+  }
+  bool MatricesDevToTensor(bool persp, const std::vector<std::shared_ptr<Surface>>& src, uint64_t matrices, uint32_t max_n, uint64_t index, uint64_t count, uint64_t dst,
+                           uint32_t dtype, const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc,
+                           bool bgr, const std::array<int64_t, 3>& border, uint32_t border_mode, uint64_t row_pitch, uint64_t plane_stride,
+                           uint64_t frame_stride, bool channels_last, uint32_t matrix_stride, uint32_t index_stride, float max_step) {
     vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
     if (src.empty() || src.size() > 128 || !matrices || !max_n || !dst) return false;
     std::vector<vpf_plane> planes;  // two jobs' planes: the second minus the first is the stride from job to job
@@ -324,9 +340,9 @@ public:
     }
     std::vector<Surface*> a;
     for (auto& s : src) a.push_back(s.get());
-    return TASK_EXEC_SUCCESS == task_->RunTensorWarpsDev(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)matrices, matrix_stride, (const void*)(uintptr_t)index,
-                                                         index_stride, max_n, (const void*)(uintptr_t)count, max_step, planes.data(), job_stride, norm, &opts,
-                                                         cc.get());
+    const auto run = persp ? &ConvertResizeSurface::RunTensorPerspsDev : &ConvertResizeSurface::RunTensorWarpsDev;
+    return TASK_EXEC_SUCCESS == ((*task_).*run)(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)matrices, matrix_stride, (const void*)(uintptr_t)index, index_stride,
+                                                max_n, (const void*)(uintptr_t)count, max_step, planes.data(), job_stride, norm, &opts, cc.get());
   }
   // additive: K letterbox jobs -> a normalised planar tensor [K, 3, dh, dw] at device address `dst` (vpf_convert_letterbox_tensor): rois[i] as
   // ExecuteRoisToTensor, dst_rects[i] = (ix, iy, iw, ih) where that region's picture goes inside dw x dh, `pad` (per output channel) everywhere else;
@@ -899,6 +915,16 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "[max_n, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous).  The kernel reads boxes and count when it runs on the task's "
            "stream: no sync, no copy to the host, capturable.  An invalid box gives a frame of normalised zeros; frames at or behind the count are "
            "not written.  At most 128 surfaces; one dispatch")
+      .def("ExecutePerspsDevToTensor", &PySurfaceConvertResizer::ExecutePerspsDevToTensor, py::arg("surfaces"), py::arg("matrices_ptr"), py::arg("max_n"),
+           py::arg("index_ptr"), py::arg("count_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
+           py::arg("bgr") = false, py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0,
+           py::arg("plane_stride") = 0, py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::arg("matrix_stride") = 36u,
+           py::arg("index_stride") = 4u, py::arg("max_step") = 0.0f, py::call_guard<py::gil_scoped_release>(),
+           "ExecuteWarpsDevToTensor for perspective warps: job k = nine float32 (m00 m01 m02 m10 m11 m12 m20 m21 m22) at matrices_ptr + k matrix_stride, "
+           "the inverse 3 x 3 homography; a pixel with w <= 0 takes the border in both modes.  The kernel reads matrices, indices and count when it runs on "
+           "the task's stream: no sync, no copy to the host, capturable.  An invalid job (a coefficient that is not finite or above 2^24, a surface index "
+           "outside the list) gives the normalised border; frames at or behind the count are not written.  max_step: the LDS hint (0 = none).  At most 128 "
+           "surfaces; one dispatch")
       .def("ExecuteWarpsDevToTensor", &PySurfaceConvertResizer::ExecuteWarpsDevToTensor, py::arg("surfaces"), py::arg("matrices_ptr"), py::arg("max_n"),
            py::arg("index_ptr"), py::arg("count_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
            py::arg("bgr") = false, py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0,
@@ -1075,6 +1101,10 @@ PYBIND11_MODULE(_PyNvCodec, m) {
           return py::make_tuple(r.x, r.y, r.width, r.height);
         }, py::arg("w"), py::arg("h"), py::arg("dw"), py::arg("dh"),
         "additive: (ix, iy, iw, ih), the aspect-preserving, centred placement of a w x h rectangle inside dw x dh (vpf_letterbox_fit; host only)");
+  m.def("PerspMaxStep", [](const std::array<float, 9>& mat, uint32_t dw, uint32_t dh) { return vpf_persp_max_step(mat.data(), vpf_size{dw, dh}); },
+        py::arg("matrix"), py::arg("dw"), py::arg("dh"),
+        "additive: the LDS hint of ONE inverse 3 x 3 matrix (nine floats, row-major) for a dw x dh destination: the bound on the source pixels per "
+        "destination pixel step, 0 where there is none (vpf_persp_max_step; host only)");
   m.def("KernelLibraryVersion", []() { return std::string(vpf_version()); });
   m.def("AllocPinned",
         [](size_t nbytes) {

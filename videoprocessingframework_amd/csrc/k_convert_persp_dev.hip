@@ -1,0 +1,99 @@
+// k_convert_persp_dev.hip — the multi-ROI perspective warp of k_convert_persp.hip with the homographies in DEVICE memory (gfx950):
+// vpf_convert_persp_tensor_dev.  A corner-regression network leaves four corners per document, plate or screen on the GPU and the solve of their
+// 3 x 3 matrices stays there; this kernel reads (frame, m[9]) of job blockIdx.z and the job count WHEN IT RUNS, so the call needs no sync and no
+// copy to the host, and a captured graph replays with the matrices of replay time.
+//   k_persp_dev    ONE dispatch over (32 x 32 destination tiles, max_n jobs).  k_warp_dev's prologue on nine floats: a workgroup loads the count
+//                  (jobs at or behind it write nothing), loads its frame index and nine floats wave-uniformly, runs the guard (persp_dev_job_ok,
+//                  vpf_job_bounds.h: an invalid job reads no frame and writes the epilogue of the border in both modes), assembles the job as the
+//                  host entry's table would hold it and runs k_persp_strip's tile (persp_strip_tile, k_convert_warp_common.h): border, per tap,
+//                  nothing staged or staged from the tile's four corners, the strip in LDS where it fits the bytes the dispatch was given,
+//                  persp_gather4's per-tap pixels where it does not — workgroup-uniform branches.
+// Every form runs k_convert_persp.hip's fp32 operations in its order: identical bits to vpf_convert_persp_tensor on the same matrices, whichever
+// form either entry picks.  The LDS is sized from the caller's hint (persp_dev_lds_bytes): a wrong hint costs time, not pixels.
+#include <cmath>
+
+#include "k_convert_warp_common.h"
+#include "k_job_launch.h"
+
+namespace vpf {
+
+// the job's four pixels of this lane filled with the border (an invalid job: both modes)
+template <int DST>
+VPF_DEV void persp_dev_fill4(const FrameDesc& f, const TensorEpi& te, uint32_t dw, uint32_t dmask, uint32_t x0, uint32_t y) {
+  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  float u[3][4];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) u[ch][k] = warp_border(te, ch);
+  warp_store4<DST>(f, x0, y, u, te, vec, nv);
+}
+
+template <int SRC, int DST>  // DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane
+__global__ __launch_bounds__(256) void k_persp_dev(const WarpDevArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh,
+                                                   uint32_t dmask, uint32_t lds_bytes) {
+  // a prologue that turns the device tables into the PerspDesc the host entry would have put into its job table, then k_persp_strip's tile
+  // 1. the count: jobs at or behind it write nothing and read neither matrix nor frame index
+  uint32_t dv_cnt = args.max_n;
+  if (args.count) {
+    const int32_t v = __builtin_amdgcn_readfirstlane(*args.count);
+    dv_cnt = v < 0 ? 0u : ((uint32_t)v < args.max_n ? (uint32_t)v : args.max_n);
+  }
+  if (blockIdx.z >= dv_cnt) return;
+  // 2. the frame index and the nine floats of this job, wave-uniform: the corner arithmetic of the tile's class stays scalar
+  PerspDesc J;
+  int32_t dv_frame = 0;
+  if (args.frame_index)
+    dv_frame = __builtin_amdgcn_readfirstlane(
+        *reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(args.frame_index) + (size_t)blockIdx.z * args.frame_stride));
+  {
+    const uint32_t* const mp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(args.matrices) + (size_t)blockIdx.z * args.matrix_stride);
+#pragma unroll
+    for (int k = 0; k < 9; k++) J.m[k] = __uint_as_float(__builtin_amdgcn_readfirstlane(mp[k]));
+  }
+  // the job's destination planes and every pitch live in vector registers (an opaque zero added to them), as in k_warp_dev: they feed per-lane
+  // addresses only, and the nine floats read above cannot be loaded again where they are used
+  uint32_t dv_zero = 0;
+  asm("" : "+v"(dv_zero));
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    J.f.d[ch] = (DST == FC_TENSOR_NHWC && ch) ? nullptr : args.d[ch] + ((size_t)blockIdx.z * args.job_stride + dv_zero);
+    J.f.dp[ch] = args.dp[ch] + dv_zero;
+  }
+  // 3. the guard (vpf_job_bounds.h): an invalid job reads no frame; its tile takes the epilogue of the border, in both modes
+  if (!persp_dev_job_ok(dv_frame, J.m, args.n_frames)) {
+    const uint32_t fx0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, fy = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;
+    if (fx0 < dw && fy < dh) persp_dev_fill4<DST>(J.f, args.e, dw, dmask, fx0, fy);
+    return;
+  }
+  // 4. the job as the host entry's table holds it
+  {
+    const FrameSrcDesc& fs = args.f[dv_frame];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) { J.f.s[ch] = fs.s[ch]; J.f.sp[ch] = fs.sp[ch] + dv_zero; }
+  }
+  // 5. k_persp_strip from here on: the tile's class and window, staged where its strip fits lds_bytes, per tap where it does not
+  const TensorEpi te = args.e;
+  persp_strip_tile<SRC, DST>(J, te, c, W, H, dw, dh, dmask, lds_bytes);
+}
+
+// ------------------------------------------------------------------------------------------
+// Host side.  No matrix is known here: the dynamic LDS comes from the caller's hint (persp_dev_lds_bytes; no hint: kWarpStripMax), 0 under
+// VPF_TUNE_NV12_RGB_VARIANT = 9 — no strip fits then, every tile samples per tap.
+// ------------------------------------------------------------------------------------------
+hipError_t launch_convert_persp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
+                                    float max_step, const TensorEpi& te, bool nhwc) {
+  if (!a.max_n || a.max_n > 65535u || !a.n_frames || a.n_frames > (uint32_t)kRoiDevFrames || !job_src_ok(src_fc)) return hipErrorInvalidValue;
+  const uint32_t dmask = job_dmask(te, nhwc);
+  const uint32_t lds = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 ? 0u : persp_dev_lds_bytes(max_step, W, H, dw, dh);
+  a.e = te;
+  const dim3 grid((dw + kWarpTileW - 1) / kWarpTileW, (dh + kWarpTileH - 1) / kWarpTileH, a.max_n);
+  hipError_t e = hipSuccess;
+  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_dev, (S, D), grid, lds, st, a, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
+  return e;
+}
+
+}  // namespace vpf

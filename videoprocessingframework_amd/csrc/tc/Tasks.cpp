@@ -581,17 +581,11 @@ TaskExecStatus ConvertResizeSurface::RunTensorRoisDev(Surface* const* frames, ui
                                                            fr.data(), &table, &norm);
   return exec_status(st, "convert + resize device-resident regions into a tensor");
 }
-TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride,
-                                                       const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count, float max_step,
-                                                       const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
-                                                       const ColorspaceConversionContext* cc) {
-  const HipMark tick("ConvertResizeSurface::RunTensorWarpsDev");
-  if (!frames || !n_frames || n_frames > kMaxDevFrames || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
-  int cs, cr;
-  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
-  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
-  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
-  vpf_warps_dev table;
+// the table of a device-matrix entry: vpf_warps_dev and vpf_persps_dev share their layout
+template <typename Table>
+static Table matrices_dev_table(const void* matrices, uint32_t matrix_stride, const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count,
+                                float max_step, const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm) {
+  Table table;
   std::memset(&table, 0, sizeof(table));
   table.matrices = static_cast<const float*>(matrices);
   table.frame_index = static_cast<const int32_t*>(frame_index);
@@ -602,10 +596,39 @@ TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, u
   table.max_step = max_step;
   tensor_job_planes(dst, 0, norm, table.dst);
   table.dst_job_stride = dst_job_stride;
+  return table;
+}
+TaskExecStatus ConvertResizeSurface::RunTensorWarpsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride,
+                                                       const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count, float max_step,
+                                                       const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
+                                                       const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorWarpsDev");
+  if (!frames || !n_frames || n_frames > kMaxDevFrames || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
+  const vpf_warps_dev table = matrices_dev_table<vpf_warps_dev>(matrices, matrix_stride, frame_index, frame_stride, max_n, count, max_step, dst, dst_job_stride, norm);
   const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
   const vpf_status st = vpf_convert_warp_tensor_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames, fr.data(),
                                                     &table, &norm, opts);
   return exec_status(st, "warp device-resident regions into a tensor");
+}
+TaskExecStatus ConvertResizeSurface::RunTensorPerspsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride,
+                                                        const void* frame_index, uint32_t frame_stride, uint32_t max_n, const void* count, float max_step,
+                                                        const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,
+                                                        const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorPerspsDev");
+  if (!frames || !n_frames || n_frames > kMaxDevFrames || !matrices || !dst || !max_n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  const std::vector<vpf_frame_src> fr = frame_srcs(frames, n_frames);
+  const vpf_persps_dev table = matrices_dev_table<vpf_persps_dev>(matrices, matrix_stride, frame_index, frame_stride, max_n, count, max_step, dst, dst_job_stride, norm);
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_persp_tensor_dev(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n_frames, fr.data(),
+                                                     &table, &norm, opts);
+  return exec_status(st, "warp device-resident regions through homographies into a tensor");
 }
 TaskExecStatus ConvertResizeSurface::RunTensorWarps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                                     const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts,

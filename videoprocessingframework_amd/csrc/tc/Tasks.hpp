@@ -85,6 +85,11 @@ public:
   // m11 m12 m20 m21 m22: destination pixel -> homogeneous source coordinates); a pixel with w <= 0 takes the border in both modes.
   TaskExecStatus RunTensorPersps(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const float* matrices, uint32_t n,
                                  const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
+  // up to max_n perspective warps whose matrices lie in DEVICE memory (vpf_convert_persp_tensor_dev): RunTensorWarpsDev with nine floats per job
+  // (m00 .. m22) at matrices + k matrix_stride; max_step: the caller's bound on the source pixels per destination pixel step (vpf_persp_max_step; 0: none)
+  TaskExecStatus RunTensorPerspsDev(Surface* const* frames, uint32_t n_frames, const void* matrices, uint32_t matrix_stride, const void* frame_index,
+                                    uint32_t frame_stride, uint32_t max_n, const void* count, float max_step, const vpf_plane* dst, uint64_t dst_job_stride,
+                                    const vpf_tensor_norm& norm, const vpf_warp_opts* opts, const ColorspaceConversionContext* ctx);
   // n letterbox jobs (vpf_convert_letterbox_tensor): job i resizes rects[i] of frames[frame_index[i]] into dst_rects[i] (destination pixels, inside
   // the task's destination size) of the planes dst[3 i .. 3 i + 2] and writes the pad everywhere else in them; opts == nullptr: pad 0 0 0.
   // RunTensorRois' colour-context rules; the entry cuts the jobs into job tables.

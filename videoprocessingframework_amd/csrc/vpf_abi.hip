@@ -340,6 +340,44 @@ static TensorEpi make_epi(const vpf_tensor_norm& norm, const uint8_t* fill = nul
   return te;
 }
 
+// The two warps with the matrices, their frame indices and the count in DEVICE memory (include/vpf_hip.h): every check that needs no matrix happens
+// here, once for both entries, the matrix check in the kernel; one dispatch.  `Table`: vpf_warps_dev (kCoefs = 6, k_convert_warp_dev.hip) or
+// vpf_persps_dev (kCoefs = 9, k_convert_persp_dev.hip), the same 96 bytes.
+static_assert(sizeof(vpf_persps_dev) == 96 && sizeof(vpf_warps_dev) == 96 && offsetof(vpf_persps_dev, matrix_stride) == offsetof(vpf_warps_dev, matrix_stride) &&
+                  offsetof(vpf_persps_dev, max_step) == 36 && offsetof(vpf_persps_dev, dst) == 40 && offsetof(vpf_persps_dev, dst_job_stride) == 88,
+              "vpf_persps_dev has the layout of vpf_warps_dev, no implicit padding");
+template <uint32_t kCoefs, typename Table, typename Launch>
+static vpf_status matrices_dev_entry(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames,
+                                     const Table* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts, Launch launch) {
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE, opts && opts->reserved)) return refused;
+  if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
+  const TensorLayout l = layout_of(*norm);
+  if (!table->matrices || (((uintptr_t)table->matrices | (uintptr_t)table->frame_index | (uintptr_t)table->count) & 3u) || table->matrix_stride < 4u * kCoefs ||
+      (table->matrix_stride & 3u) || (table->frame_index && (table->frame_stride < 4u || (table->frame_stride & 3u))) ||
+      (table->dst_job_stride & (l.elem - 1)) || !(table->max_step >= 0.f) || !std::isfinite(table->max_step))
+    return VPF_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n_frames; i++)
+    if (!tensor_src_ok(sf, ss.width, frames[i].src, true)) return VPF_ERR_BAD_ARG;
+  if (!tensor_planes_ok(table->dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
+  WarpDevArgs a;
+  std::memset(&a, 0, sizeof(a));
+  fill_frame_srcs(a.f, frames, n_frames, num_planes(sf));
+  fill_job0_dst(a.d, a.dp, table->dst, l);
+  a.matrices = table->matrices;
+  a.frame_index = table->frame_index;
+  a.count = table->count;
+  a.job_stride = table->dst_job_stride;
+  a.matrix_stride = table->matrix_stride; a.frame_stride = table->frame_index ? table->frame_stride : 0u; a.max_n = table->max_n; a.n_frames = n_frames;
+  return status_of(launch(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height, table->max_step, te, l.nhwc));
+}
+
 }  // namespace vpf
 
 using namespace vpf;
@@ -799,39 +837,23 @@ vpf_status vpf_convert_persp_tensor(const vpf_exec* exec, int sf, int cs, int cr
   return VPF_OK;
 }
 
-// The affine warp with the matrices, their frame indices and the count in DEVICE memory (include/vpf_hip.h): every check that needs no matrix happens here,
-// the matrix check in the kernel (k_convert_warp_dev.hip); one dispatch.
+// The two warps with the matrices in DEVICE memory (include/vpf_hip.h) through their one host path (matrices_dev_entry); one dispatch each.
 vpf_status vpf_convert_warp_tensor_dev(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames,
                                        const vpf_warps_dev* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
   const Mark mark("vpf_convert_warp_tensor_dev");
-  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
-  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE, opts && opts->reserved)) return refused;
-  if (!exec || !frames || !table || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
-  if (!n_frames || n_frames > (uint32_t)kRoiDevFrames || !table->max_n || table->max_n > 65535u) return VPF_ERR_BAD_ARG;
-  const TensorLayout l = layout_of(*norm);
-  if (!table->matrices || (((uintptr_t)table->matrices | (uintptr_t)table->frame_index | (uintptr_t)table->count) & 3u) || table->matrix_stride < 24u ||
-      (table->matrix_stride & 3u) || (table->frame_index && (table->frame_stride < 4u || (table->frame_stride & 3u))) ||
-      (table->dst_job_stride & (l.elem - 1)) || !(table->max_step >= 0.f) || !std::isfinite(table->max_step))
-    return VPF_ERR_BAD_ARG;
-  for (uint32_t i = 0; i < n_frames; i++)
-    if (!tensor_src_ok(sf, ss.width, frames[i].src, true)) return VPF_ERR_BAD_ARG;
-  if (!tensor_planes_ok(table->dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
-  DeviceGuard guard(exec->device);
-  if (guard.err != hipSuccess) return status_of(guard.err);
-  Yuv2RgbCoef c;
-  make_yuv2rgb(cs, cr, &c);
-  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
-  WarpDevArgs a;
-  std::memset(&a, 0, sizeof(a));
-  fill_frame_srcs(a.f, frames, n_frames, num_planes(sf));
-  fill_job0_dst(a.d, a.dp, table->dst, l);
-  a.matrices = table->matrices;
-  a.frame_index = table->frame_index;
-  a.count = table->count;
-  a.job_stride = table->dst_job_stride;
-  a.matrix_stride = table->matrix_stride; a.frame_stride = table->frame_index ? table->frame_stride : 0u; a.max_n = table->max_n; a.n_frames = n_frames;
-  return status_of(launch_convert_warp_dev(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, a, ds.width, ds.height,
-                                           table->max_step, te, l.nhwc));
+  return matrices_dev_entry<6>(exec, sf, cs, cr, ss, ds, n_frames, frames, table, norm, opts, launch_convert_warp_dev);
+}
+vpf_status vpf_convert_persp_tensor_dev(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n_frames, const vpf_frame_src* frames,
+                                        const vpf_persps_dev* table, const vpf_tensor_norm* norm, const vpf_warp_opts* opts) {
+  const Mark mark("vpf_convert_persp_tensor_dev");
+  return matrices_dev_entry<9>(exec, sf, cs, cr, ss, ds, n_frames, frames, table, norm, opts, launch_convert_persp_dev);
+}
+// The caller's LDS hint for one homography (include/vpf_hip.h): persp_step, vpf_job_bounds.h.  0: no bound.
+float vpf_persp_max_step(const float m[9], vpf_size dst) {
+  if (!m || !dims_ok(dst)) return 0.f;
+  for (int k = 0; k < 9; k++)
+    if (!(std::fabs(m[k]) <= 16777216.0f)) return 0.f;
+  return persp_step(m, dst.width, dst.height);
 }
 
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.

@@ -208,13 +208,14 @@ struct PerspArgs {
 static_assert(sizeof(PerspDesc) == 112 && sizeof(PerspArgs) == 82 * 112 + 32 && sizeof(PerspArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
               "the perspective job table must not outgrow the largest frame table");
 
-// The arguments of a warp launch whose matrices live in DEVICE memory (vpf_convert_warp_tensor_dev, k_convert_warp_dev.hip): the shape of RoiDevArgs —
+// The arguments of a warp launch whose matrices live in DEVICE memory (vpf_convert_warp_tensor_dev, k_convert_warp_dev.hip; vpf_convert_persp_tensor_dev,
+// k_convert_persp_dev.hip: nine floats per job): the shape of RoiDevArgs —
 // the source planes of up to 128 frames, where the matrices, the frame indices and the count lie, and job 0's destination planes with the stride
-// from job to job.  The kernel reads (frame, m[6]) of job blockIdx.z when it runs.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
+// from job to job.  The kernel reads (frame, m[6] or m[9]) of job blockIdx.z when it runs.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
 // 5 240 B, below the largest argument block.
 struct WarpDevArgs {
   FrameSrcDesc f[kRoiDevFrames];
-  const float* matrices;       // device: six floats per job, matrix_stride bytes apart
+  const float* matrices;       // device: six (affine) or nine (perspective) floats per job, matrix_stride bytes apart
   const int32_t* frame_index;  // device: one int per job, frame_stride bytes apart; null: every job samples f[0]
   const int32_t* count;        // device, or null: max_n
   uint8_t* d[3];               // job 0's planes (kernel channel order); job k's lie k * job_stride bytes further
@@ -294,6 +295,10 @@ hipError_t launch_convert_letterbox_dev(hipStream_t st, int src_fc, const Yuv2Rg
 // `te.pad` carries border and mode; a.e is set here; k_convert_warp_dev.hip
 hipError_t launch_convert_warp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
                                    float max_step, const TensorEpi& te, bool nhwc = false);
+// the same for homographies (nine floats per job): ONE dispatch, every tile border, per tap or staged by its own corners; `max_step` sizes the
+// dynamic LDS (persp_dev_lds_bytes, vpf_job_bounds.h); k_convert_persp_dev.hip
+hipError_t launch_convert_persp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
+                                    float max_step, const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 

@@ -11,6 +11,8 @@
 //   warp  warp_xy / warp_window / warp_strip: what the kernel computes per tile; warp_need: the launcher's closed-form bound over all tiles;
 //         warp_dev_job_ok / warp_dev_lds_bytes: the guard and the LDS bound of the device-table form (k_convert_warp_dev.hip;
 //         tests/test_warps_dev_bounds_cpu.py through tests/c/warp_dev_bounds_capi.cpp)
+//   persp persp_xy / persp_window / persp_px_in_window / persp_need: the perspective warp's (k_convert_persp.hip); persp_dev_job_ok / persp_step /
+//         persp_dev_lds_bytes: the guard, the caller's hint and the LDS bound of its device-table form (k_convert_persp_dev.hip)
 #ifndef VPF_JOB_BOUNDS_H_
 #define VPF_JOB_BOUNDS_H_
 #include <math.h>
@@ -409,43 +411,114 @@ static inline double persp_ratio_max(double a, double b, double c, double d, dou
   }
   return best;
 }
-// pixels of a tile's window along one axis, at most (r: the matrix row of that axis, r2: the last row, S: the frame's size along it, werr: what
-// is taken off every w, wmin: the smallest w of the destination less werr)
-static inline uint32_t persp_need_count(const float* r, const float* r2, uint32_t S, double tw, double th, uint32_t dw, uint32_t dh, double werr, double wmin) {
-  const double smax = (double)(S - 1), X = (double)(dw - 1), Y = (double)(dh - 1);
+// gx = max |d s / d dx|, gy = max |d s / d dy| of one coordinate row over the whole destination (r: the matrix row of that axis, r2: the last row,
+// werr: what is taken off every w): what persp_need_count multiplies by the tile's sides and what persp_step sums
+struct PerspGrad { double gx, gy; };
+static inline PerspGrad persp_grad(const float* r, const float* r2, uint32_t dw, uint32_t dh, double werr) {
+  const double X = (double)(dw - 1), Y = (double)(dh - 1);
   const double A = (double)r[0] * r2[1] - (double)r2[0] * r[1], B = (double)r[0] * r2[2] - (double)r2[0] * r[2], D = (double)r[1] * r2[2] - (double)r2[1] * r[2];
   const double w00 = (double)r2[2] - werr;
   const double gx = fmax(persp_ratio_max(B, A, w00, r2[1], Y), persp_ratio_max(B, A, w00 + (double)r2[0] * X, r2[1], Y));
   const double gy = fmax(persp_ratio_max(D, -A, w00, r2[0], X), persp_ratio_max(D, -A, w00 + (double)r2[1] * Y, r2[0], X));
-  const double span = gx * (tw - 1) + gy * (th - 1);
+  return PerspGrad{gx, gy};
+}
+// pixels of a tile's window along one axis, at most (S: the frame's size along it, wmin: the smallest w of the destination less werr)
+static inline uint32_t persp_need_count(const float* r, const float* r2, uint32_t S, double tw, double th, uint32_t dw, uint32_t dh, double werr, double wmin) {
+  const double smax = (double)(S - 1);
+  const PerspGrad g = persp_grad(r, r2, dw, dh, werr);
+  const double span = g.gx * (tw - 1) + g.gy * (th - 1);
   const double nmag = fabs((double)r[0]) * dw + fabs((double)r[1]) * dh + fabs((double)r[2]);
   const double wmag = fabs((double)r2[0]) * dw + fabs((double)r2[1]) * dh + fabs((double)r2[2]);
   const double err = 4.0 * 0x1p-23 * ((nmag + smax * wmag) / wmin + smax);
   const double n = floor(span + 2.0 * err) + 5.0;
   return n < (double)S ? (uint32_t)n : S;
 }
-static inline WarpNeed persp_need(const float m[9], uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+// what persp_need looks at before it bounds anything: the fp32 w of the four destination corners.  `bounded`: all four have w > 0 and the smallest,
+// less the rounding, is still positive — the jobs whose gradients persp_grad bounds
+struct PerspFront {
+  uint32_t nfront;
+  double werr, wmin;
+  bool bounded;
+};
+static inline PerspFront persp_front(const float m[9], uint32_t dw, uint32_t dh) {
   const uint32_t cx[4] = {0u, dw - 1, 0u, dw - 1}, cy[4] = {0u, 0u, dh - 1, dh - 1};
-  uint32_t nfront = 0;
-  double wmin = 0.0;
+  PerspFront f{0u, 0.0, 0.0, false};
   for (int k = 0; k < 4; k++) {
     const float w = (m[6] * (float)cx[k] + m[7] * (float)cy[k]) + m[8];
     if (w > 0.f) {
-      wmin = !nfront || (double)w < wmin ? (double)w : wmin;
-      nfront++;
+      f.wmin = !f.nfront || (double)w < f.wmin ? (double)w : f.wmin;
+      f.nfront++;
     }
   }
-  if (!nfront) return WarpNeed{0u};
-  const double werr = 4.0 * 0x1p-23 * (fabs((double)m[6]) * dw + fabs((double)m[7]) * dh + fabs((double)m[8]));
-  wmin -= 2.0 * werr;  // (the exact w of a corner may lie werr below the fp32 one, and werr is taken off every exact w below)
-  if (nfront != 4u || !(wmin > 0.0)) return WarpNeed{kWarpStripMax};
+  f.werr = 4.0 * 0x1p-23 * (fabs((double)m[6]) * dw + fabs((double)m[7]) * dh + fabs((double)m[8]));
+  f.wmin -= 2.0 * f.werr;  // (the exact w of a corner may lie werr below the fp32 one, and werr is taken off every exact w below)
+  f.bounded = f.nfront == 4u && f.wmin > 0.0;
+  return f;
+}
+static inline WarpNeed persp_need(const float m[9], uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  const PerspFront f = persp_front(m, dw, dh);
+  if (!f.nfront) return WarpNeed{0u};
+  if (!f.bounded) return WarpNeed{kWarpStripMax};
   const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
-  const uint32_t nx = persp_need_count(m, m + 6, W, tw, th, dw, dh, werr, wmin), rows = persp_need_count(m + 3, m + 6, H, tw, th, dw, dh, werr, wmin);
+  const uint32_t nx = persp_need_count(m, m + 6, W, tw, th, dw, dh, f.werr, f.wmin), rows = persp_need_count(m + 3, m + 6, H, tw, th, dw, dh, f.werr, f.wmin);
   uint32_t ng = (nx >> 3) + 1;  // the strip starts on the even pixel at or below x_lo
   const uint32_t ng_max = ((W - 1) >> 3) + 1;
   ng = ng < ng_max ? ng : ng_max;
   const uint64_t bytes = (uint64_t)rows * (32u * ng + 16u);
   return WarpNeed{bytes < 0xffffffffull ? (uint32_t)bytes : 0xffffffffu};
+}
+
+// ------------------------------------------------------------------------------------------
+// Device-resident homographies (k_convert_persp_dev.hip, vpf_convert_persp_tensor_dev; tests/test_persps_dev_bounds_cpu.py through
+// tests/c/persp_dev_bounds_capi.cpp).  The kernel reads (frame, m[9]) of its job from device memory, so the host entry's check of the matrix happens
+// in the kernel, and the launcher sizes the LDS without a matrix.
+// ------------------------------------------------------------------------------------------
+// The guard: the ONLY thing between untrusted device memory and a read outside a frame: warp_dev_job_ok over nine floats.  With every |m| <= 2^24
+// and dx, dy <= 65535, nx, ny and w are finite; a pixel with !(w > 0) takes the border, every other one divides two finite numbers by a positive
+// one: no NaN, and +-inf is out of range (CONSTANT) or clamped to the edge (REPLICATE), so every tap lies inside the frame (include/vpf_hip.h).
+static VPF_JB_HDI bool persp_dev_job_ok(int32_t frame, const float* m, uint32_t n_frames) {
+  bool ok = (uint32_t)frame < n_frames;
+  for (int k = 0; k < 9; k++) ok = ok && fabsf(m[k]) <= 0x1p24f;
+  return ok;
+}
+// The caller's hint for ONE matrix: the bound, over every destination pixel, of |d sx / d dx| + |d sx / d dy| and of |d sy / d dx| + |d sy / d dy|
+// (source pixels per destination pixel step) — max(gx + gy) over the two coordinate rows, gx and gy persp_need_count's.  Rounded up to fp32.  A last
+// row (0, 0, 1) gives max(|m00| + |m01|, |m10| + |m11|) / (1 - werr)^2: the affine entry's hint.  0, "no hint", where persp_need has no bound
+// either: some destination corner with !(w > 0), or the smallest w not positive after its rounding (and where the bound is no fp32 number).
+static inline float persp_step(const float m[9], uint32_t dw, uint32_t dh) {
+  const PerspFront f = persp_front(m, dw, dh);
+  if (!f.bounded) return 0.f;
+  const PerspGrad a = persp_grad(m, m + 6, dw, dh, f.werr), b = persp_grad(m + 3, m + 6, dw, dh, f.werr);
+  const double s = fmax(a.gx + a.gy, b.gx + b.gy);
+  if (!(s < 3.0e38)) return 0.f;  // (not a float: no hint)
+  float r = (float)s;
+  if ((double)r < s) r = nextafterf(r, INFINITY);
+  return r;
+}
+// The dynamic LDS of a dispatch whose matrices nobody has seen, from the caller's hint `max_step` >= persp_step of every valid job: the strip of a
+// window of floor(max_step * max(tw - 1, th - 1) + slack) + 5 pixels per axis, cut to the frame.  gx (tw - 1) + gy (th - 1) <= (gx + gy) max(tw - 1,
+// th - 1), persp_need_count's span; the + 5 is its own.  Its rounding term depends on the matrix (2 err, err = 2^-21 ((nmag + smax wmag) / wmin +
+// smax)); here it is the `slack` of matrices of moderate condition, kappa = wmag / wmin <= 8, whose coordinates lie in the frame: nmag / wmin is
+// then at most kappa (max_step (dw + dh) + S) — a step of max_step per destination pixel away from an offset inside the frame — so
+// slack = 2 * 2^-21 (8 max_step (dw + dh) + 17 S): 0.05 pixels for 1080p into 640 x 640 at a step of 3.  A matrix outside that gets a window that
+// may be short by the difference, which costs its tile the per-tap form.  Capped at kWarpStripMax, which is also the answer without a hint
+// (max_step == 0).  Never a correctness input: a tile whose strip exceeds the LDS it was given samples per tap (persp_strip_tile,
+// k_convert_warp_common.h), with identical bits.
+static inline uint32_t persp_dev_lds_count(float max_step, uint32_t S, double tw, double th, uint32_t dw, uint32_t dh) {
+  const double side = (tw > th ? tw : th) - 1.0;
+  const double slack = 0x1p-20 * (8.0 * (double)max_step * ((double)dw + (double)dh) + 17.0 * (double)S);
+  const double n = floor((double)max_step * side + slack) + 5.0;
+  return n < (double)S ? (uint32_t)n : S;
+}
+static inline uint32_t persp_dev_lds_bytes(float max_step, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  if (!(max_step > 0.f)) return kWarpStripMax;
+  const double tw = dw < kWarpTileW ? dw : kWarpTileW, th = dh < kWarpTileH ? dh : kWarpTileH;
+  const uint32_t nx = persp_dev_lds_count(max_step, W, tw, th, dw, dh), rows = persp_dev_lds_count(max_step, H, tw, th, dw, dh);
+  uint32_t ng = (nx >> 3) + 1;
+  const uint32_t ng_max = ((W - 1) >> 3) + 1;
+  ng = ng < ng_max ? ng : ng_max;
+  const uint64_t bytes = (uint64_t)rows * (32u * ng + 16u);
+  return bytes < kWarpStripMax ? (uint32_t)bytes : kWarpStripMax;
 }
 
 #endif  // VPF_JOB_BOUNDS_H_
