@@ -15,7 +15,7 @@
 #include "k_fused_common.h"
 #include "k_job_launch.h"
 #include "k_letterbox_common.h"  // lb_pad, lb_store4, lb_pad_rows: shared with k_convert_letterbox_dev.hip
-#include "vpf_job_bounds.h"  // kRoiBandRows, letterbox_strip_need, the policy's limits: shared with the CPU property test
+#include "vpf_job_bounds.h"  // kRoiBandRows: shared with the launch policy (vpf_job_plan.h) and the CPU property tests
 
 namespace vpf {
 
@@ -139,31 +139,28 @@ __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gat
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  launch_convert_resize_rois with the plane-laid walk: the strip a staged job needs is WALKED with the kernel's own fp32 tap
-// arithmetic over the tiles that meet the picture (letterbox_strip_need, vpf_job_bounds.h; tests/test_letterbox_bounds_cpu.py).  The policy is
-// the ROI kernels' (roi_job_staged: kRoiStripMax, kRoiConvMax).
+// Host side: launch_convert_resize_rois with the letterbox family of job_plan (vpf_job_plan.h): the walk is laid on the plane and clipped to the
+// picture (letterbox_strip_need, vpf_job_bounds.h), the policy is the ROI kernels'.
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
                                     uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kLetterboxBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  LetterboxArgs as, ag;
-  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const LetterboxDesc& j) {
-    const RoiStripNeed need = letterbox_strip_need(j.r.x, j.r.w, j.r.h, j.r.scx, j.r.scy, j.ix, j.iy, j.iw, j.ih, dw, dh);
-    return roi_job_staged(need) ? need.bytes : kNotStaged;
-  });
-  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
+  JobShape q;
+  job_shape(q, JOB_LETTERBOX, false, src_fc, nhwc, te, W, 0u, dw, dh);
+  job_shape_jobs(q, jobs, n, [](JobGeom& g, const LetterboxDesc& j) { g.x = j.r.x; g.w = j.r.w; g.h = j.r.h; g.scx = j.r.scx; g.scy = j.r.scy; g.ix = j.ix; g.iy = j.iy; g.iw = j.iw; g.ih = j.ih; });
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  LetterboxArgs t[2];
+  fill_job_tables(p, jobs, n, te, t);
   hipError_t e = hipSuccess;
-  if (ns) {
-    const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
-    const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &as.e) : lds;  // the strip, then the waves' staging area where both fit
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_lb_strip, (S, D), grid, lds_all, st, as, c, W, dw, dh, dmask, lds); e = hipGetLastError(); });
-    if (e != hipSuccess) return e;
-  }
-  if (ngat) {
-    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
-    const uint32_t lds_g = nhwc ? nhwc_stage_plan(te, 0u, 4, &ag.e) : 0u;
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_lb_gather, (S, D), grid, lds_g, st, ag, c, dw, dh, dmask); e = hipGetLastError(); });
+  for (int k = 0; k < p.nd && e == hipSuccess; k++) {  // staged first; its error returns before the per-tap launch
+    const JobDispatch& d = p.d[k];
+    const dim3 grid(d.gx, d.gy, d.n);
+    const uint32_t lds_all = job_launch_lds(d, te, t[k]);
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) {
+      if (d.form == JF_LB_STRIP) VPF_LAUNCH_T(k_lb_strip, (S, D), grid, lds_all, st, t[k], c, W, dw, dh, p.dmask, d.lds);
+      else VPF_LAUNCH_T(k_lb_gather, (S, D), grid, lds_all, st, t[k], c, dw, dh, p.dmask);
+      e = hipGetLastError();
+    });
   }
   return e;
 }

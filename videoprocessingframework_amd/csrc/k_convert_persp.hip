@@ -44,30 +44,29 @@ __global__ __launch_bounds__(256) void k_persp_gather(const PerspArgs args, cons
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side: launch_convert_warp's split.  A job whose bound (persp_need, vpf_job_bounds.h) fits kWarpStripMax goes to the staged dispatch, whose
-// dynamic LDS is the largest such bound; every other job to the per-tap dispatch.  Two dispatches per table rather than one with a per-tile
-// decision: the host has the matrices, so a large down-scale is known before the launch and its tiles run the small per-tap kernel at full
-// occupancy instead of the staged kernel holding LDS it cannot use.  What the host cannot know — the horizon inside a tile, a strip past the
-// bound — the staged kernel decides per tile.
+// Host side: launch_convert_warp with the perspective family of job_plan (vpf_job_plan.h, where the reason for two dispatches per table stands):
+// persp_need against kWarpStripMax (vpf_job_bounds.h).
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_persp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const PerspDesc* jobs, uint32_t dw,
                                 uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kPerspBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  PerspArgs as, ag;
-  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const PerspDesc& j) {
-    const WarpNeed need = persp_need(j.m, W, H, dw, dh);
-    return need.bytes <= kWarpStripMax ? need.bytes : kNotStaged;
-  });
-  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
-  const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
+  JobShape q;
+  job_shape(q, JOB_PERSP, false, src_fc, nhwc, te, W, H, dw, dh);
+  job_shape_jobs(q, jobs, n, [](JobGeom& g, const PerspDesc& j) { for (int k = 0; k < 9; k++) g.m[k] = j.m[k]; });
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  PerspArgs t[2];
+  fill_job_tables(p, jobs, n, te, t);
   hipError_t e = hipSuccess;
-  if (ns) {
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_strip, (S, D), dim3(gx, gy, ns), lds, st, as, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
-    if (e != hipSuccess) return e;
+  for (int k = 0; k < p.nd && e == hipSuccess; k++) {  // staged first; its error returns before the per-tap launch
+    const JobDispatch& d = p.d[k];
+    const dim3 grid(d.gx, d.gy, d.n);
+    const uint32_t lds_all = job_launch_lds(d, te, t[k]);
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) {
+      if (d.form == JF_PERSP_STRIP) VPF_LAUNCH_T(k_persp_strip, (S, D), grid, lds_all, st, t[k], c, W, H, dw, dh, p.dmask, d.lds);
+      else VPF_LAUNCH_T(k_persp_gather, (S, D), grid, lds_all, st, t[k], c, W, H, dw, dh, p.dmask);
+      e = hipGetLastError();
+    });
   }
-  if (ngat)
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_gather, (S, D), dim3(gx, gy, ngat), 0u, st, ag, c, W, H, dw, dh, dmask); e = hipGetLastError(); });
   return e;
 }
 

@@ -81,18 +81,21 @@ __global__ __launch_bounds__(256) void k_persp_dev(const WarpDevArgs args, const
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  No matrix is known here: the dynamic LDS comes from the caller's hint (persp_dev_lds_bytes; no hint: kWarpStripMax), 0 under
-// VPF_TUNE_NV12_RGB_VARIANT = 9 — no strip fits then, every tile samples per tap.
+// Host side.  No matrix is known here: job_plan (vpf_job_plan.h) sizes the ONE dispatch's LDS from the caller's hint (persp_dev_lds_bytes,
+// vpf_job_bounds.h; no hint: kWarpStripMax), nothing under VPF_TUNE_NV12_RGB_VARIANT = 9 — no strip fits then, every tile samples per tap.
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_persp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
                                     float max_step, const TensorEpi& te, bool nhwc) {
-  if (!a.max_n || a.max_n > 65535u || !a.n_frames || a.n_frames > (uint32_t)kRoiDevFrames || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  const uint32_t lds = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 ? 0u : persp_dev_lds_bytes(max_step, W, H, dw, dh);
-  a.e = te;
-  const dim3 grid((dw + kWarpTileW - 1) / kWarpTileW, (dh + kWarpTileH - 1) / kWarpTileH, a.max_n);
+  JobShape q;
+  job_shape(q, JOB_PERSP, true, src_fc, nhwc, te, W, H, dw, dh);
+  job_shape_dev(q, a.max_n, a.n_frames, max_step);
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  const JobDispatch& d = p.d[0];
+  const dim3 grid(d.gx, d.gy, d.n);
+  const uint32_t lds_all = job_launch_lds(d, te, a);  // (sets a.e)
   hipError_t e = hipSuccess;
-  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_dev, (S, D), grid, lds, st, a, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
+  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_persp_dev, (S, D), grid, lds_all, st, a, c, W, H, dw, dh, p.dmask, d.lds); e = hipGetLastError(); });
   return e;
 }
 

@@ -11,7 +11,7 @@
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
 #include "k_job_launch.h"
-#include "vpf_job_bounds.h"  // kRoiBandRows, roi_strip_need, the policy's limits: shared with the CPU property test
+#include "vpf_job_bounds.h"  // kRoiBandRows: shared with the launch policy (vpf_job_plan.h) and the CPU property tests
 
 namespace vpf {
 
@@ -103,33 +103,28 @@ __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_roi_ga
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  The strip a staged job needs is WALKED with the kernel's own fp32 tap arithmetic (vpf_lin_i0 = make_tap's i0), chunk by
-// chunk and band by band, like vpf_band_rows_exact: a bound that is a row short would be silent corruption (roi_strip_need,
-// vpf_job_bounds.h; tests/test_job_bounds_cpu.py).
+// Host side: fill the shape, ask job_plan (vpf_job_plan.h: the cap, staged or per tap per job — roi_strip_need and the policy's two limits,
+// vpf_job_bounds.h —, the grids, the strip's bytes, the channels-last staging), fill the two tables from it and launch what it names.
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,
                                       uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kRoiBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  // staged: the window fits a strip that leaves three workgroups per CU and converts at most three source pixels per destination pixel
-  // (the measured break-even of the strip against the per-tap kernels, launch_convert_resize); everything else gathers
-  RoiArgs as, ag;  // (one interleaved plane: the staging plan of each dispatch follows below, nhwc_stage_plan)
-  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const RoiDesc& j) {
-    const RoiStripNeed need = roi_strip_need(j.x, j.w, j.h, j.scx, j.scy, dw, dh);
-    return roi_job_staged(need) ? need.bytes : kNotStaged;
-  });
-  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
+  JobShape q;
+  job_shape(q, JOB_ROI, false, src_fc, nhwc, te, W, 0u, dw, dh);
+  job_shape_jobs(q, jobs, n, [](JobGeom& g, const RoiDesc& j) { g.x = j.x; g.w = j.w; g.h = j.h; g.scx = j.scx; g.scy = j.scy; });
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  RoiArgs t[2];
+  fill_job_tables(p, jobs, n, te, t);
   hipError_t e = hipSuccess;
-  if (ns) {
-    const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), ns);
-    const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &as.e) : lds;  // the strip, then the waves' staging area where both fit
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_strip, (S, D), grid, lds_all, st, as, c, W, dw, dh, dmask, lds); e = hipGetLastError(); });
-    if (e != hipSuccess) return e;
-  }
-  if (ngat) {
-    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, ngat);
-    const uint32_t lds_g = nhwc ? nhwc_stage_plan(te, 0u, 4, &ag.e) : 0u;
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_gather, (S, D), grid, lds_g, st, ag, c, dw, dh, dmask); e = hipGetLastError(); });
+  for (int k = 0; k < p.nd && e == hipSuccess; k++) {  // staged first; its error returns before the per-tap launch
+    const JobDispatch& d = p.d[k];
+    const dim3 grid(d.gx, d.gy, d.n);
+    const uint32_t lds_all = job_launch_lds(d, te, t[k]);
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) {
+      if (d.form == JF_ROI_STRIP) VPF_LAUNCH_T(k_roi_strip, (S, D), grid, lds_all, st, t[k], c, W, dw, dh, p.dmask, d.lds);
+      else VPF_LAUNCH_T(k_roi_gather, (S, D), grid, lds_all, st, t[k], c, dw, dh, p.dmask);
+      e = hipGetLastError();
+    });
   }
   return e;
 }

@@ -123,19 +123,21 @@ __global__ __launch_bounds__(256) void k_roi_dev(const RoiDevArgs args, const Yu
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  No rectangle is known here: the dynamic LDS is the most a staged tile of this destination size can need (roi_dev_lds_bytes: the
-// conversion limit bounds the strip), 0 under VPF_TUNE_NV12_RGB_VARIANT = 9 — no strip fits then, every tile samples per tap.
+// Host side.  No rectangle is known here: job_plan (vpf_job_plan.h) gives the ONE dispatch the most a staged tile of this destination size can need
+// (roi_dev_lds_bytes, vpf_job_bounds.h), nothing under VPF_TUNE_NV12_RGB_VARIANT = 9 — no strip fits then, every tile samples per tap.
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
                                           const TensorEpi& te, bool nhwc) {
-  if (!a.max_n || a.max_n > 65535u || !a.n_frames || a.n_frames > (uint32_t)kRoiDevFrames || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  const uint32_t lds = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9 ? 0u : roi_dev_lds_bytes(dw, dh);
-  a.e = te;
-  const uint32_t lds_all = nhwc ? nhwc_stage_plan(te, lds, 4, &a.e) : lds;  // the strip, then the waves' staging area where both fit
-  const dim3 grid((dw + 255) / 256, (dh + 4 * kRoiBandRows - 1) / (4 * kRoiBandRows), a.max_n);
+  JobShape q;
+  job_shape(q, JOB_ROI, true, src_fc, nhwc, te, W, H, dw, dh);
+  job_shape_dev(q, a.max_n, a.n_frames);
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  const JobDispatch& d = p.d[0];
+  const dim3 grid(d.gx, d.gy, d.n);
+  const uint32_t lds_all = job_launch_lds(d, te, a);  // (sets a.e)
   hipError_t e = hipSuccess;
-  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_dev, (S, D), grid, lds_all, st, a, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
+  with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_roi_dev, (S, D), grid, lds_all, st, a, c, W, H, dw, dh, p.dmask, d.lds); e = hipGetLastError(); });
   return e;
 }
 

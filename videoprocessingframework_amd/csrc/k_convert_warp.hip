@@ -16,8 +16,9 @@
 
 namespace vpf {
 
-// The tile (kWarpTileW x kWarpTileH), the coordinates (warp_xy), a tile's source window and strip (warp_window, warp_strip) and the launcher's bound
-// (warp_need, kWarpStripMax) stand in vpf_job_bounds.h: host, device and the CPU property test (tests/test_job_bounds_cpu.py) share them.
+// The tile (kWarpTileW x kWarpTileH), the coordinates (warp_xy), a tile's source window and strip (warp_window, warp_strip) and the bound of a job's
+// strip (warp_need, kWarpStripMax) stand in vpf_job_bounds.h: host, device and the CPU property test (tests/test_job_bounds_cpu.py) share them; the
+// launch policy that applies the bound is job_plan (vpf_job_plan.h).
 
 // warp_rep, warp_border, warp_store4, warp_gather4 (the per-tap form of a lane's four pixels) and warp_strip_tile (the staged form of a workgroup's
 // tile) stand in k_convert_warp_common.h: the device-table kernel (k_convert_warp_dev.hip) runs them too.
@@ -41,27 +42,29 @@ __global__ __launch_bounds__(256) void k_warp_gather(const WarpArgs args, const 
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side.  The dynamic LDS of a dispatch is an UPPER BOUND of every tile's strip, from the matrix alone, O(1) per job: warp_need and the
-// policy's limit kWarpStripMax, vpf_job_bounds.h.
+// Host side: fill the shape, ask job_plan (vpf_job_plan.h: the cap, staged or per tap per job — warp_need against kWarpStripMax, vpf_job_bounds.h —,
+// the tile grid, the strip's bytes), fill the two tables from it and launch what it names.
 // ------------------------------------------------------------------------------------------
 hipError_t launch_convert_warp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const WarpDesc* jobs, uint32_t dw,
                                uint32_t dh, const TensorEpi& te, bool nhwc) {
-  if (!n || n > (uint32_t)kWarpBatch || !job_src_ok(src_fc)) return hipErrorInvalidValue;
-  const uint32_t dmask = job_dmask(te, nhwc);
-  WarpArgs as, ag;
-  const JobSplit sp = split_jobs(jobs, n, te, as, ag, [&](const WarpDesc& j) {
-    const WarpNeed need = warp_need(j.m, W, H, dw, dh);
-    return need.bytes <= kWarpStripMax ? need.bytes : kNotStaged;
-  });
-  const uint32_t ns = sp.ns, ngat = sp.ngat, lds = sp.lds;
-  const uint32_t gx = (dw + kWarpTileW - 1) / kWarpTileW, gy = (dh + kWarpTileH - 1) / kWarpTileH;
+  JobShape q;
+  job_shape(q, JOB_WARP, false, src_fc, nhwc, te, W, H, dw, dh);
+  job_shape_jobs(q, jobs, n, [](JobGeom& g, const WarpDesc& j) { for (int k = 0; k < 6; k++) g.m[k] = j.m[k]; });
+  const JobPlan p = job_plan(q);
+  if (!p.ok) return hipErrorInvalidValue;
+  WarpArgs t[2];
+  fill_job_tables(p, jobs, n, te, t);
   hipError_t e = hipSuccess;
-  if (ns) {
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_warp_strip, (S, D), dim3(gx, gy, ns), lds, st, as, c, W, H, dw, dh, dmask, lds); e = hipGetLastError(); });
-    if (e != hipSuccess) return e;
+  for (int k = 0; k < p.nd && e == hipSuccess; k++) {  // staged first; its error returns before the per-tap launch
+    const JobDispatch& d = p.d[k];
+    const dim3 grid(d.gx, d.gy, d.n);
+    const uint32_t lds_all = job_launch_lds(d, te, t[k]);
+    with_src_dst(src_fc, nhwc, [&](auto S, auto D) {
+      if (d.form == JF_WARP_STRIP) VPF_LAUNCH_T(k_warp_strip, (S, D), grid, lds_all, st, t[k], c, W, H, dw, dh, p.dmask, d.lds);
+      else VPF_LAUNCH_T(k_warp_gather, (S, D), grid, lds_all, st, t[k], c, W, H, dw, dh, p.dmask);
+      e = hipGetLastError();
+    });
   }
-  if (ngat)
-    with_src_dst(src_fc, nhwc, [&](auto S, auto D) { VPF_LAUNCH_T(k_warp_gather, (S, D), dim3(gx, gy, ngat), 0u, st, ag, c, W, H, dw, dh, dmask); e = hipGetLastError(); });
   return e;
 }
 

@@ -1,8 +1,9 @@
 // k_job_launch.h — the host side the fused tensor launchers share (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip,
 // their device-table forms, the convert and relayout launchers of k_yuv2rgb.hip, k_rgb2yuv.hip and k_relayout.hip, the whole-frame launch_convert_resize and the
-// plain launch_resize_planned): the argument check, the destination alignment mask, the frame table's alignment bits, the run-time -> template-argument
-// dispatch, the launch of the instantiation it picked and the split of a host job table into its staged and its per-tap dispatch.  Inline functions, function templates over
-// callables and two launch macros: nothing is type-erased and nothing allocates, so a launcher compiles to what it was when this stood in it.
+// plain launch_resize_planned): the frame table's alignment bits, the run-time -> template-argument dispatch, the launch of the instantiation it picked
+// and, for the eight per-job launchers, what they share around job_plan (vpf_job_plan.h, where the policy stands: caps, staged or per tap, grids, LDS,
+// the alignment mask): filling the shape, filling the two zeroed job tables from the plan's per-job assignment, and the channels-last staging of a
+// dispatch.  Inline functions, function templates over callables and two launch macros: nothing is type-erased and nothing allocates.
 #ifndef VPF_K_JOB_LAUNCH_H_
 #define VPF_K_JOB_LAUNCH_H_
 #include <cstdio>
@@ -11,14 +12,9 @@
 
 #include "vpf_convert_plan.h"
 #include "vpf_internal.h"
+#include "vpf_job_plan.h"
 
 namespace vpf {
-
-inline bool job_src_ok(int src_fc) { return src_fc == FC_NV12 || src_fc == FC_YUV420 || src_fc == FC_P16; }
-
-// 4 px x element size per lane and plane: what the vector stores need (one interleaved plane: 16 B).  (`dtype` is compared whole: kEpiSwapRB is only
-// ever set for a channels-last destination, where the mask is 15 whatever the dtype — masking with kEpiDtypeMask first gives the same result.)
-inline uint32_t job_dmask(const TensorEpi& te, bool nhwc) { return nhwc || te.dtype == VPF_TENSOR_F32 ? 15u : 7u; }
 
 // f(SRC, DST): the source class and the destination layout as std::integral_constant<int, ...>, usable as template arguments
 template <class F>
@@ -156,30 +152,38 @@ inline ConvertShape convert_shape(int kind, int src, int dst, uint32_t w, uint32
   return q;
 }
 
-// The split of a host job table: `staged_bytes(job)` returns the dynamic LDS the job's strip needs, or kNotStaged for a job that samples per tap
-// (every job under VPF_TUNE_NV12_RGB_VARIANT = 9).  Fills the two zeroed tables — entries beyond a table's jobs are never read: blockIdx.z runs
-// over its jobs — and returns their job counts and the largest strip of the staged one.
-constexpr uint32_t kNotStaged = ~0u;
-struct JobSplit {
-  uint32_t ns, ngat, lds;
-};
-template <class Args, class Desc, class Need>
-inline JobSplit split_jobs(const Desc* jobs, uint32_t n, const TensorEpi& te, Args& as, Args& ag, Need&& staged_bytes) {
-  const bool all_gather = tuning(VPF_TUNE_NV12_RGB_VARIANT) == 9;
-  std::memset(&as, 0, sizeof(as));
-  std::memset(&ag, 0, sizeof(ag));
-  as.e = ag.e = te;
-  JobSplit s{0u, 0u, 0u};
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t bytes = all_gather ? kNotStaged : staged_bytes(jobs[i]);
-    if (bytes != kNotStaged) {
-      as.j[s.ns++] = jobs[i];
-      s.lds = bytes > s.lds ? bytes : s.lds;
-    } else {
-      ag.j[s.ngat++] = jobs[i];
-    }
-  }
-  return s;
+// ---- the per-job tensor launches (k_convert_roi.hip, k_convert_letterbox.hip, k_convert_warp.hip, k_convert_persp.hip and their _dev forms)
+// What job_plan (vpf_job_plan.h) looks at, less the jobs: the knob is read HERE, once per launcher call
+inline void job_shape(JobShape& q, int family, bool dev, int src_fc, bool nhwc, const TensorEpi& te, uint32_t W, uint32_t H, uint32_t dw, uint32_t dh) {
+  q.family = family; q.dev = dev; q.src_fc = src_fc; q.nhwc = nhwc; q.dtype = te.dtype;
+  q.W = W; q.H = H; q.dw = dw; q.dh = dh;
+  q.variant = tuning(VPF_TUNE_NV12_RGB_VARIANT);
+  q.n = q.max_n = q.n_frames = 0u; q.max_step = 0.f;
+}
+// ... a host table's jobs: geom(JobGeom&, const Desc&) copies the members the family's policy reads (a table beyond the largest cap is refused by
+// the plan, which then looks at no job)
+template <class Desc, class F>
+inline void job_shape_jobs(JobShape& q, const Desc* jobs, uint32_t n, F&& geom) {
+  q.n = n;
+  for (uint32_t i = 0; i < n && i < kJobTableMax; i++) geom(q.g[i], jobs[i]);
+}
+// ... a device table's counts and, for the two warps, the caller's hint
+inline void job_shape_dev(JobShape& q, uint32_t max_n, uint32_t n_frames, float max_step = 0.f) { q.max_n = max_n; q.n_frames = n_frames; q.max_step = max_step; }
+// The two zeroed tables of a host-table call, t[k] for dispatch k of the plan: every job goes behind the earlier jobs of its dispatch.  Entries
+// beyond a table's jobs are never read: blockIdx.z runs over its jobs.
+template <class Args, class Desc>
+inline void fill_job_tables(const JobPlan& p, const Desc* jobs, uint32_t n, const TensorEpi& te, Args (&t)[2]) {
+  std::memset(t, 0, sizeof(t));
+  t[0].e = t[1].e = te;
+  uint32_t cnt[2] = {0u, 0u};
+  for (uint32_t i = 0; i < n; i++) t[p.which[i]].j[cnt[p.which[i]]++] = jobs[i];
+}
+// The epilogue a dispatch passes (args.e) and the dynamic LDS it asks for: the strip, then — where the plan names a pixel count and both fit — the
+// waves' channels-last staging area (nhwc_stage_plan, vpf_internal.h)
+template <class Args>
+inline uint32_t job_launch_lds(const JobDispatch& d, const TensorEpi& te, Args& args) {
+  args.e = te;
+  return d.stage_npx ? nhwc_stage_plan(te, d.lds, d.stage_npx, &args.e) : d.lds;
 }
 
 }  // namespace vpf

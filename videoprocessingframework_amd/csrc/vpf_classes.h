@@ -1,5 +1,5 @@
 // vpf_classes.h — the format classes, frame-table sizes and resize-kernel constants both the launchers and kernels (vpf_internal.h) and the
-// HIP-free planning headers (vpf_fused_plan.h, vpf_resize_plan.h, compiled with plain g++ by the CPU tests) name.  No HIP in here.
+// HIP-free planning headers (vpf_fused_plan.h, vpf_resize_plan.h, vpf_job_plan.h, compiled with plain g++ by the CPU tests) name.  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -8,6 +8,10 @@ namespace vpf {
 // frames per frame table: the small and the large one (the tables themselves, and why there are two: vpf_internal.h)
 constexpr int kSmallBatch = 32;
 constexpr int kMaxBatch = 128;
+// jobs per job table of the per-job tensor entries and frames per device-table call (the tables, and why these sizes: vpf_internal.h; the launch
+// policy that refuses above them: vpf_job_plan.h)
+constexpr int kRoiBatch = 96, kLetterboxBatch = 82, kWarpBatch = 96, kPerspBatch = 82;
+constexpr int kRoiDevFrames = 128;
 
 enum FmtClass : int {
   FC_NV12 = 0,    // Y + interleaved UV, 4:2:0

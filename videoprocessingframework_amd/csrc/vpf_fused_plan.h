@@ -70,7 +70,7 @@ inline FusedPlan fused_plan(const FusedShape& q) {
   p.stage_npx = 4;
   auto all_aligned = [](uint64_t bits, uint32_t mask) { return (bits & mask) == 0; };
   // destination alignment the vector stores need: 4 px x element size per lane and plane (1-B elements: the 8-bit classes)
-  const uint32_t dmask = nhwc ? 15u : dst_fc == FC_TENSOR ? (q.dtype == VPF_TENSOR_F32 ? 15u : 7u) : 3u;
+  const uint32_t dmask = tens ? vpf_tensor_dmask(nhwc, q.dtype == VPF_TENSOR_F32) : 3u;
   p.vec_ok = all_aligned(q.dst_bits, dmask);
   // strip bytes a wave of the per-tap LDS kernels needs per source row (0 under variant 9, the forced generic form, and for an unaligned
   // source).  The launcher's lds_strip_bytes looked at frame 0's luma plane only; `rowb` is consumed under lds_ok alone —

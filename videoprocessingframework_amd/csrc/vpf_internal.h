@@ -108,7 +108,8 @@ struct BatchArgsTE {
 // The job table of a multi-ROI launch (vpf_convert_resize_tensor_rois, k_convert_roi.hip): per job the planes of the WHOLE source frame and
 // of the destination, the rectangle in luma pixels of the frame, and the job's own scale factors (computed on the host as every launcher
 // does: (float)w / (float)dw).  96 jobs x 96 B + the epilogue = the 9 248 B of BatchArgsTE<kMaxBatch>, the largest argument block measured.
-constexpr int kRoiBatch = 96;
+// (kRoiBatch = 96, kLetterboxBatch = 82, kWarpBatch = 96, kPerspBatch = 82, kRoiDevFrames = 128: vpf_classes.h — the HIP-free launch policy of these
+// tables, vpf_job_plan.h, names them too)
 struct RoiDesc {
   FrameDesc f;
   uint32_t x, y, w, h;
@@ -123,7 +124,6 @@ static_assert(sizeof(RoiDesc) == 96 && sizeof(RoiArgs) <= sizeof(BatchArgsTE<kMa
 // The arguments of a multi-ROI launch whose rectangles live in DEVICE memory (vpf_convert_resize_tensor_rois_dev, k_convert_roi_dev.hip): no job
 // table — the source planes of up to 128 frames (40 B each), where the boxes and their count lie, and job 0's destination planes with the stride
 // from job to job.  The kernel reads (frame, x, y, w, h) of job blockIdx.z when it runs.  5 224 B, below the largest argument block.
-constexpr int kRoiDevFrames = 128;
 struct FrameSrcDesc {
   const uint8_t* s[3];
   uint32_t sp[3];
@@ -148,7 +148,6 @@ static_assert(sizeof(FrameSrcDesc) == 40 && sizeof(RoiDevArgs) == 128 * 40 + 104
 // run to 65536 — it would keep 96 jobs per table at the price of an unpack per field in every wave; a call of 96 jobs then takes two tables
 // instead of one, which the job-table test crosses either way.)  The three pad bytes (kernel channel order R G B) travel in TensorEpi::pad:
 // pad = pad[0] | pad[1] << 8 | pad[2] << 16, bits 24 .. 31 zero.  The NHWC staging plan lives in TensorEpi::dtype (nhwc_stage_plan): no collision.
-constexpr int kLetterboxBatch = 82;
 struct LetterboxDesc {
   RoiDesc r;
   uint32_t ix, iy, iw, ih;
@@ -182,7 +181,6 @@ static_assert(sizeof(LetterboxDevArgs) == 128 * 40 + 120 && sizeof(LetterboxDevA
 // destination and the inverse matrix m = (m00 m01 m02; m10 m11 m12), destination pixel -> source coordinates in luma pixels.  96 B like RoiDesc,
 // so the same 96 jobs per table.  The three border bytes (kernel channel order R G B) and the border mode travel in TensorEpi::pad:
 // pad = border[0] | border[1] << 8 | border[2] << 16 | mode << 24.
-constexpr int kWarpBatch = 96;
 struct WarpDesc {
   FrameDesc f;
   float m[6];
@@ -196,7 +194,6 @@ static_assert(sizeof(WarpDesc) == 96 && sizeof(WarpArgs) <= sizeof(BatchArgsTE<k
 // The job table of a multi-ROI perspective warp (vpf_convert_persp_tensor, k_convert_persp.hip): WarpDesc with the inverse 3 x 3 matrix
 // m = (m00 m01 m02; m10 m11 m12; m20 m21 m22).  72 + 36 B, 112 with the tail padding of the pointers' alignment: 82 jobs per table, the letterbox
 // table's 9 216 B.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
-constexpr int kPerspBatch = 82;
 struct PerspDesc {
   FrameDesc f;
   float m[9];
@@ -265,6 +262,7 @@ hipError_t launch_remap_batch(hipStream_t st, uint32_t sw, uint32_t sh, const fl
 // dst_fc == FC_TENSOR / FC_TENSOR_NHWC take `te` (the element size sets the destination alignment tests); every other class ignores it
 hipError_t launch_convert_resize(hipStream_t st, int src_fc, int dst_fc, const Yuv2RgbCoef& c, uint32_t sw,
                                  uint32_t sh, uint32_t n, const BatchArgsL& a, uint32_t dw, uint32_t dh, const TensorEpi* te = nullptr);
+// The eight per-job launchers below dispatch on job_plan (vpf_job_plan.h): refusals, staged or per tap, grids and LDS are stated there.
 // n <= kRoiBatch jobs on frames `W` pixels wide -> FC_TENSOR planes of dw x dh: at most two dispatches (staged jobs, gather jobs); k_convert_roi.hip
 // (nhwc: FC_TENSOR_NHWC planes, one per job, here and in launch_convert_warp)
 hipError_t launch_convert_resize_rois(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const RoiDesc* jobs, uint32_t dw,

@@ -2,6 +2,8 @@
 // and device) and plain g++ compile as it stands, so that the launchers, the kernels and a CPU property test (tests/test_job_bounds_cpu.py
 // through tests/c/job_bounds_capi.cpp) use the SAME code.  The sibling of vpf_plan_bounds.h, for the same reason: a bound that is one byte
 // or one row short is silent — k_roi_strip returns without writing, k_warp_strip blends from the wrong texels.
+// How the eight launches COMBINE these — which bound decides which job, the caps, the grids, which figure goes to the kernel and which to the launch
+// — is job_plan (vpf_job_plan.h, tests/test_job_plan_cpu.py); this header holds what a job or a tile needs.
 //   ROI   roi_strip_need: the largest workgroup strip of a job, WALKED with the kernel's own fp32 tap arithmetic, and the policy's two limits
 //   letterbox  letterbox_strip_need: the same walk over tiles laid on the destination plane and clipped to the picture (k_convert_letterbox.hip;
 //         tests/test_letterbox_bounds_cpu.py through tests/c/letterbox_bounds_capi.cpp)
@@ -24,8 +26,8 @@
 #define VPF_JB_HD __host__ __device__ __forceinline__
 #define VPF_JB_HDI __host__ __device__ __forceinline__
 #else
-#define VPF_JB_HD
-#define VPF_JB_HDI inline  // (functions a translation unit may leave unused: no warning under -Wall)
+#define VPF_JB_HD inline  // (a translation unit may leave any of them unused — vpf_job_plan.h's users do: no warning under -Wall)
+#define VPF_JB_HDI inline
 #endif
 
 // ------------------------------------------------------------------------------------------

@@ -117,4 +117,9 @@ static inline int vpf_bound_lzm_rows_ok_rt(uint32_t sh, uint32_t dh, float scy, 
 static inline int vpf_bound_lzm_rows_ok(uint32_t sh, uint32_t dh, float scy) { return vpf_bound_lzm_rows_ok_rt(sh, dh, scy, 16u); }
 static inline int vpf_bound_lzm_rows_two(uint32_t sh, uint32_t dh, float scy) { return vpf_bound_lzm_rows_within(sh, dh, scy, 16u, 2u); }
 
+/* The destination alignment the vector stores of a tensor launch need, as a mask on pointer | pitch: 4 px x element size per lane and plane — 16 B
+ * for f32 planes, 8 B for f16 / bf16 ones; the one interleaved plane of a channels-last tensor takes 16-B stores whatever the element.  The one
+ * spelling fused_plan (vpf_fused_plan.h) and job_plan (vpf_job_plan.h) share; f32: dtype == VPF_TENSOR_F32. */
+static inline uint32_t vpf_tensor_dmask(int nhwc, int f32) { return nhwc || f32 ? 15u : 7u; }
+
 #endif /* VPF_PLAN_BOUNDS_H_ */
