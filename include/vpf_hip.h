@@ -591,6 +591,55 @@ VPF_API vpf_status vpf_convert_persp_tensor_dev(const vpf_exec* exec, int src_fm
 VPF_API float vpf_persp_max_step(const float m[9], vpf_size dst); /* host only; 0: no bound (also for a null, non-finite or oversized input) */
 
 /*
+ * Fused per-pixel remap -> normalised tensor: vpf_convert_warp_tensor for geometry no matrix describes — lens undistortion, fisheye and
+ * surround-view rigs, rectification, flow-driven warps, stabilisation.  One pass instead of vpf_convert(-> RGB), vpf_remap and a normalise chain.
+ * The call takes `n` jobs.  A job = (the planes of a WHOLE frame of src_size = (W, H), its destination planes, a pair of maps of dst_size).  Many
+ * jobs may name the same frame or the same maps: one camera with a batch of frames shares its maps, a rig gives every camera its own.
+ * For destination pixel (dx, dy):
+ *   sx = xmap[dy][dx], sy = ymap[dy][dx], both fp32, used as loaded (row dy of a map at (char*)map + dy * pitch, dst_size.width floats);
+ *   sx or sy NaN: the pixel takes u8[c] = border[c], unblended, in BOTH border modes (the perspective entry's !(w > 0) rule; calibration tools
+ *        mark invalid pixels this way);
+ *   else exactly vpf_convert_warp_tensor from its range test on: VPF_WARP_CONSTANT's test (-0.0 is in range, +-inf out of range),
+ *        VPF_WARP_REPLICATE's max-then-min (+-inf goes to the edge), the sampling x0 = (int)sx, x1 = min(x0 + 1, W - 1), fx = sx - (float)x0,
+ *        every texel converted with vpf_convert's arithmetic and chroma read at (x >> 1, y >> 1), u8 = trunc(fma(fy, bot - top, top) + 0.5), the
+ *        epilogue, dtype, VPF_TENSOR_BGR, VPF_TENSOR_NHWC and the narrowing of P10 / P12.
+ * Equivalently u8 is the byte vpf_remap(RGB) writes when its source is vpf_convert(frame -> RGB), its maps are these maps — clamped first under
+ * REPLICATE, NaN staying NaN — and its destination was pre-filled with `border`.  On maps written as sx = (m00 dx + m01 dy) + m02 (sy likewise)
+ * the output is bit for bit vpf_convert_warp_tensor's for that matrix.  Every element of every job's planes is written exactly once, nothing
+ * else is written (vpf_remap leaves out-of-range pixels untouched; a fresh tensor has nothing to keep, hence the border).
+ * The maps are DEVICE data: the kernel reads them when it runs on exec->stream, the host never dereferences them, and under stream capture they
+ * are read at every replay (a flow field rewritten between replays is legal).  Whatever the maps hold, the call returns VPF_OK and no byte
+ * outside a frame is read: the kernel makes every coordinate safe before it becomes an index (csrc/k_convert_remap.hip).
+ * `jobs` is a HOST array, consumed before return; 96 jobs travel per job table, one dispatch per table over (32 x 32 destination tiles, jobs):
+ * every workgroup merges the taps of its tile's in-range pixels into the tile's exact source window and decides for itself — the border, the
+ * window converted once into LDS, or four conversions per pixel (identical bits).
+ * max_step is vpf_convert_warp_tensor_dev's LDS hint: a bound on the source pixels per destination pixel step of the maps,
+ * |d sx / d dx| + |d sx / d dy| and the same for sy.  The dispatch takes the LDS that covers every tile of such maps, at most 64 KiB;
+ * max_step == 0: no hint, 64 KiB.  Never a correctness input: a tile whose window outgrows the LDS it was given is sampled per tap, with
+ * identical bits.
+ * opts == NULL means VPF_WARP_CONSTANT with border 0 0 0 and no hint.  Checked on the host before any device access, with the warp entry's list
+ * and answers: unsupported format / matrix / dtype / flag / border mode: VPF_ERR_UNSUPPORTED; null pointers, n == 0, bad sizes, short pitches,
+ * misaligned planes, non-finite scale / bias, non-zero reserved fields (the planes', opts->reserved, opts->reserved2), a null xmap / ymap, a map
+ * pointer or pitch that is not a multiple of 4, a map pitch below 4 * dst_size.width, a max_step that is negative or not finite: VPF_ERR_BAD_ARG.
+ */
+typedef struct vpf_remap_io {
+  vpf_plane src[3];     /* the WHOLE frame's planes (NV12, YUV420, P10, P12) */
+  vpf_plane dst[3];     /* three planes; one interleaved plane with VPF_TENSOR_NHWC */
+  const float* xmap;    /* DEVICE: row dy at (char*)xmap + dy * xmap_pitch, dst_size.width floats */
+  const float* ymap;    /* DEVICE, likewise */
+  uint32_t xmap_pitch, ymap_pitch; /* bytes */
+} vpf_remap_io;         /* 120 bytes, no implicit padding */
+typedef struct vpf_remap_opts {
+  uint32_t border_mode; /* VPF_WARP_CONSTANT | VPF_WARP_REPLICATE */
+  uint8_t border[3];    /* per OUTPUT channel */
+  uint8_t reserved;     /* 0 */
+  float max_step;       /* LDS hint, 0 = none */
+  uint32_t reserved2;   /* 0 */
+} vpf_remap_opts;       /* 16 bytes */
+VPF_API vpf_status vpf_convert_remap_tensor(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size, vpf_size dst_size,
+                                            uint32_t n, const vpf_remap_io* jobs, const vpf_tensor_norm* norm, const vpf_remap_opts* opts);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

@@ -717,6 +717,161 @@ def homographies_max_step(matrices, dw, dh) -> float:
     return best
 
 
+def _check_map(fn, name, m, w, h):
+    """one coordinate map of remap_to_normalized_tensor: a device float32 tensor [h, w] or [N, h, w] with unit stride along its rows"""
+    if not isinstance(m, torch.Tensor) or not m.is_cuda:
+        raise ValueError(f"{fn}: {name} must be a device tensor (the kernel reads the maps from device memory)")
+    if m.dtype != torch.float32 or m.dim() not in (2, 3) or tuple(m.shape[-2:]) != (h, w):
+        raise ValueError(f"{fn}: {name} must be torch.float32 of shape [{h}, {w}] or [N, {h}, {w}], got {m.dtype} {tuple(m.shape)}")
+    if (w > 1 and m.stride(-1) != 1) or (h > 1 and m.stride(-2) < w):
+        raise ValueError(f"{fn}: {name} needs unit stride along its rows and a row stride of at least {w}, got strides {m.stride()}")
+
+
+def remap_to_normalized_tensor(resizer, surfaces, xmap, ymap, mean, std, max_step=None, dtype=torch.float32, bgr=False, border=(0, 0, 0),
+                               border_mode="constant", out=None, cc_ctx=None, channels_last=False) -> torch.Tensor:
+    """N NV12 / YUV420 (or P10 / P12) surfaces, each sampled through a per-pixel coordinate map -> the normalised float tensor [N, 3, dh, dw]: lens
+    undistortion, fisheye and surround-view rigs, rectification, flow-driven warps — one pass instead of convert, remap and a normalise chain
+    (PySurfaceConvertResizer.ExecuteRemapToTensor, vpf_convert_remap_tensor).
+    `xmap`, `ymap`: device torch.float32 tensors [dh, dw] (one pair shared by every surface: one camera, a batch of its frames) or [N, dh, dw] (a pair
+    per surface: a rig, a flow field per frame); last stride 1, any row stride (a slice of a wider tensor works), e.g. undistort_maps(...).  Output
+    pixel (x, y) of frame i samples surfaces[i] at (xmap[y][x], ymap[y][x]) in luma pixels, remap's convention.  A pixel whose coordinate is NaN
+    takes `border` under BOTH border modes (how calibration tools mark invalid pixels); every other pixel outside the surface takes `border`
+    (per output channel, 0..255) under "constant" and the nearest edge pixel under "replicate".
+    `max_step`: a bound on the source pixels per destination pixel step of the maps (maps_max_step, calibrated offline) that sizes the kernel's
+    LDS; None: the 64 KiB default.  It never changes a pixel.
+    The kernel reads the maps when it runs: no synchronisation, no copy to the host, and a captured graph replays with the maps of replay time.
+    This function orders the call behind torch's current stream, where the maps' producer ran.  Normalisation, `out`, channels_last, the returned
+    tensor and the stream ordering: exactly as to_normalized_tensor.
+
+    ValueError for maps on the host or on another device than each other or `out`, another dtype or shape, a border value outside 0..255, an
+    unknown mode, a bad max_step.  N == 0 returns an empty tensor without a launch."""
+    fn = "remap_to_normalized_tensor"
+    if dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"{fn}: dtype must be one of {list(_TENSOR_DTYPES)}")
+    if border_mode not in _WARP_MODES:
+        raise ValueError(f"{fn}: border_mode must be one of {list(_WARP_MODES)}, got {border_mode!r}")
+    try:
+        border = [operator.index(v) for v in border]
+    except TypeError:
+        raise ValueError(f"{fn}: border must hold three integers, got {border!r}") from None
+    if len(border) != 3 or any(not 0 <= v <= 255 for v in border):
+        raise ValueError(f"{fn}: border must hold three values in 0..255, got {border}")
+    if max_step is None:
+        max_step = 0.0
+    max_step = float(max_step)
+    if not (max_step >= 0.0 and max_step < float("inf")):
+        raise ValueError(f"{fn}: max_step must be finite and not negative, got {max_step}")
+    surfaces = list(surfaces)
+    n = len(surfaces)
+    w, h = resizer.DstSize()
+    _check_map(fn, "xmap", xmap, w, h)
+    _check_map(fn, "ymap", ymap, w, h)
+    if xmap.device != ymap.device:
+        raise ValueError(f"{fn}: xmap lives on {xmap.device}, ymap on {ymap.device}")
+    if xmap.dim() != ymap.dim():
+        raise ValueError(f"{fn}: xmap and ymap must both be shared [{h}, {w}] or both per frame [N, {h}, {w}]")
+    map_stride = 0
+    if xmap.dim() == 3:
+        if xmap.shape[0] != n or ymap.shape[0] != n:
+            raise ValueError(f"{fn}: {n} surfaces need maps of shape [{n}, {h}, {w}], got {tuple(xmap.shape)} and {tuple(ymap.shape)}")
+        if n > 1:
+            if xmap.stride(0) != ymap.stride(0):
+                raise ValueError(f"{fn}: xmap and ymap need the same stride from frame to frame, got {xmap.stride(0)} and {ymap.stride(0)}")
+            map_stride = 4 * xmap.stride(0)
+    if out is not None and isinstance(out, torch.Tensor) and out.is_cuda and out.device != xmap.device:
+        raise ValueError(f"{fn}: out lives on {out.device}, the maps on {xmap.device}")
+    out, s0, s1, s2 = _tensor_out(fn, out, n, h, w, dtype, channels_last, xmap.device)
+    if n == 0:
+        return out
+    elem = out.element_size()
+    with _on_task_stream(resizer, out.device):
+        ok = resizer.ExecuteRemapToTensor(surfaces, xmap.data_ptr(), ymap.data_ptr(), out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean],
+                                          [float(v) for v in std], cc_ctx, bool(bgr), border, _WARP_MODES[border_mode], s2 * elem, s1 * elem, s0 * elem,
+                                          bool(channels_last), 4 * (xmap.stride(-2) if h > 1 else w), 4 * (ymap.stride(-2) if h > 1 else w), map_stride, max_step)
+    if not ok:
+        _refused(fn, _RESIZER_REFUSED)
+    return out
+
+
+def maps_max_step(xmap, ymap) -> float:
+    """The `max_step` hint of remap_to_normalized_tensor for given maps ([dh, dw] or [N, dh, dw], host or device): the maximum over their pixels of
+    |s[y][x + 1] - s[y][x]| + |s[y + 1][x] - s[y][x]| for s = xmap and for s = ymap — the source pixels per destination pixel step —, differences
+    that are not finite (a NaN or an infinity on either side) or that leave the map counting as 0; computed in float64 and rounded UP to float32.
+    0.0 for maps without a finite difference.  It reads the result back, so it SYNCHRONISES on device maps: meant for calibration, offline — pass
+    the largest value seen to remap_to_normalized_tensor."""
+    fn = "maps_max_step"
+    best = 0.0
+    for name, m in (("xmap", xmap), ("ymap", ymap)):
+        m = torch.as_tensor(m)
+        if not m.dtype.is_floating_point or m.dim() not in (2, 3):
+            raise ValueError(f"{fn}: {name} must be a float tensor of shape [dh, dw] or [N, dh, dw], got {m.dtype} {tuple(m.shape)}")
+        if m.numel() == 0:
+            continue
+        s = m.detach().to(torch.float64)
+        step = torch.zeros_like(s)
+        dx = (s[..., :, 1:] - s[..., :, :-1]).abs()
+        dy = (s[..., 1:, :] - s[..., :-1, :]).abs()
+        step[..., :, :-1] += torch.where(torch.isfinite(dx), dx, torch.zeros_like(dx))
+        step[..., :-1, :] += torch.where(torch.isfinite(dy), dy, torch.zeros_like(dy))
+        best = max(best, float(step.max()))
+    r = torch.tensor(best, dtype=torch.float64).to(torch.float32)
+    if float(r) < best:
+        r = torch.nextafter(r, torch.tensor(float("inf"), dtype=torch.float32))
+    return float(r)
+
+
+def undistort_maps(camera_matrix, dist_coeffs, size, new_camera_matrix=None, device=None):
+    """The (xmap, ymap) pair remap_to_normalized_tensor takes to undistort a camera: float32 tensors [dh, dw] on `device` for size = (dw, dh), from the
+    Brown-Conrady model with dist_coeffs = (k1, k2, p1, p2[, k3]).  For destination pixel (u, v), with (fx', fy', cx', cy') from new_camera_matrix
+    (default: camera_matrix) and (fx, fy, cx, cy) from camera_matrix (3 x 3: fx = [0][0], fy = [1][1], cx = [0][2], cy = [1][2]):
+      x = (u - cx') / fx',  y = (v - cy') / fy',  r2 = x^2 + y^2,  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+      xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),  yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y
+      sx = fx xd + cx,  sy = fy yd + cy
+    computed in float64 on the host and rounded to float32 once.  ValueError for another shape, a non-finite value, fx' or fy' of 0."""
+    fn = "undistort_maps"
+    import numpy as np
+
+    def host64(v):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        return torch.from_numpy(np.array(v, dtype=np.float64))
+
+    K = host64(camera_matrix)
+    Kn = K if new_camera_matrix is None else host64(new_camera_matrix)
+    d = host64(dist_coeffs).reshape(-1)
+    if tuple(K.shape) != (3, 3) or tuple(Kn.shape) != (3, 3):
+        raise ValueError(f"{fn}: camera matrices must have shape [3, 3], got {tuple(K.shape)} and {tuple(Kn.shape)}")
+    if d.numel() not in (4, 5):
+        raise ValueError(f"{fn}: dist_coeffs must hold (k1, k2, p1, p2) or (k1, k2, p1, p2, k3), got {d.numel()} values")
+    if not bool(torch.isfinite(K).all() and torch.isfinite(Kn).all() and torch.isfinite(d).all()):
+        raise ValueError(f"{fn}: camera matrices and dist_coeffs must be finite")
+    try:
+        dw, dh = (operator.index(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: size must be (dw, dh), two integers") from None
+    if not (1 <= dw <= 65536 and 1 <= dh <= 65536):
+        raise ValueError(f"{fn}: dw and dh must lie in 1 .. 65536, got {(dw, dh)}")
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    fxn, fyn, cxn, cyn = float(Kn[0, 0]), float(Kn[1, 1]), float(Kn[0, 2]), float(Kn[1, 2])
+    if fxn == 0.0 or fyn == 0.0:
+        raise ValueError(f"{fn}: the focal lengths of the new camera matrix must not be 0")
+    k1, k2, p1, p2 = (float(v) for v in d[:4])
+    k3 = float(d[4]) if d.numel() == 5 else 0.0
+    u = torch.arange(dw, dtype=torch.float64)[None, :]
+    v = torch.arange(dh, dtype=torch.float64)[:, None]
+    x = ((u - cxn) / fxn).expand(dh, dw)
+    y = ((v - cyn) / fyn).expand(dh, dw)
+    r2 = x * x + y * y
+    rad = 1.0 + k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2)
+    xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * (x * x))
+    yd = y * rad + p1 * (r2 + 2.0 * (y * y)) + 2.0 * p2 * x * y
+    sx = (fx * xd + cx).to(torch.float32).contiguous()
+    sy = (fy * yd + cy).to(torch.float32).contiguous()
+    if device is not None:
+        sx, sy = sx.to(device), sy.to(device)
+    return sx, sy
+
+
 def _dst_rects_list(dst_rects, n, w, h, fn):
     """dst_rects -> list of n 4-tuples of Python ints inside the w x h destination: ValueError for a device tensor, a non-integer dtype, another
     length than the rois', an empty rectangle or one that leaves the destination"""

@@ -33,6 +33,7 @@ EXPORTS = [
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
     "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
     "vpf_convert_persp_tensor", "vpf_convert_letterbox_tensor_dev", "vpf_convert_persp_tensor_dev", "vpf_persp_max_step",
+    "vpf_convert_remap_tensor",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -85,6 +86,17 @@ class WarpOpts(C.Structure):
 
 
 WARP_CONSTANT, WARP_REPLICATE = 0, 1
+
+
+class RemapIO(C.Structure):
+    """vpf_remap_io: one job of vpf_convert_remap_tensor — the WHOLE source frame's planes, the destination planes, the job's two coordinate maps
+    (DEVICE addresses) and their pitches in bytes"""
+    _fields_ = [("src", Plane * 3), ("dst", Plane * 3), ("xmap", C.c_void_p), ("ymap", C.c_void_p), ("xmap_pitch", C.c_uint32), ("ymap_pitch", C.c_uint32)]
+
+
+class RemapOpts(C.Structure):
+    """vpf_remap_opts: vpf_warp_opts plus the LDS hint (0: none)"""
+    _fields_ = [("border_mode", C.c_uint32), ("border", C.c_uint8 * 3), ("reserved", C.c_uint8), ("max_step", C.c_float), ("reserved2", C.c_uint32)]
 
 
 class LetterboxIO(C.Structure):
@@ -231,6 +243,7 @@ def lib() -> C.CDLL:
                                                   C.POINTER(WarpOpts)]
         L.vpf_convert_persp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(PerspsDev), PN,
                                                    C.POINTER(WarpOpts)]
+        L.vpf_convert_remap_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(RemapIO), PN, C.POINTER(RemapOpts)]
         L.vpf_persp_max_step.argtypes = [C.POINTER(C.c_float), Size]
         L.vpf_persp_max_step.restype = C.c_float
         L.vpf_convert_letterbox_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(LetterboxDev), PN,
@@ -486,6 +499,39 @@ def convert_warp_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, warps, norm: 
                                        C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
     if check:
         _check(st, "vpf_convert_warp_tensor")
+    return st
+
+
+def make_remap_jobs(jobs) -> "C.Array[RemapIO]":
+    """jobs: list of (src_desc, dst_desc, (xmap_ptr, xmap_pitch), (ymap_ptr, ymap_pitch)) with desc as in planes(); src_desc = the planes of the WHOLE
+    frame, the map pointers DEVICE addresses of float32 rows, the pitches in bytes"""
+    arr = (RemapIO * len(jobs))()
+    for i, (s, d, xm, ym) in enumerate(jobs):
+        s, d = planes(s), planes(d)
+        for k in range(3):
+            arr[i].src[k].ptr, arr[i].src[k].pitch = s[k].ptr, s[k].pitch
+            arr[i].dst[k].ptr, arr[i].dst[k].pitch = d[k].ptr, d[k].pitch
+        arr[i].xmap, arr[i].xmap_pitch = xm[0] or None, xm[1]
+        arr[i].ymap, arr[i].ymap_pitch = ym[0] or None, ym[1]
+    return arr
+
+
+def make_remap_opts(border_mode=WARP_CONSTANT, border=(0, 0, 0), max_step=0.0) -> RemapOpts:
+    o = RemapOpts()
+    o.border_mode, o.max_step = border_mode, max_step
+    for k in range(3):
+        o.border[k] = border[k]
+    return o
+
+
+def convert_remap_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, jobs, norm: TensorNorm, opts: RemapOpts = None, n=None, check=True) -> int:
+    """jobs: RemapIO array from make_remap_jobs(); every job sampled through its pair of device maps into dw x dh and normalised, 96 jobs per job
+    table; the kernel reads the maps when it runs on ex.stream: no sync, no copy, capturable"""
+    st = lib().vpf_convert_remap_tensor(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                        (len(jobs) if jobs is not None else 0) if n is None else n, jobs,
+                                        C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_remap_tensor")
     return st
 
 

@@ -405,6 +405,33 @@ public:
                                                              (const void*)(uintptr_t)rects, rect_stride, max_n, (const void*)(uintptr_t)count, planes.data(),
                                                              job_stride, norm, &opts, cc.get());
   }
+  // additive: n surfaces, each through a per-pixel map pair -> a normalised planar tensor [n, 3, dh, dw] at device address `dst`
+  // (vpf_convert_remap_tensor): frame i comes from src[i] through the float32 maps at xmap + i map_stride / ymap + i map_stride (DEVICE addresses;
+  // map_stride 0: one pair for every frame; a pitch of 0: tight rows of dw floats), read by the kernel when it runs on the task's stream.  A NaN
+  // coordinate takes the border in both modes.  max_step: the LDS hint (0: none).  border, border_mode, tensor layout and mean / std as
+  // ExecuteWarpsToTensor
+  bool ExecuteRemapToTensor(const std::vector<std::shared_ptr<Surface>>& src, uint64_t xmap, uint64_t ymap, uint64_t dst, uint32_t dtype,
+                            const std::vector<double>& mean, const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr,
+                            const std::array<int64_t, 3>& border, uint32_t border_mode, uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride,
+                            bool channels_last, uint32_t xmap_pitch, uint32_t ymap_pitch, uint64_t map_stride, float max_step) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (src.empty() || !xmap || !ymap || !dst) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, src.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    vpf_remap_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    opts.border_mode = border_mode;
+    opts.max_step = max_step;
+    for (int c = 0; c < 3; c++) {
+      if (border[c] < 0 || border[c] > 255) return false;
+      opts.border[c] = (uint8_t)border[c];
+    }
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    return TASK_EXEC_SUCCESS == task_->RunTensorRemap(a.data(), (uint32_t)a.size(), (const void*)(uintptr_t)xmap, xmap_pitch ? xmap_pitch : 4u * task_dst_w_,
+                                                      (const void*)(uintptr_t)ymap, ymap_pitch ? ymap_pitch : 4u * task_dst_w_, map_stride, planes.data(), norm,
+                                                      &opts, cc.get());
+  }
   size_t GetStream() const { return (size_t)task_->GetStream(); }
   uint32_t task_dst_w_ = 0, task_dst_h_ = 0;
 };
@@ -970,6 +997,17 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "0 = contiguous).  The kernel reads boxes, placements and count when it runs on the task's stream: no sync, no copy to the host, capturable.  "
            "An invalid box or placement gives a frame of the normalised pad; frames at or behind the count are not written.  At most 128 surfaces; one "
            "dispatch.  ValueError for a bad pad")
+      .def("ExecuteRemapToTensor", &PySurfaceConvertResizer::ExecuteRemapToTensor, py::arg("surfaces"), py::arg("xmap_ptr"), py::arg("ymap_ptr"), py::arg("ptr"),
+           py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("border") = std::array<int64_t, 3>{0, 0, 0}, py::arg("border_mode") = 0u, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,
+           py::arg("frame_stride") = 0, py::arg("channels_last") = false, py::arg("xmap_pitch") = 0u, py::arg("ymap_pitch") = 0u, py::arg("map_stride") = 0,
+           py::arg("max_step") = 0.0f, py::call_guard<py::gil_scoped_release>(),
+           "Per-pixel remap of the surfaces: frame i of a planar tensor [n, 3, dh, dw] at device address ptr (strides in bytes, 0 = contiguous) is "
+           "surfaces[i] sampled at (xmap[y][x], ymap[y][x]) — float32 maps of the task's destination size in DEVICE memory at xmap_ptr / ymap_ptr + "
+           "i map_stride (0 = every frame shares one pair), rows xmap_pitch / ymap_pitch bytes apart (0 = tight) — and normalised.  The kernel reads the "
+           "maps when it runs on the task's stream: no sync, no copy to the host, capturable.  A NaN coordinate takes the border in both modes.  "
+           "max_step: the caller's bound on the source pixels per destination pixel step of the maps, which sizes the LDS (0 = none); one dispatch per "
+           "96 frames")
       .def("Stream", &PySurfaceConvertResizer::GetStream, "the hipStream_t every Execute* launches on (as an integer)")
       .def("DstSize", [](const PySurfaceConvertResizer& r) { return py::make_tuple(r.task_dst_w_, r.task_dst_h_); }, "(width, height) of the output");
 

@@ -719,6 +719,29 @@ TaskExecStatus ConvertResizeSurface::RunTensorLetterboxDev(Surface* const* frame
                                                          fr.data(), &table, &norm, opts);
   return exec_status(st, "letterbox device-resident regions into a tensor");
 }
+TaskExecStatus ConvertResizeSurface::RunTensorRemap(Surface* const* ins, uint32_t n, const void* xmap, uint32_t xmap_pitch, const void* ymap, uint32_t ymap_pitch,
+                                                    uint64_t map_stride, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_remap_opts* opts,
+                                                    const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorRemap");
+  if (!ins || !n || !xmap || !ymap || !dst) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(ins, n, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  std::vector<vpf_remap_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(ins[i], io[i].src);
+    tensor_job_planes(dst, i, norm, io[i].dst);
+    io[i].xmap = reinterpret_cast<const float*>(static_cast<const uint8_t*>(xmap) + (uint64_t)i * map_stride);
+    io[i].ymap = reinterpret_cast<const float*>(static_cast<const uint8_t*>(ymap) + (uint64_t)i * map_stride);
+    io[i].xmap_pitch = xmap_pitch;
+    io[i].ymap_pitch = ymap_pitch;
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_remap_tensor(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n, io.data(), &norm,
+                                                 opts);
+  return exec_status(st, "remap surfaces into a tensor");
+}
 HipStream ConvertResizeSurface::GetStream() const { return pImpl->str; }
 
 // ------------------------------------------------------------------------------------------ TensorToSurface

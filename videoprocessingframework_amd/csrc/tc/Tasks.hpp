@@ -102,6 +102,13 @@ public:
   TaskExecStatus RunTensorLetterboxDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride, const void* dst_rects,
                                        uint32_t rect_stride, uint32_t max_n, const void* count, const vpf_plane* dst, uint64_t dst_job_stride,
                                        const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts, const ColorspaceConversionContext* ctx);
+  // n per-pixel remaps of surfaces (vpf_convert_remap_tensor): frame i of the tensor is inputs[i] sampled through the pair of float32 maps at
+  // xmap + i map_stride / ymap + i map_stride (DEVICE memory, rows of the task's destination width xmap_pitch / ymap_pitch bytes apart;
+  // map_stride 0: every frame shares one pair), read by the kernel when it runs on the task's stream — no sync, no copy, capturable.  A pixel whose
+  // coordinate is NaN takes the border in both modes; opts == nullptr: VPF_WARP_CONSTANT with border 0 0 0 and no LDS hint.  dst as RunTensor.
+  TaskExecStatus RunTensorRemap(Surface* const* inputs, uint32_t n, const void* xmap, uint32_t xmap_pitch, const void* ymap, uint32_t ymap_pitch,
+                                uint64_t map_stride, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_remap_opts* opts,
+                                const ColorspaceConversionContext* ctx);
   HipStream GetStream() const;  // the stream every Run* launches on
 
 private:

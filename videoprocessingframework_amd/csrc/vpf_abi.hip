@@ -856,6 +856,50 @@ float vpf_persp_max_step(const float m[9], vpf_size dst) {
   return persp_step(m, dst.width, dst.height);
 }
 
+// Many per-pixel remaps of decoded frames -> one batch of normalised planes (include/vpf_hip.h): the warp entry's checks, then the maps' — their
+// pointers and pitches only: the maps are device data the host never reads —, kRemapBatch jobs per job table, one dispatch each (k_convert_remap.hip).
+static_assert(sizeof(vpf_remap_io) == 120 && offsetof(vpf_remap_io, dst) == 48 && offsetof(vpf_remap_io, xmap) == 96 && offsetof(vpf_remap_io, ymap) == 104 &&
+                  offsetof(vpf_remap_io, xmap_pitch) == 112 && offsetof(vpf_remap_io, ymap_pitch) == 116 && sizeof(vpf_remap_opts) == 16,
+              "vpf_remap_io and vpf_remap_opts have no implicit padding");
+vpf_status vpf_convert_remap_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_remap_io* jobs,
+                                    const vpf_tensor_norm* norm, const vpf_remap_opts* opts) {
+  const Mark mark("vpf_convert_remap_tensor");
+  if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
+  if (const vpf_status refused = norm_status(norm, opts && opts->border_mode > VPF_WARP_REPLICATE,
+                                             opts && (opts->reserved || opts->reserved2 || !(opts->max_step >= 0.f) || !std::isfinite(opts->max_step))))
+    return refused;
+  if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
+  const TensorLayout l = layout_of(*norm);
+  for (uint32_t i = 0; i < n; i++) {
+    const vpf_remap_io& io = jobs[i];
+    if (!io.xmap || !io.ymap || (((uintptr_t)io.xmap | (uintptr_t)io.ymap | io.xmap_pitch | io.ymap_pitch) & 3u) || (uint64_t)io.xmap_pitch < 4ull * ds.width ||
+        (uint64_t)io.ymap_pitch < 4ull * ds.width)
+      return VPF_ERR_BAD_ARG;
+    if (!tensor_src_ok(sf, ss.width, io.src, true)) return VPF_ERR_BAD_ARG;
+    if (!tensor_planes_ok(io.dst, l, ds.width, true)) return VPF_ERR_BAD_ARG;
+  }
+  DeviceGuard guard(exec->device);
+  if (guard.err != hipSuccess) return status_of(guard.err);
+  Yuv2RgbCoef c;
+  make_yuv2rgb(cs, cr, &c);
+  const TensorEpi te = make_epi(*norm, opts ? opts->border : nullptr, opts ? opts->border_mode : 0u);
+  RemapDesc table[kRemapBatch];
+  for (uint32_t base = 0; base < n; base += kRemapBatch) {
+    const uint32_t m = (n - base < (uint32_t)kRemapBatch) ? n - base : (uint32_t)kRemapBatch;
+    for (uint32_t i = 0; i < m; i++) {
+      const vpf_remap_io& io = jobs[base + i];
+      vpf_plane d[3];
+      const int nd = tensor_planes(io.dst, l, d);
+      fill_desc(table[i].f, io.src, num_planes(sf), d, nd);
+      table[i].xm = io.xmap; table[i].ym = io.ymap; table[i].xp = io.xmap_pitch; table[i].yp = io.ymap_pitch;
+    }
+    const hipError_t e = launch_convert_remap(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, ss.height, m, table, ds.width, ds.height,
+                                              opts ? opts->max_step : 0.f, te, l.nhwc);
+    if (e != hipSuccess) return status_of(e);
+  }
+  return VPF_OK;
+}
+
 // Planar float tensor -> NV12 / YUV420 (include/vpf_hip.h): quantise, BT.601 RGB -> YUV and the 4:2:0 mean in one kernel.
 int vpf_tensor_convert_supported(int df, int cs, int cr) {
   return (df == VPF_FMT_NV12 || df == VPF_FMT_YUV420) && classify(VPF_FMT_RGB_PLANAR, VPF_FMT_YUV420, cs, cr) == FAM_RGB2YUV;

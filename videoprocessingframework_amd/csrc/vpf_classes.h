@@ -11,6 +11,7 @@ constexpr int kMaxBatch = 128;
 // jobs per job table of the per-job tensor entries and frames per device-table call (the tables, and why these sizes: vpf_internal.h; the launch
 // policy that refuses above them: vpf_job_plan.h)
 constexpr int kRoiBatch = 96, kLetterboxBatch = 82, kWarpBatch = 96, kPerspBatch = 82;
+constexpr int kRemapBatch = 96;  // jobs per table of the per-pixel remap entry (vpf_remap_plan.h: a launch of its own, no family of job_plan)
 constexpr int kRoiDevFrames = 128;
 
 enum FmtClass : int {

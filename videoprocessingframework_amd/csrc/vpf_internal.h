@@ -224,6 +224,21 @@ struct WarpDevArgs {
 static_assert(sizeof(WarpDevArgs) == 128 * 40 + 120 && sizeof(WarpDevArgs) <= sizeof(BatchArgsTE<kMaxBatch>),
               "the device-warp arguments must not outgrow the largest frame table");
 
+// The job table of a per-pixel remap into a tensor (vpf_convert_remap_tensor, k_convert_remap.hip): per job the planes of the WHOLE source frame and
+// of the destination, and where the job's two coordinate maps lie in DEVICE memory — row dy of a map at byte dy * pitch, dw floats.  96 B like
+// WarpDesc, so the same 96 jobs per table.  Border bytes and mode travel in TensorEpi::pad as in WarpArgs.
+struct RemapDesc {
+  FrameDesc f;
+  const float* xm;  // device
+  const float* ym;  // device
+  uint32_t xp, yp;  // bytes
+};
+struct RemapArgs {
+  RemapDesc j[kRemapBatch];
+  TensorEpi e;
+};
+static_assert(sizeof(RemapDesc) == 96 && sizeof(RemapArgs) <= sizeof(BatchArgsTE<kMaxBatch>), "the remap job table must not outgrow the largest frame table");
+
 // The prologue of a tensor -> NV12 / YUV420 launch (vpf_tensor_convert): q[c] = rint(clamp(x[c] * scale[c] + bias[c], 0, 255)) feeds the RGB -> YUV
 // arithmetic.  Channel order is the kernels' R G B; BGR is the host's swap of planes and parameters.
 struct TensorPro {
@@ -297,6 +312,11 @@ hipError_t launch_convert_warp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef
 // dynamic LDS (persp_dev_lds_bytes, vpf_job_bounds.h); k_convert_persp_dev.hip
 hipError_t launch_convert_persp_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, WarpDevArgs& a, uint32_t dw, uint32_t dh,
                                     float max_step, const TensorEpi& te, bool nhwc = false);
+// n <= kRemapBatch jobs on frames of W x H pixels, each through its own pair of device maps -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of dw x dh:
+// ONE dispatch (remap_plan, vpf_remap_plan.h), every tile border, staged or per tap by the exact window of the coordinates it loaded; `max_step`
+// sizes the dynamic LDS; `te.pad` carries border and mode; k_convert_remap.hip
+hipError_t launch_convert_remap(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, uint32_t n, const RemapDesc* jobs, uint32_t dw,
+                                uint32_t dh, float max_step, const TensorEpi& te, bool nhwc = false);
 
 int tuning(int key);
 

@@ -15,6 +15,8 @@
 //         tests/test_warps_dev_bounds_cpu.py through tests/c/warp_dev_bounds_capi.cpp)
 //   persp persp_xy / persp_window / persp_px_in_window / persp_need: the perspective warp's (k_convert_persp.hip); persp_dev_job_ok / persp_step /
 //         persp_dev_lds_bytes: the guard, the caller's hint and the LDS bound of its device-table form (k_convert_persp_dev.hip)
+//   remap remap_tap / remap_win_none / remap_win_add / remap_win_merge: what ONE pixel of a per-pixel map contributes to its tile's source window and
+//         how contributions merge (k_convert_remap.hip; tests/test_remap_tensor_cpu.py through tests/c/remap_bounds_capi.cpp)
 #ifndef VPF_JOB_BOUNDS_H_
 #define VPF_JOB_BOUNDS_H_
 #include <math.h>
@@ -522,5 +524,55 @@ static inline uint32_t persp_dev_lds_bytes(float max_step, uint32_t W, uint32_t 
   const uint64_t bytes = (uint64_t)rows * (32u * ng + 16u);
   return bytes < kWarpStripMax ? (uint32_t)bytes : kWarpStripMax;
 }
+
+// ------------------------------------------------------------------------------------------
+// Per-pixel remap (k_convert_remap.hip, vpf_convert_remap_tensor): the coordinates are DATA — two floats per destination pixel, loaded from device
+// memory nobody has checked — so the tile's window is not estimated from corners: it is the exact merge of what every pixel contributes.
+// ------------------------------------------------------------------------------------------
+// What ONE pixel with the loaded coordinates (sx, sy) does: `in` — it samples the frame — and then its four taps (x0|x1, y0|y1) and the coordinate
+// (cx, cy) the blend takes its fractions from; otherwise it takes the border, taps and coordinate are those of pixel (0, 0) and are never blended.
+// The ONLY thing between untrusted floats and an index: a NaN in either coordinate is REPLACED BY A SELECT (no min, max or median is asked what
+// it does with a NaN) and the pixel is out of range in both modes; REPLICATE's max-then-min puts +-inf on the edge; CONSTANT's test lets -0.0 in
+// and +-inf out; a coordinate that failed the test is replaced by 0 — again a select — BEFORE the float -> int conversion.  So the conversion only
+// ever sees values in [0, W - 1] x [0, H - 1] (W, H <= 65536: exact floats), and x0 <= x1 <= W - 1, y0 <= y1 <= H - 1 whatever was loaded.
+struct RemapTap {
+  float cx, cy;
+  uint32_t x0, x1, y0, y1;
+  bool in;
+};
+static VPF_JB_HDI RemapTap remap_tap(float sx, float sy, bool rep, uint32_t W, uint32_t H) {
+  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
+  const bool nan = sx != sx || sy != sy;
+  sx = nan ? 0.f : sx;
+  sy = nan ? 0.f : sy;
+  if (rep) {  // a max, then a min: warp_xy's
+    sx = fminf(fmaxf(sx, 0.f), wmax);
+    sy = fminf(fmaxf(sy, 0.f), hmax);
+  }
+  RemapTap t;
+  t.in = !nan && sx >= 0.f && sx <= wmax && sy >= 0.f && sy <= hmax;
+  t.cx = t.in ? sx : 0.f;
+  t.cy = t.in ? sy : 0.f;
+  t.x0 = (uint32_t)(int)t.cx;
+  t.y0 = (uint32_t)(int)t.cy;
+  t.x1 = t.x0 + 1 < W ? t.x0 + 1 : W - 1;
+  t.y1 = t.y0 + 1 < H ? t.y0 + 1 : H - 1;
+  return t;
+}
+// The window of a set of pixels: the smallest rectangle that holds the taps of its in-range pixels; `empty`: it has none (x_lo > x_hi then).
+static VPF_JB_HDI WarpWin remap_win_none() { return WarpWin{0xffffffffu, 0u, 0xffffffffu, 0u, true}; }
+static VPF_JB_HDI void remap_win_add(WarpWin& w, const RemapTap& t) {
+  if (!t.in) return;
+  w.x_lo = t.x0 < w.x_lo ? t.x0 : w.x_lo; w.x_hi = t.x1 > w.x_hi ? t.x1 : w.x_hi;
+  w.y_lo = t.y0 < w.y_lo ? t.y0 : w.y_lo; w.y_hi = t.y1 > w.y_hi ? t.y1 : w.y_hi;
+  w.empty = false;
+}
+static VPF_JB_HDI WarpWin remap_win_merge(const WarpWin& a, const WarpWin& b) {
+  return WarpWin{a.x_lo < b.x_lo ? a.x_lo : b.x_lo, a.x_hi > b.x_hi ? a.x_hi : b.x_hi, a.y_lo < b.y_lo ? a.y_lo : b.y_lo, a.y_hi > b.y_hi ? a.y_hi : b.y_hi,
+                 a.empty && b.empty};
+}
+// whether the strip of a window fits `lds_bytes`: rows x row bytes in 64 bits — a window may be the whole of a 65536 x 65536 frame, whose strip's
+// bytes do not fit 32
+static VPF_JB_HDI bool remap_strip_fits(const WarpStrip& s, uint32_t lds_bytes) { return (uint64_t)s.rows * s.rowbytes <= (uint64_t)lds_bytes; }
 
 #endif  // VPF_JOB_BOUNDS_H_
