@@ -640,6 +640,41 @@ VPF_API vpf_status vpf_convert_remap_tensor(const vpf_exec* exec, int src_fmt, i
                                             uint32_t n, const vpf_remap_io* jobs, const vpf_tensor_norm* norm, const vpf_remap_opts* opts);
 
 /*
+ * ANTIALIASED letterbox into the tensor: vpf_convert_letterbox_tensor's jobs, options, plane rules and refusals, unchanged, with the bare bilinear
+ * pair replaced by the TRIANGLE filter whose support grows with the scale — the filter of PIL's Image.resize(BILINEAR) and of torch's
+ * F.interpolate(mode="bilinear", antialias=True), what training pipelines resize with.  Past a 2 x down-scale the bilinear pair skips source pixels
+ * (4K -> 640 x 640 is 6 x: two of every six per axis reach the output); here every source pixel of the rectangle contributes.  With dst_rect =
+ * the whole destination a job is an antialiased ROI, with rect = the whole frame as well the antialiased whole-frame call.
+ * A job has the source rectangle (x, y, w, h) and the picture (ix, iy, iw, ih).  Per axis, in = w or h and out = iw or ih; every operation below
+ * is an individually rounded fp32 operation, the three divisions IEEE-rounded:
+ *   s = (float)in / (float)out        fs = max(s, 1.0f)       inv = 1.0f / fs
+ *   for destination index d of the picture:
+ *     c  = ((float)d + 0.5f) * s
+ *     lo = max(0,  (int)((c - fs) + 0.5f))          (C truncation, then the clamp)
+ *     hi = min(in, (int)((c + fs) + 0.5f))          taps k = lo .. hi-1
+ *     t_k = max(0.0f, 1.0f - fabsf(((float)k + 0.5f) - c) * inv)       (multiply and subtract rounded separately)
+ *     S = t_lo + ... + t_(hi-1)  (plain adds, ascending)               r = 1.0f / S
+ * hi > lo and S >= 0.5 always hold: the pixel nearest c has t >= 0.5.  P[ch](i, j) is the byte vpf_convert(src_fmt -> RGB_PLANAR, color_space,
+ * color_range) gives frame pixel (x + i, y + j), as a float; chroma at absolute ((x + i) >> 1, (y + j) >> 1), as in the ROI entry.  Nothing
+ * outside the rectangle contributes.  Horizontal first, then vertical, with no rounding to a byte in between (torch's float path):
+ *   H(j, dx)[ch]  = r_x(dx) * fold_k fmaf(tx_k, P[ch](lo_x + k, j), acc)         acc from 0.0f, k ascending
+ *   V(dx, dy)[ch] = r_y(dy) * fold_j fmaf(ty_j, H(lo_y + j, dx)[ch], acc)        acc from 0.0f, j ascending
+ *   u8  = min(255.0f, truncf(V + 0.5f))
+ *   out = round_to_dtype(fmaf(u8, scale[c], bias[c]))                            exactly vpf_convert_resize_tensor's epilogue
+ * Outside the picture an element takes pad[c] and the epilogue.  Every element of every job's dst_size planes is written exactly once, and nothing
+ * else is written.  On an axis with s <= 1 the window is the two or three nearest pixels: the result is within 1 LSB of
+ * vpf_convert_letterbox_tensor there, and is NOT claimed bit-identical to it.  Against torch's float path rounded half up the bytes are within 1 LSB
+ * and equal in all but a fraction of a percent; against PIL's and torch's uint8 paths, which round to bytes between the passes, within 1 LSB
+ * (measured shares: DESIGN.md 4.26).
+ * It accepts NV12 / YUV420 / P10 / P12 sources (16-bit samples narrowed at the load), f32 / f16 / bf16, VPF_TENSOR_BGR, VPF_TENSOR_NHWC.  `jobs` is
+ * a HOST array, consumed before return; 82 jobs travel per job table, each table in at most two dispatches (jobs whose tiles convert their source
+ * window once into LDS and fold from there, and jobs beyond about 6.8 x that convert per tap: identical bits).  opts == NULL means pad 0 0 0.
+ */
+VPF_API vpf_status vpf_convert_letterbox_tensor_aa(const vpf_exec* exec, int src_fmt, int color_space, int color_range, vpf_size src_size,
+                                                   vpf_size dst_size, uint32_t n, const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm,
+                                                   const vpf_letterbox_opts* opts);
+
+/*
  * Fused planar float tensor -> NV12 / YUV420 in one pass: the way back from a model's output ([N, 3, H, W] f32 / f16 / bf16) to what an
  * encoder takes.  src[0..2] are the three planes of the frame in input channel order (R G B, or B G R with VPF_TENSOR_BGR; scale[c] / bias[c]
  * belong to input plane c), size.width elements per row, `pitch` in bytes; dst is NV12 ([0], [1]) or YUV420 ([0..2]).

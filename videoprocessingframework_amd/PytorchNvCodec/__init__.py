@@ -904,7 +904,7 @@ def _dst_rects_list(dst_rects, n, w, h, fn):
 
 
 def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_rects=None, pad=(114, 114, 114), dtype=torch.float32, bgr=False, out=None,
-                                   cc_ctx=None, channels_last=False):
+                                   cc_ctx=None, channels_last=False, *, antialias=False):
     """Letterbox: K rectangles of NV12 / YUV420 (or P10 / P12) surfaces, each resized into a rectangle of its own inside its [3, dh, dw] frame and the
     rest of the frame padded with a constant — the aspect-preserving input of a detector (YOLO's 114-grey letterbox) and of ReID / face / OCR networks
     that take padded crops —, normalised, in one dispatch per 82 jobs (PySurfaceConvertResizer.ExecuteLetterboxToTensor, vpf_convert_letterbox_tensor).
@@ -920,7 +920,13 @@ def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_
 
     `out`, channels_last and the stream ordering: exactly as to_normalized_tensor.  ValueError for what rois_to_normalized_tensor refuses, for a pad
     that is not three integers in 0..255, for rois and dst_rects of different lengths and for a dst_rect that is empty or leaves the destination.
-    K == 0 returns an empty tensor and an empty placement without a launch."""
+    K == 0 returns an empty tensor and an empty placement without a launch.
+
+    antialias=True (keyword only): inside its rectangle a job goes through the triangle filter whose support grows with the scale — PIL's
+    Image.resize(BILINEAR) and F.interpolate(mode="bilinear", antialias=True), within 1 LSB of either — instead of the bare bilinear pair, which past a
+    2 x down-scale skips source pixels (PySurfaceConvertResizer.ExecuteLetterboxAAToTensor, vpf_convert_letterbox_tensor_aa).  With rois=None and
+    dst_rects = the whole destination, [(0, 0, dw, dh)] * K, this is the antialiased whole-frame call; with rois and that dst_rects the antialiased
+    ROI call.  The same arguments, refusals and return value; the default, antialias=False, is bit for bit what it was."""
     fn = "letterbox_to_normalized_tensor"
     try:
         import PyNvCodec as nvc
@@ -950,8 +956,9 @@ def letterbox_to_normalized_tensor(resizer, surfaces, mean, std, rois=None, dst_
         return out, placement
     elem = out.element_size()
     with _on_task_stream(resizer, out.device):
-        ok = resizer.ExecuteLetterboxToTensor(surfaces, jobs, rects, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
-                                              cc_ctx, bool(bgr), pad, s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
+        execute = resizer.ExecuteLetterboxAAToTensor if antialias else resizer.ExecuteLetterboxToTensor
+        ok = execute(surfaces, jobs, rects, out.data_ptr(), _TENSOR_DTYPES[dtype], [float(m) for m in mean], [float(v) for v in std],
+                     cc_ctx, bool(bgr), pad, s2 * elem, s1 * elem, s0 * elem, bool(channels_last))
     if not ok:
         _refused(fn, _RESIZER_REFUSED)
     return out, placement

@@ -33,7 +33,7 @@ EXPORTS = [
     "vpf_tensor_convert_supported", "vpf_tensor_convert", "vpf_tensor_convert_batch",
     "vpf_convert_letterbox_tensor", "vpf_letterbox_fit", "vpf_convert_resize_tensor_rois_dev", "vpf_convert_warp_tensor_dev",
     "vpf_convert_persp_tensor", "vpf_convert_letterbox_tensor_dev", "vpf_convert_persp_tensor_dev", "vpf_persp_max_step",
-    "vpf_convert_remap_tensor",
+    "vpf_convert_remap_tensor", "vpf_convert_letterbox_tensor_aa",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_BGR = 1
@@ -238,6 +238,7 @@ def lib() -> C.CDLL:
         L.vpf_convert_persp_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(PerspIO), PN, C.POINTER(WarpOpts)]
         L.vpf_convert_letterbox_tensor.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(LetterboxIO), PN,
                                                    C.POINTER(LetterboxOpts)]
+        L.vpf_convert_letterbox_tensor_aa.argtypes = L.vpf_convert_letterbox_tensor.argtypes
         L.vpf_convert_resize_tensor_rois_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(RoisDev), PN]
         L.vpf_convert_warp_tensor_dev.argtypes = [PE, C.c_int, C.c_int, C.c_int, Size, Size, C.c_uint32, C.POINTER(FrameSrc), C.POINTER(WarpsDev), PN,
                                                   C.POINTER(WarpOpts)]
@@ -593,6 +594,17 @@ def convert_letterbox_tensor(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, jobs, no
                                             C.byref(norm) if norm is not None else None, C.byref(opts) if opts is not None else None)
     if check:
         _check(st, "vpf_convert_letterbox_tensor")
+    return st
+
+
+def convert_letterbox_tensor_aa(ex: Exec, src_fmt, cs, cr, sw, sh, dw, dh, jobs, norm: TensorNorm, opts: LetterboxOpts = None, n=None, check=True) -> int:
+    """convert_letterbox_tensor's arguments; inside its dst_rect every rectangle goes through the triangle filter whose support grows with the scale
+    (PIL's BILINEAR, torch's antialias=True) instead of the bare bilinear pair"""
+    st = lib().vpf_convert_letterbox_tensor_aa(C.byref(ex) if ex is not None else None, src_fmt, cs, cr, Size(sw, sh), Size(dw, dh),
+                                               len(jobs) if n is None else n, jobs, C.byref(norm) if norm is not None else None,
+                                               C.byref(opts) if opts is not None else None)
+    if check:
+        _check(st, "vpf_convert_letterbox_tensor_aa")
     return st
 
 

@@ -379,6 +379,39 @@ public:
     return TASK_EXEC_SUCCESS == task_->RunTensorLetterbox(a.data(), (uint32_t)a.size(), index.data(), rects.data(), drects.data(), (uint32_t)rois.size(),
                                                           planes.data(), norm, &opts, cc.get());
   }
+  // additive: the same jobs through the antialiasing triangle filter (vpf_convert_letterbox_tensor_aa): ExecuteLetterboxToTensor's arguments and answers
+  bool ExecuteLetterboxAAToTensor(const std::vector<std::shared_ptr<Surface>>& src, const std::vector<std::array<int64_t, 5>>& rois,
+                                  const std::vector<std::array<int64_t, 4>>& dst_rects, uint64_t dst, uint32_t dtype, const std::vector<double>& mean,
+                                  const std::vector<double>& std, std::shared_ptr<ColorspaceConversionContext> cc, bool bgr, const std::vector<int64_t>& pad,
+                                  uint64_t row_pitch, uint64_t plane_stride, uint64_t frame_stride, bool channels_last) {
+    vpf_tensor_norm norm = norm_of(dtype, mean, std, bgr);
+    if (pad.size() != 3) throw std::invalid_argument("pad needs three values");
+    vpf_letterbox_opts opts;
+    std::memset(&opts, 0, sizeof(opts));
+    for (int c = 0; c < 3; c++) {
+      if (pad[c] < 0 || pad[c] > 255) throw std::invalid_argument("pad values must lie in 0..255");
+      opts.pad[c] = (uint8_t)pad[c];
+    }
+    if (rois.size() != dst_rects.size()) throw std::invalid_argument("rois and dst_rects must have the same length");
+    if (src.empty() || rois.empty() || !dst) return false;
+    std::vector<vpf_plane> planes;
+    if (!tensor_planes(dst, dtype, rois.size(), task_dst_w_, task_dst_h_, row_pitch, plane_stride, frame_stride, channels_last, norm, planes)) return false;
+    std::vector<Surface*> a;
+    for (auto& s : src) a.push_back(s.get());
+    std::vector<uint32_t> index(rois.size());
+    std::vector<vpf_rect> rects(rois.size()), drects(rois.size());
+    for (size_t i = 0; i < rois.size(); i++) {
+      for (int k = 0; k < 5; k++)
+        if (rois[i][k] < 0 || rois[i][k] > 0xffffffffll) return false;
+      for (int k = 0; k < 4; k++)
+        if (dst_rects[i][k] < 0 || dst_rects[i][k] > 0xffffffffll) return false;
+      index[i] = (uint32_t)rois[i][0];
+      rects[i] = vpf_rect{(uint32_t)rois[i][1], (uint32_t)rois[i][2], (uint32_t)rois[i][3], (uint32_t)rois[i][4]};
+      drects[i] = vpf_rect{(uint32_t)dst_rects[i][0], (uint32_t)dst_rects[i][1], (uint32_t)dst_rects[i][2], (uint32_t)dst_rects[i][3]};
+    }
+    return TASK_EXEC_SUCCESS == task_->RunTensorLetterboxAA(a.data(), (uint32_t)a.size(), index.data(), rects.data(), drects.data(), (uint32_t)rois.size(),
+                                                            planes.data(), norm, &opts, cc.get());
+  }
   // additive: up to max_n letterbox jobs whose boxes lie in DEVICE memory -> a normalised planar tensor [max_n, 3, dh, dw] at device address `dst`
   // (vpf_convert_letterbox_tensor_dev): ExecuteRoisDevToTensor's boxes and count, plus job k's placement, four int32 (ix, iy, iw, ih) at rects +
   // k rect_stride (rects 0: the kernel fits box k into dw x dh), `pad` (per output channel) wherever the frame shows no picture;
@@ -985,6 +1018,12 @@ PYBIND11_MODULE(_PyNvCodec, m) {
            "K letterbox jobs: rectangle rois[i] = (surface_index, x, y, w, h) resized into dst_rects[i] = (ix, iy, iw, ih) of its [3, dh, dw] frame of the "
            "planar tensor at device address ptr, pad (per output channel, 0..255) everywhere else in the frame, normalised (strides in bytes, 0 = "
            "contiguous); one dispatch per 82 regions.  ValueError for a bad pad and for rois / dst_rects of different lengths")
+      .def("ExecuteLetterboxAAToTensor", &PySurfaceConvertResizer::ExecuteLetterboxAAToTensor, py::arg("surfaces"), py::arg("rois"), py::arg("dst_rects"),
+           py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr, py::arg("bgr") = false,
+           py::arg("pad") = std::vector<int64_t>{0, 0, 0}, py::arg("row_stride") = 0, py::arg("plane_stride") = 0, py::arg("frame_stride") = 0,
+           py::arg("channels_last") = false, py::call_guard<py::gil_scoped_release>(),
+           "ExecuteLetterboxToTensor with the antialiasing triangle filter (PIL's BILINEAR, torch's antialias=True) inside every dst_rect: every source "
+           "pixel of a rectangle contributes, whatever the down-scale factor; the same arguments, refusals and ValueErrors")
       .def("ExecuteLetterboxDevToTensor", &PySurfaceConvertResizer::ExecuteLetterboxDevToTensor, py::arg("surfaces"), py::arg("boxes_ptr"), py::arg("max_n"),
            py::arg("count_ptr"), py::arg("rects_ptr"), py::arg("ptr"), py::arg("dtype"), py::arg("mean"), py::arg("std"), py::arg("cc_ctx") = nullptr,
            py::arg("bgr") = false, py::arg("pad") = std::vector<int64_t>{0, 0, 0}, py::arg("row_stride") = 0, py::arg("plane_stride") = 0,

@@ -694,6 +694,28 @@ TaskExecStatus ConvertResizeSurface::RunTensorLetterbox(Surface* const* frames, 
                                                      io.data(), &norm, opts);
   return exec_status(st, "letterbox regions into a tensor");
 }
+TaskExecStatus ConvertResizeSurface::RunTensorLetterboxAA(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects,
+                                                          const vpf_rect* dst_rects, uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm,
+                                                          const vpf_letterbox_opts* opts, const ColorspaceConversionContext* cc) {
+  const HipMark tick("ConvertResizeSurface::RunTensorLetterboxAA");
+  if (!frames || !n_frames || !frame_index || !rects || !dst_rects || !dst || !n) return TASK_EXEC_FAIL;
+  int cs, cr;
+  if (!resolve_ctx(*pImpl->pair, cc, &cs, &cr)) return TASK_EXEC_FAIL;
+  if (!surfaces_match(frames, n_frames, pImpl->in, pImpl->sw, pImpl->sh)) return TASK_EXEC_FAIL;
+  std::vector<vpf_letterbox_io> io(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (frame_index[i] >= n_frames) return TASK_EXEC_FAIL;
+    std::memset(&io[i], 0, sizeof(io[i]));
+    fill_planes(frames[frame_index[i]], io[i].src);
+    tensor_job_planes(dst, i, norm, io[i].dst);
+    io[i].rect = rects[i];
+    io[i].dst_rect = dst_rects[i];
+  }
+  const vpf_exec ex = make_exec(pImpl->ctx, pImpl->str);
+  const vpf_status st = vpf_convert_letterbox_tensor_aa(&ex, pImpl->in, cs, cr, vpf_size{pImpl->sw, pImpl->sh}, vpf_size{pImpl->dw, pImpl->dh}, n,
+                                                        io.data(), &norm, opts);
+  return exec_status(st, "letterbox regions through the antialiasing filter into a tensor");
+}
 TaskExecStatus ConvertResizeSurface::RunTensorLetterboxDev(Surface* const* frames, uint32_t n_frames, const void* boxes, uint32_t box_stride,
                                                            const void* dst_rects, uint32_t rect_stride, uint32_t max_n, const void* count,
                                                            const vpf_plane* dst, uint64_t dst_job_stride, const vpf_tensor_norm& norm,

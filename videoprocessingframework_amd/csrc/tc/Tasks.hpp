@@ -96,6 +96,10 @@ public:
   TaskExecStatus RunTensorLetterbox(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, const vpf_rect* dst_rects,
                                     uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts,
                                     const ColorspaceConversionContext* ctx);
+  // the same jobs through the antialiasing triangle filter (vpf_convert_letterbox_tensor_aa): RunTensorLetterbox's arguments and rules
+  TaskExecStatus RunTensorLetterboxAA(Surface* const* frames, uint32_t n_frames, const uint32_t* frame_index, const vpf_rect* rects, const vpf_rect* dst_rects,
+                                      uint32_t n, const vpf_plane* dst, const vpf_tensor_norm& norm, const vpf_letterbox_opts* opts,
+                                      const ColorspaceConversionContext* ctx);
   // up to max_n letterbox jobs whose boxes lie in DEVICE memory (vpf_convert_letterbox_tensor_dev): RunTensorRoisDev's boxes and count, plus job k's
   // placement, four int32 (ix, iy, iw, ih) at dst_rects + k rect_stride, or nullptr: the kernel fits box k into the task's destination size
   // (vpf_letterbox_fit).  dst = the WHOLE planes of job 0; opts == nullptr: pad 0 0 0.  The same colour-context rules as RunTensor.

@@ -699,9 +699,9 @@ vpf_rect vpf_letterbox_fit(vpf_size src, vpf_size dst) {
 
 // Many rectangles of decoded frames, each resized into a rectangle of its own inside its destination planes, the rest padded (include/vpf_hip.h):
 // the ROI entry's checks and colour rules, kLetterboxBatch jobs per job table, each table at most two dispatches (k_convert_letterbox.hip).
-vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
-                                        const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts) {
-  const Mark mark("vpf_convert_letterbox_tensor");
+// (`aa`: the antialiased entry, which shares every check, the colour rules, the cut into job tables and the job descriptors: only the launcher differs)
+static vpf_status letterbox_tensor_call(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n, const vpf_letterbox_io* jobs,
+                                        const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts, bool aa) {
   if (tensor_src_class(sf) < 0 || !cscr_ok(cs, cr)) return VPF_ERR_UNSUPPORTED;
   if (const vpf_status refused = norm_status(norm, false, opts && opts->reserved)) return refused;
   if (!exec || !jobs || !n || !dims_ok(ss) || !dims_ok(ds)) return VPF_ERR_BAD_ARG;
@@ -729,10 +729,23 @@ vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, in
       j.ix = io.dst_rect.x; j.iy = io.dst_rect.y; j.iw = io.dst_rect.width; j.ih = io.dst_rect.height;
       j.r.scx = (float)j.r.w / (float)j.iw; j.r.scy = (float)j.r.h / (float)j.ih;
     }
-    const hipError_t e = launch_convert_letterbox(static_cast<hipStream_t>(exec->stream), tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, l.nhwc);
+    const hipStream_t st = static_cast<hipStream_t>(exec->stream);
+    const hipError_t e = aa ? launch_convert_letterbox_aa(st, tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, l.nhwc)
+                            : launch_convert_letterbox(st, tensor_src_class(sf), c, ss.width, m, table, ds.width, ds.height, te, l.nhwc);
     if (e != hipSuccess) return status_of(e);
   }
   return VPF_OK;
+}
+vpf_status vpf_convert_letterbox_tensor(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
+                                        const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts) {
+  const Mark mark("vpf_convert_letterbox_tensor");
+  return letterbox_tensor_call(exec, sf, cs, cr, ss, ds, n, jobs, norm, opts, false);
+}
+// The same jobs through the triangle filter of PIL and of torch's antialias=True (include/vpf_hip.h; k_convert_letterbox_aa.hip).
+vpf_status vpf_convert_letterbox_tensor_aa(const vpf_exec* exec, int sf, int cs, int cr, vpf_size ss, vpf_size ds, uint32_t n,
+                                           const vpf_letterbox_io* jobs, const vpf_tensor_norm* norm, const vpf_letterbox_opts* opts) {
+  const Mark mark("vpf_convert_letterbox_tensor_aa");
+  return letterbox_tensor_call(exec, sf, cs, cr, ss, ds, n, jobs, norm, opts, true);
 }
 
 // The same with the boxes, the optional placements and the count in DEVICE memory (include/vpf_hip.h): every check that needs no box happens here

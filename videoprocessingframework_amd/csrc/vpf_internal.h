@@ -294,6 +294,10 @@ hipError_t launch_convert_persp(hipStream_t st, int src_fc, const Yuv2RgbCoef& c
 // and `te.pad` everywhere else: at most two dispatches (staged jobs, gather jobs); k_convert_letterbox.hip
 hipError_t launch_convert_letterbox(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
                                     uint32_t dh, const TensorEpi& te, bool nhwc = false);
+// the same jobs through the triangle filter whose support grows with the scale (vpf_convert_letterbox_tensor_aa): at most two dispatches, staged jobs
+// and per-tap jobs, by aa_plan (vpf_aa_plan.h); k_convert_letterbox_aa.hip
+hipError_t launch_convert_letterbox_aa(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t n, const LetterboxDesc* jobs, uint32_t dw,
+                                       uint32_t dh, const TensorEpi& te, bool nhwc = false);
 // up to a.max_n jobs whose rectangles the kernel reads from device memory, on frames of W x H pixels -> FC_TENSOR (nhwc: FC_TENSOR_NHWC) planes of
 // dw x dh: ONE dispatch, every tile staged or per tap by its own window; a.e is set here; k_convert_roi_dev.hip
 hipError_t launch_convert_resize_rois_dev(hipStream_t st, int src_fc, const Yuv2RgbCoef& c, uint32_t W, uint32_t H, RoiDevArgs& a, uint32_t dw, uint32_t dh,
