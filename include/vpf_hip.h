@@ -656,16 +656,17 @@ VPF_API vpf_status vpf_convert_remap_tensor(const vpf_exec* exec, int src_fmt, i
  *     S = t_lo + ... + t_(hi-1)  (plain adds, ascending)               r = 1.0f / S
  * hi > lo and S >= 0.5 always hold: the pixel nearest c has t >= 0.5.  P[ch](i, j) is the byte vpf_convert(src_fmt -> RGB_PLANAR, color_space,
  * color_range) gives frame pixel (x + i, y + j), as a float; chroma at absolute ((x + i) >> 1, (y + j) >> 1), as in the ROI entry.  Nothing
- * outside the rectangle contributes.  Horizontal first, then vertical, with no rounding to a byte in between (torch's float path):
+ * outside the rectangle contributes.  Horizontal first, then vertical, with no rounding to a byte in between (as torch's float path):
  *   H(j, dx)[ch]  = r_x(dx) * fold_k fmaf(tx_k, P[ch](lo_x + k, j), acc)         acc from 0.0f, k ascending
  *   V(dx, dy)[ch] = r_y(dy) * fold_j fmaf(ty_j, H(lo_y + j, dx)[ch], acc)        acc from 0.0f, j ascending
  *   u8  = min(255.0f, truncf(V + 0.5f))
  *   out = round_to_dtype(fmaf(u8, scale[c], bias[c]))                            exactly vpf_convert_resize_tensor's epilogue
  * Outside the picture an element takes pad[c] and the epilogue.  Every element of every job's dst_size planes is written exactly once, and nothing
  * else is written.  On an axis with s <= 1 the window is the two or three nearest pixels: the result is within 1 LSB of
- * vpf_convert_letterbox_tensor there, and is NOT claimed bit-identical to it.  Against torch's float path rounded half up the bytes are within 1 LSB
- * and equal in all but a fraction of a percent; against PIL's and torch's uint8 paths, which round to bytes between the passes, within 1 LSB
- * (measured shares: DESIGN.md 4.26).
+ * vpf_convert_letterbox_tensor there, and is NOT claimed bit-identical to it.  The bytes are within 1 LSB of the plain float64 triangle filter
+ * (weights normalised by their sum, rounded half up) everywhere, and of torch's float path rounded half up for pictures wider and taller than one
+ * pixel (torch itself leaves the filter on a picture one pixel wide whose height is resampled), equal in all but a fraction of a percent; against
+ * PIL's and torch's uint8 paths, which round to bytes between the passes, within 1 LSB on the measured shapes (shares: DESIGN.md 4.26).
  * It accepts NV12 / YUV420 / P10 / P12 sources (16-bit samples narrowed at the load), f32 / f16 / bf16, VPF_TENSOR_BGR, VPF_TENSOR_NHWC.  `jobs` is
  * a HOST array, consumed before return; 82 jobs travel per job table, each table in at most two dispatches (jobs whose tiles convert their source
  * window once into LDS and fold from there, and jobs beyond about 6.8 x that convert per tap: identical bits).  opts == NULL means pad 0 0 0.

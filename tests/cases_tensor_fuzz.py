@@ -8,7 +8,13 @@ CASES_PER_SEED[family] calls of a seed one after the other from the same generat
 
 What is drawn PER JOB and not per call: the frame the job reads, its geometry, and the layout of its destination planes (LAYOUT_KINDS) — all jobs of
 a host-table call sit in one canary-filled buffer at differing row pitches and base alignments (job_geo / pack).  The device-table entries have one
-destination and a job stride, so their stride and base are drawn instead (dev_geo)."""
+destination and a job stride, so their stride and base are drawn instead (dev_geo).
+
+Ten families: whole, rois, rois_dev, letterbox, warp, warp_dev, encode, persp, and the two youngest entries — letterbox_aa
+(vpf_convert_letterbox_tensor_aa: the letterbox family's draws under a per-call class, so that the 64 x 16 tile, the 32 x 8 tile and the per-tap
+dispatch of csrc/vpf_aa_plan.h all occur) and remap (vpf_convert_remap_tensor: a job names its map pair by kind, parameters and seed, and maps_of
+builds the coordinates on the host).  A family has a BASE of its own and shares no generator state with another: adding one changes no case of
+the others."""
 import math
 
 import numpy as np
@@ -17,12 +23,13 @@ from test_letterbox_tensor_cpu import fit_reference
 from test_persp_tensor_cpu import NAMED
 
 F = np.float32
-FAMILIES = ("whole", "rois", "rois_dev", "letterbox", "warp", "warp_dev", "encode", "persp")
-BASE = {"whole": 21000, "rois": 23000, "rois_dev": 25000, "letterbox": 27000, "warp": 29000, "warp_dev": 31000, "encode": 33000, "persp": 35000}
-CASES_PER_SEED = {"whole": 4, "rois": 5, "rois_dev": 5, "letterbox": 5, "warp": 5, "warp_dev": 5, "encode": 6, "persp": 5}
-# jobs per job table (kRoiBatch, kWarpBatch, kLetterboxBatch, kPerspBatch of csrc/vpf_internal.h)
-TABLE = {"rois": 96, "warp": 96, "letterbox": 82, "persp": 82}
-OVER_TABLE = {"rois": (97, 110), "warp": (97, 110), "letterbox": (83, 90), "persp": (83, 90)}
+FAMILIES = ("whole", "rois", "rois_dev", "letterbox", "warp", "warp_dev", "encode", "persp", "letterbox_aa", "remap")
+BASE = {"whole": 21000, "rois": 23000, "rois_dev": 25000, "letterbox": 27000, "warp": 29000, "warp_dev": 31000, "encode": 33000, "persp": 35000,
+        "letterbox_aa": 37000, "remap": 39000}
+CASES_PER_SEED = {"whole": 4, "rois": 5, "rois_dev": 5, "letterbox": 5, "warp": 5, "warp_dev": 5, "encode": 6, "persp": 5, "letterbox_aa": 5, "remap": 5}
+# jobs per job table (kRoiBatch, kWarpBatch, kLetterboxBatch, kPerspBatch, kRemapBatch of csrc/vpf_internal.h and csrc/vpf_classes.h)
+TABLE = {"rois": 96, "warp": 96, "letterbox": 82, "persp": 82, "letterbox_aa": 82, "remap": 96}
+OVER_TABLE = {"rois": (97, 110), "warp": (97, 110), "letterbox": (83, 90), "persp": (83, 90), "letterbox_aa": (83, 90), "remap": (97, 110)}
 LIMIT = 16777216.0  # |matrix coefficient| limit of the warp entries (include/vpf_hip.h)
 SOURCES = ("NV12", "YUV420", "P10", "P12")
 PARAM_NAMES = ("imagenet", "unit", "symmetric")
@@ -211,6 +218,60 @@ def roi_case(rng, entry="rois"):
 
 def letterbox_case(rng):
     return roi_case(rng, "letterbox")
+
+
+# ------------------------------------------------------------------------------------------------ the antialiased letterbox
+# what a call's jobs are held to (the per-call class draw), so that all three dispatch kinds of csrc/vpf_aa_plan.h occur:
+#   mild   every job within about 0.4 .. 3 x per axis, up-scales included: the staged dispatch takes the 64 x 16 tile
+#   steep  one job or more between 3.6 x and 6.5 x on BOTH axes on a picture of at least 32 x 8, and none steeper: the 32 x 8 tile
+#   any    unrestricted: thumbnails (1 x 1 and 2 x 2 pictures) of large rectangles, which sample per tap, next to small rectangles at large factors,
+#          which still stage
+AA_CLASSES = ("mild", "steep", "steep", "any", "any", "any")
+AA_MILD, AA_STEEP_LO, AA_STEEP_HI = 3.0, 3.6, 6.5
+
+
+def cap_factor(rect, W, H, iw, ih, top):
+    """the rectangle shrunk until neither axis is more than `top` times its picture; an edge that touched the frame's right / bottom edge still does"""
+    x, y, w, h = rect
+    nw, nh = min(w, max(1, int(top * iw))), min(h, max(1, int(top * ih)))
+    return (W - nw if x + w == W else x, H - nh if y + h == H else y, nw, nh)
+
+
+def letterbox_aa_case(rng):
+    """vpf_convert_letterbox_tensor_aa: roi_case(rng, "letterbox") with the class draw above.  A steep call takes a frame of at least 240 x 120 and
+    a destination of at least 40 x 12 (32 x 8 across the job table) so that its steep jobs exist"""
+    call = draw_common(rng, "letterbox_aa")
+    cls = _pick(rng, AA_CLASSES)
+    n, over = draw_job_count(rng, "letterbox_aa")
+    if cls == "steep":
+        call["W"], call["H"] = _i(rng, 240, 420), _i(rng, 120, 300)
+        call["dw"], call["dh"] = (_i(rng, 32, 40), _i(rng, 8, 16)) if over else (_i(rng, 40, 90), _i(rng, 12, 70))
+    else:
+        call["dw"], call["dh"] = (_i(rng, 1, 24), _i(rng, 1, 16)) if over else draw_dst_size(rng)
+    call["cls"] = cls
+    call["pad"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    hot = _i(rng, 0, n - 1)   # the job a steep call is steep by
+    call["jobs"] = []
+    for i in range(n):
+        job = dict(frame=_i(rng, 0, len(call["frames"]) - 1))
+        if cls == "any" and rng.integers(2) == 0:        # a thumbnail of a large rectangle
+            w, h = _i(rng, (W + 1) // 2, W), _i(rng, (H + 1) // 2, H)
+            iw, ih = _i(rng, 1, min(2, dw)), _i(rng, 1, min(2, dh))
+            job["rect"] = (_i(rng, 0, W - w), _i(rng, 0, H - h), w, h)
+            job["dst_rect"] = (_i(rng, 0, dw - iw), _i(rng, 0, dh - ih), iw, ih)
+        elif cls == "steep" and (i == hot or rng.integers(4) == 0):
+            iw, ih = _i(rng, 32, min(dw, int(W / 3.7))), _i(rng, 8, min(dh, int(H / 3.7)))
+            w = min(max(int(iw * rng.uniform(AA_STEEP_LO, AA_STEEP_HI)), math.ceil(AA_STEEP_LO * iw)), int(AA_STEEP_HI * iw), W)
+            h = min(max(int(ih * rng.uniform(AA_STEEP_LO, AA_STEEP_HI)), math.ceil(AA_STEEP_LO * ih)), int(AA_STEEP_HI * ih), H)
+            job["rect"] = (_i(rng, 0, W - w), _i(rng, 0, H - h), w, h)
+            job["dst_rect"] = (_i(rng, 0, dw - iw), _i(rng, 0, dh - ih), iw, ih)
+        else:
+            rect = draw_rect(rng, W, H, dw, dh)
+            job["dst_rect"] = draw_inner(rng, rect[2], rect[3], dw, dh)
+            job["rect"] = rect if cls == "any" else cap_factor(rect, W, H, job["dst_rect"][2], job["dst_rect"][3], AA_MILD if cls == "mild" else AA_STEEP_HI)
+        call["jobs"].append(job)
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
 
 
 def box_valid(f, x, y, w, h, n_frames, W, H):
@@ -497,6 +558,143 @@ def persp_case(rng):
     return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
 
 
+# ------------------------------------------------------------------------------------------------ per-pixel maps
+# A description stays one printable line, so a job names its maps instead of holding them: call["maps"] is a list of map PAIRS — kind, parameters,
+# seed, pitches and leads — and job["maps"] an index into it (two jobs may share a pair on different frames); pair_maps / maps_of build the
+# coordinates on the host.  Kinds:
+#   affine      draw_matrix written out by warp_maps(..., mode 0): unclamped, the kernel clamps under REPLICATE (bit for bit the affine entry)
+#   homography  draw_homography through persp_maps, pixels where w > 0 fails set to NaN
+#   barrel      lens undistortion (the float64 restatement of tests/test_remap_tensor_cpu.py) with drawn k1, k2
+#   local       a smooth affine map plus a jitter of a few pixels: moderate windows
+#   random      every pixel anywhere in [-5, W + 5] x [-5, H + 5]: the window is the whole frame
+#   outside     every coordinate out of range      nan   all NaN      one   a single in-range pixel, everything else NaN or left of the frame
+#   strip_*     REMAP_NAMED: tile (0, 0) spans an exact window, the rest is NaN
+# Any kind may pass through sprinkle (the special coordinates of tests/test_remap_tensor_cpu.py at seeded places).
+REMAP_KINDS = ("affine", "homography", "barrel", "local", "random", "outside", "nan", "one")
+REMAP_WEIGHTS = (4, 3, 3, 4, 4, 3, 1, 1)
+REMAP_MIX = tuple(c for c, w in zip(REMAP_KINDS, REMAP_WEIGHTS) for _ in range(w))
+REMAP_SMOOTH = ("affine", "barrel", "local")   # the kinds a true max_step is taken from
+# name: (W, H, x_hi, y_hi, strip bytes) — the in-range pixels of destination tile (0, 0) span frame columns 0 .. x_hi and rows 0 .. y_hi.  A strip row
+# is 32 B per unit of eight columns plus 16 (warp_strip, csrc/vpf_job_bounds.h), and without a hint the launch gives 65 536 - 32 bytes:
+#   strip_65504   44 units, 46 rows x 1 424 B = 65 504: exactly what the launch gives — it stages
+#   strip_65520   31 units, 65 rows x 1 008 B = 65 520: the smallest strip above it (a strip is a multiple of 16 and no odd multiple gives 65 536) — per tap
+REMAP_NAMED = {"strip_65504": (360, 140, 351, 45, 65504), "strip_65520": (300, 140, 247, 64, 65520)}
+
+
+def pair_maps(call, pair):
+    """(sx, sy): float32 [dh, dw] of one map pair of a remap call"""
+    from test_remap_tensor_cpu import _undistort_numpy, sprinkle
+    from test_persp_tensor_cpu import persp_maps
+    from test_warp_tensor_cpu import warp_maps
+    W, H, dw, dh, kind = call["W"], call["H"], call["dw"], call["dh"], pair["kind"]
+    rng = np.random.default_rng(pair["seed"])
+    nan = np.full((dh, dw), np.nan, F)
+    if kind == "affine":
+        sx, sy = warp_maps(pair["m"], dw, dh, W, H, 0)
+    elif kind == "homography":
+        sx, sy, front = persp_maps(pair["m"], dw, dh, W, H, 0)
+        sx, sy = np.where(front, sx, F(np.nan)).astype(F), np.where(front, sy, F(np.nan)).astype(F)
+    elif kind == "barrel":   # a camera whose principal point is the frame's centre, onto a dw x dh view of the whole frame
+        K = [[0.8 * W, 0, (W - 1) / 2], [0, 0.8 * W, (H - 1) / 2], [0, 0, 1]]
+        Kn = [[0.8 * dw, 0, (dw - 1) / 2], [0, 0.8 * W * dh / H, (dh - 1) / 2], [0, 0, 1]]
+        sx, sy = _undistort_numpy(K, (pair["k1"], pair["k2"], 0.002, -0.001, 0.01), (dw, dh), Kn)
+    elif kind == "local":
+        sx, sy = warp_maps(pair["m"], dw, dh, W, H, 0)
+        sx, sy = (sx + rng.uniform(-pair["jitter"], pair["jitter"], (dh, dw)).astype(F)).astype(F), (sy + rng.uniform(-pair["jitter"], pair["jitter"], (dh, dw)).astype(F)).astype(F)
+    elif kind == "random":
+        sx, sy = rng.uniform(-5, W + 5, (dh, dw)).astype(F), rng.uniform(-5, H + 5, (dh, dw)).astype(F)
+    elif kind == "outside":
+        sx, sy = np.full((dh, dw), pair["at"][0], F), np.full((dh, dw), pair["at"][1], F)
+    elif kind == "nan":
+        sx, sy = nan.copy(), nan.copy()
+    elif kind == "one":
+        sx, sy = np.full((dh, dw), -7.0, F), nan.copy()
+        sx[:, :dw // 2] = np.nan
+        k = int(rng.integers(dw * dh))
+        sx.flat[k], sy.flat[k] = F(W - 1), F(rng.uniform(0, H - 1))
+    else:
+        _, _, x_hi, y_hi, _ = REMAP_NAMED[kind]
+        sx, sy = nan.copy(), nan.copy()
+        tw, th = min(dw, 32), min(dh, 32)
+        sx[:th, :tw], sy[:th, :tw] = rng.uniform(0, x_hi - 0.5, (th, tw)).astype(F), rng.uniform(0, y_hi - 0.5, (th, tw)).astype(F)
+        sx[:th, :tw][rng.uniform(size=(th, tw)) < 0.2] = np.nan                # (some pixels of the tile take the border)
+        sx[0, 0], sy[0, 0] = 0.25, 0.5                                         # taps 0 | 1: the window's first column and row
+        sx[th - 1, tw - 1], sy[th - 1, tw - 1] = x_hi - 0.5, y_hi - 0.5        # taps x_hi - 1 | x_hi: its last
+    sx, sy = np.ascontiguousarray(sx, dtype=F), np.ascontiguousarray(sy, dtype=F)
+    return sprinkle(sx, sy, W, H, pair["sprinkle"]) if pair["sprinkle"] is not None else (sx, sy)
+
+
+def maps_of(call, job):
+    return pair_maps(call, call["maps"][job["maps"]])
+
+
+def maps_step(sx, sy):
+    """the largest |d s / d dx| + |d s / d dy| over both maps, differences that are not finite left out (what PytorchNvCodec.maps_max_step bounds)"""
+    best = 0.0
+    for m in (sx.astype(np.float64), sy.astype(np.float64)):
+        with np.errstate(invalid="ignore"):
+            gx, gy = np.abs(np.diff(m, axis=1, append=m[:, -1:])), np.abs(np.diff(m, axis=0, append=m[-1:, :]))
+        gx, gy = np.where(np.isfinite(gx), gx, 0.0), np.where(np.isfinite(gy), gy, 0.0)
+        best = max(best, float((gx + gy).max()))
+    return best
+
+
+def draw_pair(rng, call, kind=None):
+    W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    kind = _pick(rng, REMAP_MIX) if kind is None else kind
+    pair = dict(kind=kind, seed=_i(rng, 0, (1 << 30) - 1))
+    if kind == "affine":
+        pair["m"] = draw_matrix(rng, W, H, dw, dh)
+    elif kind == "homography":
+        pair["m"] = draw_homography(rng, W, H, dw, dh)
+    elif kind == "barrel":
+        pair["k1"], pair["k2"] = round(float(rng.uniform(-0.4, 0.3)), 4), round(float(rng.uniform(-0.1, 0.1)), 4)
+    elif kind == "local":
+        s, t = _log_uniform(rng, 0.4, 2.0), rng.uniform(0, 2 * math.pi)
+        pair["m"] = centred(s * math.cos(t), -s * math.sin(t), s * math.sin(t), s * math.cos(t), W, H, dw, dh, rng.uniform(-4, 4), rng.uniform(-4, 4))
+        pair["jitter"] = round(float(rng.uniform(0.5, 4.0)), 2)
+    elif kind == "outside":
+        pair["at"] = _pick(rng, ((-3.5, H / 2.0), (W + 0.5, -0.25), (W / 2.0, H + 2.0), (-1e30, 0.0)))
+    pair["sprinkle"] = _i(rng, 0, (1 << 30) - 1) if kind not in REMAP_NAMED and rng.integers(2) else None
+    # map rows padded by 0 .. 32 bytes, the bases at 0, 4, 8, 12 mod 16: both loads of remap_load4 (tests/test_gpu_remap_tensor.py::test_seeded_calls)
+    pair.update(xpitch=4 * dw + 4 * _i(rng, 0, 8), ypitch=4 * dw + 4 * _i(rng, 0, 8), xlead=4 * _i(rng, 0, 3), ylead=4 * _i(rng, 0, 3))
+    return pair
+
+
+def remap_case(rng):
+    """vpf_convert_remap_tensor: per job the frame, the map pair (a new one, or an earlier job's), the destination layout; per call the border mode,
+    the border, the hint (0, 1e-3 — nothing fits —, a true bound of the smooth maps x 1 .. 1.5, 50) and 1 .. 12 jobs, or 97 .. 110 at a small
+    destination.  One wide frame in three is wider than 2048 (the packed window's 16-bit halves above 2047).  About one call in ten holds a named
+    map (REMAP_NAMED) on its frame, without a hint and with the knob at 0"""
+    call = draw_common(rng, "remap")
+    if call["W"] >= 900 and rng.integers(3) == 0:
+        call["W"] = _i(rng, 2049, 2100)
+    named = _pick(rng, tuple(REMAP_NAMED)) if rng.integers(10) == 0 else None
+    n, over = draw_job_count(rng, "remap")
+    call["dw"], call["dh"] = (_i(rng, 1, 24), _i(rng, 1, 16)) if over else draw_dst_size(rng)
+    if named is not None:
+        call["W"], call["H"], call["tune"] = REMAP_NAMED[named][0], REMAP_NAMED[named][1], 0
+        call["dw"], call["dh"] = max(call["dw"], 2), max(call["dh"], 2)
+    call["mode"] = _i(rng, 0, 1)
+    call["border"] = (_i(rng, 0, 255), _i(rng, 0, 255), _i(rng, 0, 255))
+    call["maps"], call["jobs"] = [], []
+    for _ in range(n):
+        if call["maps"] and rng.integers(4) == 0:
+            k = _i(rng, 0, len(call["maps"]) - 1)
+        else:
+            k = len(call["maps"])
+            call["maps"].append(draw_pair(rng, call))
+        call["jobs"].append(dict(frame=_i(rng, 0, len(call["frames"]) - 1), maps=k))
+    if named is not None:
+        call["maps"][call["jobs"][_i(rng, 0, n - 1)]["maps"]] = draw_pair(rng, call, named)
+    hint = int(rng.integers(4))
+    call["max_step"] = (0.0, f32(1e-3), None, 50.0)[hint] if named is None else 0.0
+    if call["max_step"] is None:
+        steps = [maps_step(*pair_maps(call, dict(p, sprinkle=None))) for p in call["maps"] if p["kind"] in REMAP_SMOOTH]
+        call["max_step"] = f32(min(max(steps) * rng.uniform(1.0, 1.5) + 1e-3, 1e6)) if steps else 0.0
+    return pack(settle_sources(call), [_pick(rng, LAYOUT_KINDS) for _ in range(n)])
+
+
 # ------------------------------------------------------------------------------------------------ whole frames and the way back
 def whole_case(rng):
     """vpf_convert_resize_tensor(_batch): (W, H) -> (dw, dh) drawn like tests/test_gpu_parity.py::test_fuzz_resize_and_fused — a ratio of 0.15 .. 3
@@ -541,4 +739,4 @@ def encode_case(rng):
 
 
 GENERATORS = {"whole": whole_case, "rois": roi_case, "rois_dev": rois_dev_case, "letterbox": letterbox_case, "warp": warp_case, "warp_dev": warp_dev_case,
-              "encode": encode_case, "persp": persp_case}
+              "encode": encode_case, "persp": persp_case, "letterbox_aa": letterbox_aa_case, "remap": remap_case}

@@ -1,5 +1,6 @@
 """Seeded differential fuzz of the fused tensor entries on the MI355X: vpf_convert_resize_tensor(_batch), vpf_convert_resize_tensor_rois(_dev),
-vpf_convert_letterbox_tensor, vpf_convert_warp_tensor(_dev), vpf_convert_persp_tensor and vpf_tensor_convert(_batch).
+vpf_convert_letterbox_tensor(_aa), vpf_convert_warp_tensor(_dev), vpf_convert_persp_tensor, vpf_convert_remap_tensor and
+vpf_tensor_convert(_batch).
 
 The calls come from tests/cases_tensor_fuzz.py (one description per call, reproducible from the seed and the case index; tests/
 test_tensor_fuzz_cases_cpu.py checks the generator, that the library accepts every call, that both kernel forms of every entry are reached and
@@ -9,19 +10,25 @@ alignments (JobsBuf: TensorBuf / NhwcBuf parts laid over one allocation), so tha
 holds both kernel forms, and the staged dispatch's LDS is the largest of unlike needs.
 
 Ground truth, as in the entries' own tests: the CPU oracle composed as the definition says (roi_reference_u8, letterbox_reference_u8,
-warp_reference_u8, persp_reference_u8, oracle.convert_resize; 16-bit sources narrowed by oracle.convert(P10 | P12 -> NV12) first), then reference_bits; the way back:
+warp_reference_u8, persp_reference_u8, remap_reference_u8, aa_ref of tests/c/aa_ref_capi.cpp with the pad around it, oracle.convert_resize; 16-bit sources narrowed by oracle.convert(P10 | P12 -> NV12) first), then reference_bits; the way back:
 quantise_numpy, then oracle.convert(RGB_PLANAR -> YUV420 -> NV12).  Every written element must be bit-identical (assert_bits: no tolerance), every
 other byte of the buffer must still be the canary, jobs behind a device count must not be written, invalid device entries take the zero / border
 fill, and a device-table call must equal the host-table call on the same jobs.  The perspective entry runs every call twice more on the same
 uploads: in its other kernel form (the tuning knob at the other of 0 and 9: the two buffers byte-identical) and, for the jobs whose last row is
-(0, 0, 1), through vpf_convert_warp_tensor at the same planes (the header promises the affine entry's bits).
+(0, 0, 1), through vpf_convert_warp_tensor at the same planes (the header promises the affine entry's bits).  The antialiased letterbox runs
+every call in its other form too; the remap does both: the other form, and its jobs on unsprinkled affine maps through vpf_convert_warp_tensor.
+The remap's maps live in allocations of their own whose every byte that is no coordinate is 0xFF (NaNs: a read outside a map shows in the output).
 
 Seeds: VPF_FUZZ_FIRST / VPF_FUZZ_SEEDS as in tests/test_gpu_parity.py (64 by default; VPF_FUZZ_SEEDS=500 is the soak, profiles/).
 Wall time of the default 64 seeds per function on one MI355X (the sum of pytest --durations over its 64 tests, references on 16 CPU threads
 included; the whole module: 448 passed in 8.6 s; the 500-seed soak: 3500 passed in 47.6 s, profiles/r15_tensor_fuzz_soak.txt):
   whole_frame_tensor 0.9 s   rois 1.1 s   rois_dev 0.7 s   letterbox 1.1 s   warp 1.5 s   warp_dev 0.7 s   encode 0.6 s
 With the perspective family (its three calls per case included): persp 1.8 s, the whole module: 512 passed in 10.1 s; the 500-seed soak of
-test_fuzz_persp alone: 500 passed in 19.6 s (profiles/r19_persp_fuzz_soak.txt)."""
+test_fuzz_persp alone: 500 passed in 19.6 s (profiles/r19_persp_fuzz_soak.txt).
+With the antialiased letterbox and the remap (two and two or three calls per case), one run of the whole module: persp 1.7 s, letterbox_aa 2.7 s
+(1.6 x persp: the reference's cost per picture pixel grows with the square of the factor), remap 2.3 s (1.3 x), 640 passed in 15.0 s; the
+500-seed soaks: letterbox_aa 500 passed in 23.7 s, remap 500 passed in 22.0 s (profiles/letterbox_aa_fuzz_soak.txt, profiles/remap_fuzz_soak.txt).
+Neither new function has failed on any seed."""
 import os
 
 import numpy as np
@@ -32,6 +39,7 @@ import cases_tensor_fuzz as cases
 import test_gpu_tensor_in as tin
 import test_gpu_tensor_nhwc as nhwc_tests
 from gpu_util import DevPlanes, stream_handle
+from test_gpu_remap_tensor import DevMaps
 from test_gpu_tensor_nhwc import NhwcBuf, hwc
 from test_gpu_tensor_out import CANARY, ELEM, PARAMS, TensorBuf, assert_bits, reference_bits
 from test_gpu_warps_dev import POISON
@@ -111,15 +119,16 @@ def want_of(call, u8):
     return hwc(bits) if call["nhwc"] else bits
 
 
-def host_table_family(capi, orc, family, seed, also=None):
-    """whole, rois, letterbox, warp, persp: one call per case into a JobsBuf, every job against its reference; also(call, descs, buf, got, what):
-    further checks of a family on the same uploads"""
+def host_table_family(capi, orc, family, seed, also=None, prepare=None):
+    """whole, rois, letterbox, warp, persp, letterbox_aa, remap: one call per case into a JobsBuf, every job against its reference;
+    also(call, descs, buf, got, what): further checks of a family on the same uploads; prepare(call): the device addresses invoke() takes as `tables`"""
     for k, call in enumerate(cases.cases(family, seed)):
         what = f"{family} seed {seed} case {k}"
         srcs, devs = upload_frames(orc, call)
         buf = JobsBuf(call)
         descs = [d.desc() for d in devs]
-        tuned(capi, call, lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, buf.buf.data_ptr()))
+        tables = prepare(call) if prepare is not None else None
+        tuned(capi, call, lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, buf.buf.data_ptr(), tables))
         got, intact = buf.frames()
         if family == "whole":
             refs = []
@@ -246,6 +255,64 @@ def test_fuzz_persp(capi, orc, seed):
     plane, denormal and tiny w (coordinates of +-inf and above 1e29), footprints wholly outside, cancelling coefficients up to 2^24 and the sawtooth
     that takes the per-pixel fallback; both border modes; both kernel forms byte-identical; lifted jobs equal to the affine entry"""
     host_table_family(capi, orc, "persp", seed, persp_other_form_and_affine_entry(capi))
+
+
+def other_form(capi):
+    """the same call on the same uploads with the tuning knob at the other of 0 and 9: the two buffers byte-identical, canaries included"""
+    def also(call, descs, buf, got, what):
+        other = JobsBuf(call)
+        tuned(capi, dict(call, tune=9 - call["tune"]), lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, other.buf.data_ptr()))
+        assert torch.equal(buf.buf, other.buf), f"{what}: the two kernel forms (tuning knob 0 and 9) differ: {cases.describe(call)}"
+    return also
+
+
+@pytest.mark.parametrize("seed", _FUZZ_SEEDS)
+def test_fuzz_letterbox_aa(capi, orc, seed):
+    """vpf_convert_letterbox_tensor_aa: calls of mild jobs (0.4 .. 3 x, the 64 x 16 tile), calls with a 3.6 .. 6.5 x job (the 32 x 8 tile) and
+    unrestricted calls (thumbnails of large rectangles per tap next to staged jobs), one or two job tables, per-job frame, rectangle, placement and
+    layout, the pad around every picture; both kernel forms byte-identical"""
+    host_table_family(capi, orc, "letterbox_aa", seed, other_form(capi))
+
+
+def remap_checks(capi):
+    """-> (prepare, also) of the remap family.  prepare uploads every map pair of the call once (DevMaps of tests/test_gpu_remap_tensor.py: each map
+    in an allocation of its own at the pair's pitch and lead, everything that is no coordinate holding NaN bytes, so that a read outside a map shows
+    in the output).  also runs the call in its other kernel form (the tuning knob at the other of 0 and 9, no LDS against the hint's: byte-identical
+    buffers) and the jobs whose maps are an affine matrix's coordinates, unsprinkled, through vpf_convert_warp_tensor at the same planes (the header
+    promises its bits; it promises nothing of the kind for the perspective entry, so homography jobs are not held against it)"""
+    live = {}
+
+    def prepare(call):
+        live["maps"] = [DevMaps(*cases.pair_maps(call, p), xpitch=p["xpitch"], ypitch=p["ypitch"], xlead=p["xlead"], ylead=p["ylead"]) for p in call["maps"]]
+        for m, p in zip(live["maps"], call["maps"]):
+            assert (m.x()[0] % 16, m.y()[0] % 16) == (p["xlead"] % 16, p["ylead"] % 16)
+        live["tables"] = dict(maps=[(m.x()[0], m.y()[0]) for m in live["maps"]])
+        return live["tables"]
+
+    def also(call, descs, buf, got, what):
+        other = JobsBuf(call)
+        tuned(capi, dict(call, tune=9 - call["tune"]), lambda: invoke(capi, call, capi.make_exec(stream_handle()), descs, other.buf.data_ptr(), live["tables"]))
+        assert torch.equal(buf.buf, other.buf), f"{what}: the two kernel forms (tuning knob 0 and 9) differ: {cases.describe(call)}"
+        plain = [i for i, j in enumerate(call["jobs"]) if call["maps"][j["maps"]]["kind"] == "affine" and call["maps"][j["maps"]]["sprinkle"] is None]
+        if not plain:
+            return
+        affine = dict(call, entry="warp", jobs=[dict(call["jobs"][i], m=call["maps"][call["jobs"][i]["maps"]]["m"]) for i in plain])
+        third = JobsBuf(affine)   # the same layout: every job at its own planes, the other jobs' parts stay canary
+        tuned(capi, affine, lambda: invoke(capi, affine, capi.make_exec(stream_handle()), descs, third.buf.data_ptr()))
+        frames, intact = third.frames()
+        for i, f in zip(plain, frames):
+            assert_bits(got[i], f, f"{what} job {i}: maps of an affine matrix, vpf_convert_warp_tensor gives other bits: {cases.describe(call)}")
+        assert intact, f"{what}: vpf_convert_warp_tensor on the affine jobs wrote outside their elements: {cases.describe(call)}"
+    return prepare, also
+
+
+@pytest.mark.parametrize("seed", _FUZZ_SEEDS)
+def test_fuzz_remap(capi, orc, seed):
+    """vpf_convert_remap_tensor: affine, homography (NaN behind the plane), barrel, jittered, random, outside, all-NaN and one-pixel maps, any of them
+    sprinkled with the special coordinates; shared pairs, map pitches and bases at 0 / 4 / 8 / 12 mod 16; both border modes; every hint; frames wider
+    than 2048; the two named strips at the edge of what a launch gives; both kernel forms byte-identical; affine maps equal to the affine entry"""
+    prepare, also = remap_checks(capi)
+    host_table_family(capi, orc, "remap", seed, also, prepare)
 
 
 def encode_inputs(call):

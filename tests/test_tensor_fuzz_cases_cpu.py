@@ -9,8 +9,16 @@
     knob's 9 forces the per-tap form and would make the condition empty; and every source format, dtype, channel order, layout, border mode, a
     two-table call, a call whose jobs differ in alignment and a unit clamped at the right edge occur per entry; the perspective entry's tile
     classes, its per-pixel fallback and its dispatches without LDS or without staged jobs besides (persp_reach);
+  - the antialiased letterbox (test_reach_letterbox_aa, decided by aa_plan of csrc/vpf_aa_plan.h per job table): staged under the 64 x 16 tile,
+    staged under the 32 x 8 tile and per tap each hold at least 10 % of the jobs; a table with a staged and a per-tap dispatch; a call whose two
+    tables take unlike tile shapes or forms; a rectangle at the right edge of a frame with W % 8 != 0, an odd ix, s < 1 on one axis with s > 3 on
+    the other, a tile window that is the whole rectangle.  Measured over the default seeds: 4 329 jobs, 2 622 / 1 157 / 550;
+  - the remap (test_reach_remap, test_remap_named_strips, decided by the kernel's window functions behind tests/c/remap_bounds_capi.cpp and
+    remap_plan, with launch_convert_remap's 32 bytes behind the strip restated): border, staged and per-tap tiles each hold at least 10 % of the
+    tiles; shared map pairs, map bases at 0 / 4 / 8 / 12 mod 16, a tile with one in-range pixel, windows beyond columns 255 and 2 047, every hint,
+    and the two named strips of 65 504 bytes (stages) and 65 520 bytes (per tap).  Measured: 9 924 tiles, 1 678 / 4 100 / 4 146;
   - the independent link: the composed FP32 ground truth of the GPU test (roi_reference_u8, letterbox_reference_u8, warp_reference_u8,
-    persp_reference_u8) against the same composition with every oracle call in EXACT mode, at most 2 codes apart
+    persp_reference_u8, remap_reference_u8) against the same composition with every oracle call in EXACT mode, at most 2 codes apart
     (test_composed_fp32_reference_is_near_the_exact_chain)."""
 import ctypes as C
 import os
@@ -22,6 +30,7 @@ import pytest
 import cases_tensor_fuzz as cases
 from test_letterbox_tensor_cpu import letterbox_reference_u8
 from test_persp_tensor_cpu import persp_maps, persp_reference_u8
+from test_remap_tensor_cpu import clamp_maps, remap_reference_u8
 from test_roi_tensor_cpu import roi_reference_u8
 from test_tensor_in_cpu import PARAM_SETS as DENORM_SETS
 from test_tensor_in_cpu import denorm_scale_bias_f32
@@ -36,7 +45,8 @@ SEEDS = range(64)        # the default seed set of the GPU test
 SOAK = range(500)        # the soak's seeds (VPF_FUZZ_SEEDS=500): validity and acceptance are checked for these too
 NO_GPU = 1 << 20         # a device index no machine has: a call that passes validation stops at the device switch
 FAKE_DST, FAKE_SRC, FAKE_TABLE = 0x40000000, 0x10000000, 0x70000000
-HOST_TABLE = ("rois", "letterbox", "warp", "persp")
+HOST_TABLE = ("rois", "letterbox", "warp", "persp", "letterbox_aa", "remap")
+EXACT_CHAIN = ("rois", "letterbox", "warp", "persp", "remap")   # the families whose ground truth the oracle has an EXACT mode for
 P16 = ("P10", "P12")
 
 
@@ -69,7 +79,7 @@ def dev_dst(call, base):
 
 def invoke(capi, call, ex, srcs, base, tables=None, check=True):
     """run the decode-side call a description names: srcs = the plane descriptors of its frames, base = the address of its destination buffer,
-    tables = the device addresses of a device-table call (boxes / mats, index, count)"""
+    tables = the device addresses of a device-table call (boxes / mats, index, count), or of a remap call's map pairs (maps: [(xmap, ymap)])"""
     entry, jobs = call["entry"], call.get("jobs")
     norm = capi.make_tensor_norm(*PARAMS[call["params"]], dtype=call["dtype"], bgr=call["bgr"], nhwc=call["nhwc"])
     head = (ex, getattr(capi, call["sf"]), call["cs"], call["cr"], call["W"], call["H"])
@@ -83,9 +93,18 @@ def invoke(capi, call, ex, srcs, base, tables=None, check=True):
     if entry == "letterbox":
         arr = capi.make_letterbox_jobs([(srcs[j["frame"]], dst_planes(call, j, base), j["rect"], j["dst_rect"]) for j in jobs])
         return capi.convert_letterbox_tensor(*head, dw, dh, arr, norm, capi.make_letterbox_opts(call["pad"]), check=check)
+    if entry == "letterbox_aa":
+        arr = capi.make_letterbox_jobs([(srcs[j["frame"]], dst_planes(call, j, base), j["rect"], j["dst_rect"]) for j in jobs])
+        return capi.convert_letterbox_tensor_aa(*head, dw, dh, arr, norm, capi.make_letterbox_opts(call["pad"]), check=check)
     if entry == "warp":
         arr = capi.make_warps([(srcs[j["frame"]], dst_planes(call, j, base), j["m"]) for j in jobs])
         return capi.convert_warp_tensor(*head, dw, dh, arr, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
+    if entry == "remap":
+        def maps(j):
+            p, (xa, ya) = call["maps"][j["maps"]], tables["maps"][j["maps"]]
+            return (xa, p["xpitch"]), (ya, p["ypitch"])
+        arr = capi.make_remap_jobs([(srcs[j["frame"]], dst_planes(call, j, base), *maps(j)) for j in jobs])
+        return capi.convert_remap_tensor(*head, dw, dh, arr, norm, capi.make_remap_opts(call["mode"], call["border"], call["max_step"]), check=check)
     if entry == "persp":
         arr = capi.make_persps([(srcs[j["frame"]], dst_planes(call, j, base), j["m"]) for j in jobs])
         return capi.convert_persp_tensor(*head, dw, dh, arr, norm, capi.make_warp_opts(call["mode"], call["border"]), check=check)
@@ -189,9 +208,29 @@ def rgb_order(call, triple):
     return tuple(triple[::-1]) if call["bgr"] else tuple(triple)
 
 
+_AA = []
+
+
+def aa_lib():
+    """tests/c/aa_ref_capi.cpp, compiled once per process (tests/test_letterbox_aa_cpu.py::build_aa)"""
+    if not _AA:
+        import tempfile
+
+        from test_letterbox_aa_cpu import build_aa
+        _AA.append(tempfile.TemporaryDirectory(prefix="fuzz_aa"))
+        _AA.append(build_aa(_AA[0].name))
+    return _AA[1]
+
+
 def job_u8(orc, call, job, rgb):
     """[3, dh, dw] R G B bytes of one job: the composed FP32 reference the GPU tests of the entry use"""
     W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
+    if call["entry"] == "letterbox_aa":   # as tests/test_gpu_letterbox_aa.py::ref_u8: the definition on the converted frame, the pad around it
+        from test_gpu_letterbox_tensor import place
+        from test_letterbox_aa_cpu import aa_ref
+        return place(aa_ref(aa_lib(), rgb, job["rect"], job["dst_rect"][2], job["dst_rect"][3]), job["dst_rect"], dw, dh, rgb_order(call, call["pad"]))
+    if "maps" in job:
+        return remap_reference_u8(orc, None, call["cs"], call["cr"], W, H, *cases.maps_of(call, job), rgb_order(call, call["border"]), call["mode"], rgb=rgb)
     if "m" in job and len(job["m"]) == 9:
         return persp_reference_u8(orc, None, call["cs"], call["cr"], W, H, job["m"], dw, dh, rgb_order(call, call["border"]), call["mode"], rgb=rgb)
     if "m" in job:
@@ -204,10 +243,13 @@ def job_u8(orc, call, job, rgb):
 def job_u8_exact(orc, call, job, rgb):
     """the same composition with every oracle call in EXACT mode (rgb: the EXACT conversion), on the same float32 maps"""
     W, H, dw, dh = call["W"], call["H"], call["dw"], call["dh"]
-    if "m" in job:
+    if "m" in job or "maps" in job:
         packed = np.ascontiguousarray(np.stack(rgb, axis=-1).reshape(H, 3 * W))
         border = rgb_order(call, call["border"])
-        if len(job["m"]) == 9:   # as persp_reference_u8: pixels with !front are out of range (CONSTANT) or any pixel (REPLICATE), the border afterwards
+        if "maps" in job:        # as remap_reference_u8: clamped first under REPLICATE, a NaN stays a NaN and leaves the pre-filled border
+            sx, sy = clamp_maps(*cases.maps_of(call, job), W, H, call["mode"])
+            front = np.ones((dh, dw), bool)
+        elif len(job["m"]) == 9:   # as persp_reference_u8: pixels with !front are out of range (CONSTANT) or any pixel (REPLICATE), the border afterwards
             sx, sy, front = persp_maps(job["m"], dw, dh, W, H, call["mode"])
             fill = np.float32(-1 if call["mode"] == 0 else 0)
             sx, sy = np.ascontiguousarray(np.where(front, sx, fill)), np.ascontiguousarray(np.where(front, sy, fill))
@@ -272,8 +314,20 @@ def test_geometry_and_layouts_are_valid(family):
             if "dst_rect" in job:
                 ix, iy, iw, ih = job["dst_rect"]
                 assert iw >= 1 and ih >= 1 and ix >= 0 and iy >= 0 and ix + iw <= dw and iy + ih <= dh, what
+            if family == "letterbox_aa":   # the class a call was drawn under holds for every job of it
+                fx, fy = job["rect"][2] / job["dst_rect"][2], job["rect"][3] / job["dst_rect"][3]
+                top = {"mild": cases.AA_MILD, "steep": cases.AA_STEEP_HI, "any": 65536.0}[call["cls"]]
+                assert fx <= top and fy <= top, what
             if "m" in job:
                 assert len(job["m"]) == (9 if family == "persp" else 6) and all(abs(v) <= cases.LIMIT and float(np.float32(v)) == v for v in job["m"]), what
+        if family == "remap":
+            assert call["max_step"] >= 0 and np.isfinite(call["max_step"]) and float(np.float32(call["max_step"])) == call["max_step"], what
+            assert {j["maps"] for j in call["jobs"]} == set(range(len(call["maps"]))), what
+            for p in call["maps"]:   # include/vpf_hip.h: a map pointer and pitch are multiples of 4, the pitch at least 4 x dw
+                assert p["xpitch"] % 4 == 0 and p["ypitch"] % 4 == 0 and min(p["xpitch"], p["ypitch"]) >= 4 * dw and p["xlead"] % 4 == 0 and p["ylead"] % 4 == 0, what
+        if family == "letterbox_aa" and call["cls"] == "steep":
+            assert any(cases.AA_STEEP_LO <= j["rect"][2] / j["dst_rect"][2] and cases.AA_STEEP_LO <= j["rect"][3] / j["dst_rect"][3] and j["dst_rect"][2] >= 32
+                       and j["dst_rect"][3] >= 8 for j in call["jobs"]), what
         # include/vpf_hip.h: plane pointers and pitches are multiples of the element size, pitch >= width x element size (3 x: one interleaved plane)
         rb = (3 if call["nhwc"] else 1) * dw * e
         if "jobs" in call:
@@ -337,6 +391,8 @@ def test_every_call_passes_validation(family):
             sts = invoke_encode(capi, call, ex, FAKE_SRC, dsts, check=False)
         else:
             tables = dict(boxes=FAKE_TABLE, mats=FAKE_TABLE, index=FAKE_TABLE + 0x100000, count=None if call.get("count") is None else FAKE_TABLE + 0x200000)
+            if family == "remap":   # fake map addresses at the alignment the description gives them (4, 8, 12 mod 16 among them)
+                tables = dict(maps=[(FAKE_TABLE + 0x200000 * k + p["xlead"], FAKE_TABLE + 0x200000 * k + 0x100000 + p["ylead"]) for k, p in enumerate(call["maps"])])
             sts = [invoke(capi, call, ex, fake_sources(call), FAKE_DST, tables, check=False)]
         assert all(st == capi.ERR_NO_DEVICE for st in sts), (what, [capi.status_string(st) for st in sts])
 
@@ -482,7 +538,7 @@ def persp_reach(L):
     assert no_lds >= 1 and per_tap_only >= 1 and zero_w >= 1 and infinite >= 1, (no_lds, per_tap_only, zero_w, infinite)
 
 
-@pytest.mark.parametrize("family", [f for f in cases.FAMILIES if f not in ("whole", "encode")])
+@pytest.mark.parametrize("family", [f for f in cases.FAMILIES if f not in ("whole", "encode", "letterbox_aa", "remap")])
 def test_reach(bounds, family):
     """a condition, not a measurement: the fuzz of this entry is worth running only if it holds"""
     share = {"staged": 0, "per_tap": 0}
@@ -542,14 +598,203 @@ def test_reach_of_the_single_form_entries(family):
         assert any(c["w"] % 2 and c["h"] % 2 for c in calls) and any(c["w"] % 16 == 0 and c["h"] % 2 == 0 and c["src"]["kind"] == "contiguous" for c in calls)
 
 
+AA_SRC_FC = {"NV12": 0, "YUV420": 1, "P10": 7, "P12": 7}   # FmtClass of csrc/vpf_classes.h, as tests/test_letterbox_aa_cpu.py names them
+
+
+def aa_tables(aa, call):
+    """the launcher's cut restated: the jobs in tables of 82, each planned by aa_plan of csrc/vpf_aa_plan.h (tests/test_letterbox_aa_cpu.py::plan)
+    under the default policy -> [(dispatches, which)] per table"""
+    from test_letterbox_aa_cpu import plan
+    out = []
+    for at in range(0, len(call["jobs"]), cases.TABLE["letterbox_aa"]):
+        chunk = call["jobs"][at:at + cases.TABLE["letterbox_aa"]]
+        geoms = [(j["rect"][2], j["rect"][3], j["dst_rect"][2], j["dst_rect"][3]) for j in chunk]
+        ok, _, ds, which = plan(aa, geoms, call["dw"], call["dh"], src_fc=AA_SRC_FC[call["sf"]], nhwc=int(call["nhwc"]), dtype=call["dtype"], variant=0)
+        assert ok == 1, cases.describe(call)
+        out.append((ds, [int(w) for w in which]))
+    return out
+
+
+def test_reach_letterbox_aa():
+    """conditions, decided by aa_plan table by table as the launcher cuts the jobs, counted over the default seeds on the calls with the knob at 0:
+    each of {staged under the 64 x 16 tile, staged under the 32 x 8 tile, per tap} holds at least 10 % of the jobs; a call with a staged and a per-tap
+    dispatch; a call of two tables, and one whose two tables take different tile shapes or forms; every source format, dtype, channel order and
+    layout; both knob values; mixed destination alignment; a rectangle at the right edge of a frame with W % 8 != 0; a picture at an odd ix; a job
+    with s < 1 on one axis and s > 3 on the other; a staged job whose tile window is its whole rectangle"""
+    from test_letterbox_aa_cpu import AA_GATHER, tiles
+    aa = aa_lib()
+    T = tiles(aa)
+    share = {"tile0": 0, "tile1": 0, "per_tap": 0}
+    seen = dict(sf=set(), dtype=set(), bgr=set(), nhwc=set(), tune=set(), cls=set())
+    n_jobs = both = two_tables = unlike_tables = mixed_alignment = right_edge = odd_ix = cross = whole_window = 0
+    for seed, k, call in all_cases("letterbox_aa"):
+        for key in seen:
+            seen[key].add(call[key])
+        jobs = call["jobs"]
+        mixed_alignment += len({(cases.plane_offsets(call, j)[0][0] % 16, j["layout"]["row"] % 16) for j in jobs}) > 1
+        if call["tune"] != 0:
+            continue
+        two_tables += len(jobs) > cases.TABLE["letterbox_aa"]
+        right_edge += call["W"] % 8 != 0 and any(j["rect"][0] + j["rect"][2] == call["W"] for j in jobs)
+        odd_ix += any(j["dst_rect"][0] % 2 for j in jobs)
+        cross += any(min(j["rect"][2] / j["dst_rect"][2], j["rect"][3] / j["dst_rect"][3]) < 1 and max(j["rect"][2] / j["dst_rect"][2], j["rect"][3] / j["dst_rect"][3]) > 3
+                     for j in jobs)
+        tables = aa_tables(aa, call)
+        kinds, at = [], 0
+        for ds, which in tables:
+            both += len(ds) == 2
+            kinds.append(tuple((d["form"], d["tile"]) for d in ds))
+            for j, wh in zip(jobs[at:], which):
+                d = ds[wh]
+                n_jobs += 1
+                if d["form"] == AA_GATHER:
+                    share["per_tap"] += 1
+                    continue
+                share[f"tile{d['tile']}"] += 1
+                tw, th, _ = T[d["tile"]]
+                (_, _, w, h), (_, _, iw, ih) = j["rect"], j["dst_rect"]
+                whole_window += aa.aa_c_window_bound(w, iw, tw) == w and aa.aa_c_window_bound(h, ih, th) == h
+            at += len(which)
+        unlike_tables += len(tables) == 2 and kinds[0] != kinds[1]
+    print("letterbox_aa jobs under the default policy", n_jobs, share, "tables with a staged and a per-tap dispatch", both, "calls of two tables", two_tables,
+          "of unlike tables", unlike_tables, "mixed alignment", mixed_alignment, "right edge at W % 8 != 0", right_edge, "odd ix", odd_ix,
+          "s < 1 on one axis and s > 3 on the other", cross, "staged jobs whose tile window is the whole rectangle", whole_window)
+    assert all(v >= 0.1 * n_jobs for v in share.values()), (share, n_jobs)
+    assert both >= 1 and two_tables >= 1 and unlike_tables >= 1
+    assert seen["sf"] == set(cases.SOURCES) and seen["dtype"] == {0, 1, 2} and seen["bgr"] == {False, True} and seen["nhwc"] == {False, True}, seen
+    assert seen["tune"] == {0, 9} and seen["cls"] == set(cases.AA_CLASSES), seen
+    assert mixed_alignment >= 1 and right_edge >= 1 and odd_ix >= 1 and cross >= 1 and whole_window >= 1
+
+
+@pytest.fixture(scope="module")
+def rm():
+    """tests/c/remap_bounds_capi.cpp: the window a workgroup of k_remap_tile merges, warp_strip, remap_strip_fits and remap_plan, compiled with g++
+    as tests/test_remap_tensor_cpu.py compiles it"""
+    import tempfile
+
+    from conftest import native_test_build
+    with tempfile.TemporaryDirectory(prefix="fuzz_rm") as tmp:
+        so = os.path.join(tmp, "libremapbounds.so")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Werror", "-Wno-unused-function", *native_test_build()[0],
+                               "-I" + os.path.join(ROOT, "videoprocessingframework_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "tests", "c", "remap_bounds_capi.cpp"), "-o", so, "-lm"])
+        L = C.CDLL(so)
+    u32, vp = C.c_uint32, C.c_void_p
+    L.rm_tile_window.argtypes, L.rm_tile_window.restype = [vp, vp, u32, u32, u32, u32, u32, C.c_int, u32, u32, vp], None
+    L.rm_strip_fits.argtypes, L.rm_strip_fits.restype = [u32] * 5, C.c_int
+    L.rm_plan.argtypes, L.rm_plan.restype = [C.c_int, C.c_int, u32, u32, u32, u32, u32, C.c_float, C.c_int, vp], None
+    return L
+
+
+REMAP_WIN_BYTES, REMAP_LDS_MAX = 32, 64 * 1024   # kRemapWinBytes of csrc/k_convert_remap.hip, kWarpStripMax of csrc/vpf_job_bounds.h
+
+
+def remap_strip_given(rm, call):
+    """the launcher's arithmetic restated (launch_convert_remap): remap_plan's LDS for the hint; the workgroup's eight reduction words ride behind the
+    strip — 32 bytes more are asked for where that stays within 64 KiB, and the strip gives them up where it does not -> the kernel's lds_bytes"""
+    o = np.zeros(6, np.uint32)
+    rm.rm_plan(AA_SRC_FC[call["sf"]], int(call["nhwc"]), call["dtype"], call["W"], call["H"], call["dw"], call["dh"], call["max_step"], call["tune"], o.ctypes.data)
+    assert o[0] == 1 and o[3] == cases.TABLE["remap"], cases.describe(call)
+    lds = int(o[4])
+    lds_all = 0 if not lds else min(lds + REMAP_WIN_BYTES, REMAP_LDS_MAX)
+    return lds_all - REMAP_WIN_BYTES if lds_all else 0
+
+
+def remap_tiles(rm, call, job, strip):
+    """per 32 x 32 destination tile of one job, by the kernel's own functions: (outcome, in-range pixels, window (x_lo, x_hi, y_lo, y_hi), strip bytes)
+    with outcome "border" (no in-range pixel), "staged", or "per_tap" (the window's strip outgrows what the dispatch was given)"""
+    sx, sy = cases.maps_of(call, job)
+    W, H, dw, dh, rep = call["W"], call["H"], call["dw"], call["dh"], call["mode"]
+    with np.errstate(invalid="ignore"):
+        inr = ~(np.isnan(sx) | np.isnan(sy)) if rep else (sx >= 0) & (sx <= np.float32(W - 1)) & (sy >= 0) & (sy <= np.float32(H - 1))
+    out = []
+    for by in range((dh + 31) // 32):
+        for bx in range((dw + 31) // 32):
+            o = np.zeros(7, np.uint32)
+            rm.rm_tile_window(sx.ctypes.data, sy.ctypes.data, dw, dw, dh, bx, by, rep, W, H, o.ctypes.data)
+            n_in = int(inr[32 * by:32 * by + 32, 32 * bx:32 * bx + 32].sum())
+            assert bool(o[0]) == (n_in == 0), (bx, by, cases.describe(call))
+            win, nbytes = tuple(int(v) for v in o[1:5]), int(o[5]) | int(o[6]) << 32
+            out.append(("border" if o[0] else "staged" if rm.rm_strip_fits(*win, strip) else "per_tap", n_in, win, nbytes))
+    return out
+
+
+def test_reach_remap(rm):
+    """conditions, decided by the kernel's own functions (tests/c/remap_bounds_capi.cpp) and remap_plan, counted over the default seeds on the calls
+    with the knob at 0: each of the three tile outcomes holds at least 10 % of the tiles; both border modes, every source format, dtype, channel
+    order and layout, both knob values; a two-table call; a shared map pair; a map base at 4, 8 and 12 mod 16; a tile with exactly one in-range
+    pixel; windows that reach beyond column 255 and beyond column 2047 (the upper bits of the packed 16-bit halves); every hint; both named cases"""
+    share = {"border": 0, "staged": 0, "per_tap": 0}
+    seen = dict(sf=set(), dtype=set(), bgr=set(), nhwc=set(), tune=set(), mode=set())
+    kinds, bases, hints = set(), set(), set()
+    two_tables = shared = one_pixel = above_255 = above_2047 = mixed_alignment = three_in_one_job = 0
+    for seed, k, call in all_cases("remap"):
+        for key in seen:
+            seen[key].add(call[key])
+        jobs = call["jobs"]
+        kinds |= {p["kind"] for p in call["maps"]}
+        bases |= {p["xlead"] % 16 for p in call["maps"]} | {p["ylead"] % 16 for p in call["maps"]}
+        hints.add("none" if call["max_step"] == 0 else "tiny" if call["max_step"] < 0.01 else "fifty" if call["max_step"] == 50.0 else "true")
+        two_tables += len(jobs) > cases.TABLE["remap"]
+        shared += any(a["maps"] == b["maps"] and a["frame"] != b["frame"] for i, a in enumerate(jobs) for b in jobs[i + 1:])
+        mixed_alignment += len({(cases.plane_offsets(call, j)[0][0] % 16, j["layout"]["row"] % 16) for j in jobs}) > 1
+        if call["tune"] != 0:
+            continue
+        strip = remap_strip_given(rm, call)
+        for job in jobs:
+            tiles = remap_tiles(rm, call, job, strip)
+            for outcome, n_in, win, _ in tiles:
+                share[outcome] += 1
+                one_pixel += n_in == 1
+                above_255 += outcome != "border" and win[1] > 255
+                above_2047 += outcome != "border" and win[1] > 2047
+            three_in_one_job += len({t[0] for t in tiles}) == 3
+    n = sum(share.values())
+    print("remap tiles under the default policy", n, share, "jobs holding all three outcomes", three_in_one_job, "two tables", two_tables, "calls with a shared pair", shared,
+          "mixed alignment", mixed_alignment, "tiles with one in-range pixel", one_pixel, "windows beyond column 255", above_255, "beyond 2047", above_2047, "kinds", sorted(kinds))
+    assert all(v >= 0.1 * n for v in share.values()), (share, n)
+    assert seen["sf"] == set(cases.SOURCES) and seen["dtype"] == {0, 1, 2} and seen["bgr"] == {False, True} and seen["nhwc"] == {False, True}, seen
+    assert seen["tune"] == {0, 9} and seen["mode"] == {0, 1}, seen
+    assert two_tables >= 1 and shared >= 1 and mixed_alignment >= 1 and one_pixel >= 1 and above_255 >= 1 and above_2047 >= 1
+    assert bases == {0, 4, 8, 12} and hints == {"none", "tiny", "true", "fifty"}, (bases, hints)
+    assert kinds == set(cases.REMAP_KINDS) | set(cases.REMAP_NAMED), kinds
+
+
+def test_remap_named_strips(rm):
+    """the two named cases among the default seeds: without a hint the launch gives a strip of 65 536 - 32 bytes (remap_strip_given: the arithmetic
+    of launch_convert_remap); tile (0, 0) of strip_65504 spans frame columns 0 .. 351 and rows 0 .. 45 — 46 rows of 32 x 44 + 16 bytes, exactly what
+    the launch gives, and it stages —, that of strip_65520 columns 0 .. 247 and rows 0 .. 64 — 65 rows of 32 x 31 + 16 bytes, 16 more, the smallest
+    strip above it (a strip is a multiple of 16 bytes, and 65 536 is no odd multiple of one) — and it goes per tap; every other tile is border"""
+    found = {name: 0 for name in cases.REMAP_NAMED}
+    for seed, k, call in all_cases("remap"):
+        for job in call["jobs"]:
+            name = call["maps"][job["maps"]]["kind"]
+            if name not in cases.REMAP_NAMED:
+                continue
+            W, H, x_hi, y_hi, nbytes = cases.REMAP_NAMED[name]
+            assert (call["W"], call["H"], call["max_step"], call["tune"]) == (W, H, 0.0, 0), cases.describe(call)
+            strip = remap_strip_given(rm, call)
+            assert strip == 65536 - 32 == 65504
+            tiles = remap_tiles(rm, call, job, strip)
+            outcome, n_in, win, got = tiles[0]
+            assert win == (0, x_hi, 0, y_hi) and got == nbytes == (y_hi + 1) * (32 * ((x_hi >> 3) + 1) + 16) and n_in >= 2, (name, win, got)
+            assert outcome == {"strip_65504": "staged", "strip_65520": "per_tap"}[name] and (got <= strip) == (name == "strip_65504")
+            assert all(t[0] == "border" for t in tiles[1:]), name
+            found[name] += 1
+    print("named strips among the default seeds", found)
+    assert all(v >= 1 for v in found.values()), found
+
+
 # ------------------------------------------------------------------------------------------------ the independent link
-@pytest.mark.parametrize("family", HOST_TABLE)
+@pytest.mark.parametrize("family", EXACT_CHAIN)
 def test_composed_fp32_reference_is_near_the_exact_chain(oracle, family):
     """every job of every case of the default seeds: the composed FP32 reference (what the GPU must equal bit for bit) against the same composition
     in the oracle's EXACT mode — convert EXACT, crop, resize or remap EXACT with the same float32 maps — at most 2 codes apart: the conversions
     differ by at most 1 (tests/test_oracle_kat.py), a bilinear blend is a convex combination and carries that 1 through unamplified, and the
     fp32 blend against the exact blend of equal inputs adds at most 1.
-    Measured maximum over these cases: rois 1, letterbox 1, warp 1, persp 1 (the bound stays 2)."""
+    Measured maximum over these cases: rois 1, letterbox 1, warp 1, persp 1, remap 1 (the bound stays 2).  The remap's composition is the warp's
+    on maps it was handed instead of maps it computed, so the argument applies unchanged; the antialiased letterbox has no EXACT mode in the oracle
+    and is tied to the outside by tests/test_letterbox_aa_definition_cpu.py instead."""
     oracle.set_threads(16)
     worst = n = 0
     for seed, k, call in all_cases(family):
