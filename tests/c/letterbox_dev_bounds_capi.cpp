@@ -40,5 +40,21 @@ uint32_t ld_tiles(uint32_t x, uint32_t w, uint32_t h, uint32_t ix, uint32_t iy, 
     }
   return t;
 }
+// ... and for the tiles that meet the picture the four values the staged kernels fill their strip from, win[4 * t ..] = first, last (frame pixels),
+// lo, hi (rectangle rows); the others: 0
+uint32_t ld_tile_windows(uint32_t x, uint32_t w, uint32_t h, uint32_t ix, uint32_t iy, uint32_t iw, uint32_t ih, uint32_t dw, uint32_t dh, uint32_t* win) {
+  const float scx = (float)w / (float)iw, scy = (float)h / (float)ih;
+  const uint32_t ixe = ix + iw - 1, iye = iy + ih - 1;
+  uint32_t t = 0;
+  for (uint32_t Y0 = 0; Y0 < dh; Y0 += 4 * kRoiBandRows)
+    for (uint32_t xs = 0; xs < dw; xs += 256, t++) {
+      const uint32_t Y1 = Y0 + 4 * kRoiBandRows - 1 < dh - 1 ? Y0 + 4 * kRoiBandRows - 1 : dh - 1, xe = xs + 255 < dw - 1 ? xs + 255 : dw - 1;
+      win[4 * t] = win[4 * t + 1] = win[4 * t + 2] = win[4 * t + 3] = 0;
+      if (xs > ixe || xe < ix || Y0 > iye || Y1 < iy) continue;
+      const RoiTileWin r = letterbox_tile_window(x, w, h, scx, scy, ix, iy, iw, ih, xs, xe, Y0, Y1).w;
+      win[4 * t] = r.first; win[4 * t + 1] = r.last; win[4 * t + 2] = r.lo; win[4 * t + 3] = r.hi;
+    }
+  return t;
+}
 
 }  // extern "C"

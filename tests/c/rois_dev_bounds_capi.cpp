@@ -32,5 +32,17 @@ uint32_t rd_tiles(uint32_t x, uint32_t w, uint32_t h, uint32_t dw, uint32_t dh, 
     }
   return t;
 }
+// ... and the four values the staged kernels fill their strip from, win[4 * t ..] = first, last (frame pixels), lo, hi (rectangle rows)
+uint32_t rd_tile_windows(uint32_t x, uint32_t w, uint32_t h, uint32_t dw, uint32_t dh, uint32_t* win) {
+  const float scx = (float)w / (float)dw, scy = (float)h / (float)dh;
+  uint32_t t = 0;
+  for (uint32_t Y0 = 0; Y0 < dh; Y0 += 4 * kRoiBandRows)
+    for (uint32_t xs = 0; xs < dw; xs += 256, t++) {
+      const uint32_t Y1 = Y0 + 4 * kRoiBandRows - 1 < dh - 1 ? Y0 + 4 * kRoiBandRows - 1 : dh - 1, xe = xs + 255 < dw - 1 ? xs + 255 : dw - 1;
+      const RoiTileWin r = roi_tile_window(x, w, h, scx, scy, xs, xe, Y0, Y1);
+      win[4 * t] = r.first; win[4 * t + 1] = r.last; win[4 * t + 2] = r.lo; win[4 * t + 3] = r.hi;
+    }
+  return t;
+}
 
 }  // extern "C"

@@ -41,6 +41,7 @@ def ld(tmp_path_factory):
     L.ld_lds_bytes.argtypes, L.ld_lds_bytes.restype = [u32, u32], u32
     L.ld_job_need.argtypes, L.ld_job_need.restype = [u32] * 9 + [C.POINTER(C.c_double)], u32
     L.ld_tiles.argtypes, L.ld_tiles.restype = [u32] * 10 + [C.c_void_p] * 4, u32
+    L.ld_tile_windows.argtypes, L.ld_tile_windows.restype = [u32] * 9 + [C.c_void_p], u32
     return L
 
 
@@ -363,6 +364,38 @@ def test_tile_need_agrees_with_the_job_need_and_fits_the_lds(ld):
         sm = s[m]
         n_staged += int(sm.all()); n_tap += int(not sm.any()); n_mixed += int(sm.any() and not sm.all()); n_missed += int((~m).any())
     assert n_staged > 200 and n_tap > 200 and n_mixed > 0 and n_missed > 200, (n_staged, n_tap, n_mixed, n_missed)
+
+
+def test_tile_window_is_the_staged_kernels_make_tap_arithmetic(ld):
+    """letterbox_tile_window's first, last, lo, hi of every tile that meets the picture against the clip and the four make_tap<LINEAR> calls of the
+    staged form, restated in numpy float32 (test_job_bounds_cpu.lin_taps): the tile's columns and rows clipped to the picture, in picture pixels,
+    then first = x + tap(cxs).i0, last = x + tap(cxe).i1, lo = tap(cys).i0, hi = tap(cye).i1 on the rectangle with the scale (float)w / (float)iw.
+    Both staged kernels (k_lb_strip, k_lb_dev) fill and address their strip from these four values."""
+    from test_job_bounds_cpu import lin_taps
+    rng = np.random.default_rng(20261)
+    edge = [(0, 1, 1, 0, 0, 1, 1, 1, 1), (7, 640, 360, 0, 0, 1, 1, 1, 1),                  # a 1 x 1 destination
+            (5, 300, 40, 0, 0, 257, 16, 257, 16), (0, 31, 9, 200, 1, 57, 2, 257, 3),       # dw = 257: a second tile one column wide
+            (3, 200, 90, 0, 0, 64, 17, 64, 17), (0, 8, 5, 10, 15, 100, 2, 256, 17),        # dh = 17: a second band one row high
+            (130, 1, 77, 11, 0, 1, 16, 24, 16), (0, 1, 1, 0, 0, 257, 17, 257, 17),         # a rectangle of width 1
+            (9, 50, 70, 256, 3, 1, 11, 257, 17), (9, 50, 70, 299, 0, 1, 40, 300, 40), (0, 640, 360, 63, 47, 1, 1, 64, 48)]  # a picture at the plane's last column
+    for (x, w, h, ix, iy, iw, ih, dw, dh) in edge + list(_draws(rng, N_DRAWS)):
+        what = (x, w, h, ix, iy, iw, ih, dw, dh)
+        nx, ny = (dw + 255) // 256, (dh + 15) // 16
+        win = np.empty((ny * nx, 4), np.uint32)
+        assert ld.ld_tile_windows(x, w, h, ix, iy, iw, ih, dw, dh, win.ctypes.data) == ny * nx
+        xs, Y0 = np.arange(0, dw, 256), np.arange(0, dh, 16)
+        xe, Y1 = np.minimum(xs + 255, dw - 1), np.minimum(Y0 + 15, dh - 1)
+        ixe, iye = ix + iw - 1, iy + ih - 1
+        mx, my = ~((xs > ixe) | (xe < ix)), ~((Y0 > iye) | (Y1 < iy))
+        assert mx.any() and my.any(), what
+        cxs, cxe = np.maximum(xs, ix)[mx] - ix, np.minimum(xe, ixe)[mx] - ix
+        cys, cye = np.maximum(Y0, iy)[my] - iy, np.minimum(Y1, iye)[my] - iy
+        want = np.zeros((ny, nx, 4), np.int64)
+        sub = want[np.ix_(my, mx)]
+        sub[..., 0], sub[..., 1] = (x + lin_taps(cxs, w, iw)[0])[None, :], (x + lin_taps(cxe, w, iw)[1])[None, :]
+        sub[..., 2], sub[..., 3] = lin_taps(cys, h, ih)[0][:, None], lin_taps(cye, h, ih)[1][:, None]
+        want[np.ix_(my, mx)] = sub
+        assert np.array_equal(win.astype(np.int64).reshape(ny, nx, 4), want), what
 
 
 def test_gpu_cases_hold_every_form(ld):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import cases_rois_dev as cases
-from test_job_bounds_cpu import roi_cases
+from test_job_bounds_cpu import lin_taps, roi_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
@@ -33,6 +33,7 @@ def rd(tmp_path_factory):
     L.rd_lds_bytes.argtypes, L.rd_lds_bytes.restype = [u32, u32], u32
     L.rd_job_need.argtypes, L.rd_job_need.restype = [u32] * 5 + [C.POINTER(C.c_double)], u32
     L.rd_tiles.argtypes, L.rd_tiles.restype = [u32] * 6 + [C.c_void_p] * 3, u32
+    L.rd_tile_windows.argtypes, L.rd_tile_windows.restype = [u32] * 5 + [C.c_void_p], u32
     return L
 
 
@@ -109,6 +110,28 @@ def test_tile_need_agrees_with_the_job_need(rd):
         assert not tiles(rd, x, w, h, dw, dh, 0)[2].any()                 # VPF_TUNE_NV12_RGB_VARIANT = 9: no LDS, every tile per tap
         n_staged += int(s.all()); n_tap += int(not s.any()); n_mixed += int(s.any() and not s.all())
     assert n_staged > 300 and n_tap > 300 and n_mixed > 0, (n_staged, n_tap, n_mixed)
+
+
+def test_tile_window_is_the_staged_kernels_make_tap_arithmetic(rd):
+    """roi_tile_window's first, last, lo, hi of every tile against the four make_tap<LINEAR> calls of the staged form, restated in numpy float32
+    (test_job_bounds_cpu.lin_taps): first = x + tap(xs).i0, last = x + tap(xe).i1, lo = tap(Y0).i0, hi = tap(Y1).i1 on the rectangle's size.  Both
+    staged kernels (k_roi_strip, k_roi_dev) fill and address their strip from these four values."""
+    rng = np.random.default_rng(20251)
+    edge = [(0, 0, 1, 1, 1, 1), (7, 3, 640, 360, 1, 1),      # a 1 x 1 destination
+            (5, 0, 300, 40, 257, 16), (0, 0, 31, 9, 257, 3),  # dw = 257: a second tile one column wide
+            (3, 1, 200, 90, 64, 17), (0, 0, 8, 5, 256, 17),   # dh = 17: a second band one row high
+            (130, 2, 1, 77, 24, 16), (0, 0, 1, 1, 257, 17),   # a rectangle of width 1
+            (4095, 0, 1, 9, 300, 40), (3840, 0, 256, 64, 513, 33)]  # a rectangle that ends at the last column of a 4096-wide frame
+    for (x, y, w, h, dw, dh) in edge + list(roi_cases(rng, N_JOBS)):
+        nx, ny = (dw + 255) // 256, (dh + 15) // 16
+        win = np.empty((ny * nx, 4), np.uint32)
+        assert rd.rd_tile_windows(x, w, h, dw, dh, win.ctypes.data) == ny * nx
+        xs, Y0 = np.arange(0, dw, 256), np.arange(0, dh, 16)
+        xe, Y1 = np.minimum(xs + 255, dw - 1), np.minimum(Y0 + 15, dh - 1)
+        first, last = x + lin_taps(xs, w, dw)[0], x + lin_taps(xe, w, dw)[1]
+        lo, hi = lin_taps(Y0, h, dh)[0], lin_taps(Y1, h, dh)[1]
+        want = np.stack([np.tile(first, ny), np.tile(last, ny), np.repeat(lo, nx), np.repeat(hi, nx)], axis=1)  # band-major
+        assert np.array_equal(win.astype(np.int64), want), (x, y, w, h, dw, dh)
 
 
 def test_gpu_cases_hold_tiles_of_both_forms(rd):

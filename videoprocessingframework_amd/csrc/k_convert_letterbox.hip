@@ -10,11 +10,10 @@
 //   k_lb_gather   per-tap texel_rgb: jobs whose window does not pay or does not fit (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
 // Definition (include/vpf_hip.h): inside the picture the byte vpf_convert_resize_tensor_rois defines for rect -> (iw, ih) at (dx - ix, dy - iy) —
 // make_tap<LINEAR> on the rectangle with scale (float)w / (float)iw, frame texels at absolute coordinates, bilerp, truncation —, outside pad[c];
-// then the tensor epilogue.  Both kernels run exactly the ROI kernels' fp32 operations in their order on the picture: identical bits.
-#include "k_bilinear_blend.h"
-#include "k_fused_common.h"
+// then the tensor epilogue.  Both kernels run exactly the ROI kernels' fp32 operations in their order on the picture: identical bits.  The per-tap
+// body is lb_gather4 (k_letterbox_common.h), which k_lb_dev runs as well; the staged tile is typed here and in k_lb_dev.
 #include "k_job_launch.h"
-#include "k_letterbox_common.h"  // lb_pad, lb_store4, lb_pad_rows: shared with k_convert_letterbox_dev.hip
+#include "k_letterbox_common.h"  // lb_pad, lb_store4, lb_pad_rows, lb_gather4: shared with k_convert_letterbox_dev.hip
 #include "vpf_job_bounds.h"  // kRoiBandRows: shared with the launch policy (vpf_job_plan.h) and the CPU property tests
 
 namespace vpf {
@@ -93,8 +92,9 @@ __global__ __launch_bounds__(256) void k_lb_strip(const LetterboxArgs args, cons
 }
 
 // ------------------------------------------------------------------------------------------
-// The gather form: k_roi_gather on the plane (four rows x 64 lanes x 4 pixels per workgroup, a wave = one row).  A lane whose four
-// columns miss the picture loads nothing; a wave whose row or columns miss it branches over the conversion as a whole.
+// The gather form: k_roi_gather on the plane (four rows x 64 lanes x 4 pixels per workgroup, a wave = one row through lb_gather4,
+// k_letterbox_common.h).  A lane whose four columns miss the picture loads nothing; a wave whose row or columns miss it branches over the conversion
+// as a whole.
 // ------------------------------------------------------------------------------------------
 template <int SRC, int DST>  // (FC_TENSOR_NHWC: four waves per SIMD asked for, as k_roi_gather)
 __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gather(const LetterboxArgs args, const Yuv2RgbCoef c, uint32_t dw,
@@ -107,35 +107,17 @@ __global__ __launch_bounds__(256, (DST == FC_TENSOR_NHWC ? 4 : 1)) void k_lb_gat
   if (x0 >= dw || y >= dh) return;
   const uint32_t ix = L.ix, iy = L.iy, ixe = ix + L.iw - 1, iye = iy + L.ih - 1;
   const bool row_in = y >= iy && y <= iye;
-  const Tap ty = make_tap<VPF_INTERP_LINEAR>(row_in ? y - iy : 0u, J.scy, J.h);
-  float u[3][4];
+  Tap tx[4];
+  bool in[4];
 #pragma unroll
-  for (int ch = 0; ch < 3; ch++)
-#pragma unroll
-    for (int k = 0; k < 4; k++) u[ch][k] = lb_pad(args.e, ch);
-  if (row_in && x0 + 3 >= ix && x0 <= ixe) {  // the lane holds picture: all four pixels' texels in flight together, as k_roi_gather has them
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t x = x0 + k;  // (a column right of the plane is right of the picture: pad, not stored)
-      // a column outside the picture takes the taps of the nearest picture column — texels of the rectangle — and keeps the pad
-      const Tap tx = make_tap<VPF_INTERP_LINEAR>(x < ix ? 0u : (x > ixe ? ixe - ix : x - ix), J.scx, J.w);
-      float p00[3], p01[3], p10[3], p11[3];
-      texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i0, p00);
-      texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i0, p01);
-      texel_rgb<SRC>(f, c, J.x + tx.i0, J.y + ty.i1, p10);
-      texel_rgb<SRC>(f, c, J.x + tx.i1, J.y + ty.i1, p11);
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) {
-        const float v = __builtin_truncf(bilerp(p00[ch], p01[ch], p10[ch], p11[ch], tx.f, ty.f));
-        u[ch][k] = x >= ix && x <= ixe ? v : u[ch][k];
-      }
-    }
+  for (int k = 0; k < 4; k++) {
+    const uint32_t x = x0 + k;  // (a column right of the plane is right of the picture: pad, not stored)
+    in[k] = x >= ix && x <= ixe;
+    tx[k] = make_tap<VPF_INTERP_LINEAR>(x < ix ? 0u : (x > ixe ? ixe - ix : x - ix), J.scx, J.w);
   }
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
-  lb_store4<DST>(f, x0, y, u, args.e, vec, nv, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+  lb_gather4<SRC, DST>(f, c, J.x, J.y, tx, in, make_tap<VPF_INTERP_LINEAR>(row_in ? y - iy : 0u, J.scy, J.h), row_in && x0 + 3 >= ix && x0 <= ixe, x0, y,
+                       args.e, tensor_vec_ok<DST>(f, nv, dmask), nv, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@
 #include "k_bilinear_blend.h"
 #include "k_fused_common.h"
 #include "k_job_launch.h"
-#include "k_letterbox_common.h"  // lb_pad, lb_store4
+#include "k_letterbox_common.h"  // lb_fill_pad, lb_store4
 #include "vpf_aa_plan.h"
 
 namespace vpf {
@@ -25,11 +25,6 @@ VPF_DEV void lbaa_put(float (&u)[3][4], uint32_t k, const float (&v)[3]) {
   for (int kk = 0; kk < 4; kk++)
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) u[ch][kk] = (uint32_t)kk == k ? v[ch] : u[ch][kk];
-}
-VPF_DEV bool lbaa_vec(const FrameDesc& f, bool nhwc, uint32_t nv, uint32_t dmask) {
-  bool vec = nv == 4;
-  for (int ch = 0; ch < (nhwc ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
-  return vec;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -53,12 +48,9 @@ __global__ __launch_bounds__(256) void k_lbaa_strip(const LetterboxArgs args, co
   const uint32_t x0 = xs + (tid & (lpr - 1)) * npx, y = Y0 + tid / lpr;
   const bool live = x0 <= xe && y <= Y1;
   const uint32_t nv = live ? (xe - x0 + 1 < npx ? xe - x0 + 1 : npx) : 0u;
-  const bool vec = lbaa_vec(f, DST == FC_TENSOR_NHWC, nv, dmask);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   float u[3][4];
-#pragma unroll
-  for (int ch = 0; ch < 3; ch++)
-#pragma unroll
-    for (int k = 0; k < 4; k++) u[ch][k] = lb_pad(te, ch);
+  lb_fill_pad(u, te);
   if (xs > ixe || xe < ix || Y0 > iye || Y1 < iy) {  // the tile misses the picture: pad, nothing converted
     if (live) lb_store4<DST>(f, x0, y, u, te, vec, nv, kNoStage, tid & 63);
     return;
@@ -109,10 +101,7 @@ __global__ __launch_bounds__(256) void k_lbaa_gather(const LetterboxArgs args, c
   const uint32_t ix = L.ix, iy = L.iy, ixe = ix + L.iw - 1, iye = iy + L.ih - 1;
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
   float u[3][4];
-#pragma unroll
-  for (int ch = 0; ch < 3; ch++)
-#pragma unroll
-    for (int k = 0; k < 4; k++) u[ch][k] = lb_pad(args.e, ch);
+  lb_fill_pad(u, args.e);
   if (y >= iy && y <= iye && x0 + 3 >= ix && x0 <= ixe) {  // the lane holds picture
     const AaAxis ax = aa_axis_s(J.w, J.scx), ay = aa_axis_s(J.h, J.scy);
 #pragma nounroll
@@ -124,7 +113,7 @@ __global__ __launch_bounds__(256) void k_lbaa_gather(const LetterboxArgs args, c
       lbaa_put(u, k, v);
     }
   }
-  lb_store4<DST>(f, x0, y, u, args.e, lbaa_vec(f, DST == FC_TENSOR_NHWC, nv, dmask), nv, kNoStage, threadIdx.x & 63);
+  lb_store4<DST>(f, x0, y, u, args.e, tensor_vec_ok<DST>(f, nv, dmask), nv, kNoStage, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------

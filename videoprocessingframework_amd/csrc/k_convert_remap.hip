@@ -82,9 +82,7 @@ __global__ __launch_bounds__(256) void k_remap_tile(const RemapArgs args, const 
   const uint32_t x0 = xs + (tid % kWarpLanesX) * 4, y = ys + tid / kWarpLanesX;
   const bool mine = x0 < dw && y < dh;
   const uint32_t nv = mine ? (dw - x0 < 4 ? dw - x0 : 4) : 0u;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   // 1. the coordinates
   float sx[4] = {0.f, 0.f, 0.f, 0.f}, sy[4] = {0.f, 0.f, 0.f, 0.f};
   if (mine) {

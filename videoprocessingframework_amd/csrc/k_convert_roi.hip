@@ -6,64 +6,35 @@
 //   k_roi_gather   per-tap texel_rgb: jobs whose window does not pay or does not fit (large down-scales), VPF_TUNE_NV12_RGB_VARIANT = 9
 // Definition (include/vpf_hip.h): taps are make_tap<LINEAR> on the RECTANGLE's size (they clamp at its edges), texels are frame pixels
 // (x + i, y + j) converted with vpf_convert's arithmetic — chroma at absolute ((x + i) >> 1, (y + j) >> 1) —, then bilerp, truncation
-// and the tensor epilogue.  Both kernels run exactly those fp32 operations in that order: identical bits.
+// and the tensor epilogue.  Both kernels run exactly those fp32 operations in that order: identical bits.  The staged body is roi_strip_tile
+// (k_convert_roi_common.h), which k_roi_dev runs as well; the per-tap pixel is typed here and in k_roi_dev.
 // P10 / P12 frames (FC_P16) take the same two kernels: their 16-bit samples are narrowed to 8 bits at the load (k_fused_common.h).
-#include "k_bilinear_blend.h"
-#include "k_fused_common.h"
+#include "k_convert_roi_common.h"
+#include "k_dev_table.h"  // tile_window_uniform
 #include "k_job_launch.h"
-#include "vpf_job_bounds.h"  // kRoiBandRows: shared with the launch policy (vpf_job_plan.h) and the CPU property tests
+#include "vpf_job_bounds.h"  // kRoiBandRows, roi_tile_window: shared with the launch policy (vpf_job_plan.h) and the CPU property tests
 
 namespace vpf {
 
 // ------------------------------------------------------------------------------------------
-// The staged form.  convert_strip_wg_task (k_convert_resize.hip) with per-job geometry: the strip's pixels are ABSOLUTE frame pixels
-// [base_px, ..) x rows [y + R_lo, y + R_hi], base_px = the even pixel at or below the first tap (a conversion unit = 8 pixels x 2 luma
-// rows under ONE chroma row, so units start on chroma pairs of the frame, whatever the parity of the rectangle's corner); the blend
-// addresses them through rectangle-relative taps.  A unit that would read past the frame's right edge takes byte loads clamped to the
-// row's last sample instead of the 8-byte ones (its surplus pixels are converted and never blended): no byte outside the frame's own
-// rows is read.  Rows need no clamp: every row of the window lies in the rectangle, every chroma row under it in the frame.
+// The staged form: the tile's window (roi_tile_window, vpf_job_bounds.h: what the launch policy sized the strip with), then roi_strip_tile
+// (k_convert_roi_common.h).
 // ------------------------------------------------------------------------------------------
 template <int SRC, int DST>  // DST = FC_TENSOR: three planes per job; FC_TENSOR_NHWC: one interleaved plane
 __global__ __launch_bounds__(256) void k_roi_strip(const RoiArgs args, const Yuv2RgbCoef c, uint32_t W, uint32_t dw, uint32_t dh, uint32_t dmask,
                                                    uint32_t lds_bytes) {
   constexpr int R = kRoiBandRows;
   const RoiDesc& J = args.j[blockIdx.z];
-  const FrameDesc& f = J.f;
-  const uint32_t rx = J.x, ry = J.y, rw = J.w, rh = J.h;
-  const float scx = J.scx, scy = J.scy;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, tid = threadIdx.x;
   const uint32_t Y0 = blockIdx.y * (4 * R), xs = blockIdx.x * 256;  // the grid covers the destination exactly: Y0 < dh, xs < dw
   const uint32_t Y1 = (Y0 + 4 * R - 1 < dh - 1) ? Y0 + 4 * R - 1 : dh - 1, xe = (xs + 255 < dw - 1) ? xs + 255 : dw - 1;
-  const uint32_t first = rx + make_tap<VPF_INTERP_LINEAR>(xs, scx, rw).i0, last = rx + make_tap<VPF_INTERP_LINEAR>(xe, scx, rw).i1;  // frame pixels
-  const uint32_t base_px = first & ~1u;
-  const uint32_t R_lo_rel = __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y0, scy, rh).i0);
-  const uint32_t R_lo = ry + R_lo_rel, R_hi = ry + __builtin_amdgcn_readfirstlane(make_tap<VPF_INTERP_LINEAR>(Y1, scy, rh).i1);  // frame rows
-  uint8_t* const strip = reinterpret_cast<uint8_t*>(dyn_strip);
-  const uint32_t ng = ((last - base_px) >> 3) + 1;
-  const uint32_t rowbytes = 32u * ng + 16u;  // whole units + the second tap's dword behind the last pixel (weight 0 there)
-  if ((R_hi - R_lo + 1) * rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, launch_convert_resize_rois)
-  strip_fill_window<SRC>(f, c, W, strip, base_px, R_lo, R_hi, ng, rowbytes, tid);  // (k_fused_common.h: shared with k_warp_strip)
-  __syncthreads();
-  const uint32_t ya = Y0 + wv * R;
-  if (ya > Y1) return;
-  const uint32_t yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;
-  const Tap row_taps = band_row_taps(ya, yb, scy, rh);  // every lane of the wave still active here
-  const uint32_t x0 = xs + lane * 4;
-  if (x0 >= dw) return;
-  const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
-  const ColTapsX T = make_col_taps_x(base_px - rx, x0, dw, rw, scx);  // tap offsets from the strip's first pixel (frame pixel base_px = rectangle pixel base_px - x, modulo 2^32)
-  const TensorEpi te = args.e;
-  band_blend_rows<3, R>(strip, rowbytes, R_lo_rel, ya, yb, row_taps, T, [&](uint32_t y, const float* o) {  // o: pixel-major R G B, + 0.5 added
-    if constexpr (DST == FC_TENSOR_NHWC) {
-      tensor_store4_nhwc_trunc<false>(f.d[0] + (size_t)y * f.dp[0], x0, o, 1, 3, te, vec, nv, wv, lane);
-    } else {
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) tensor_store4_trunc<false>(f.d[ch] + (size_t)y * f.dp[ch], x0, o + ch, 3, te, ch, vec, nv);
-    }
-  });
+  RoiTileWin win = roi_tile_window(J.x, J.w, J.h, J.scx, J.scy, xs, xe, Y0, Y1);
+  tile_window_uniform(win);
+  if (win.rows * win.rowbytes > lds_bytes) return;  // (never: the launcher sized the strip with this arithmetic, launch_convert_resize_rois)
+  const uint32_t ya = Y0 + wv * R, yb = (ya + R - 1 < Y1) ? ya + R - 1 : Y1;  // this wave's rows (none when ya > Y1)
+  const uint32_t x0 = xs + lane * 4;                                        // this lane's four columns (none when x0 >= dw)
+  const uint32_t nv = x0 < dw ? (dw - x0 < 4 ? dw - x0 : 4) : 0;
+  roi_strip_tile<SRC, DST>(J.f, c, W, J.x, J.y, J.w, J.h, J.scx, J.scy, win, dw, ya, yb, x0, nv, tensor_vec_ok<DST>(J.f, nv, dmask), wv, lane, tid, args.e);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -52,9 +52,7 @@ VPF_DEV void warp_gather4(const WarpDesc& J, const Yuv2RgbCoef& c, const TensorE
     }
   }
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   warp_store4<DST>(f, x0, y, u, te, vec, nv);
 }
 
@@ -78,9 +76,7 @@ VPF_DEV void warp_strip_tile(const WarpDesc& J, const TensorEpi& te, const Yuv2R
   w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
   w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   if (w.empty) {  // (CONSTANT only: a clamped coordinate is always in range)
     if (!mine) return;
     if constexpr (DST == FC_TENSOR_NHWC) {
@@ -168,9 +164,7 @@ VPF_DEV void persp_gather4(const PerspDesc& J, const Yuv2RgbCoef& c, const Tenso
     for (int ch = 0; ch < 3; ch++) u[ch][k] = in ? v[ch] : warp_border(te, ch);
   }
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   warp_store4<DST>(f, x0, y, u, te, vec, nv);
 }
 
@@ -196,9 +190,7 @@ VPF_DEV void persp_strip_tile(const PerspDesc& J, const TensorEpi& te, const Yuv
   w.x_lo = __builtin_amdgcn_readfirstlane(w.x_lo); w.x_hi = __builtin_amdgcn_readfirstlane(w.x_hi);
   w.y_lo = __builtin_amdgcn_readfirstlane(w.y_lo); w.y_hi = __builtin_amdgcn_readfirstlane(w.y_hi);
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   if (pw.cls == kPerspTileBorder) {  // behind the plane: both modes
     if (!mine) return;
     float u[3][4];

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "k_convert_warp_common.h"
+#include "k_dev_table.h"
 #include "k_job_launch.h"
 
 namespace vpf {
@@ -19,9 +20,7 @@ namespace vpf {
 template <int DST>
 VPF_DEV void warp_dev_fill4(const FrameDesc& f, const TensorEpi& te, uint32_t dw, uint32_t dmask, uint32_t x0, uint32_t y) {
   const uint32_t nv = dw - x0 < 4 ? dw - x0 : 4;
-  bool vec = nv == 4;
-#pragma unroll
-  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  const bool vec = tensor_vec_ok<DST>(f, nv, dmask);
   float u[3][4];
 #pragma unroll
   for (int ch = 0; ch < 3; ch++)
@@ -35,12 +34,7 @@ __global__ __launch_bounds__(256) void k_warp_dev(const WarpDevArgs args, const 
                                                   uint32_t dmask, uint32_t lds_bytes) {
   // a prologue that turns the device tables into the WarpDesc the host entry would have put into its job table, then k_warp_strip's tile
   // 1. the count: jobs at or behind it write nothing and read neither matrix nor frame index
-  uint32_t dv_cnt = args.max_n;
-  if (args.count) {
-    const int32_t v = __builtin_amdgcn_readfirstlane(*args.count);
-    dv_cnt = v < 0 ? 0u : ((uint32_t)v < args.max_n ? (uint32_t)v : args.max_n);
-  }
-  if (blockIdx.z >= dv_cnt) return;
+  if (blockIdx.z >= dev_job_count(args.count, args.max_n)) return;
   // 2. the frame index and the six floats of this job, wave-uniform: the window arithmetic below stays scalar
   WarpDesc J;
   int32_t dv_frame = 0;
@@ -57,11 +51,7 @@ __global__ __launch_bounds__(256) void k_warp_dev(const WarpDevArgs args, const 
   // without this the planar kernels spill 8 - 13 scalar registers
   uint32_t dv_zero = 0;
   asm("" : "+v"(dv_zero));
-#pragma unroll
-  for (int ch = 0; ch < 3; ch++) {
-    J.f.d[ch] = (DST == FC_TENSOR_NHWC && ch) ? nullptr : args.d[ch] + ((size_t)blockIdx.z * args.job_stride + dv_zero);
-    J.f.dp[ch] = args.dp[ch] + dv_zero;
-  }
+  dev_dst_planes<DST>(args, blockIdx.z, J.f, dv_zero);
   // 3. the guard (vpf_job_bounds.h): an invalid job reads no frame; its tile takes the epilogue of the border, in both modes
   if (!warp_dev_job_ok(dv_frame, J.m, args.n_frames)) {
     const uint32_t fx0 = blockIdx.x * kWarpTileW + (threadIdx.x % kWarpLanesX) * 4, fy = blockIdx.y * kWarpTileH + threadIdx.x / kWarpLanesX;

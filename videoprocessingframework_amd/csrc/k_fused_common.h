@@ -54,6 +54,15 @@ template <int CAP>
 VPF_DEV TensorEpi epi_of(const BatchArgsT<CAP>&) { return TensorEpi{}; }  // 8-bit launches: never read
 template <int CAP>
 VPF_DEV TensorEpi epi_of(const BatchArgsTE<CAP>& a) { return a.e; }
+// `vec` of the four-pixel stores below for the per-job kernels: a lane holds four pixels and every plane it stores to (FC_TENSOR_NHWC: the one
+// interleaved plane) has base and pitch clear under the launcher's alignment mask (JobPlan::dmask, AaPlan::dmask)
+template <int DST>
+VPF_DEV bool tensor_vec_ok(const FrameDesc& f, uint32_t nv, uint32_t dmask) {
+  bool vec = nv == 4;
+#pragma unroll
+  for (int ch = 0; ch < (DST == FC_TENSOR_NHWC ? 1 : 3); ch++) vec = vec && ((((uintptr_t)f.d[ch] | f.dp[ch]) & dmask) == 0);
+  return vec;
+}
 // `row` = byte address of row y of channel plane `ch` at column 0; u[] = the 8-bit values of columns x0 .. x0 + 3 (nv of them valid)
 template <bool NT>
 VPF_DEV void tensor_store4(uint8_t* row, uint32_t x0, const float u[4], const TensorEpi& e, int ch, bool vec, uint32_t nv) {
